@@ -19,6 +19,7 @@ import argparse
 import json
 import math
 import os
+import random
 import sys
 import time
 
@@ -218,7 +219,7 @@ def pmc_traffic(cls, config="paired"):
     return None
 
 
-def launch_ranks(n):
+def launch_ranks(n, extra=()):
     """Parent of a multi-GPU run started as plain `python bench.py --gpus N`: N child rank processes, one per device.
     The parent never initialises a GPU (no exec of a GPU-holding process, no fork after HIP init): children are fresh
     interpreters with the torchrun environment contract (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT)."""
@@ -240,7 +241,7 @@ def launch_ranks(n):
                 env = dict(os.environ)
                 env.update(RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1",
                            MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-                procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), *sys.argv[1:]], env=env, cwd=ROOT,
+                procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), *sys.argv[1:], *extra], env=env, cwd=ROOT,
                                               stdout=cap if r == 0 else subprocess.DEVNULL))
             while any(p.poll() is None for p in procs):
                 if any(p.poll() not in (None, 0) for p in procs):    # a failed rank leaves its peers waiting in a collective
@@ -329,6 +330,43 @@ def build(args, dev, rank):
     return (lambda: m.optimize_parameters(x, y)), m.nets, m, mac, text, lambda: {"loss": float(m.loss), "skipped_steps": m.skipped_steps}
 
 
+# What a caller of each timed step receives: the harness attributes the step leaves behind (images, losses) and the updated
+# parameters of every network it trains.  `--dump-outputs` writes them after the last timed step.
+STEP_OUTPUTS = {"paired": ["fake", "loss_G", "loss_D"],
+                "cycle": ["fake_B", "recl_A", "fake_A", "recl_B", "loss_G", "loss_D_A", "loss_D_B"],
+                "cas-constlab": ["fake_BC", "fake_BB", "fake_AC", "fake_AB", "loss_SR", "loss_C", "psnr_SR", "psnr_C"],
+                "x8": ["loss"]}
+STEP_NETS = {"paired": ["netG", "netD"], "cycle": ["netG_A", "netG_B", "netD_A", "netD_B"], "cas-constlab": ["netG_A2C", "netG_C2B"]}
+DUMP_SAMPLE = 1 << 20          # elements kept of a larger array: a fixed, seeded sample (4 MB in float32)
+DUMP_LIMIT = 64 << 20          # bytes, all files together
+
+
+def dump_outputs(config, harness, path):
+    """Write the last step's outputs as <path>/<name>.npy (float64 stays float64, everything else float32).  An array of more
+    than DUMP_SAMPLE elements is replaced by the elements at DUMP_SAMPLE sorted indices drawn from a seed-0 generator, so two
+    runs (or two builds) with the same arguments store the same positions."""
+    import numpy as np
+    arrays = {name: getattr(harness, name) for name in STEP_OUTPUTS[config]}
+    nets = ([(f"net{i}", n) for i, n in enumerate(harness.nets)] if config == "x8"
+            else [(name, getattr(harness, name)) for name in STEP_NETS[config]])
+    for name, net in nets:
+        arrays[f"{name}_params"] = torch.cat([p.detach().reshape(-1).float() for p in net.parameters()])
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, v in arrays.items():
+        t = torch.as_tensor(v).detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, f"--dump-outputs: more than {DUMP_LIMIT >> 20} MB"
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2**20:.1f} MB) to {path}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -345,9 +383,14 @@ def main():
     ap.add_argument("--init-scale", type=float, default=None, help="x8: factor on the trunk convolutions' initial weights (default 0.1 for fp16, 1 otherwise)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        return launch_ranks(args.gpus)
+        # ranks start in ROOT: hand them the directory as an absolute path (the last occurrence of an option wins)
+        return launch_ranks(args.gpus, ["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
     for k, v in DEFAULTS[args.config].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -372,6 +415,7 @@ def main():
     torch.cuda.set_device(dev)
 
     torch.manual_seed(0)                         # identical init on every rank, then broadcast anyway
+    random.seed(0)                               # the cycle harness's image pools draw from Python's generator
     step, nets, harness, per_img_mac, workload, losses = build(args, dev, rank)
     use_dist = world > 1 or dist.is_initialized()          # one rank + SRCGAN_FORCE_DIST=1 rehearses the RCCL path
     dinfo, gsync = None, None
@@ -405,6 +449,8 @@ def main():
         elapsed = float(t)
     loss_vals = losses()
     peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9
+    if args.dump_outputs and rank == 0:          # before the profiled step below changes the state
+        dump_outputs(args.config, harness, args.dump_outputs)
 
     # ---- per-kernel roofline: one extra step with HIP events around every conv launch (launch stream)
     roofline, kernels = None, []

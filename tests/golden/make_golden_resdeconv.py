@@ -9,6 +9,7 @@ parameter holders are created in the reference's order, so the same seed reprodu
 bit-for-bit, which the stored per-parameter fingerprints (sum, sum of squares, first 4 values) verify -- plus inputs,
 outputs, the loss, fingerprints of every parameter gradient and a few small gradients in full.
 """
+import copy
 import os
 import sys
 
@@ -74,6 +75,14 @@ def main():
             out["gfp/" + k] = fingerprint(p.grad)
             if k in full:
                 out["grad/" + k] = npy(p.grad)
+        if tag == "resdeconv_r34":
+            # 16 residual blocks: float32 rounding alone moves a gradient's sum by ~3e-4 of its norm, and by a different amount on
+            # every CPU code path -- so the gradient fingerprints are also stored from a float64 run of the same instance
+            m64 = copy.deepcopy(m).double()
+            m64.zero_grad()
+            nn.L1Loss()(m64(x.double()), t.double()).backward()
+            for k, p in m64.named_parameters():
+                out["gfp64/" + k] = fingerprint(p.grad)
         np.savez(os.path.join(OUT, f"{tag}.npz"), **out)
         print(tag, tuple(y.shape), float(loss), len(names), "parameters")
 

@@ -10,6 +10,20 @@ from conftest import load_golden, sub, rel_err
 TOL = 2e-5   # fp32 accumulation-order noise only; the restatement calls the same ATen ops
 
 
+def _assert_grads(sd, ref, tol):
+    """Every stored gradient against the oracle's, relative L2 within ``tol`` -- except a gradient that is exactly zero in exact
+    arithmetic: a bias feeding straight into a normalisation of each channel on its own (InstanceNorm, or GroupNorm with one
+    channel per group) is removed by the mean subtraction, so both sides hold only rounding noise there (the reference's is ~1e-8
+    of the largest gradient) and comparing two noises would test a CPU's summation order.  Such a gradient -- the reference's
+    below 1e-6 of the largest gradient -- must be zero to that level here too."""
+    top = max(float(torch.as_tensor(v).double().norm()) for v in ref.values())
+    for k, v in ref.items():
+        if float(torch.as_tensor(v).double().norm()) <= 1e-6 * top:
+            assert float(sd[k].grad.double().norm()) <= 1e-6 * top, k
+        else:
+            assert rel_err(sd[k].grad, v) < tol, k
+
+
 def _req(sd):
     return {k: (v.clone().requires_grad_(True) if v.is_floating_point() and "running" not in k else v.clone())
             for k, v in sd.items()}
@@ -99,8 +113,7 @@ def test_nlayer_d_instance_norm():
     assert rel_err(y, g["y"]) < TOL
     assert abs(float(loss) - float(g["loss"])) < 1e-6
     assert rel_err(x.grad, g["dx"]) < 1e-4
-    for k, v in sub(g, "grad/").items():
-        assert rel_err(sd[k].grad, v) < 1e-4, k
+    _assert_grads(sd, sub(g, "grad/"), 1e-4)          # (the convolution biases in front of InstanceNorm have zero gradient)
     with torch.no_grad():
         assert rel_err(oracle.nlayer_d_forward(sd, x, False), g["y_eval"]) < TOL
     mine = oracle.nlayer_d_state(ic, ndf, nl, norm="instance")
@@ -245,11 +258,17 @@ def test_resdeconv(tag):
     loss.backward()
     assert rel_err(y, g["y"]) < TOL
     assert abs(float(loss) - float(g["loss"])) < 1e-5
-    for k in names:
-        ref = g["gfp/" + k]
-        mine = _fp(sd[k].grad)
-        assert abs(mine[0] - ref[0]) <= 2e-4 * max(1.0, np.sqrt(ref[1])), k
-        assert abs(mine[1] - ref[1]) <= 1e-3 * max(ref[1], 1e-12), k
+    if "gfp64/" + names[0] in g:
+        # deep configuration: float32 rounding alone moves a gradient's sum by up to ~3e-4 of its norm, differently on every CPU
+        # code path; the fingerprints are pinned in float64 instead, against the reference's float64 run, far more tightly
+        sd64 = {k: p.detach().double().requires_grad_(True) for k, p in holder.named_parameters()}
+        oracle.l1_loss(oracle.resdeconv_forward(sd64, torch.from_numpy(g["x"]).double()), torch.from_numpy(g["t"]).double()).backward()
+        fps = {k: (_fp(sd64[k].grad), g["gfp64/" + k], 1e-8) for k in names}
+    else:
+        fps = {k: (_fp(sd[k].grad), g["gfp/" + k], 2e-4) for k in names}
+    for k, (mine, ref, tol) in fps.items():
+        assert abs(mine[0] - ref[0]) <= tol * max(1.0, np.sqrt(ref[1])), k
+        assert abs(mine[1] - ref[1]) <= 5 * tol * max(ref[1], 1e-12), k
     for k, v in sub(g, "grad/").items():
         assert rel_err(sd[k].grad, v) < 1e-4, k
 
@@ -270,8 +289,7 @@ def test_small_sr_models(tag):
     loss.backward()
     assert rel_err(y, g["y"]) < TOL
     assert abs(float(loss) - float(g["loss"])) < 1e-6
-    for k, v in sub(g, "grad/").items():
-        assert rel_err(sd[k].grad, v) < TOL, k
+    _assert_grads(sd, sub(g, "grad/"), TOL)           # (EDSR: the residual convolutions' biases in front of GroupNorm(32) on 32 channels)
     torch.manual_seed(0)
     net = srcgan_amd.EDSR(*cfg) if tag.startswith("edsr") else (srcgan_amd.SRCNN if tag == "srcnn" else srcgan_amd.ESPCN)(ic, oc, up)
     assert list(net.state_dict().keys()) == list(ref.keys())
