@@ -394,6 +394,18 @@ int srcgan_metric_scratch_floats(int B, int C, int H, int W);
 int srcgan_metric_ae(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* scratch, void* stream);
 int srcgan_metric_ssim(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* scratch, void* stream);
 
+/* DSSIM training loss (losses.py:170-180): (1 - SSIM(pred, truth)) / 2 with the metric's SSIM (11x11 gaussian sigma 1.5 "valid"
+ * depth-wise windows, dynamic range L from the prediction's min / max).  pred / truth: [B,C,H,W] f32 NCHW, contiguous; H, W >= 11.
+ *   srcgan_dssim_loss_fwd: out[0] = the loss (a device scalar); range[0..1] = min / max of pred, which backward reads (device, 2 floats);
+ *                          scratch: srcgan_metric_scratch_floats(B, C, H, W) floats.
+ *   srcgan_dssim_loss_bwd: dpred = gout[0] * dloss/dpred, dtruth = gout[0] * dloss/dtruth ([B,C,H,W] f32, overwritten); gout is a device
+ *                          scalar, range the buffer the forward wrote for the same inputs.  dtruth may be NULL (no target gradient).
+ *                          One fused pass per 32x32 output tile; deterministic (every element written once, no atomics). */
+int srcgan_dssim_loss_fwd(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* range,
+                          float* scratch, void* stream);
+int srcgan_dssim_loss_bwd(const float* pred, const float* truth, int B, int C, int H, int W, const float* range,
+                          const float* gout, float* dpred, float* dtruth, void* stream);
+
 /* Space-to-depth forms of an image-channel tensor for a 4x4 stride-2 pad-1 first layer (NLayerDiscriminator, model/model.py:612):
  * block (j,i) of the (H/2+1) x (W/2+1) grid = the 2x2 pixels (2j-1+dy, 2i-1+dx) as a 32-channel record [dy][dx][8], zero
  * outside the image / past C; the layer becomes a 2x2 stride-1 convolution with K = 4 x 32 and no padded K.
