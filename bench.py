@@ -14,6 +14,11 @@ on one synthetic batch resident in HBM:
 starts N fresh rank processes (one per GPU, RCCL over xGMI, rendezvous on 127.0.0.1) before anything touches a GPU, relays rank
 0's JSON line and exits non-zero if a rank fails.  Under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (WORLD_SIZE set) it is a rank.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, `--dump-outputs` if given, print the line
+(`roofline` and `cpu_baseline` null, `kernels` empty).  `--full` adds what takes runs of its own: one extra step with every
+convolution launch bracketed by HIP events (`roofline`, `kernels`; off with `--no-kernel-profile`) and, on one GPU, the timed CPU
+oracle baseline (`cpu_baseline`; off with `--no-cpu-baseline`).  The timed steps and the headline figures are the same either way.
 """
 import argparse
 import json
@@ -381,13 +386,17 @@ def main():
     ap.add_argument("--micro-batch", type=int, default=None, help="x8: images per gradient-accumulation slice (default 16)")
     ap.add_argument("--loss-scale", type=float, default=None, help="x8: loss scale (default 1024 for fp16, 1 otherwise)")
     ap.add_argument("--init-scale", type=float, default=None, help="x8: factor on the trunk convolutions' initial weights (default 0.1 for fp16, 1 otherwise)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel profile step and (one GPU) the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-kernel-profile", action="store_true", help="with --full: skip the per-kernel profile step")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last one computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    kernel_profile = args.full and not args.no_kernel_profile
+    cpu_base = args.full and not args.no_cpu_baseline
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # ranks start in ROOT: hand them the directory as an absolute path (the last occurrence of an option wins)
         return launch_ranks(args.gpus, ["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
@@ -452,11 +461,11 @@ def main():
     if args.dump_outputs and rank == 0:          # before the profiled step below changes the state
         dump_outputs(args.config, harness, args.dump_outputs)
 
-    # ---- per-kernel roofline: one extra step with HIP events around every conv launch (launch stream)
+    # ---- per-kernel roofline (--full): one extra step with HIP events around every conv launch (launch stream)
     roofline, kernels = None, []
     # EVERY rank runs the extra step (it contains the gradient collectives: a rank-0-only step would leave rank 0's
     # all-reduces without partners); only rank 0 brackets its launches with events.
-    if not args.no_kernel_profile:
+    if kernel_profile:
         if rank == 0:
             N.prof_enable(True)
         step()
@@ -493,7 +502,7 @@ def main():
                        "gradient_exchange": (f"{dinfo['backend']} all-reduce over {dinfo['world_size']} rank(s) of flat f32 gradient arenas, in place: networks that run "
                                              "once per step inside their native backward (generator: 4 RRDB-range phases on a side stream, overlapped); "
                                              "networks that run several times per step once, accumulated, in front of optimizer.step()") if use_dist else "none (1 rank)"},
-            "dist": None if not use_dist else {**dinfo, "grad_sync": dict(gsync.stats), "steps_counted": args.warmup + args.steps + (0 if args.no_kernel_profile else 1),
+            "dist": None if not use_dist else {**dinfo, "grad_sync": dict(gsync.stats), "steps_counted": args.warmup + args.steps + (1 if kernel_profile else 0),
                                                 "param_bytes": sum(p.numel() * 4 for net in nets for p in net.parameters())},
             "algorithmic_tflop_per_image": 2 * per_img_mac / 1e12,
             "step_tflops": 2 * per_img_mac * imgs / elapsed / 1e12,
@@ -503,7 +512,7 @@ def main():
             "kernels": [{"kernel": k["cls"], "launches": k["count"], "ms": round(k["ms"], 3),
                          "tflops": round(k["flops"] / (k["ms"] * 1e-3) / 1e12, 1)} for k in kernels[:10]],
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             out["cpu_baseline"] = cpu_baseline(args.config, args.nb, args.lr_size, 4 if args.config == "x8" else args.up, host_cores())
         else:
             out["cpu_baseline"] = None

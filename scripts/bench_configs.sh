@@ -7,7 +7,7 @@ OUT=${GRAFT_REPO_ROOT:-$(pwd)}/gpurun_out
 mkdir -p $OUT
 for c in $CFGS; do
   echo "== $c"
-  timeout -k 10 900 python bench.py --config $c --steps 4 --warmup 2 > $OUT/bench_${c}_$R.json 2> $OUT/bench_${c}_$R.err || { echo "FAILED $c"; tail -5 $OUT/bench_${c}_$R.err; }
+  timeout -k 10 900 python bench.py --config $c --steps 4 --warmup 2 --full > $OUT/bench_${c}_$R.json 2> $OUT/bench_${c}_$R.err || { echo "FAILED $c"; tail -5 $OUT/bench_${c}_$R.err; }
   python - <<PY
 import json
 try:

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile: run on the GPU box through gpurun from the repo root.
-#   1. bench.py (default arguments) -> gpurun_out/bench_rNN.json
+#   1. bench.py --full (roofline and CPU baseline included) -> $OUT/bench_rNN.json
 #   2. rocprofv3 --kernel-trace --stats of the same bench command (CPU baseline leg skipped: identical GPU work)
 #   3. HBM traffic of the same command: FETCH_SIZE and WRITE_SIZE in two separate --pmc passes
 #      (MI355X_MICROARCH.md: they do not fit one pass; no trace domains combined with --pmc)
@@ -22,10 +22,10 @@ cd $ROOT
 ( while true; do sleep 60; echo "[profile_round] $R: still running $(date +%T)"; done ) &
 HB=$!
 trap "kill $HB 2>/dev/null" EXIT
-echo "[profile_round] $R: bench"; timeout -k 10 900 python bench.py $ARGS $BASE > $OUT/bench_$R.json 2> $OUT/bench_$R.err
+echo "[profile_round] $R: bench"; timeout -k 10 900 python bench.py --full $ARGS $BASE > $OUT/bench_$R.json 2> $OUT/bench_$R.err
 cd /tmp && export TMPDIR=/tmp
 echo "[profile_round] $R: kernel trace"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$R -- python $ROOT/bench.py --no-cpu-baseline $ARGS > $OUT/prof_$R.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$R -- python $ROOT/bench.py --full --no-cpu-baseline $ARGS > $OUT/prof_$R.log 2>&1
 echo "[profile_round] $R: FETCH_SIZE pass"
 timeout -k 10 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$R -- python $ROOT/bench.py --no-cpu-baseline --no-kernel-profile $ARGS --steps 2 --warmup 1 > $OUT/pmc_fetch_$R.log 2>&1
 echo "[profile_round] $R: WRITE_SIZE pass"

@@ -91,7 +91,7 @@ print("ok")
 
 def test_bench_two_ranks_on_one_device_over_gloo():
     """bench.py's whole control flow with world_size 2 (torch.distributed.run, 127.0.0.1): broadcast, the generator reduce under
-    the discriminator step, barriers, MAX of the timing, the instrumented extra step on every rank, one JSON line from rank 0.
+    the discriminator step, barriers, MAX of the timing, the instrumented extra step of --full on every rank, one JSON line from rank 0.
     Both ranks share the box's one GPU and talk over gloo (rehearsal hooks in srcgan_amd/dist.py); RCCL itself is covered with
     one rank above."""
     env = dict(os.environ)
@@ -100,7 +100,7 @@ def test_bench_two_ranks_on_one_device_over_gloo():
         env.pop(k, None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "2", "--nb", "1", "--lr-size", "64"],
+                          "--batch", "2", "--nb", "1", "--lr-size", "64", "--full"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
