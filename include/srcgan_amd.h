@@ -301,7 +301,7 @@ typedef struct srcgan_net_opts {
  * elements each; nblocks = their total.  out_u64: one device word (zeroed and accumulated on `stream`). */
 int srcgan_params_fingerprint(const void* table_dev, int ntensors, long nblocks, void* out_u64, void* stream);
 int srcgan_rddbnet_num_params(const srcgan_rddbnet_cfg* c);
-size_t srcgan_rddbnet_ws_bytes(const srcgan_rddbnet_cfg* c);        /* forward workspace (kept for backward) */
+size_t srcgan_rddbnet_ws_bytes(const srcgan_rddbnet_cfg* c);        /* training-forward workspace (kept for backward; grows with nb) */
 size_t srcgan_rddbnet_bwd_scratch_bytes(const srcgan_rddbnet_cfg* c);
 int srcgan_rddbnet_forward(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,
                            void* ws, float* y_nchw, void* stream);
@@ -313,6 +313,18 @@ int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const float* x_nchw, 
                               void* ws, float* y_nchw, const srcgan_net_opts* opt, void* stream);
 int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const float* dy_nchw, const float* const* params,
                                void* ws, void* scratch, float* const* grads, float* dx_nchw, const srcgan_net_opts* opt, void* stream);
+/* Inference forward (no backward can follow).  Same cfg, parameter order and packed-weight handling (opt->wpack / pack / guard;
+ * the pack buffer of srcgan_rddbnet_wpack_bytes serves both) as srcgan_rddbnet_forward_ex, and the same launches, so the output is
+ * bit-identical to it; only the workspace differs.  Its activation part (srcgan_rddbnet_infer_ws_bytes minus
+ * srcgan_rddbnet_wpack_bytes) does not depend on nb: the trunk runs on THREE dense buffers in rotation (RDB r+1 takes the buffer
+ * that is neither RDB r's nor its RRDB's input buffer) plus an nf-channel copy of the first trunk input for the global skip;
+ * tensors at any other resolution (up-sampler stages, legacy tails, RDDBNetA's down stages) ping-pong between two buffers; no
+ * LeakyReLU sign mask is written.  Serves every cfg srcgan_rddbnet_ws_bytes accepts (0 + srcgan_last_error otherwise).
+ * flags: must be 0 or 1.  Bit 0 ("keep the unfused HR tail") is accepted and changes nothing: a fused tail kernel was built,
+ * measured slower than the launches it replaces and not kept, so the tail is always unfused. */
+size_t srcgan_rddbnet_infer_ws_bytes(const srcgan_rddbnet_cfg* c);
+int srcgan_rddbnet_infer(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params, void* ws,
+                         float* y_nchw, const srcgan_net_opts* opt, int flags, void* stream);
 
 /* NLayerDiscriminator (model/model.py:595-639).  params in state_dict order of the
  * learnable tensors: conv0.w, conv0.b, [conv_l.w, bn_l.gamma, bn_l.beta]*, conv_last.w, conv_last.b.

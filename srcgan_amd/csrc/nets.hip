@@ -320,6 +320,92 @@ extern "C" size_t srcgan_rddbnet_bwd_scratch_bytes(const srcgan_rddbnet_cfg* c) 
 
 extern "C" size_t srcgan_rddbnet_wpack_bytes(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return 0; return P.total - P.wpk; }
 
+// ---- where the forward's activations live.  The launch sequence of a generator is ONE walker (rddb_forward_walk) over a
+// buffer-naming policy: the training policy keeps every tensor a backward reads (one dense buffer per ResidualDenseBlock_5, the
+// LeakyReLU sign masks, every up-sampler stage), the inference policy keeps only what a later launch of the same pass reads.
+namespace {
+struct RddbNames {
+    size_t xin, fea0, dn[5], T, U[6], out, tail[16], wpk, total;
+    std::vector<size_t> A;      // dense buffer of RDB r
+    size_t home;                // inference: nf-channel copy (whole leading planes) of the trunk input, which the rotation overwrites
+    bool rolling;               // inference policy
+    long bm_bytes, um_bytes;    // sign masks (0 = not written)
+    size_t bm, um;
+};
+
+static void rddb_train_names(const RddbPlan& P, RddbNames& N) {
+    N.xin = P.xin; N.fea0 = P.fea0; N.T = P.T; N.out = P.out; N.wpk = P.wpk; N.total = P.total;
+    for (int s = 0; s < 5; ++s) N.dn[s] = P.dn[s];
+    for (int s = 0; s < 6; ++s) N.U[s] = P.U[s];
+    for (int k = 0; k < 16; ++k) N.tail[k] = k < P.ntail ? P.tail[k].out : 0;
+    const int nbuf = P.legacy == 2 ? 1 : 3 * P.nrr;
+    N.A.resize(nbuf);
+    for (int r = 0; r < nbuf; ++r) N.A[r] = P.A + (size_t)r * P.szA;
+    N.home = 0; N.rolling = false;
+    N.bm = P.bm; N.bm_bytes = P.bm_bytes; N.um = P.um; N.um_bytes = P.um_bytes;
+}
+
+// Inference: the workspace does not grow with nb.  THREE dense buffers rotate: RDB r reads its own buffer and writes channels
+// [0,nf) of the next one, and RDB 3i+2 also reads the RRDB input (buffer of RDB 3i), so the buffer of RDB r+1 is the one that
+// is neither RDB r's nor RDB 3i's -- for r = 3i+2 that is the buffer of RDB 3i+1, dead by then.  The network's first trunk
+// input (trunk_conv's skip; SRDN: the two stack skips, one after the other) is copied to `home`.  Everything at a resolution
+// other than the trunk's ping-pongs between two buffers; no sign mask is written.
+static void rddb_infer_names(const srcgan_rddbnet_cfg* c, const RddbPlan& P, RddbNames& N) {
+    const size_t e = P.esz, B = c->B, nf = c->nf;
+    Bump b;
+    N.rolling = true; N.bm = N.um = 0; N.bm_bytes = N.um_bytes = 0;
+    for (int k = 0; k < 16; ++k) N.tail[k] = 0;
+    N.xin = b.take(B * c->H * c->W * P.in_cs * e);
+    N.fea0 = 0;
+    for (int s = 0; s < 5; ++s) N.dn[s] = 0;
+    if (P.ndn) {     // HR->LR stages: conv_first's output and the stage outputs alternate; the last stage writes the trunk input
+        const size_t pp0 = b.take(B * c->H * c->W * nf * e);
+        const size_t pp1 = P.ndn > 1 ? b.take(B * (c->H >> 1) * (c->W >> 1) * nf * e) : 0;
+        N.fea0 = pp0;
+        for (int s = 0; s < P.ndn; ++s) N.dn[s] = (s & 1) ? pp0 : pp1;
+    }
+    const size_t szA = align_up((size_t)P.nplane * P.plane_bytes, 256);
+    const int nbuf = P.legacy == 2 ? 1 : 3 * P.nrr;
+    size_t slot[3] = {0, 0, 0};
+    for (int k = 0; k < (P.legacy == 2 ? 1 : 3); ++k) slot[k] = b.take(szA);
+    N.A.resize(nbuf);
+    int cur = 0, rrdb_in = 0;
+    for (int r = 0; r < nbuf; ++r) {
+        if (r % 3 == 0) rrdb_in = cur;
+        N.A[r] = slot[cur];
+        int nxt = 0;
+        while (nxt == cur || nxt == rrdb_in) ++nxt;
+        cur = nxt;
+    }
+    N.home = P.nrr ? b.take((size_t)((nf + P.kce - 1) / P.kce) * P.plane_bytes) : 0;
+    N.T = P.legacy == 2 ? 0 : b.take(B * P.Ht * P.Wt * nf * e);       // legacy RDDBNet has no trunk output
+    for (int s = 0; s < 6; ++s) N.U[s] = 0;
+    if (P.legacy == 1 || P.legacy == 2) {
+        N.U[0] = b.take(B * P.Ht * P.Wt * nf * e);
+        size_t pp[2];
+        for (int k = 0; k < 2; ++k) pp[k] = b.take(B * P.HO * P.WO * nf * e);
+        for (int k = 0; k < P.ntail; ++k) N.tail[k] = pp[k & 1];
+    } else if (P.legacy == 3) {
+        N.U[0] = N.T;
+    } else {        // stage s has 4^s times the trunk's pixels: even stages share one buffer, odd stages the other
+        size_t pp[2] = {0, 0};
+        for (int k = 0; k < 2 && k <= P.nst; ++k) {
+            const int top = ((P.nst - k) & ~1) + k;        // largest stage <= nst with the parity of k
+            pp[k] = b.take(B * (P.Ht << top) * (P.Wt << top) * nf * e);
+        }
+        for (int s = 0; s <= P.nst; ++s) N.U[s] = pp[s & 1];
+    }
+    N.out = b.take(B * P.HO * P.WO * P.out_cs * e);
+    N.wpk = b.off;
+    N.total = N.wpk + (P.total - P.wpk);       // the packed-weight region of the training plan, as is
+}
+}  // namespace
+
+extern "C" size_t srcgan_rddbnet_infer_ws_bytes(const srcgan_rddbnet_cfg* c) {
+    RddbPlan P; if (rddb_plan(c, P)) return 0;
+    RddbNames N; rddb_infer_names(c, P, N); return N.total;
+}
+
 // the four parity packs of up-sampler stage s are equally spaced: the stage runs as ONE launch (conv_igemm.hip, npar), which is also
 // the form that writes the LeakyReLU sign mask of the last stage's output
 static inline bool up_packs_spaced(const RddbPlan& P, int s) {
@@ -328,20 +414,22 @@ static inline bool up_packs_spaced(const RddbPlan& P, int s) {
 }
 static inline bool up_mask_written(const RddbPlan& P) { return P.um_bytes && P.nst > 0 && up_packs_spaced(P, P.nst - 1); }
 
-extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,
-                                         void* ws, float* y_nchw, const srcgan_net_opts* opt, void* st) {
-    RddbPlan P;
-    SG_TRY(rddb_plan(c, P));
+static int rddb_forward_walk(const srcgan_rddbnet_cfg* c, const RddbPlan& P, const RddbNames& N, const float* x_nchw,
+                             const float* const* params, void* ws, float* y_nchw, const srcgan_net_opts* opt, void* st) {
     SG_REQUIRE(x_nchw && params && ws && y_nchw, "srcgan_rddbnet_forward: null pointer");
     SG_REQUIRE(((uintptr_t)ws % 256) == 0, "srcgan_rddbnet_forward: workspace must be 256-byte aligned");
     const int dt = c->dtype, nf = c->nf, gc = c->gc, B = c->B;
     char* w8 = (char*)ws;
     // packed weights: a persistent buffer of the caller's (packed once per optimiser step) or a region of this call's workspace
-    char* wp = (opt && opt->wpack) ? (char*)opt->wpack : w8 + P.wpk;
+    char* wp = (opt && opt->wpack) ? (char*)opt->wpack : w8 + N.wpk;
     SG_REQUIRE(((uintptr_t)wp % 256) == 0, "srcgan_rddbnet_forward: wpack must be 256-byte aligned");
     const bool do_pack = !(opt && opt->wpack) || opt->pack;
     auto T_ = [&](size_t off, int cs) { return tref(w8 + off, cs); };
-    auto Abuf = [&](int r) { return tref(w8 + P.A + (size_t)r * P.szA, P.kce, 0, P.plane_bytes); };
+    auto Abuf = [&](int r) { return tref(w8 + N.A[r], P.kce, 0, P.plane_bytes); };
+    // inference: copy the nf leading channels of a dense buffer (whole planes of the blocked layout: one contiguous copy) to `home`
+    auto to_home = [&](TRef a) {
+        return hipMemcpyAsync(w8 + N.home, a.p, (size_t)((nf + P.kce - 1) / P.kce) * P.plane_bytes, hipMemcpyDeviceToDevice, (hipStream_t)st);
+    };
 
     // ---- pack weights for this call (f32 canonical -> dtype, MFMA-friendly): ONE batched launch
     PackList packs(dt, wp);
@@ -365,21 +453,22 @@ extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const floa
     if (do_pack) SG_TRY(packs.run(P.legacy == 1 ? "rddbB_fwd" : P.legacy == 2 ? "rddbL_fwd" : P.legacy == 3 ? "srdn_fwd" : "rddb_fwd", params[0], st, pack_guard(opt)));
 
     // ---- input: NCHW f32 -> NHWC (channels zero-padded to 8)
-    SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, c->in_ch, c->H, c->W, P.in_cs, dt, st));
+    SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + N.xin, B, c->in_ch, c->H, c->W, P.in_cs, dt, st));
     // conv_first (rddb.py:89,108).  The trunk input lives in channels [0,nf) of the first dense buffer so the
     // first RDB reads it in place and the global skip (rddb.py:110) reads it back later.
     const int H = P.Ht, W = P.Wt;
     TRef trunk_in = Abuf(0);
-    TRef fea = P.ndn ? T_(P.fea0, nf) : trunk_in;
-    SG_TRY(Conv(dt, 3, 3, 1).in(T_(P.xin, P.in_cs), B, c->H, c->W, P.in_cs).w(wp + P.w_first_f, params[P.p_first_b])
+    TRef fea = P.ndn ? T_(N.fea0, nf) : trunk_in;
+    SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.xin, P.in_cs), B, c->H, c->W, P.in_cs).w(wp + P.w_first_f, params[P.p_first_b])
                .out(fea, c->H, c->W, nf).pad(1, 1).run(st));
     // optional HR->LR stages (build-defined RDDBNetA): 3x3 s2 p1 + bias + LeakyReLU
     for (int s = 0; s < P.ndn; ++s) {
-        TRef o = (s == P.ndn - 1) ? trunk_in : T_(P.dn[s], nf);
+        TRef o = (s == P.ndn - 1) ? trunk_in : T_(N.dn[s], nf);
         SG_TRY(Conv(dt, 3, 3, 2).in(fea, B, c->H >> s, c->W >> s, nf).w(wp + P.w_dn_f[s], params[P.p_dn0 + 2 * s + 1])
                    .out(o, c->H >> (s + 1), c->W >> (s + 1), nf).pad(1, 1).lrelu().run(st));
         fea = o;
     }
+    if (N.rolling && P.nrr) { SG_HIP(to_home(trunk_in)); trunk_in = tref(w8 + N.home, P.kce, 0, P.plane_bytes); }
     // RRDB trunk (rddb.py:62-68,78-82).  The legacy RDDBNet computes it and throws it away (model.py:382-383): skipped.
     for (int i = 0; i < P.nrr; ++i) {
         for (int j = 0; j < 3; ++j) {
@@ -389,12 +478,12 @@ extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const floa
                 const int cin = nf + k * gc;
                 Conv cv(dt, 3, 3, 1);
                 cv.in(A, B, H, W, cin).w(wp + P.w_rdb_f[r * 5 + k], params[P.prdb(r) + k * 2 + 1]).out(sl(A, cin), H, W, gc).pad(1, 1).lrelu();
-                if (P.bm_bytes) cv.sign_out((char*)A.p + P.bm + (size_t)k * P.bm_bytes);
+                if (N.bm_bytes) cv.sign_out((char*)A.p + N.bm + (size_t)k * N.bm_bytes);
                 SG_TRY(cv.run(st));
             }
             // conv5 + residual(s) -> channels [0,nf) of the next dense buffer (or the trunk output)
             const bool last = (r == P.nrr * 3 - 1);
-            TRef dst = last ? T_(P.T, nf) : Abuf(r + 1);
+            TRef dst = last ? T_(N.T, nf) : Abuf(r + 1);
             Conv cv(dt, 3, 3, 1);
             cv.in(A, B, H, W, P.C).w(wp + P.w_rdb_f[r * 5 + 4], params[P.prdb(r) + 4 * 2 + 1]).out(dst, H, W, nf).pad(1, 1);
             if (j < 2) cv.alpha(0.2f).res1(A, nf, 1.f);
@@ -405,22 +494,23 @@ extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const floa
             TRef d0 = Abuf((i + 1) * 3);
             SG_TRY(srcgan_add_inplace_planes(d0.p, d0.cs, 0, d0.plane, trunk_in.p, trunk_in.cs, 0, trunk_in.plane, nullptr, 0, 0, 0, 0.f,
                                              (long)B * H * W, nf, dt, st));
+            if (N.rolling) SG_HIP(to_home(d0));       // the decoder's input takes the encoder input's place
         }
     }
     if (P.legacy == 3) {       // fea = fea + RRDB_decoder(fea) (srdn.py:72-73): T += fea1, then conv_last reads T (= U[0])
-        TRef f1 = Abuf(c->nb * 3), Tt = T_(P.T, nf);
+        TRef f1 = N.rolling ? trunk_in : Abuf(c->nb * 3), Tt = T_(N.T, nf);
         SG_TRY(srcgan_add_inplace_planes(Tt.p, Tt.cs, 0, 0, f1.p, f1.cs, 0, f1.plane, nullptr, 0, 0, 0, 0.f, (long)B * H * W, nf, dt, st));
     }
     // trunk_conv + global skip (rddb.py:109-110)
     if (P.legacy != 2 && P.legacy != 3)
-        SG_TRY(Conv(dt, 3, 3, 1).in(T_(P.T, nf), B, H, W, nf).w(wp + P.w_trunk_f, params[P.p_trunk_b]).out(T_(P.U[0], nf), H, W, nf)
+        SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.T, nf), B, H, W, nf).w(wp + P.w_trunk_f, params[P.p_trunk_b]).out(T_(N.U[0], nf), H, W, nf)
                    .pad(1, 1).res1(trunk_in, nf, 1.f).run(st));
     if (P.legacy == 1 || P.legacy == 2) {
         // legacy tail (model.py:384-390, 427-439): [nearest x2 -> 3x3 conv -> LeakyReLU] stages, HRconv applied repeatedly
-        TRef cur = P.legacy == 2 ? trunk_in : T_(P.U[0], nf);
+        TRef cur = P.legacy == 2 ? trunk_in : T_(N.U[0], nf);
         for (int k = 0; k < P.ntail; ++k) {
             const RddbPlan::TailOp& o = P.tail[k];
-            TRef dst = T_(o.out, nf);
+            TRef dst = T_(N.tail[k], nf);
             if (o.conv)
                 SG_TRY(Conv(dt, 3, 3, 1).in(cur, B, o.hin, o.win, nf).w(wp + P.lw_f[o.w], params[P.p_lg[o.w] + 1]).out(dst, o.hout, o.wout, nf)
                            .pad(1, 1).lrelu().run(st));
@@ -428,10 +518,10 @@ extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const floa
                 SG_TRY(srcgan_upsample2_nhwc(cur.p, cur.cs, cur.coff, cur.plane, dst.p, dst.cs, B, o.hin, o.win, nf, dt, st));
             cur = dst;
         }
-        SG_HIP(hipMemsetAsync(w8 + P.out, 0, (size_t)B * P.HO * P.WO * P.out_cs * P.esz, (hipStream_t)st));
-        SG_TRY(Conv(dt, 3, 3, 1).in(cur, B, P.HO, P.WO, nf).w(wp + P.w_last_f, params[P.p_last_b]).out(T_(P.out, P.out_cs), P.HO, P.WO, c->out_ch)
+        SG_HIP(hipMemsetAsync(w8 + N.out, 0, (size_t)B * P.HO * P.WO * P.out_cs * P.esz, (hipStream_t)st));
+        SG_TRY(Conv(dt, 3, 3, 1).in(cur, B, P.HO, P.WO, nf).w(wp + P.w_last_f, params[P.p_last_b]).out(T_(N.out, P.out_cs), P.HO, P.WO, c->out_ch)
                    .pad(1, 1).run(st));
-        SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + P.out, y_nchw, B, c->out_ch, P.HO, P.WO, P.out_cs, 0, dt, st));
+        SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + N.out, y_nchw, B, c->out_ch, P.HO, P.WO, P.out_cs, 0, dt, st));
         return 0;
     }
     // up-sampler: ConvTranspose2d(k2,s2) + LeakyReLU == 4 x (1x1 conv -> stride-2 scatter) (rddb.py:93-97,111-112)
@@ -441,23 +531,44 @@ extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const floa
         if (up_packs_spaced(P, s)) {
             // all four output parities in one launch (the input is read from HBM once: conv_igemm.hip, npar)
             Conv cv(dt, 1, 1, 1);
-            cv.in(T_(P.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][0]).out(T_(P.U[s + 1], nf), h, w, nf).scatter(2, 0, 0, 2 * h, 2 * w).lrelu();
+            cv.in(T_(N.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][0]).out(T_(N.U[s + 1], nf), h, w, nf).scatter(2, 0, 0, 2 * h, 2 * w).lrelu();
             cv.d.npar = 4; cv.d.wpar_stride = wstep;
-            if (P.um_bytes && s == P.nst - 1) cv.sign_out(w8 + P.um);       // LeakyReLU sign of the tensor conv_last reads
+            if (N.um_bytes && s == P.nst - 1) cv.sign_out(w8 + N.um);       // LeakyReLU sign of the tensor conv_last reads
             SG_TRY(cv.run(st));
         } else
         for (int q = 0; q < 4; ++q)
-            SG_TRY(Conv(dt, 1, 1, 1).in(T_(P.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][q]).out(T_(P.U[s + 1], nf), h, w, nf)
+            SG_TRY(Conv(dt, 1, 1, 1).in(T_(N.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][q]).out(T_(N.U[s + 1], nf), h, w, nf)
                        .scatter(2, q >> 1, q & 1, 2 * h, 2 * w).lrelu().run(st));
     }
     // conv_last (no bias, rddb.py:98,113) as a convolution to all out_cs = 8 padded channels: the packed weight rows beyond out_ch
     // are zero, so channels out_ch.. come out as the zeros the padding wants -- and the output is 16 bytes per pixel through the
     // vectorised epilogue (with Cout = 3 it took the per-element form: three 2-byte stores per pixel of a 1024x1024 image, and a
     // 268 MB memset in front; 0.67 ms + 0.06 ms per step at the bench size)
-    SG_TRY(Conv(dt, 3, 3, 1).in(T_(P.U[P.nst], nf), B, P.HO, P.WO, nf).w(wp + P.w_last_f).out(T_(P.out, P.out_cs), P.HO, P.WO, P.out_cs)
+    SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.U[P.nst], nf), B, P.HO, P.WO, nf).w(wp + P.w_last_f).out(T_(N.out, P.out_cs), P.HO, P.WO, P.out_cs)
                .pad(1, 1).run(st));
-    SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + P.out, y_nchw, B, c->out_ch, P.HO, P.WO, P.out_cs, 0, dt, st));
+    SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + N.out, y_nchw, B, c->out_ch, P.HO, P.WO, P.out_cs, 0, dt, st));
     return 0;
+}
+
+extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,
+                                         void* ws, float* y_nchw, const srcgan_net_opts* opt, void* st) {
+    RddbPlan P;
+    SG_TRY(rddb_plan(c, P));
+    RddbNames N;
+    rddb_train_names(P, N);
+    return rddb_forward_walk(c, P, N, x_nchw, params, ws, y_nchw, opt, st);
+}
+
+// Inference forward: same launches, same kernels, same descriptors as srcgan_rddbnet_forward_ex apart from buffer addresses and
+// the sign masks, which are not written.  flags bit 0 (keep the unfused HR tail) is accepted: the tail is always unfused.
+extern "C" int srcgan_rddbnet_infer(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params, void* ws,
+                                    float* y_nchw, const srcgan_net_opts* opt, int flags, void* st) {
+    RddbPlan P;
+    SG_TRY(rddb_plan(c, P));
+    SG_REQUIRE((flags & ~1) == 0, "srcgan_rddbnet_infer: unknown flags 0x%x", flags);
+    RddbNames N;
+    rddb_infer_names(c, P, N);
+    return rddb_forward_walk(c, P, N, x_nchw, params, ws, y_nchw, opt, st);
 }
 
 extern "C" int srcgan_rddbnet_forward(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,

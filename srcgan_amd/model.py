@@ -149,37 +149,44 @@ class _GradArena:
             self.offsets.append(off)          # offsets[i] .. offsets[i + 1] = parameter i
 
 
+def _rddb_prepare(x, cfg_items, params):
+    """Checks and allocations both generator forwards (autograd Function, inference) share.
+    -> (x, None, None, pstate, layout, empty output) for an empty batch, else (x, cfg, plist, pstate, layout, y)."""
+    N.require_cuda(x, "RDDBNet.forward")
+    in_ch, out_ch, up, nf, nb, gc, dtype, down = cfg_items[:8]
+    legacy = cfg_items[8] if len(cfg_items) > 8 else 0
+    pstate = cfg_items[9] if len(cfg_items) > 9 else None
+    if x.dim() != 4 or x.shape[1] != in_ch:
+        raise ValueError(f"RDDBNet expects [B,{in_ch},H,W], got {tuple(x.shape)}")
+    x = x.detach().contiguous().float()
+    B, _, H, W = x.shape
+    f = (up if down == 0 else 1)
+    HO, WO = (H * f, W * f) if down <= 1 else (H // down, W // down)
+    layout = (in_ch, out_ch, up, nf, nb, gc, dtype, down, legacy)
+    if B == 0:          # an empty batch yields an empty output and zero gradients, as aten::convolution does
+        return x, None, None, pstate, layout, x.new_zeros((0, out_ch, HO, WO))
+    cfg = N.RddbCfg(in_ch, out_ch, up, nf, nb, gc, B, H, W, dtype, down, legacy)
+    for p in params:
+        N.require_cuda(p, "RDDBNet parameter")
+    plist = [p.detach().contiguous() for p in params]
+    if any(p.dtype != torch.float32 for p in plist):
+        raise TypeError("RDDBNet parameters must be float32 (canonical weights stay f32)")
+    y = torch.empty(B, out_ch, HO, WO, dtype=torch.float32, device=x.device)
+    return x, cfg, plist, pstate, layout, y
+
+
 class _RddbFn(torch.autograd.Function):
     """One native forward / one native backward for the whole generator."""
 
     @staticmethod
     def forward(ctx, x, cfg_items, *params):
-        N.require_cuda(x, "RDDBNet.forward")
         lib = N.lib()
-        in_ch, out_ch, up, nf, nb, gc, dtype, down = cfg_items[:8]
-        legacy = cfg_items[8] if len(cfg_items) > 8 else 0
-        pstate = cfg_items[9] if len(cfg_items) > 9 else None
-        if x.dim() != 4 or x.shape[1] != in_ch:
-            raise ValueError(f"RDDBNet expects [B,{in_ch},H,W], got {tuple(x.shape)}")
-        x = x.detach().contiguous().float()
-        B, _, H, W = x.shape
-        if B == 0:          # an empty batch yields an empty output and zero gradients, as aten::convolution does
-            f0 = (up if down == 0 else 1)
-            ctx.empty = True
+        x, cfg, plist, pstate, layout, y = _rddb_prepare(x, cfg_items, params)
+        ctx.empty = cfg is None
+        if ctx.empty:
             ctx.save_for_backward(*params)
-            return x.new_zeros((0, out_ch) + ((H * f0, W * f0) if down <= 1 else (H // down, W // down)))
-        ctx.empty = False
-        cfg = N.RddbCfg(in_ch, out_ch, up, nf, nb, gc, B, H, W, dtype, down, legacy)
-        for p in params:
-            N.require_cuda(p, "RDDBNet parameter")
-        plist = [p.detach().contiguous() for p in params]
-        if any(p.dtype != torch.float32 for p in plist):
-            raise TypeError("RDDBNet parameters must be float32 (canonical weights stay f32)")
+            return y
         ws = N.workspace(lib.srcgan_rddbnet_ws_bytes(C.byref(cfg)), x.device)
-        f = (up if down == 0 else 1)
-        HO, WO = (H * f, W * f) if down <= 1 else (H // down, W // down)
-        y = torch.empty(B, out_ch, HO, WO, dtype=torch.float32, device=x.device)
-        layout = (in_ch, out_ch, up, nf, nb, gc, dtype, down, legacy)
         opt = pstate.opts(lib.srcgan_rddbnet_wpack_bytes, cfg, plist, layout, False, x.device) if pstate is not None else None
         N.check(lib.srcgan_rddbnet_forward_ex(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(),
                                               C.byref(opt) if opt is not None else None, N.stream_ptr(x.device)), "srcgan_rddbnet_forward")
@@ -231,6 +238,30 @@ class _RddbFn(torch.autograd.Function):
         return (dx, None, *grads)
 
 
+def _rddb_infer(x, cfg_items, params):
+    """Forward under ``torch.no_grad()``: one native call on the depth-independent inference workspace (three rotating dense
+    buffers, no sign masks, no per-stage retention: ``srcgan_rddbnet_infer``), released on return.  Same kernels in the same order as
+    ``_RddbFn.forward``, hence the same bits."""
+    lib = N.lib()
+    x, cfg, plist, pstate, layout, y = _rddb_prepare(x, cfg_items, params)
+    if cfg is None:
+        return y
+    ws = N.workspace(lib.srcgan_rddbnet_infer_ws_bytes(C.byref(cfg)), x.device)
+    opt = pstate.opts(lib.srcgan_rddbnet_wpack_bytes, cfg, plist, layout, False, x.device) if pstate is not None else None
+    N.check(lib.srcgan_rddbnet_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(),
+                                     C.byref(opt) if opt is not None else None, 0, N.stream_ptr(x.device)), "srcgan_rddbnet_infer")
+    if pstate is not None:
+        pstate.done(False)
+    return y
+
+
+def _rddb_forward(x, cfg_items, params):
+    """Grad mode on: the autograd Function (workspace kept for backward), also when nothing requires grad.  Off: inference."""
+    if torch.is_grad_enabled():
+        return _RddbFn.apply(x, cfg_items, *params)
+    return _rddb_infer(x, cfg_items, params)
+
+
 # Data-parallel hooks (srcgan_amd.dist.GradSync.attach): an object with ``cuts(nrr) -> [rrdb indices]`` (phase boundaries of the
 # generator's backward) and ``phase_done(arena, params, cfg, lo, hi, nrr)``, called right after the native call that finalised the
 # gradients of RRDBs [lo, hi) (plus the tail when hi == nrr, the head when lo == 0) was queued: the hook launches their all-reduce
@@ -271,7 +302,7 @@ class RDDBNet(nn.Module):
     def forward(self, x):
         cfg = (*self._cfg, N.dtype_id(self.compute_dtype), self._down(), 0, self._pack)
         # parameters in state_dict order == the order the native planner assumes
-        return _RddbFn.apply(x, cfg, *self.parameters())
+        return _rddb_forward(x, cfg, list(self.parameters()))
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
@@ -299,7 +330,7 @@ class RDDBNetA(RDDBNet):
         # native order: conv_first, down_layers, trunk, trunk_conv, conv_last
         ps = [self.conv_first.weight, self.conv_first.bias, *self.down_layers.parameters(),
               *self.RRDB_trunk.parameters(), self.trunk_conv.weight, self.trunk_conv.bias, self.conv_last.weight]
-        return _RddbFn.apply(x, cfg, *ps)
+        return _rddb_forward(x, cfg, ps)
 
 
 class _LegacyRRDB(_HolderOnly):
@@ -349,7 +380,7 @@ class RDDBNetB(nn.Module):
         if self.mode == "x2":       # upconv2 is not on the x2 graph (model.py:430-432): its .grad stays None, as in the reference
             skip = {id(self.upconv2.weight), id(self.upconv2.bias)}
             ps = [p.detach() if id(p) in skip else p for p in ps]
-        return _RddbFn.apply(x, cfg, *ps)
+        return _rddb_forward(x, cfg, ps)
 
     def extra_repr(self):
         return f"native gfx950, mode={self.mode}, compute_dtype={self.compute_dtype}"
@@ -373,7 +404,7 @@ class LegacyRDDBNet(RDDBNetB):
         # the trunk is not on the graph: pass its parameters detached so autograd leaves their .grad at None
         trunk = {id(p) for p in self.RRDB_trunk.parameters()} | {id(self.trunk_conv.weight), id(self.trunk_conv.bias)}
         ps = [p.detach() if id(p) in trunk else p for p in self.parameters()]
-        return _RddbFn.apply(x, cfg, *ps)
+        return _rddb_forward(x, cfg, ps)
 
 
 # ------------------------------------------------------------------------------------------------ ResDeconv colouriser
@@ -657,7 +688,7 @@ class SRDN(nn.Module):
     def forward(self, x):
         cfg = (*self._cfg, N.dtype_id(self.compute_dtype), 0, 3)
         skip = {id(self.trunk_conv.weight), id(self.trunk_conv.bias)}
-        return _RddbFn.apply(x, cfg, *[p.detach() if id(p) in skip else p for p in self.parameters()])
+        return _rddb_forward(x, cfg, [p.detach() if id(p) in skip else p for p in self.parameters()])
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
