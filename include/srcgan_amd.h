@@ -320,11 +320,18 @@ int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const float* dy_nchw
  * that is neither RDB r's nor its RRDB's input buffer) plus an nf-channel copy of the first trunk input for the global skip;
  * tensors at any other resolution (up-sampler stages, legacy tails, RDDBNetA's down stages) ping-pong between two buffers; no
  * LeakyReLU sign mask is written.  Serves every cfg srcgan_rddbnet_ws_bytes accepts (0 + srcgan_last_error otherwise).
- * flags: must be 0 or 1.  Bit 0 ("keep the unfused HR tail") is accepted and changes nothing: a fused tail kernel was built,
- * measured slower than the launches it replaces and not kept, so the tail is always unfused. */
+ * The HR tail is always unfused: a fused tail kernel was built, measured slower than the launches it replaces and not kept
+ * (DESIGN section 8, row 5c). */
 size_t srcgan_rddbnet_infer_ws_bytes(const srcgan_rddbnet_cfg* c);
 int srcgan_rddbnet_infer(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params, void* ws,
-                         float* y_nchw, const srcgan_net_opts* opt, int flags, void* stream);
+                         float* y_nchw, const srcgan_net_opts* opt, void* stream);
+/* Parameter layout questions, answered by the planner that defines the layout.  num_rrdb: RRDBs in the trunk (SRDN: both stacks;
+ * legacy RDDBNet: 0), -1 on a bad cfg.  phase_params: the parameters [*first, *end) (state_dict order) whose gradients a backward
+ * call over the RRDBs [lo, hi) finalises (srcgan_net_opts.rrdb_lo/hi): hi == num_rrdb extends the range to the last parameter,
+ * lo == 0 to parameter 0, so gap-free descending phases tile [0, num_params) and a network without a trunk is one range.
+ * Non-zero + srcgan_last_error on a bad cfg or a range outside [0, num_rrdb]. */
+int srcgan_rddbnet_num_rrdb(const srcgan_rddbnet_cfg* c);
+int srcgan_rddbnet_phase_params(const srcgan_rddbnet_cfg* c, int lo, int hi, int* first, int* end);
 
 /* NLayerDiscriminator (model/model.py:595-639).  params in state_dict order of the
  * learnable tensors: conv0.w, conv0.b, [conv_l.w, bn_l.gamma, bn_l.beta]*, conv_last.w, conv_last.b.

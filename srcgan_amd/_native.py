@@ -179,7 +179,9 @@ SIGNATURES = {
     "srcgan_rddbnet_forward_ex": (_I, [C.POINTER(RddbCfg), _P, _P, _P, _P, C.POINTER(NetOpts), _P]),
     "srcgan_rddbnet_backward_ex": (_I, [C.POINTER(RddbCfg), _P, _P, _P, _P, _P, _P, C.POINTER(NetOpts), _P]),
     "srcgan_rddbnet_infer_ws_bytes": (_S, [C.POINTER(RddbCfg)]),
-    "srcgan_rddbnet_infer": (_I, [C.POINTER(RddbCfg), _P, _P, _P, _P, C.POINTER(NetOpts), _I, _P]),
+    "srcgan_rddbnet_infer": (_I, [C.POINTER(RddbCfg), _P, _P, _P, _P, C.POINTER(NetOpts), _P]),
+    "srcgan_rddbnet_num_rrdb": (_I, [C.POINTER(RddbCfg)]),
+    "srcgan_rddbnet_phase_params": (_I, [C.POINTER(RddbCfg), _I, _I, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "srcgan_nlayerd_wpack_bytes": (_S, [C.POINTER(NLayerDCfg)]),
     "srcgan_nlayerd_forward_ex": (_I, [C.POINTER(NLayerDCfg), _P, _P, _P, _P, _P, _P, C.POINTER(NetOpts), _P]),
     "srcgan_nlayerd_backward_ex": (_I, [C.POINTER(NLayerDCfg), _P, _P, _P, _P, _P, _P, C.POINTER(NetOpts), _P]),

@@ -145,30 +145,37 @@ static inline const unsigned long long* pack_guard(const srcgan_net_opts* o) {
 }
 
 // ======================================================================================== RDDBNet
+// The generator families: the values of srcgan_rddbnet_cfg.legacy (include/srcgan_amd.h describes each)
+enum RddbFamily { RDDB_PLAIN = 0, RDDB_NETB = 1, RDDB_LEGACY = 2, RDDB_SRDN = 3 };
+
+// What does not depend on where the activations live: validated geometry, the tail's op list, packed-weight offsets, parameter
+// indices.  Activation and mask offsets belong to the buffer-naming policy (RddbNames).
 struct RddbPlan {
     int dtype, esz, nf, gc, nb, C, nst, ndn, kce, nplane; long plane_bytes;
     int B, H, W;           // input
-    size_t bm; long bm_bytes;   // sign masks of a dense buffer's four LeakyReLU slices: offset inside the buffer, bytes per slice (0 = not used)
-    size_t um; long um_bytes;   // sign mask of the last up-sampler stage's output (8 bytes per HR pixel; 0 = not used): conv_last's input gradient
-                                // reads it instead of the 64-channel activation (2.1 GB at the bench size)
     int Ht, Wt;            // trunk resolution
     int HO, WO;            // output resolution
     int in_cs, out_cs;
     int nparams;
-    size_t xin, fea0, dn[5], A, szA, T, U[6], out, wpk, total;
+    // the family, and the facts about it the walkers branch on
+    RddbFamily family;
+    bool x2_tail;             // tail = nearest x2 / shared 3x3 convs + LeakyReLU, conv_last with bias (model/model.py:347-440)
+    bool has_trunk_conv;      // trunk_conv + global skip behind the RRDBs
+    int nup;                  // ConvTranspose up-sampler stages that run (the tail families up-sample in their tail: 0)
+    int nrr;                  // RRDBs in the trunk (SRDN: encoder + decoder = 2 nb, srdn.py:56-74; legacy RDDBNet: 0)
+    int ndense;               // dense buffers (legacy RDDBNet discards its trunk: one buffer holds conv_first's output)
+    const char* tag;          // pack-cache tag stem ("_fwd" / "_bwd" / "_bwd_dx" is appended at the call)
+    size_t wpack_bytes;                            // packed weights: total size; the offsets below are relative to its start
     size_t w_rdb_d0, w_rdb_dsz;                    // contiguous region of the composite dense-block dgrad packs
-    // packed weights (offsets relative to wpk): per conv
     size_t w_first_f, w_first_d, w_trunk_f, w_trunk_d, w_last_f, w_last_d;
     std::vector<size_t> w_rdb_f, w_rdb_d;          // [nb*15]
     size_t w_up_f[5][4], w_up_d[5];
     size_t w_dn_f[5], w_dn_d[5][4];
     // parameter indices
     int p_first_w, p_first_b, p_rdb0, p_trunk_w, p_trunk_b, p_up0, p_dn0, p_last_w;
-    // legacy generators (model/model.py:347-440): tail = nearest x2 / shared 3x3 convs + LeakyReLU, conv_last with bias
-    int legacy, ntail, nlw, p_lg[3], p_last_b;
-    int nrr;                  // RRDBs in the trunk (legacy 3 = SRDN: encoder + decoder = 2 nb, srdn.py:56-74)
-    int prdb(int r) const { return p_rdb0 + r * 10 + ((legacy == 3 && r >= 3 * nb) ? 2 : 0); }     // SRDN: trunk_conv's two parameters sit between the stacks
-    struct TailOp { int conv, w, hin, win, hout, wout; size_t out; } tail[16];     // conv: 1 = 3x3 conv w + LReLU, 0 = nearest x2
+    int ntail, nlw, p_lg[3], p_last_b;       // nearest-x2 tail: ops, shared weights and their parameters, conv_last's bias
+    int prdb(int r) const { return p_rdb0 + r * 10 + ((family == RDDB_SRDN && r >= 3 * nb) ? 2 : 0); }     // SRDN: trunk_conv's two parameters sit between the stacks
+    struct TailOp { int conv, w, hin, win, hout, wout; } tail[16];     // conv: 1 = 3x3 conv w + LReLU, 0 = nearest x2
     size_t lw_f[3], lw_d[3];
 };
 
@@ -184,46 +191,38 @@ static int rddb_plan(const srcgan_rddbnet_cfg* c, RddbPlan& P) {
     SG_REQUIRE(c->down >= 0 && (c->down == 0 || ((c->down & (c->down - 1)) == 0 && c->down <= 16)), "rddbnet: bad down factor");
     SG_REQUIRE(!(c->down > 1 && c->up > 1), "rddbnet: up and down are exclusive");
     SG_REQUIRE(c->legacy >= 0 && c->legacy <= 3, "rddbnet: legacy must be 0..3");
-    SG_REQUIRE(c->legacy == 0 || c->legacy == 3 || (c->down == 0 && (c->up == 2 || c->up == 4 || (c->legacy == 2 && c->up == 1))),
+    P.family = (RddbFamily)c->legacy;
+    P.x2_tail = P.family == RDDB_NETB || P.family == RDDB_LEGACY;
+    SG_REQUIRE(!P.x2_tail || (c->down == 0 && (c->up == 2 || c->up == 4 || (P.family == RDDB_LEGACY && c->up == 1))),
                "rddbnet: legacy generators take mode x2 / x4 (legacy RDDBNet also x1) and no down factor");
-    SG_REQUIRE(c->legacy != 3 || (c->up == 1 && c->down == 0), "rddbnet: SRDN keeps the resolution (its upscale_factor is unused, srdn.py:67-74): pass up = 1");
-    P.legacy = c->legacy == 3 ? 3 : c->legacy; P.ntail = 0; P.nlw = 0;
-    P.nrr = c->legacy == 3 ? 2 * c->nb : (c->legacy == 2 ? 0 : c->nb);
+    SG_REQUIRE(P.family != RDDB_SRDN || (c->up == 1 && c->down == 0), "rddbnet: SRDN keeps the resolution (its upscale_factor is unused, srdn.py:67-74): pass up = 1");
+    P.has_trunk_conv = P.family == RDDB_PLAIN || P.family == RDDB_NETB;
+    P.nrr = P.family == RDDB_SRDN ? 2 * c->nb : (P.family == RDDB_LEGACY ? 0 : c->nb);
+    P.ndense = P.family == RDDB_LEGACY ? 1 : 3 * P.nrr;
+    P.tag = P.family == RDDB_NETB ? "rddbB" : P.family == RDDB_LEGACY ? "rddbL" : P.family == RDDB_SRDN ? "srdn" : "rddb";
+    P.ntail = 0; P.nlw = 0;
     P.dtype = c->dtype; P.esz = c->dtype == SRCGAN_F32 ? 4 : 2;
     P.nf = c->nf; P.gc = c->gc; P.nb = c->nb; P.C = c->nf + 4 * c->gc;
     P.B = c->B; P.H = c->H; P.W = c->W;
     P.nst = c->down > 0 ? 0 : log2i(c->up);
+    P.nup = P.x2_tail ? 0 : P.nst;
     P.ndn = c->down > 1 ? log2i(c->down) : 0;
     if (P.ndn) SG_REQUIRE(c->H % c->down == 0 && c->W % c->down == 0, "rddbnet: H, W must be divisible by the down factor");
     P.Ht = c->H >> P.ndn; P.Wt = c->W >> P.ndn;
     P.HO = P.Ht << P.nst; P.WO = P.Wt << P.nst;
     P.in_cs = img_cs(c->in_ch); P.out_cs = img_cs(c->out_ch);
-    const size_t e = P.esz, B = c->B;
-    Bump b;
-    P.xin = b.take(B * c->H * c->W * P.in_cs * e);
-    P.fea0 = P.ndn ? b.take(B * c->H * c->W * c->nf * e) : 0;     // conv_first output at HR (HR->LR variant only)
-    for (int s = 0; s < P.ndn; ++s) P.dn[s] = b.take(B * (c->H >> (s + 1)) * (c->W >> (s + 1)) * c->nf * e);
     // dense buffers use the blocked layout [plane = 64-byte channel chunk][pixel][64 B]: every operand fetch of the 3x3 kernel
     // and of the dense wgrad is then >= 1 KiB contiguous (64-byte pieces at a 384-byte pixel stride ran at half rate)
-    P.kce = 64 / P.esz; P.nplane = (P.C + P.kce - 1) / P.kce; P.plane_bytes = (long)B * P.Ht * P.Wt * 64;
-    // one bit per element for LeakyReLU' (instead of re-reading the activation in the backward pass): bf16, 32-channel slices
-    static const bool no_sign = sg_env("SRCGAN_NO_SIGNMASK") != nullptr || sg_env("SRCGAN_DMA_CFG") != nullptr;
-    P.bm_bytes = (!no_sign && sg_is16(c->dtype) && c->gc == 32 && c->nf % 32 == 0 && c->legacy != 2) ? (long)B * P.Ht * P.Wt * 4 : 0;
-    P.bm = align_up((size_t)P.nplane * P.plane_bytes, 256);
-    P.szA = align_up(P.bm + 4 * (size_t)P.bm_bytes, 256);
-    P.A = b.take(P.szA * (c->legacy == 2 ? 1 : 3 * P.nrr));        // legacy RDDBNet discards its trunk: one buffer holds conv_first's output
-    P.T = b.take(B * P.Ht * P.Wt * c->nf * e);
-    for (int s = 0; s <= ((c->legacy == 1 || c->legacy == 2) ? 0 : P.nst); ++s) P.U[s] = b.take(B * (P.Ht << s) * (P.Wt << s) * c->nf * e);
-    if (c->legacy == 3) P.U[0] = P.T;                  // SRDN: conv_last reads trunk output + skip, accumulated in place in T
-    if (c->legacy == 1 || c->legacy == 2) {
+    P.kce = 64 / P.esz; P.nplane = (P.C + P.kce - 1) / P.kce; P.plane_bytes = (long)c->B * P.Ht * P.Wt * 64;
+    if (P.x2_tail) {
         int h = P.Ht, w = P.Wt;
         auto op = [&](int conv, int wi) {
             RddbPlan::TailOp& o = P.tail[P.ntail++];
             o.conv = conv; o.w = wi; o.hin = h; o.win = w;
             if (!conv) { h *= 2; w *= 2; }
-            o.hout = h; o.wout = w; o.out = b.take(B * h * w * c->nf * e);
+            o.hout = h; o.wout = w;
         };
-        if (c->legacy == 1) {           // RDDBNetB (model.py:427-439): weights 0 = upconv1, 1 = upconv2, 2 = HRconv
+        if (P.family == RDDB_NETB) {    // RDDBNetB (model.py:427-439): weights 0 = upconv1, 1 = upconv2, 2 = HRconv
             if (c->up == 4) { op(0, 0); op(1, 0); op(0, 0); op(1, 1); }
             else { op(0, 0); op(1, 0); op(1, 0); }
             for (int k = 0; k < 8; ++k) op(1, 2);
@@ -235,10 +234,6 @@ static int rddb_plan(const srcgan_rddbnet_cfg* c, RddbPlan& P) {
             P.nlw = 2;
         }
     }
-    P.out = b.take(B * P.HO * P.WO * P.out_cs * e);
-    P.um_bytes = (!no_sign && sg_is16(c->dtype) && c->nf == 64 && P.nst > 0 && c->legacy == 0) ? (long)B * P.HO * P.WO * 8 : 0;
-    P.um = P.um_bytes ? b.take((size_t)P.um_bytes) : 0;
-    P.wpk = b.off;
     Bump wb;
     auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, c->dtype)); };
     P.w_first_f = pk(c->nf, P.in_cs, 9); P.w_first_d = pk(c->in_ch, c->nf, 9);
@@ -260,89 +255,60 @@ static int rddb_plan(const srcgan_rddbnet_cfg* c, RddbPlan& P) {
     for (int i = 0; i < nrdb; ++i)
         for (int j = 0; j < 5; ++j) P.w_rdb_d[i * 5 + j] = pk(j == 0 ? c->nf : c->gc, c->nf + (4 - j) * c->gc, 9);
     P.w_rdb_dsz = wb.off - P.w_rdb_d0;
-    P.total = align_up(P.wpk + wb.off + 256, 256);
+    P.wpack_bytes = wb.off + 256;
     // parameter indices (state_dict order)
     int n = 0;
     P.p_first_w = n++; P.p_first_b = n++;
     P.p_dn0 = n; n += 2 * P.ndn;
     P.p_rdb0 = n; n += c->nb * 30;
     P.p_trunk_w = n++; P.p_trunk_b = n++;
-    if (c->legacy == 3) n += c->nb * 30;          // RRDB_decoder
-    if (c->legacy == 1 || c->legacy == 2) { P.p_up0 = n; for (int k = 0; k < P.nlw; ++k) { P.p_lg[k] = n; n += 2; } }
-    else { P.p_up0 = n; n += P.nst; }
+    if (P.family == RDDB_SRDN) n += c->nb * 30;          // RRDB_decoder
+    P.p_up0 = n;
+    if (P.x2_tail) for (int k = 0; k < P.nlw; ++k) { P.p_lg[k] = n; n += 2; }
+    else n += P.nst;
     P.p_last_w = n++;
-    P.p_last_b = (c->legacy == 1 || c->legacy == 2) ? n++ : -1;
+    P.p_last_b = P.x2_tail ? n++ : -1;
     P.nparams = n;
     return 0;
 }
 
-}  // namespace
-
-extern "C" int srcgan_rddbnet_num_params(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return -1; return P.nparams; }
-extern "C" size_t srcgan_rddbnet_ws_bytes(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return 0; return P.total; }
-
-namespace {
-struct RddbBwdPlan {
-    size_t dout, dU[6], dT, Pg[3], szP, dfea_dn[5], dxin, slab, colscr, biasred, total;
-};
-static void rddb_bwd_plan(const srcgan_rddbnet_cfg* c, const RddbPlan& P, RddbBwdPlan& Q) {
-    const size_t e = P.esz, B = c->B;
-    Bump b;
-    Q.dout = b.take(B * P.HO * P.WO * P.out_cs * e);
-    for (int s = 0; s <= ((P.legacy == 1 || P.legacy == 2) ? 0 : P.nst); ++s) Q.dU[s] = b.take(B * (P.Ht << s) * (P.Wt << s) * c->nf * e);
-    if (P.legacy == 1 || P.legacy == 2) { Q.dU[1] = b.take(B * P.HO * P.WO * c->nf * e); Q.dU[2] = b.take(B * P.HO * P.WO * c->nf * e); }   // ping-pong
-    Q.dT = b.take(B * P.Ht * P.Wt * c->nf * e);
-    Q.szP = align_up((size_t)P.nplane * P.plane_bytes, 256);
-    for (int i = 0; i < 3; ++i) Q.Pg[i] = b.take(Q.szP);
-    for (int s = 0; s <= P.ndn; ++s) Q.dfea_dn[s] = b.take(B * (c->H >> s) * (c->W >> s) * c->nf * e);
-    Q.dxin = b.take(B * c->H * c->W * P.in_cs * e);
-    size_t slab = 0;
-    auto mx = [&](size_t v) { if (v > slab) slab = v; };
-    mx(wgrad_slab(c->B, c->H, c->W, c->nf, P.in_cs, 3, 3, 1));
-    for (int k = 0; k < 5; ++k) mx(wgrad_slab(c->B, P.Ht, P.Wt, k < 4 ? c->gc : c->nf, c->nf + k * c->gc, 3, 3, 1));
-    mx(wgrad_slab(c->B, P.Ht, P.Wt, c->nf, c->nf, 3, 3, 1));
-    for (int s = 0; s < ((P.legacy == 1 || P.legacy == 2) ? 0 : P.nst); ++s) mx(wgrad_slab(c->B, P.Ht << s, P.Wt << s, c->nf, c->nf, 2, 2, 2));
-    for (int k = 0; k < P.ntail; ++k) if (P.tail[k].conv) mx(wgrad_slab(c->B, P.tail[k].hout, P.tail[k].wout, c->nf, c->nf, 3, 3, 1));
-    for (int s = 0; s < P.ndn; ++s) mx(wgrad_slab(c->B, c->H >> (s + 1), c->W >> (s + 1), c->nf, c->nf, 3, 3, 2));
-    mx(wgrad_slab(c->B, P.HO, P.WO, c->out_ch, c->nf, 3, 3, 1));
-    mx(srcgan_wgrad_dense_slab_bytes(P.C, P.C, c->dtype, c->B, P.Ht, P.Wt));
-    Q.slab = b.take(slab);
-    const long maxpix = (long)B * (P.HO > c->H ? P.HO : c->H) * (P.WO > c->W ? P.WO : c->W);
-    Q.colscr = b.take((size_t)2 * srcgan_col_reduce_blocks(maxpix) * P.C * sizeof(float));
-    Q.total = b.off + 256;
-}
-}  // namespace
-
-extern "C" size_t srcgan_rddbnet_bwd_scratch_bytes(const srcgan_rddbnet_cfg* c) {
-    RddbPlan P; if (rddb_plan(c, P)) return 0;
-    RddbBwdPlan Q; rddb_bwd_plan(c, P, Q); return Q.total;
-}
-
-extern "C" size_t srcgan_rddbnet_wpack_bytes(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return 0; return P.total - P.wpk; }
-
-// ---- where the forward's activations live.  The launch sequence of a generator is ONE walker (rddb_forward_walk) over a
+// ---- where the forward's activations live.  The launch sequence of a generator is ONE walker (RddbCall::forward) over a
 // buffer-naming policy: the training policy keeps every tensor a backward reads (one dense buffer per ResidualDenseBlock_5, the
 // LeakyReLU sign masks, every up-sampler stage), the inference policy keeps only what a later launch of the same pass reads.
-namespace {
 struct RddbNames {
-    size_t xin, fea0, dn[5], T, U[6], out, tail[16], wpk, total;
+    size_t xin = 0, fea0 = 0, dn[5] = {}, T = 0, U[6] = {}, out = 0, tail[16] = {}, wpk = 0, total = 0;      // 0 = the policy has no such buffer
     std::vector<size_t> A;      // dense buffer of RDB r
-    size_t home;                // inference: nf-channel copy (whole leading planes) of the trunk input, which the rotation overwrites
-    bool rolling;               // inference policy
-    long bm_bytes, um_bytes;    // sign masks (0 = not written)
-    size_t bm, um;
+    size_t home = 0;            // inference: nf-channel copy (whole leading planes) of the trunk input, which the rotation overwrites
+    bool rolling = false;       // inference policy
+    size_t bm = 0; long bm_bytes = 0;   // sign masks of a dense buffer's four LeakyReLU slices: offset inside the buffer, bytes per slice (0 = not written)
+    size_t um = 0; long um_bytes = 0;   // sign mask of the last up-sampler stage's output (8 bytes per HR pixel; 0 = not written): conv_last's input gradient
+                                // reads it instead of the 64-channel activation (2.1 GB at the bench size)
 };
 
-static void rddb_train_names(const RddbPlan& P, RddbNames& N) {
-    N.xin = P.xin; N.fea0 = P.fea0; N.T = P.T; N.out = P.out; N.wpk = P.wpk; N.total = P.total;
-    for (int s = 0; s < 5; ++s) N.dn[s] = P.dn[s];
-    for (int s = 0; s < 6; ++s) N.U[s] = P.U[s];
-    for (int k = 0; k < 16; ++k) N.tail[k] = k < P.ntail ? P.tail[k].out : 0;
-    const int nbuf = P.legacy == 2 ? 1 : 3 * P.nrr;
-    N.A.resize(nbuf);
-    for (int r = 0; r < nbuf; ++r) N.A[r] = P.A + (size_t)r * P.szA;
-    N.home = 0; N.rolling = false;
-    N.bm = P.bm; N.bm_bytes = P.bm_bytes; N.um = P.um; N.um_bytes = P.um_bytes;
+// Training: every tensor has a buffer of its own, in the forward's order; the backward (RddbBwd) reads the same names.
+static void rddb_train_names(const srcgan_rddbnet_cfg* c, const RddbPlan& P, RddbNames& N) {
+    const size_t e = P.esz, B = c->B, nf = c->nf;
+    Bump b;
+    N.xin = b.take(B * c->H * c->W * P.in_cs * e);
+    if (P.ndn) N.fea0 = b.take(B * c->H * c->W * nf * e);     // conv_first output at HR (HR->LR variant only)
+    for (int s = 0; s < P.ndn; ++s) N.dn[s] = b.take(B * (c->H >> (s + 1)) * (c->W >> (s + 1)) * nf * e);
+    // one bit per element for LeakyReLU' (instead of re-reading the activation in the backward pass): bf16, 32-channel slices
+    static const bool no_sign = sg_env("SRCGAN_NO_SIGNMASK") != nullptr || sg_env("SRCGAN_DMA_CFG") != nullptr;
+    N.bm_bytes = (!no_sign && sg_is16(c->dtype) && c->gc == 32 && nf % 32 == 0 && P.family != RDDB_LEGACY) ? (long)B * P.Ht * P.Wt * 4 : 0;
+    N.bm = align_up((size_t)P.nplane * P.plane_bytes, 256);
+    const size_t szA = align_up(N.bm + 4 * (size_t)N.bm_bytes, 256);
+    const size_t A0 = b.take(szA * P.ndense);
+    N.A.resize(P.ndense);
+    for (int r = 0; r < P.ndense; ++r) N.A[r] = A0 + (size_t)r * szA;
+    N.T = b.take(B * P.Ht * P.Wt * nf * e);
+    for (int s = 0; s <= P.nup; ++s) N.U[s] = b.take(B * (P.Ht << s) * (P.Wt << s) * nf * e);
+    if (P.family == RDDB_SRDN) N.U[0] = N.T;           // SRDN: conv_last reads trunk output + skip, accumulated in place in T
+    for (int k = 0; k < P.ntail; ++k) N.tail[k] = b.take(B * P.tail[k].hout * P.tail[k].wout * nf * e);
+    N.out = b.take(B * P.HO * P.WO * P.out_cs * e);
+    N.um_bytes = (!no_sign && sg_is16(c->dtype) && nf == 64 && P.nst > 0 && P.family == RDDB_PLAIN) ? (long)B * P.HO * P.WO * 8 : 0;
+    if (N.um_bytes) N.um = b.take((size_t)N.um_bytes);
+    N.wpk = b.off;
+    N.total = N.wpk + P.wpack_bytes;
 }
 
 // Inference: the workspace does not grow with nb.  THREE dense buffers rotate: RDB r reads its own buffer and writes channels
@@ -353,11 +319,8 @@ static void rddb_train_names(const RddbPlan& P, RddbNames& N) {
 static void rddb_infer_names(const srcgan_rddbnet_cfg* c, const RddbPlan& P, RddbNames& N) {
     const size_t e = P.esz, B = c->B, nf = c->nf;
     Bump b;
-    N.rolling = true; N.bm = N.um = 0; N.bm_bytes = N.um_bytes = 0;
-    for (int k = 0; k < 16; ++k) N.tail[k] = 0;
+    N.rolling = true;
     N.xin = b.take(B * c->H * c->W * P.in_cs * e);
-    N.fea0 = 0;
-    for (int s = 0; s < 5; ++s) N.dn[s] = 0;
     if (P.ndn) {     // HR->LR stages: conv_first's output and the stage outputs alternate; the last stage writes the trunk input
         const size_t pp0 = b.take(B * c->H * c->W * nf * e);
         const size_t pp1 = P.ndn > 1 ? b.take(B * (c->H >> 1) * (c->W >> 1) * nf * e) : 0;
@@ -365,27 +328,25 @@ static void rddb_infer_names(const srcgan_rddbnet_cfg* c, const RddbPlan& P, Rdd
         for (int s = 0; s < P.ndn; ++s) N.dn[s] = (s & 1) ? pp0 : pp1;
     }
     const size_t szA = align_up((size_t)P.nplane * P.plane_bytes, 256);
-    const int nbuf = P.legacy == 2 ? 1 : 3 * P.nrr;
     size_t slot[3] = {0, 0, 0};
-    for (int k = 0; k < (P.legacy == 2 ? 1 : 3); ++k) slot[k] = b.take(szA);
-    N.A.resize(nbuf);
+    for (int k = 0; k < 3 && k < P.ndense; ++k) slot[k] = b.take(szA);
+    N.A.resize(P.ndense);
     int cur = 0, rrdb_in = 0;
-    for (int r = 0; r < nbuf; ++r) {
+    for (int r = 0; r < P.ndense; ++r) {
         if (r % 3 == 0) rrdb_in = cur;
         N.A[r] = slot[cur];
         int nxt = 0;
         while (nxt == cur || nxt == rrdb_in) ++nxt;
         cur = nxt;
     }
-    N.home = P.nrr ? b.take((size_t)((nf + P.kce - 1) / P.kce) * P.plane_bytes) : 0;
-    N.T = P.legacy == 2 ? 0 : b.take(B * P.Ht * P.Wt * nf * e);       // legacy RDDBNet has no trunk output
-    for (int s = 0; s < 6; ++s) N.U[s] = 0;
-    if (P.legacy == 1 || P.legacy == 2) {
+    if (P.nrr) N.home = b.take((size_t)((nf + P.kce - 1) / P.kce) * P.plane_bytes);
+    if (P.family != RDDB_LEGACY) N.T = b.take(B * P.Ht * P.Wt * nf * e);       // legacy RDDBNet has no trunk output
+    if (P.x2_tail) {
         N.U[0] = b.take(B * P.Ht * P.Wt * nf * e);
         size_t pp[2];
         for (int k = 0; k < 2; ++k) pp[k] = b.take(B * P.HO * P.WO * nf * e);
         for (int k = 0; k < P.ntail; ++k) N.tail[k] = pp[k & 1];
-    } else if (P.legacy == 3) {
+    } else if (P.family == RDDB_SRDN) {
         N.U[0] = N.T;
     } else {        // stage s has 4^s times the trunk's pixels: even stages share one buffer, odd stages the other
         size_t pp[2] = {0, 0};
@@ -397,35 +358,91 @@ static void rddb_infer_names(const srcgan_rddbnet_cfg* c, const RddbPlan& P, Rdd
     }
     N.out = b.take(B * P.HO * P.WO * P.out_cs * e);
     N.wpk = b.off;
-    N.total = N.wpk + (P.total - P.wpk);       // the packed-weight region of the training plan, as is
+    N.total = N.wpk + P.wpack_bytes;       // the packed-weight region is the training policy's, as is
 }
+
+struct RddbBwdPlan {
+    size_t dout, dU[6], Pg[3], szP, dfea_dn[5], dxin, slab, colscr, total;
+};
+static void rddb_bwd_plan(const srcgan_rddbnet_cfg* c, const RddbPlan& P, RddbBwdPlan& Q) {
+    const size_t e = P.esz, B = c->B;
+    Bump b;
+    Q.dout = b.take(B * P.HO * P.WO * P.out_cs * e);
+    for (int s = 0; s <= P.nup; ++s) Q.dU[s] = b.take(B * (P.Ht << s) * (P.Wt << s) * c->nf * e);
+    if (P.x2_tail) { Q.dU[1] = b.take(B * P.HO * P.WO * c->nf * e); Q.dU[2] = b.take(B * P.HO * P.WO * c->nf * e); }   // ping-pong
+    Q.szP = align_up((size_t)P.nplane * P.plane_bytes, 256);
+    for (int i = 0; i < 3; ++i) Q.Pg[i] = b.take(Q.szP);
+    for (int s = 0; s <= P.ndn; ++s) Q.dfea_dn[s] = b.take(B * (c->H >> s) * (c->W >> s) * c->nf * e);
+    Q.dxin = b.take(B * c->H * c->W * P.in_cs * e);
+    size_t slab = 0;
+    auto mx = [&](size_t v) { if (v > slab) slab = v; };
+    mx(wgrad_slab(c->B, c->H, c->W, c->nf, P.in_cs, 3, 3, 1));
+    for (int k = 0; k < 5; ++k) mx(wgrad_slab(c->B, P.Ht, P.Wt, k < 4 ? c->gc : c->nf, c->nf + k * c->gc, 3, 3, 1));
+    mx(wgrad_slab(c->B, P.Ht, P.Wt, c->nf, c->nf, 3, 3, 1));
+    for (int s = 0; s < P.nup; ++s) mx(wgrad_slab(c->B, P.Ht << s, P.Wt << s, c->nf, c->nf, 2, 2, 2));
+    for (int k = 0; k < P.ntail; ++k) if (P.tail[k].conv) mx(wgrad_slab(c->B, P.tail[k].hout, P.tail[k].wout, c->nf, c->nf, 3, 3, 1));
+    for (int s = 0; s < P.ndn; ++s) mx(wgrad_slab(c->B, c->H >> (s + 1), c->W >> (s + 1), c->nf, c->nf, 3, 3, 2));
+    mx(wgrad_slab(c->B, P.HO, P.WO, c->out_ch, c->nf, 3, 3, 1));
+    mx(srcgan_wgrad_dense_slab_bytes(P.C, P.C, c->dtype, c->B, P.Ht, P.Wt));
+    Q.slab = b.take(slab);
+    const long maxpix = (long)B * (P.HO > c->H ? P.HO : c->H) * (P.WO > c->W ? P.WO : c->W);
+    Q.colscr = b.take((size_t)2 * srcgan_col_reduce_blocks(maxpix) * P.C * sizeof(float));
+    Q.total = b.off + 256;
+}
+
 }  // namespace
 
+extern "C" int srcgan_rddbnet_num_params(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return -1; return P.nparams; }
+extern "C" int srcgan_rddbnet_num_rrdb(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return -1; return P.nrr; }
+extern "C" size_t srcgan_rddbnet_wpack_bytes(const srcgan_rddbnet_cfg* c) { RddbPlan P; if (rddb_plan(c, P)) return 0; return P.wpack_bytes; }
+extern "C" size_t srcgan_rddbnet_ws_bytes(const srcgan_rddbnet_cfg* c) {
+    RddbPlan P; if (rddb_plan(c, P)) return 0;
+    RddbNames N; rddb_train_names(c, P, N); return N.total;
+}
 extern "C" size_t srcgan_rddbnet_infer_ws_bytes(const srcgan_rddbnet_cfg* c) {
     RddbPlan P; if (rddb_plan(c, P)) return 0;
     RddbNames N; rddb_infer_names(c, P, N); return N.total;
 }
-
-// the four parity packs of up-sampler stage s are equally spaced: the stage runs as ONE launch (conv_igemm.hip, npar), which is also
-// the form that writes the LeakyReLU sign mask of the last stage's output
-static inline bool up_packs_spaced(const RddbPlan& P, int s) {
-    const long wstep = (long)(P.w_up_f[s][1] - P.w_up_f[s][0]);
-    return wstep > 0 && P.w_up_f[s][2] == P.w_up_f[s][0] + 2 * (size_t)wstep && P.w_up_f[s][3] == P.w_up_f[s][0] + 3 * (size_t)wstep;
+extern "C" size_t srcgan_rddbnet_bwd_scratch_bytes(const srcgan_rddbnet_cfg* c) {
+    RddbPlan P; if (rddb_plan(c, P)) return 0;
+    RddbBwdPlan Q; rddb_bwd_plan(c, P, Q); return Q.total;
 }
-static inline bool up_mask_written(const RddbPlan& P) { return P.um_bytes && P.nst > 0 && up_packs_spaced(P, P.nst - 1); }
 
-static int rddb_forward_walk(const srcgan_rddbnet_cfg* c, const RddbPlan& P, const RddbNames& N, const float* x_nchw,
-                             const float* const* params, void* ws, float* y_nchw, const srcgan_net_opts* opt, void* st) {
-    SG_REQUIRE(x_nchw && params && ws && y_nchw, "srcgan_rddbnet_forward: null pointer");
-    SG_REQUIRE(((uintptr_t)ws % 256) == 0, "srcgan_rddbnet_forward: workspace must be 256-byte aligned");
-    const int dt = c->dtype, nf = c->nf, gc = c->gc, B = c->B;
-    char* w8 = (char*)ws;
-    // packed weights: a persistent buffer of the caller's (packed once per optimiser step) or a region of this call's workspace
-    char* wp = (opt && opt->wpack) ? (char*)opt->wpack : w8 + N.wpk;
+// The parameters [first, end) a backward call over the RRDBs [lo, hi) finalises (state_dict order): hi == nrr extends the range to
+// the last parameter, lo == 0 to parameter 0; a network without a trunk is one range.
+extern "C" int srcgan_rddbnet_phase_params(const srcgan_rddbnet_cfg* c, int lo, int hi, int* first, int* end) {
+    RddbPlan P;
+    SG_TRY(rddb_plan(c, P));
+    SG_REQUIRE(first && end, "srcgan_rddbnet_phase_params: null pointer");
+    SG_REQUIRE(lo >= 0 && lo <= hi && hi <= P.nrr, "srcgan_rddbnet_phase_params: RRDB range [%d,%d) outside [0,%d)", lo, hi, P.nrr);
+    *first = lo == 0 ? 0 : P.prdb(3 * lo);
+    *end = hi == P.nrr ? P.nparams : P.prdb(3 * hi);
+    return 0;
+}
+
+namespace {
+
+// ---- one native call on a generator: what the forward and the backward both need to address their operands
+struct RddbCall {
+    const srcgan_rddbnet_cfg* c; const RddbPlan& P; const RddbNames& N;
+    const float* const* params; const srcgan_net_opts* opt; void* st;
+    const int dt, nf, gc, B, H, W;      // H, W: trunk resolution
+    char* w8;
+    char* wp;            // packed weights: a persistent buffer of the caller's (packed once per optimiser step) or a region of this call's workspace
+    bool do_pack;
+    RddbCall(const srcgan_rddbnet_cfg* c_, const RddbPlan& P_, const RddbNames& N_, const float* const* params_, void* ws,
+             const srcgan_net_opts* opt_, void* st_)
+        : c(c_), P(P_), N(N_), params(params_), opt(opt_), st(st_), dt(c_->dtype), nf(c_->nf), gc(c_->gc), B(c_->B), H(P_.Ht), W(P_.Wt),
+          w8((char*)ws), wp((opt_ && opt_->wpack) ? (char*)opt_->wpack : (char*)ws + N_.wpk), do_pack(!(opt_ && opt_->wpack) || opt_->pack) {}
+    TRef T_(size_t off, int cs) const { return tref(w8 + off, cs); }
+    TRef Abuf(int r) const { return tref(w8 + N.A[r], P.kce, 0, P.plane_bytes); }
+    int forward(const float* x_nchw, float* y_nchw) const;
+};
+
+int RddbCall::forward(const float* x_nchw, float* y_nchw) const {
+    SG_REQUIRE(x_nchw && params && w8 && y_nchw, "srcgan_rddbnet_forward: null pointer");
+    SG_REQUIRE(((uintptr_t)w8 % 256) == 0, "srcgan_rddbnet_forward: workspace must be 256-byte aligned");
     SG_REQUIRE(((uintptr_t)wp % 256) == 0, "srcgan_rddbnet_forward: wpack must be 256-byte aligned");
-    const bool do_pack = !(opt && opt->wpack) || opt->pack;
-    auto T_ = [&](size_t off, int cs) { return tref(w8 + off, cs); };
-    auto Abuf = [&](int r) { return tref(w8 + N.A[r], P.kce, 0, P.plane_bytes); };
     // inference: copy the nf leading channels of a dense buffer (whole planes of the blocked layout: one contiguous copy) to `home`
     auto to_home = [&](TRef a) {
         return hipMemcpyAsync(w8 + N.home, a.p, (size_t)((nf + P.kce - 1) / P.kce) * P.plane_bytes, hipMemcpyDeviceToDevice, (hipStream_t)st);
@@ -441,8 +458,8 @@ static int rddb_forward_walk(const srcgan_rddbnet_cfg* c, const RddbPlan& P, con
             const int cin = nf + k * gc, cout = k < 4 ? gc : nf;
             packs.add(params[P.prdb(i) + k * 2], wp + P.w_rdb_f[i * 5 + k], cout, cin, 3, 3, (long)cin * 9, 9, 3, 1, 0);
         }
-    if (P.legacy != 3) packs.add(params[P.p_trunk_w], wp + P.w_trunk_f, nf, nf, 3, 3, (long)nf * 9, 9, 3, 1, 0);
-    for (int s = 0; s < ((P.legacy == 1 || P.legacy == 2) ? 0 : P.nst); ++s)
+    if (P.family != RDDB_SRDN) packs.add(params[P.p_trunk_w], wp + P.w_trunk_f, nf, nf, 3, 3, (long)nf * 9, 9, 3, 1, 0);
+    for (int s = 0; s < P.nup; ++s)
         for (int q = 0; q < 4; ++q)   // ConvTranspose2d weight [ci][co][2][2]; parity (a,b) = q: rows = co, k = ci
             packs.add(params[P.p_up0 + s], wp + P.w_up_f[s][q], nf, nf, 1, 1, 4, (long)nf * 4, 0, 0, q);
     for (int k = 0; k < P.nlw; ++k)
@@ -450,13 +467,12 @@ static int rddb_forward_walk(const srcgan_rddbnet_cfg* c, const RddbPlan& P, con
     packs.add(params[P.p_last_w], wp + P.w_last_f, c->out_ch, nf, 3, 3, (long)nf * 9, 9, 3, 1, 0);
 
     SG_REQUIRE(!(opt && opt->pack == 2) || (opt->wpack && opt->guard), "srcgan_rddbnet_forward: pack == 2 needs wpack and guard");
-    if (do_pack) SG_TRY(packs.run(P.legacy == 1 ? "rddbB_fwd" : P.legacy == 2 ? "rddbL_fwd" : P.legacy == 3 ? "srdn_fwd" : "rddb_fwd", params[0], st, pack_guard(opt)));
+    if (do_pack) SG_TRY(packs.run((std::string(P.tag) + "_fwd").c_str(), params[0], st, pack_guard(opt)));
 
     // ---- input: NCHW f32 -> NHWC (channels zero-padded to 8)
     SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + N.xin, B, c->in_ch, c->H, c->W, P.in_cs, dt, st));
     // conv_first (rddb.py:89,108).  The trunk input lives in channels [0,nf) of the first dense buffer so the
     // first RDB reads it in place and the global skip (rddb.py:110) reads it back later.
-    const int H = P.Ht, W = P.Wt;
     TRef trunk_in = Abuf(0);
     TRef fea = P.ndn ? T_(N.fea0, nf) : trunk_in;
     SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.xin, P.in_cs), B, c->H, c->W, P.in_cs).w(wp + P.w_first_f, params[P.p_first_b])
@@ -490,24 +506,24 @@ static int rddb_forward_walk(const srcgan_rddbnet_cfg* c, const RddbPlan& P, con
             else cv.alpha(0.04f).res1(A, nf, 0.2f).res2(Abuf(i * 3), nf, 1.f);   // RRDB: 0.2*(0.2*x5 + x_rdb3) + x_rrdb
             SG_TRY(cv.run(st));
         }
-        if (P.legacy == 3 && i == c->nb - 1) {       // SRDN: fea = fea + RRDB_encoder(fea) (srdn.py:70-71), in the decoder's first buffer
+        if (P.family == RDDB_SRDN && i == c->nb - 1) {       // SRDN: fea = fea + RRDB_encoder(fea) (srdn.py:70-71), in the decoder's first buffer
             TRef d0 = Abuf((i + 1) * 3);
             SG_TRY(srcgan_add_inplace_planes(d0.p, d0.cs, 0, d0.plane, trunk_in.p, trunk_in.cs, 0, trunk_in.plane, nullptr, 0, 0, 0, 0.f,
                                              (long)B * H * W, nf, dt, st));
             if (N.rolling) SG_HIP(to_home(d0));       // the decoder's input takes the encoder input's place
         }
     }
-    if (P.legacy == 3) {       // fea = fea + RRDB_decoder(fea) (srdn.py:72-73): T += fea1, then conv_last reads T (= U[0])
+    if (P.family == RDDB_SRDN) {       // fea = fea + RRDB_decoder(fea) (srdn.py:72-73): T += fea1, then conv_last reads T (= U[0])
         TRef f1 = N.rolling ? trunk_in : Abuf(c->nb * 3), Tt = T_(N.T, nf);
         SG_TRY(srcgan_add_inplace_planes(Tt.p, Tt.cs, 0, 0, f1.p, f1.cs, 0, f1.plane, nullptr, 0, 0, 0, 0.f, (long)B * H * W, nf, dt, st));
     }
     // trunk_conv + global skip (rddb.py:109-110)
-    if (P.legacy != 2 && P.legacy != 3)
+    if (P.has_trunk_conv)
         SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.T, nf), B, H, W, nf).w(wp + P.w_trunk_f, params[P.p_trunk_b]).out(T_(N.U[0], nf), H, W, nf)
                    .pad(1, 1).res1(trunk_in, nf, 1.f).run(st));
-    if (P.legacy == 1 || P.legacy == 2) {
+    if (P.x2_tail) {
         // legacy tail (model.py:384-390, 427-439): [nearest x2 -> 3x3 conv -> LeakyReLU] stages, HRconv applied repeatedly
-        TRef cur = P.legacy == 2 ? trunk_in : T_(N.U[0], nf);
+        TRef cur = P.family == RDDB_LEGACY ? trunk_in : T_(N.U[0], nf);
         for (int k = 0; k < P.ntail; ++k) {
             const RddbPlan::TailOp& o = P.tail[k];
             TRef dst = T_(N.tail[k], nf);
@@ -525,50 +541,47 @@ static int rddb_forward_walk(const srcgan_rddbnet_cfg* c, const RddbPlan& P, con
         return 0;
     }
     // up-sampler: ConvTranspose2d(k2,s2) + LeakyReLU == 4 x (1x1 conv -> stride-2 scatter) (rddb.py:93-97,111-112)
-    for (int s = 0; s < P.nst; ++s) {
+    for (int s = 0; s < P.nup; ++s) {
         const int h = H << s, w = W << s;
-        const long wstep = (long)(P.w_up_f[s][1] - P.w_up_f[s][0]);
-        if (up_packs_spaced(P, s)) {
-            // all four output parities in one launch (the input is read from HBM once: conv_igemm.hip, npar)
-            Conv cv(dt, 1, 1, 1);
-            cv.in(T_(N.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][0]).out(T_(N.U[s + 1], nf), h, w, nf).scatter(2, 0, 0, 2 * h, 2 * w).lrelu();
-            cv.d.npar = 4; cv.d.wpar_stride = wstep;
-            if (N.um_bytes && s == P.nst - 1) cv.sign_out(w8 + N.um);       // LeakyReLU sign of the tensor conv_last reads
-            SG_TRY(cv.run(st));
-        } else
-        for (int q = 0; q < 4; ++q)
-            SG_TRY(Conv(dt, 1, 1, 1).in(T_(N.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][q]).out(T_(N.U[s + 1], nf), h, w, nf)
-                       .scatter(2, q >> 1, q & 1, 2 * h, 2 * w).lrelu().run(st));
+        // all four output parities in one launch (the input is read from HBM once: conv_igemm.hip, npar): the stage's four packs
+        // are equal-sized and consecutive (rddb_plan), hence equally spaced
+        Conv cv(dt, 1, 1, 1);
+        cv.in(T_(N.U[s], nf), B, h, w, nf).w(wp + P.w_up_f[s][0]).out(T_(N.U[s + 1], nf), h, w, nf).scatter(2, 0, 0, 2 * h, 2 * w).lrelu();
+        cv.d.npar = 4; cv.d.wpar_stride = (long)(P.w_up_f[s][1] - P.w_up_f[s][0]);
+        if (N.um_bytes && s == P.nup - 1) cv.sign_out(w8 + N.um);       // LeakyReLU sign of the tensor conv_last reads
+        SG_TRY(cv.run(st));
     }
     // conv_last (no bias, rddb.py:98,113) as a convolution to all out_cs = 8 padded channels: the packed weight rows beyond out_ch
     // are zero, so channels out_ch.. come out as the zeros the padding wants -- and the output is 16 bytes per pixel through the
     // vectorised epilogue (with Cout = 3 it took the per-element form: three 2-byte stores per pixel of a 1024x1024 image, and a
     // 268 MB memset in front; 0.67 ms + 0.06 ms per step at the bench size)
-    SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.U[P.nst], nf), B, P.HO, P.WO, nf).w(wp + P.w_last_f).out(T_(N.out, P.out_cs), P.HO, P.WO, P.out_cs)
+    SG_TRY(Conv(dt, 3, 3, 1).in(T_(N.U[P.nup], nf), B, P.HO, P.WO, nf).w(wp + P.w_last_f).out(T_(N.out, P.out_cs), P.HO, P.WO, P.out_cs)
                .pad(1, 1).run(st));
     SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + N.out, y_nchw, B, c->out_ch, P.HO, P.WO, P.out_cs, 0, dt, st));
     return 0;
 }
 
-extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,
-                                         void* ws, float* y_nchw, const srcgan_net_opts* opt, void* st) {
+}  // namespace
+
+static int rddb_forward(const srcgan_rddbnet_cfg* c, bool infer, const float* x_nchw, const float* const* params, void* ws,
+                        float* y_nchw, const srcgan_net_opts* opt, void* st) {
     RddbPlan P;
     SG_TRY(rddb_plan(c, P));
     RddbNames N;
-    rddb_train_names(P, N);
-    return rddb_forward_walk(c, P, N, x_nchw, params, ws, y_nchw, opt, st);
+    if (infer) rddb_infer_names(c, P, N); else rddb_train_names(c, P, N);
+    return RddbCall(c, P, N, params, ws, opt, st).forward(x_nchw, y_nchw);
+}
+
+extern "C" int srcgan_rddbnet_forward_ex(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,
+                                         void* ws, float* y_nchw, const srcgan_net_opts* opt, void* st) {
+    return rddb_forward(c, false, x_nchw, params, ws, y_nchw, opt, st);
 }
 
 // Inference forward: same launches, same kernels, same descriptors as srcgan_rddbnet_forward_ex apart from buffer addresses and
-// the sign masks, which are not written.  flags bit 0 (keep the unfused HR tail) is accepted: the tail is always unfused.
+// the sign masks, which are not written.
 extern "C" int srcgan_rddbnet_infer(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params, void* ws,
-                                    float* y_nchw, const srcgan_net_opts* opt, int flags, void* st) {
-    RddbPlan P;
-    SG_TRY(rddb_plan(c, P));
-    SG_REQUIRE((flags & ~1) == 0, "srcgan_rddbnet_infer: unknown flags 0x%x", flags);
-    RddbNames N;
-    rddb_infer_names(c, P, N);
-    return rddb_forward_walk(c, P, N, x_nchw, params, ws, y_nchw, opt, st);
+                                    float* y_nchw, const srcgan_net_opts* opt, void* st) {
+    return rddb_forward(c, true, x_nchw, params, ws, y_nchw, opt, st);
 }
 
 extern "C" int srcgan_rddbnet_forward(const srcgan_rddbnet_cfg* c, const float* x_nchw, const float* const* params,
@@ -576,144 +589,92 @@ extern "C" int srcgan_rddbnet_forward(const srcgan_rddbnet_cfg* c, const float* 
     return srcgan_rddbnet_forward_ex(c, x_nchw, params, ws, y_nchw, nullptr, st);
 }
 
-extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const float* dy_nchw, const float* const* params,
-                                          void* ws, void* scratch, float* const* grads, float* dx_nchw, const srcgan_net_opts* opt, void* st) {
-    RddbPlan P;
-    SG_TRY(rddb_plan(c, P));
-    RddbBwdPlan Q;
-    rddb_bwd_plan(c, P, Q);
-    SG_REQUIRE(dy_nchw && params && ws && scratch && grads, "srcgan_rddbnet_backward: null pointer");
-    SG_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)scratch % 256) == 0, "srcgan_rddbnet_backward: buffers must be 256-byte aligned");
-    const int dt = c->dtype, nf = c->nf, gc = c->gc, B = c->B, H = P.Ht, W = P.Wt;
-    char* w8 = (char*)ws; char* s8 = (char*)scratch;
-    char* wp = (opt && opt->wpack) ? (char*)opt->wpack : w8 + P.wpk;
-    const bool do_pack = !(opt && opt->wpack) || opt->pack;
-    // Phased backward (data parallel: the gradients of the RRDBs a phase covers are final when it returns, so their all-reduce
-    // starts while earlier blocks still compute).  A call handles the RRDBs [lo, hi), last to first; the call with hi == nrr also
-    // runs everything behind the trunk (conv_last, up-sampler, trunk_conv), the call with lo == 0 everything in front of it
-    // (conv_first / down-sampling stages, dx).  Calls must come in descending, gap-free order on one stream with the same
-    // scratch: the running gradient sits in the scratch between them.
-    int r_lo = 0, r_hi = P.nrr;
-    if (opt && opt->rrdb_hi > 0) { r_lo = opt->rrdb_lo; r_hi = opt->rrdb_hi; }
-    SG_REQUIRE(r_lo >= 0 && r_lo <= r_hi && r_hi <= P.nrr, "srcgan_rddbnet_backward: RRDB range [%d,%d) outside [0,%d)", r_lo, r_hi, P.nrr);
-    SG_REQUIRE(P.nrr > 0 || (r_lo == 0), "srcgan_rddbnet_backward: a network without a trunk has one phase");
-    const bool first_phase = r_hi == P.nrr, last_phase = r_lo == 0;
-    float* slab = (float*)(s8 + Q.slab); float* colscr = (float*)(s8 + Q.colscr);
-    auto T_ = [&](size_t off, int cs) { return tref(w8 + off, cs); };
-    auto S_ = [&](size_t off, int cs) { return tref(s8 + off, cs); };
-    auto Abuf = [&](int r) { return tref(w8 + P.A + (size_t)r * P.szA, P.kce, 0, P.plane_bytes); };
-    auto G = [&](int idx) { return grads[idx]; };
-    const long npix_t = (long)B * H * W;
+namespace {
 
-    // ---- packed dgrad weights (flipped / transposed views of the canonical tensors): ONE batched launch
-    const bool pack_dx = dx_nchw || (opt && opt->wpack);       // a persistent pack serves later calls that may want dx
-    if (first_phase && do_pack) {
-        PackList packs(dt, wp);
-        const WLayout L = lay_dgrad_s1(nf, 3, 3);
-        packs.add(params[P.p_last_w], wp + P.w_last_d, nf, c->out_ch, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
-        for (int s = 0; s < ((P.legacy == 1 || P.legacy == 2) ? 0 : P.nst); ++s)   // deconv dgrad = 2x2 s2 conv over dy: rows = ci, k = co, tap = (a,b)
-            packs.add(params[P.p_up0 + s], wp + P.w_up_d[s], nf, nf, 2, 2, (long)nf * 4, 4, 2, 1, 0);
-        for (int k = 0; k < P.nlw; ++k)
-            packs.add(params[P.p_lg[k]], wp + P.lw_d[k], nf, nf, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
-        if (P.legacy != 3) packs.add(params[P.p_trunk_w], wp + P.w_trunk_d, nf, nf, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
-        SG_TRY(sg_fill_zero_guarded(wp + P.w_rdb_d0, P.w_rdb_dsz, pack_guard(opt), (hipStream_t)st));
-        for (int r = 0; r < P.nrr * 3; ++r) {
-            const float a5 = (r % 3 == 2) ? 0.04f : 0.2f;       // d(x5)/d(block out), RDB3 carries the RRDB 0.2 too
-            for (int j = 0; j < 5; ++j) {
-                const int rows = j == 0 ? nf : gc, ss = j == 0 ? 0 : nf + (j - 1) * gc, ktot = nf + (4 - j) * gc;
-                for (int m = 5; m > j; --m) {                   // block of K coming from forward conv m
-                    const int cin_m = nf + (m - 1) * gc, cout_m = m == 5 ? nf : gc;
-                    const int k_off = m == 5 ? 0 : nf + (4 - m) * gc;
-                    packs.add(params[P.prdb(r) + (m - 1) * 2], wp + P.w_rdb_d[r * 5 + j], rows, cout_m, 3, 3,
-                                                   9, (long)cin_m * 9, -3, -1, (long)ss * 9 + 8, k_off, ktot, m == 5 ? a5 : 1.f);
-                }
+// ---- the backward, in stages that mirror the forward's order in reverse.  The running gradient of the trunk-resolution feature
+// (dU0) and the three rotating dense gradient buffers (Pg) sit in the scratch, also between the calls of a phased backward.
+struct RddbBwd : RddbCall {
+    const RddbBwdPlan& Q;
+    char* s8; float* const* grads;
+    float* slab; float* colscr;
+    const long npix_t;
+    RddbBwd(const RddbCall& call, const RddbBwdPlan& Q_, void* scratch, float* const* grads_)
+        : RddbCall(call), Q(Q_), s8((char*)scratch), grads(grads_), slab((float*)(s8 + Q_.slab)), colscr((float*)(s8 + Q_.colscr)),
+          npix_t((long)B * H * W) {}
+    TRef S_(size_t off, int cs) const { return tref(s8 + off, cs); }
+    float* G(int idx) const { return grads[idx]; }
+    TRef dout() const { return S_(Q.dout, P.out_cs); }
+    TRef dU0() const { return S_(Q.dU[0], nf); }
+    // Dense gradient buffers (3, rotating): Gd = [dy5 (nf) | dy4 | dy3 | dy2 | dy1] -- the mirror image of the forward
+    // dense buffer.  Slice j of the block input gets its gradient from ONE conv over the channel prefix holding
+    // dy5..dy_{j+1} (composite transposed weights), so every gradient element is written exactly once: no
+    // read-modify-write accumulation, and the same prefix-read / slice-write pattern as forward.
+    TRef Pg(int g) const { return tref(s8 + Q.Pg[g], P.kce, 0, P.plane_bytes); }
+    int pack_dgrad(bool pack_dx) const;
+    int output_plain() const;
+    int output_tail() const;
+    int trunk_entry() const;
+    int rrdb_range(int r_lo, int r_hi) const;
+    int input_side(float* dx_nchw) const;
+};
+
+// ---- packed dgrad weights (flipped / transposed views of the canonical tensors): ONE batched launch
+int RddbBwd::pack_dgrad(bool pack_dx) const {
+    PackList packs(dt, wp);
+    const WLayout L = lay_dgrad_s1(nf, 3, 3);
+    packs.add(params[P.p_last_w], wp + P.w_last_d, nf, c->out_ch, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
+    for (int s = 0; s < P.nup; ++s)   // deconv dgrad = 2x2 s2 conv over dy: rows = ci, k = co, tap = (a,b)
+        packs.add(params[P.p_up0 + s], wp + P.w_up_d[s], nf, nf, 2, 2, (long)nf * 4, 4, 2, 1, 0);
+    for (int k = 0; k < P.nlw; ++k)
+        packs.add(params[P.p_lg[k]], wp + P.lw_d[k], nf, nf, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
+    if (P.family != RDDB_SRDN) packs.add(params[P.p_trunk_w], wp + P.w_trunk_d, nf, nf, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
+    SG_TRY(sg_fill_zero_guarded(wp + P.w_rdb_d0, P.w_rdb_dsz, pack_guard(opt), (hipStream_t)st));
+    for (int r = 0; r < P.nrr * 3; ++r) {
+        const float a5 = (r % 3 == 2) ? 0.04f : 0.2f;       // d(x5)/d(block out), RDB3 carries the RRDB 0.2 too
+        for (int j = 0; j < 5; ++j) {
+            const int rows = j == 0 ? nf : gc, ss = j == 0 ? 0 : nf + (j - 1) * gc, ktot = nf + (4 - j) * gc;
+            for (int m = 5; m > j; --m) {                   // block of K coming from forward conv m
+                const int cin_m = nf + (m - 1) * gc, cout_m = m == 5 ? nf : gc;
+                const int k_off = m == 5 ? 0 : nf + (4 - m) * gc;
+                packs.add(params[P.prdb(r) + (m - 1) * 2], wp + P.w_rdb_d[r * 5 + j], rows, cout_m, 3, 3,
+                                               9, (long)cin_m * 9, -3, -1, (long)ss * 9 + 8, k_off, ktot, m == 5 ? a5 : 1.f);
             }
         }
-        for (int s = 0; s < P.ndn; ++s)
-            for (int q = 0; q < 4; ++q) {
-                // 3x3 s2 p1 dgrad, output parity (a,b): rows with ky = a+1 (mod 2).  a=0: ky=1 (1 tap); a=1: ky=2,0 (2 taps)
-                const int a = q >> 1, bb = q & 1;
-                const int ty = a ? 2 : 1, tx = bb ? 2 : 1;
-                const long off = (a ? 2 : 1) * 3 + (bb ? 2 : 1);
-                packs.add(params[P.p_dn0 + 2 * s], wp + P.w_dn_d[s][q], nf, nf, ty, tx, 9, (long)nf * 9, -6, -2, off);
-            }
-        if (pack_dx) {
-            const WLayout L0 = lay_dgrad_s1(c->in_ch, 3, 3);
-            packs.add(params[P.p_first_w], wp + P.w_first_d, c->in_ch, nf, 3, 3, L0.sr, L0.sk, L0.sty, L0.stx, L0.off);
-        }
-        SG_TRY(packs.run(P.legacy == 1 ? (pack_dx ? "rddbB_bwd_dx" : "rddbB_bwd") : P.legacy == 2 ? (pack_dx ? "rddbL_bwd_dx" : "rddbL_bwd")
-                                       : P.legacy == 3 ? (pack_dx ? "srdn_bwd_dx" : "srdn_bwd")
-                                       : (pack_dx ? "rddb_bwd_dx" : "rddb_bwd"), params[0], st, pack_guard(opt)));
     }
+    for (int s = 0; s < P.ndn; ++s)
+        for (int q = 0; q < 4; ++q) {
+            // 3x3 s2 p1 dgrad, output parity (a,b): rows with ky = a+1 (mod 2).  a=0: ky=1 (1 tap); a=1: ky=2,0 (2 taps)
+            const int a = q >> 1, bb = q & 1;
+            const int ty = a ? 2 : 1, tx = bb ? 2 : 1;
+            const long off = (a ? 2 : 1) * 3 + (bb ? 2 : 1);
+            packs.add(params[P.p_dn0 + 2 * s], wp + P.w_dn_d[s][q], nf, nf, ty, tx, 9, (long)nf * 9, -6, -2, off);
+        }
+    if (pack_dx) {
+        const WLayout L0 = lay_dgrad_s1(c->in_ch, 3, 3);
+        packs.add(params[P.p_first_w], wp + P.w_first_d, c->in_ch, nf, 3, 3, L0.sr, L0.sk, L0.sty, L0.stx, L0.off);
+    }
+    return packs.run((std::string(P.tag) + (pack_dx ? "_bwd_dx" : "_bwd")).c_str(), params[0], st, pack_guard(opt));
+}
 
-    // ---- dy: NCHW f32 -> NHWC
-    TRef dout = S_(Q.dout, P.out_cs);
-    TRef dU0 = S_(Q.dU[0], nf);
-    if (first_phase) {
-    SG_TRY(srcgan_nchw_f32_to_nhwc(dy_nchw, dout.p, B, c->out_ch, P.HO, P.WO, P.out_cs, dt, st));
-    if (P.legacy == 1 || P.legacy == 2) {
-        // ---- legacy tail backward.  dcur = gradient w.r.t. an op's output, already times LeakyReLU' of that output.
-        TRef tin = P.legacy == 2 ? Abuf(0) : T_(P.U[0], nf);          // tail input (not an activation output)
-        auto obuf = [&](int k) { return k < 0 ? tin : T_(P.tail[k].out, nf); };
-        TRef Fl = obuf(P.ntail - 1);
-        if (G(P.p_last_w))
-            SG_TRY(wgrad_call(dt, dout, P.HO, P.WO, c->out_ch, Fl, B, P.HO, P.WO, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(P.p_last_w), st, G(P.p_last_b)));
-        else if (G(P.p_last_b)) SG_TRY(bias_grad(dt, dout, (long)B * P.HO * P.WO, c->out_ch, 1.f, G(P.p_last_b), colscr, st));
-        int pp = 0;
-        auto nextbuf = [&](int k_in) { if (k_in < 0) return dU0; pp ^= 1; return S_(Q.dU[1 + pp], nf); };   // k_in: index of the op whose output gets this gradient
-        TRef dcur = nextbuf(P.ntail - 1);
-        {
-            Conv cv(dt, 3, 3, 1);
-            cv.in(dout, B, P.HO, P.WO, P.out_cs).w(wp + P.w_last_d).out(dcur, P.HO, P.WO, nf).pad(1, 1);
-            if (P.ntail > 0 && P.tail[P.ntail - 1].conv) cv.mask(Fl, 0);
-            SG_TRY(cv.run(st));
-        }
-        bool seen[3] = {false, false, false};
-        for (int k = P.ntail - 1; k >= 0; --k) {
-            const RddbPlan::TailOp& o = P.tail[k];
-            TRef xin_k = obuf(k - 1);
-            const bool in_act = k > 0 && P.tail[k - 1].conv;          // the op's input is a LeakyReLU output
-            TRef dst = nextbuf(k - 1);
-            if (o.conv) {
-                const int pw = P.p_lg[o.w];
-                if (G(pw)) SG_TRY(wgrad_call(dt, dcur, o.hout, o.wout, nf, xin_k, B, o.hin, o.win, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(pw), st, G(pw + 1), seen[o.w] ? 1 : 0));
-                else if (G(pw + 1)) SG_REQUIRE(false, "rddbnet (legacy): a shared convolution's bias gradient needs its weight gradient too");
-                seen[o.w] = true;
-                Conv cv(dt, 3, 3, 1);
-                cv.in(dcur, B, o.hout, o.wout, nf).w(wp + P.lw_d[o.w]).out(dst, o.hin, o.win, nf).pad(1, 1);
-                if (in_act) cv.mask(xin_k, 0);
-                SG_TRY(cv.run(st));
-            } else {
-                // nearest x2 backward = 2x2 block sums; the up-sampled tensor's own LeakyReLU' (if any) is applied at its resolution
-                SG_REQUIRE(xin_k.plane == 0 || !in_act, "rddbnet (legacy): unexpected blocked activation");
-                SG_TRY(srcgan_sum2x2_nhwc(dcur.p, dcur.cs, dst.p, dst.cs, in_act ? xin_k.p : nullptr, xin_k.cs, 0.2f, B, o.hin, o.win, nf, dt, st));
-            }
-            dcur = dst;
-        }
-        // unused parameters of the forward (upconv2 in mode x2): their gradient is zero here, None in the reference
-        for (int k = 0; k < P.nlw; ++k)
-            if (!seen[k]) {
-                if (G(P.p_lg[k])) SG_HIP(hipMemsetAsync(G(P.p_lg[k]), 0, (size_t)nf * nf * 9 * sizeof(float), (hipStream_t)st));
-                if (G(P.p_lg[k] + 1)) SG_HIP(hipMemsetAsync(G(P.p_lg[k] + 1), 0, (size_t)nf * sizeof(float), (hipStream_t)st));
-            }
-    } else {
+// ---- output side of the ConvTranspose families: conv_last, then the up-sampler stages; leaves d(U[0]) in dU0
+int RddbBwd::output_plain() const {
     // conv_last
-    TRef Ul = T_(P.U[P.nst], nf);
+    TRef Ul = T_(N.U[P.nup], nf);
     if (G(P.p_last_w))
-        SG_TRY(wgrad_call(dt, dout, P.HO, P.WO, c->out_ch, Ul, B, P.HO, P.WO, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(P.p_last_w), st));
+        SG_TRY(wgrad_call(dt, dout(), P.HO, P.WO, c->out_ch, Ul, B, P.HO, P.WO, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(P.p_last_w), st));
     {
         Conv cv(dt, 3, 3, 1);
-        cv.in(dout, B, P.HO, P.WO, P.out_cs).w(wp + P.w_last_d).out(S_(Q.dU[P.nst], nf), P.HO, P.WO, nf).pad(1, 1);
-        if (P.nst > 0) {                      // LeakyReLU after the last deconv
-            if (P.um_bytes && up_mask_written(P)) { cv.sign_in(w8 + P.um); cv.d.mslope = 0.2f; }
+        cv.in(dout(), B, P.HO, P.WO, P.out_cs).w(wp + P.w_last_d).out(S_(Q.dU[P.nup], nf), P.HO, P.WO, nf).pad(1, 1);
+        if (P.nup > 0) {                      // LeakyReLU after the last deconv
+            if (N.um_bytes) { cv.sign_in(w8 + N.um); cv.d.mslope = 0.2f; }
             else cv.mask(Ul, 0);
         }
         SG_TRY(cv.run(st));
     }
     // up-sampler stages, last to first
-    for (int s = P.nst - 1; s >= 0; --s) {
+    for (int s = P.nup - 1; s >= 0; --s) {
         const int h = H << s, w = W << s;
-        TRef dHR = S_(Q.dU[s + 1], nf), Us = T_(P.U[s], nf);
+        TRef dHR = S_(Q.dU[s + 1], nf), Us = T_(N.U[s], nf);
         if (G(P.p_up0 + s))   // dW[ci][co][a][b] = sum x[y,x,ci] * dy[2y+a,2x+b,co]: wgrad with roles (dy := x, x := dy), k2 s2
             SG_TRY(wgrad_call(dt, Us, h, w, nf, dHR, B, 2 * h, 2 * w, nf, 2, 2, 2, 0, 0, WLayout{(long)nf * 4, 4, 2, 1, 0}, 1.f, slab, G(P.p_up0 + s), st));
         Conv cv(dt, 2, 2, 2);
@@ -721,38 +682,82 @@ extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const flo
         if (s > 0) cv.mask(Us, 0);
         SG_TRY(cv.run(st));
     }
+    return 0;
+}
+
+// ---- output side of the nearest-x2 tail families: conv_last (with bias), then the tail's op list; leaves d(tail input) in dU0.
+// dcur = gradient w.r.t. an op's output, already times LeakyReLU' of that output.
+int RddbBwd::output_tail() const {
+    TRef tin = P.family == RDDB_LEGACY ? Abuf(0) : T_(N.U[0], nf);          // tail input (not an activation output)
+    auto obuf = [&](int k) { return k < 0 ? tin : T_(N.tail[k], nf); };
+    TRef Fl = obuf(P.ntail - 1);
+    if (G(P.p_last_w))
+        SG_TRY(wgrad_call(dt, dout(), P.HO, P.WO, c->out_ch, Fl, B, P.HO, P.WO, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(P.p_last_w), st, G(P.p_last_b)));
+    else if (G(P.p_last_b)) SG_TRY(bias_grad(dt, dout(), (long)B * P.HO * P.WO, c->out_ch, 1.f, G(P.p_last_b), colscr, st));
+    int pp = 0;
+    auto nextbuf = [&](int k_in) { if (k_in < 0) return dU0(); pp ^= 1; return S_(Q.dU[1 + pp], nf); };   // k_in: index of the op whose output gets this gradient
+    TRef dcur = nextbuf(P.ntail - 1);
+    {
+        Conv cv(dt, 3, 3, 1);
+        cv.in(dout(), B, P.HO, P.WO, P.out_cs).w(wp + P.w_last_d).out(dcur, P.HO, P.WO, nf).pad(1, 1);
+        if (P.ntail > 0 && P.tail[P.ntail - 1].conv) cv.mask(Fl, 0);
+        SG_TRY(cv.run(st));
     }
-    }                            // first_phase: everything behind the trunk
-    TRef dfea = dU0;
-    if (P.legacy != 2) {
-    // U0 = fea + trunk_conv(T): d(trunk_conv out) = dU0, d(fea) += dU0 (joined at the end)
-    TRef Tt = T_(P.T, nf), dT = S_(Q.dT, nf);
-    if (first_phase && P.legacy != 3) {
-    if (G(P.p_trunk_w))
-        SG_TRY(wgrad_call(dt, dU0, H, W, nf, Tt, B, H, W, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(P.p_trunk_w), st, G(P.p_trunk_b)));
-    else if (G(P.p_trunk_b)) SG_TRY(bias_grad(dt, dU0, npix_t, nf, 1.f, G(P.p_trunk_b), colscr, st));
+    bool seen[3] = {false, false, false};
+    for (int k = P.ntail - 1; k >= 0; --k) {
+        const RddbPlan::TailOp& o = P.tail[k];
+        TRef xin_k = obuf(k - 1);
+        const bool in_act = k > 0 && P.tail[k - 1].conv;          // the op's input is a LeakyReLU output
+        TRef dst = nextbuf(k - 1);
+        if (o.conv) {
+            const int pw = P.p_lg[o.w];
+            if (G(pw)) SG_TRY(wgrad_call(dt, dcur, o.hout, o.wout, nf, xin_k, B, o.hin, o.win, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(pw), st, G(pw + 1), seen[o.w] ? 1 : 0));
+            else if (G(pw + 1)) SG_REQUIRE(false, "rddbnet (legacy): a shared convolution's bias gradient needs its weight gradient too");
+            seen[o.w] = true;
+            Conv cv(dt, 3, 3, 1);
+            cv.in(dcur, B, o.hout, o.wout, nf).w(wp + P.lw_d[o.w]).out(dst, o.hin, o.win, nf).pad(1, 1);
+            if (in_act) cv.mask(xin_k, 0);
+            SG_TRY(cv.run(st));
+        } else {
+            // nearest x2 backward = 2x2 block sums; the up-sampled tensor's own LeakyReLU' (if any) is applied at its resolution
+            SG_REQUIRE(xin_k.plane == 0 || !in_act, "rddbnet (legacy): unexpected blocked activation");
+            SG_TRY(srcgan_sum2x2_nhwc(dcur.p, dcur.cs, dst.p, dst.cs, in_act ? xin_k.p : nullptr, xin_k.cs, 0.2f, B, o.hin, o.win, nf, dt, st));
+        }
+        dcur = dst;
     }
-    // Dense gradient buffers (3, rotating): Gd = [dy5 (nf) | dy4 | dy3 | dy2 | dy1] -- the mirror image of the forward
-    // dense buffer.  Slice j of the block input gets its gradient from ONE conv over the channel prefix holding
-    // dy5..dy_{j+1} (composite transposed weights), so every gradient element is written exactly once: no
-    // read-modify-write accumulation, and the same prefix-read / slice-write pattern as forward.
-    auto Pg = [&](int g) { return tref(s8 + Q.Pg[g], P.kce, 0, P.plane_bytes); };
-    if (!first_phase) {
-    } else if (P.legacy == 3) {
-        // SRDN: d(decoder output) = d(fea2) = dU0 itself (no trunk_conv): into the first gradient buffer's channels [0,nf)
-        TRef g0 = Pg(0);
+    // unused parameters of the forward (upconv2 in mode x2): their gradient is zero here, None in the reference
+    for (int k = 0; k < P.nlw; ++k)
+        if (!seen[k]) {
+            if (G(P.p_lg[k])) SG_HIP(hipMemsetAsync(G(P.p_lg[k]), 0, (size_t)nf * nf * 9 * sizeof(float), (hipStream_t)st));
+            if (G(P.p_lg[k] + 1)) SG_HIP(hipMemsetAsync(G(P.p_lg[k] + 1), 0, (size_t)nf * sizeof(float), (hipStream_t)st));
+        }
+    return 0;
+}
+
+// ---- from dU0 into channels [0,nf) of the first dense gradient buffer
+int RddbBwd::trunk_entry() const {
+    if (!P.has_trunk_conv) {
+        // SRDN: d(decoder output) = d(fea2) = dU0 itself (no trunk_conv)
+        TRef g0 = Pg(0), d0 = dU0();
         SG_HIP(hipMemsetAsync(g0.p, 0, (size_t)cdiv(nf, P.kce) * P.plane_bytes, (hipStream_t)st));
-        SG_TRY(srcgan_add_inplace_planes(g0.p, g0.cs, 0, g0.plane, dU0.p, dU0.cs, 0, 0, nullptr, 0, 0, 0, 0.f, npix_t, nf, dt, st));
-    } else
-    SG_TRY(Conv(dt, 3, 3, 1).in(dU0, B, H, W, nf).w(wp + P.w_trunk_d).out(Pg(0), H, W, nf).pad(1, 1).run(st));
-    (void)dT;
+        return srcgan_add_inplace_planes(g0.p, g0.cs, 0, g0.plane, d0.p, d0.cs, 0, 0, nullptr, 0, 0, 0, 0.f, npix_t, nf, dt, st);
+    }
+    // U0 = fea + trunk_conv(T): d(trunk_conv out) = dU0, d(fea) += dU0 (joined on the input side)
+    if (G(P.p_trunk_w))
+        SG_TRY(wgrad_call(dt, dU0(), H, W, nf, T_(N.T, nf), B, H, W, nf, 3, 3, 1, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(P.p_trunk_w), st, G(P.p_trunk_b)));
+    else if (G(P.p_trunk_b)) SG_TRY(bias_grad(dt, dU0(), npix_t, nf, 1.f, G(P.p_trunk_b), colscr, st));
+    return Conv(dt, 3, 3, 1).in(dU0(), B, H, W, nf).w(wp + P.w_trunk_d).out(Pg(0), H, W, nf).pad(1, 1).run(st);
+}
+
+// ---- the RRDBs [r_lo, r_hi), last to first
+int RddbBwd::rrdb_range(int r_lo, int r_hi) const {
     for (int i = r_hi - 1; i >= r_lo; --i) {
-        if (P.legacy == 3 && i == c->nb - 1) {
+        if (P.family == RDDB_SRDN && i == c->nb - 1) {
             // between the stacks: d(fea1) = d(fea2) + d(decoder input); it feeds the encoder's output AND the skip around it
-            TRef g0 = Pg(0);
-            SG_TRY(srcgan_add_inplace_planes(g0.p, g0.cs, 0, g0.plane, dU0.p, dU0.cs, 0, 0, nullptr, 0, 0, 0, 0.f, npix_t, nf, dt, st));
-            SG_HIP(hipMemsetAsync(dU0.p, 0, (size_t)npix_t * nf * P.esz, (hipStream_t)st));
-            SG_TRY(srcgan_add_inplace_planes(dU0.p, dU0.cs, 0, 0, g0.p, g0.cs, 0, g0.plane, nullptr, 0, 0, 0, 0.f, npix_t, nf, dt, st));
+            TRef g0 = Pg(0), d0 = dU0();
+            SG_TRY(srcgan_add_inplace_planes(g0.p, g0.cs, 0, g0.plane, d0.p, d0.cs, 0, 0, nullptr, 0, 0, 0, 0.f, npix_t, nf, dt, st));
+            SG_HIP(hipMemsetAsync(d0.p, 0, (size_t)npix_t * nf * P.esz, (hipStream_t)st));
+            SG_TRY(srcgan_add_inplace_planes(d0.p, d0.cs, 0, 0, g0.p, g0.cs, 0, g0.plane, nullptr, 0, 0, 0, 0.f, npix_t, nf, dt, st));
         }
         for (int j3 = 2; j3 >= 0; --j3) {                  // RDB3, RDB2, RDB1 use Pg(0), Pg(1), Pg(2)
             const int r = i * 3 + j3, g = 2 - j3;
@@ -768,7 +773,7 @@ extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const flo
                 if (j > 0) {
                     // slice x_j is a LeakyReLU output: multiply by its derivative -> this IS dy_j
                     cv.out(sl(Gd, nf + (4 - j) * gc), H, W, gc);
-                    if (P.bm_bytes) { cv.sign_in((const char*)A.p + P.bm + (size_t)(j - 1) * P.bm_bytes); cv.d.mslope = 0.2f; }
+                    if (N.bm_bytes) { cv.sign_in((const char*)A.p + N.bm + (size_t)(j - 1) * N.bm_bytes); cv.d.mslope = 0.2f; }
                     else cv.mask(sl(A, nf + (j - 1) * gc), 0);
                 } else {
                     cv.out(nxt, H, W, nf).res1(Gd, nf, bres);
@@ -800,17 +805,23 @@ extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const flo
             SG_TRY(slice_grad(1));
         }
     }
-    if (!last_phase) return 0;
-    TRef dcur = Pg(0);
-    // gradient w.r.t. the trunk input feature = dcur + dU0 (global skip); for the HR->LR variant the trunk input
-    // is a LeakyReLU output, so its derivative is applied in the same pass.
-    TRef trunk_in = Abuf(0);
-    SG_TRY(srcgan_add_inplace_planes(dU0.p, dU0.cs, dU0.coff, dU0.plane, dcur.p, dcur.cs, dcur.coff, dcur.plane,
-                                     P.ndn ? trunk_in.p : nullptr, trunk_in.cs, 0, trunk_in.plane, 0.2f, npix_t, nf, dt, st));
-    }                            // (dU0 is not needed any more: the join is accumulated into it, NHWC)
+    return 0;
+}
+
+// ---- input side: the global-skip join, the down stages, conv_first, dx
+int RddbBwd::input_side(float* dx_nchw) const {
+    TRef dfea = dU0();
+    if (P.nrr) {
+        // gradient w.r.t. the trunk input feature = dcur + dU0 (global skip); for the HR->LR variant the trunk input
+        // is a LeakyReLU output, so its derivative is applied in the same pass.
+        // (dU0 is not needed any more: the join is accumulated into it, NHWC)
+        TRef dcur = Pg(0), trunk_in = Abuf(0);
+        SG_TRY(srcgan_add_inplace_planes(dfea.p, dfea.cs, dfea.coff, dfea.plane, dcur.p, dcur.cs, dcur.coff, dcur.plane,
+                                         P.ndn ? trunk_in.p : nullptr, trunk_in.cs, 0, trunk_in.plane, 0.2f, npix_t, nf, dt, st));
+    }
     for (int s = P.ndn - 1; s >= 0; --s) {     // 3x3 s2 p1 stages of RDDBNetA, last to first
         const int hi = c->H >> s, wi = c->W >> s, ho = hi / 2, wo = wi / 2;
-        TRef xin_s = s == 0 ? T_(P.fea0, nf) : T_(P.dn[s - 1], nf);
+        TRef xin_s = s == 0 ? T_(N.fea0, nf) : T_(N.dn[s - 1], nf);
         const int pw = P.p_dn0 + 2 * s;
         if (G(pw)) SG_TRY(wgrad_call(dt, dfea, ho, wo, nf, xin_s, B, hi, wi, nf, 3, 3, 2, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(pw), st, G(pw + 1)));
         else if (G(pw + 1)) SG_TRY(bias_grad(dt, dfea, (long)B * ho * wo, nf, 1.f, G(pw + 1), colscr, st));
@@ -826,7 +837,7 @@ extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const flo
         dfea = dst;
     }
     // conv_first
-    TRef xin = T_(P.xin, P.in_cs);
+    TRef xin = T_(N.xin, P.in_cs);
     if (G(P.p_first_w))
         SG_TRY(wgrad_call(dt, dfea, c->H, c->W, nf, xin, B, c->H, c->W, c->in_ch, 3, 3, 1, 1, 1, lay_fwd(c->in_ch, 3, 3), 1.f, slab, G(P.p_first_w), st, G(P.p_first_b)));
     else if (G(P.p_first_b)) SG_TRY(bias_grad(dt, dfea, (long)B * c->H * c->W, nf, 1.f, G(P.p_first_b), colscr, st));
@@ -836,6 +847,42 @@ extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const flo
         SG_TRY(Conv(dt, 3, 3, 1).in(dfea, B, c->H, c->W, nf).w(wp + P.w_first_d).out(dxin, c->H, c->W, c->in_ch).pad(1, 1).run(st));
         SG_TRY(srcgan_nhwc_to_nchw_f32(dxin.p, dx_nchw, B, c->in_ch, c->H, c->W, P.in_cs, 0, dt, st));
     }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int srcgan_rddbnet_backward_ex(const srcgan_rddbnet_cfg* c, const float* dy_nchw, const float* const* params,
+                                          void* ws, void* scratch, float* const* grads, float* dx_nchw, const srcgan_net_opts* opt, void* st) {
+    RddbPlan P;
+    SG_TRY(rddb_plan(c, P));
+    RddbNames N;
+    rddb_train_names(c, P, N);
+    RddbBwdPlan Q;
+    rddb_bwd_plan(c, P, Q);
+    SG_REQUIRE(dy_nchw && params && ws && scratch && grads, "srcgan_rddbnet_backward: null pointer");
+    SG_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)scratch % 256) == 0, "srcgan_rddbnet_backward: buffers must be 256-byte aligned");
+    // Phased backward (data parallel: the gradients of the RRDBs a phase covers are final when it returns, so their all-reduce
+    // starts while earlier blocks still compute).  A call handles the RRDBs [lo, hi), last to first; the call with hi == nrr also
+    // runs everything behind the trunk (conv_last, up-sampler, trunk_conv), the call with lo == 0 everything in front of it
+    // (conv_first / down-sampling stages, dx).  Calls must come in descending, gap-free order on one stream with the same
+    // scratch: the running gradient sits in the scratch between them.  srcgan_rddbnet_phase_params names a phase's parameters.
+    int r_lo = 0, r_hi = P.nrr;
+    if (opt && opt->rrdb_hi > 0) { r_lo = opt->rrdb_lo; r_hi = opt->rrdb_hi; }
+    SG_REQUIRE(r_lo >= 0 && r_lo <= r_hi && r_hi <= P.nrr, "srcgan_rddbnet_backward: RRDB range [%d,%d) outside [0,%d)", r_lo, r_hi, P.nrr);
+    SG_REQUIRE(P.nrr > 0 || (r_lo == 0), "srcgan_rddbnet_backward: a network without a trunk has one phase");
+    const bool first_phase = r_hi == P.nrr, last_phase = r_lo == 0;
+    const RddbBwd K(RddbCall(c, P, N, params, ws, opt, st), Q, scratch, grads);
+    if (first_phase) {
+        const bool pack_dx = dx_nchw || (opt && opt->wpack);       // a persistent pack serves later calls that may want dx
+        if (K.do_pack) SG_TRY(K.pack_dgrad(pack_dx));
+        // dy: NCHW f32 -> NHWC
+        SG_TRY(srcgan_nchw_f32_to_nhwc(dy_nchw, K.dout().p, c->B, c->out_ch, P.HO, P.WO, P.out_cs, c->dtype, st));
+        SG_TRY(P.x2_tail ? K.output_tail() : K.output_plain());
+        if (P.nrr) SG_TRY(K.trunk_entry());
+    }
+    SG_TRY(K.rrdb_range(r_lo, r_hi));
+    if (last_phase) SG_TRY(K.input_side(dx_nchw));
     return 0;
 }
 

@@ -179,24 +179,13 @@ class GradSync:
         return sorted({(nrr * j) // k for j in range(k)})
 
     @torch.no_grad()
-    def phase_done(self, arena, params, cfg, lo: int, hi: int, nrr: int) -> None:
-        """The native call that finalised the gradients of RRDBs [lo, hi) (+ tail if hi == nrr, + head if lo == 0; everything when
-        nrr == 0) has been queued on the current stream: reduce that slice of the arena on the side stream, in place."""
+    def phase_done(self, arena, params, first: int, end: int, last: bool) -> None:
+        """The native call that finalised the gradients of the parameters [first, end) (for a generator phase: what
+        ``srcgan_rddbnet_phase_params`` names) has been queued on the current stream: reduce that slice of the arena on the side
+        stream, in place.  ``last``: the backward call is complete with this phase."""
         if not self._active or arena is None or arena.flat.numel() == 0 or self._deferred(params):
             return
-        n = len(params)
-        if nrr > 0 and not (lo == 0 and hi == nrr):
-            ndn = 0
-            d = int(getattr(cfg, "down", 0))
-            while d > 1:
-                ndn, d = ndn + 1, d >> 1
-            p_rdb0 = 2 + 2 * ndn
-            i0 = p_rdb0 + 30 * lo if lo > 0 else 0
-            i1 = n if hi == nrr else p_rdb0 + 30 * hi
-        else:
-            i0, i1 = 0, n
-        a, b = arena.offsets[i0], arena.offsets[i1]
-        last = (lo == 0)
+        a, b = arena.offsets[first], arena.offsets[end]
         flat = arena.flat
         cuda = flat.is_cuda
         main = torch.cuda.current_stream(flat.device) if cuda else None

@@ -217,14 +217,14 @@ class _RddbFn(torch.autograd.Function):
         opt = pstate.opts(lib.srcgan_rddbnet_wpack_bytes, cfg, params, ctx.layout, True, dy.device) if pstate is not None else N.NetOpts(None, 0, 0, 0, None)
         gptr, pptr = N.ptr_array(grads), N.ptr_array(params)
         hook = ctx.phase_hook
-        nrr = 0 if cfg.legacy == 2 else (2 * cfg.nb if cfg.legacy == 3 else cfg.nb)
+        nrr = lib.srcgan_rddbnet_num_rrdb(C.byref(cfg))
         # phases: RRDB ranges, last to first (one phase unless a data-parallel hook asks for more)
         cuts = hook.cuts(cfg, nrr, params) if (hook is not None and nrr > 1) else [0]
         hi = nrr
         for lo in sorted(set(cuts) | {0}, reverse=True):
             if lo >= hi and hi != nrr:
                 continue
-            opt.rrdb_lo, opt.rrdb_hi = (lo, hi) if nrr > 0 else (0, 0)
+            opt.rrdb_lo, opt.rrdb_hi = lo, hi
             N.check(lib.srcgan_rddbnet_backward_ex(C.byref(cfg), dy.data_ptr(), pptr, ctx.ws.data_ptr(), scratch.data_ptr(), gptr,
                                                    dx.data_ptr() if need_dx else None, C.byref(opt), N.stream_ptr(dy.device)),
                     "srcgan_rddbnet_backward")
@@ -232,7 +232,9 @@ class _RddbFn(torch.autograd.Function):
                 pstate.done(True)
             opt.pack = 0
             if hook is not None:
-                hook.phase_done(arena, params, cfg, lo, hi, nrr)
+                first, end = C.c_int(), C.c_int()
+                N.check(lib.srcgan_rddbnet_phase_params(C.byref(cfg), lo, hi, C.byref(first), C.byref(end)), "srcgan_rddbnet_phase_params")
+                hook.phase_done(arena, params, first.value, end.value, lo == 0)
             hi = lo
         ctx.ws = None
         return (dx, None, *grads)
@@ -249,7 +251,7 @@ def _rddb_infer(x, cfg_items, params):
     ws = N.workspace(lib.srcgan_rddbnet_infer_ws_bytes(C.byref(cfg)), x.device)
     opt = pstate.opts(lib.srcgan_rddbnet_wpack_bytes, cfg, plist, layout, False, x.device) if pstate is not None else None
     N.check(lib.srcgan_rddbnet_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(),
-                                     C.byref(opt) if opt is not None else None, 0, N.stream_ptr(x.device)), "srcgan_rddbnet_infer")
+                                     C.byref(opt) if opt is not None else None, N.stream_ptr(x.device)), "srcgan_rddbnet_infer")
     if pstate is not None:
         pstate.done(False)
     return y
@@ -263,9 +265,9 @@ def _rddb_forward(x, cfg_items, params):
 
 
 # Data-parallel hooks (srcgan_amd.dist.GradSync.attach): an object with ``cuts(nrr) -> [rrdb indices]`` (phase boundaries of the
-# generator's backward) and ``phase_done(arena, params, cfg, lo, hi, nrr)``, called right after the native call that finalised the
-# gradients of RRDBs [lo, hi) (plus the tail when hi == nrr, the head when lo == 0) was queued: the hook launches their all-reduce
-# on its side stream while the next phase computes.
+# generator's backward) and ``phase_done(arena, params, first, end, last)``, called right after the native call that finalised the
+# gradients of the parameters [first, end) (``srcgan_rddbnet_phase_params``; ``last``: the backward is complete) was queued: the hook
+# launches their all-reduce on its side stream while the next phase computes.
 _phase_hooks = {}
 
 
@@ -451,7 +453,7 @@ class _ResDeconvFn(torch.autograd.Function):
                                               N.ptr_array(grads), dx.data_ptr() if need_dx else None, N.stream_ptr(dy.device)), "srcgan_resdeconv_backward")
         ctx.ws = None
         if ctx.phase_hook is not None:
-            ctx.phase_hook.phase_done(arena, params, cfg, 0, 0, 0)
+            ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
         return (dx, None, None, None, None, *grads)
 
 
@@ -582,7 +584,7 @@ class _SrNetFn(torch.autograd.Function):
                                           N.ptr_array(grads), dx.data_ptr() if need_dx else None, N.stream_ptr(dy.device)), "srcgan_srnet_backward")
         ctx.ws = None
         if ctx.phase_hook is not None:
-            ctx.phase_hook.phase_done(arena, params, cfg, 0, 0, 0)
+            ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
         return (dx, None, *grads)
 
 
@@ -744,7 +746,7 @@ class _NLayerDFn(torch.autograd.Function):
         ctx.pstate.done(True)
         ctx.ws = None
         if ctx.phase_hook is not None and arena is not None:
-            ctx.phase_hook.phase_done(arena, params, cfg, 0, 0, 0)
+            ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
         return (dx, None, None, None, *grads)
 
 

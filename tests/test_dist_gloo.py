@@ -49,20 +49,24 @@ def _worker(rank, world, port, q):
         dist.all_reduce(cover)
         assert torch.equal(cover, torch.ones(37))
         # 4. the in-backward form: arena slices of generator phases, reduced in place; together they cover the arena exactly once
-        import types
+        import ctypes as C
+        from srcgan_amd import _native as N
         from srcgan_amd.model import _GradArena
         nb = 5
         shapes = [(4, 3), (4,)] + [(2, 2)] * (30 * nb) + [(4, 4), (4,), (3, 3), (1, 3)]
         ps = [torch.nn.Parameter(torch.zeros(s)) for s in shapes]
         arena = _GradArena(ps, [True] * len(ps))
         arena.flat.copy_(torch.arange(arena.flat.numel(), dtype=torch.float32) * (rank + 1))
-        cfg = types.SimpleNamespace(legacy=0, down=0)
+        cfg = N.RddbCfg(3, 3, 2, 8, nb, 8, 1, 8, 8, N.F32, 0, 0)       # the plain order with nb = 5, up = 2: the 156 shapes above
+        assert N.lib().srcgan_rddbnet_num_params(C.byref(cfg)) == len(ps) and N.lib().srcgan_rddbnet_num_rrdb(C.byref(cfg)) == nb
         gs = sd.GradSync(bucket_mb=0.0001, phases=3)
         cuts = gs.cuts(cfg, nb)
         assert cuts[0] == 0 and len(cuts) == 3, cuts
         hi = nb
         for lo in sorted(cuts, reverse=True):
-            gs.phase_done(arena, ps, cfg, lo, hi, nb)
+            first, end = C.c_int(), C.c_int()
+            N.check(N.lib().srcgan_rddbnet_phase_params(C.byref(cfg), lo, hi, C.byref(first), C.byref(end)), "srcgan_rddbnet_phase_params")
+            gs.phase_done(arena, ps, first.value, end.value, lo == 0)
             hi = lo
         want = torch.arange(arena.flat.numel(), dtype=torch.float32) * (sum(range(1, world + 1)) / world)
         assert torch.allclose(arena.flat, want), float((arena.flat - want).abs().max())
@@ -89,7 +93,7 @@ def _worker(rank, world, port, q):
         for call in range(3):                                            # three backward calls of one step
             ar = _GradArena(ps2, [True] * len(ps2))
             ar.flat.copy_(torch.arange(ar.flat.numel(), dtype=torch.float32) + 10.0 * call + rank)
-            gs2.phase_done(ar, [p.detach() for p in ps2], types.SimpleNamespace(legacy=0, down=0), 0, 0, 0)      # must not reduce
+            gs2.phase_done(ar, [p.detach() for p in ps2], 0, len(ps2), True)      # must not reduce
             for p, v in zip(ps2, ar.views):                              # what AccumulateGrad does: adopt, then add in place
                 if p.grad is None:
                     p.grad = v

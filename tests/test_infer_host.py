@@ -129,3 +129,75 @@ def test_bench_configuration(lib, capsys):
     # one 3 x 2048 x 2048 -> 8192 x 8192 scene has 4 x the pixels
     s = _cfg(up=4, nb=23, B=1, H=2048, W=2048, dtype=1)
     assert l.srcgan_rddbnet_infer_ws_bytes(C.byref(s)) < l.srcgan_rddbnet_ws_bytes(C.byref(s)) / 5
+
+
+# ---- parameter layout questions the native planner answers (srcgan_rddbnet_num_rrdb / srcgan_rddbnet_phase_params)
+LAYOUT = {**{k: FAMILIES[k] for k in ("rddbnet_x1", "rddbnet_x4", "rddbneta_d2", "rddbneta_d4", "srdn", "rddbnetb_x2", "rddbnetb_x4")},
+          "legacy_x1": dict(up=1, legacy=2), "legacy_x4": dict(up=4, legacy=2)}
+
+
+def _phase(l, c, lo, hi):
+    first, end = C.c_int(-1), C.c_int(-1)
+    rc = l.srcgan_rddbnet_phase_params(C.byref(c), lo, hi, C.byref(first), C.byref(end))
+    return rc, first.value, end.value
+
+
+def test_layout_symbols_are_declared_bound_and_exported(lib):
+    from srcgan_amd import _native as N
+    _, path = lib
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"\bT (srcgan_[a-z0-9_]+)", out))
+    for s in ("srcgan_rddbnet_num_rrdb", "srcgan_rddbnet_phase_params"):
+        assert s in header_symbols() and s in N.SIGNATURES and s in exported, s
+
+
+@pytest.mark.parametrize("nb", [1, 5])
+@pytest.mark.parametrize("name", sorted(LAYOUT))
+def test_phase_ranges_tile_the_parameters(lib, name, nb):
+    l, _ = lib
+    kw = LAYOUT[name]
+    c = _cfg(nb=nb, **kw)
+    n, nrr = l.srcgan_rddbnet_num_params(C.byref(c)), l.srcgan_rddbnet_num_rrdb(C.byref(c))
+    assert n > 0 and nrr == {0: nb, 1: nb, 2: 0, 3: 2 * nb}[kw.get("legacy", 0)]
+    assert _phase(l, c, 0, nrr) == (0, 0, n)                    # one phase (also the network without a trunk): everything
+    # every gap-free descending cut list: its ranges tile [0, n) exactly once, last phase first
+    for mask in range(1 << max(nrr - 1, 0)):
+        cuts = [0] + [k for k in range(1, nrr) if mask >> (k - 1) & 1]
+        hi, want_end = nrr, n
+        for lo in sorted(cuts, reverse=True):
+            rc, first, end = _phase(l, c, lo, hi)
+            assert rc == 0 and 0 <= first < end == want_end, (cuts, lo, hi, first, end)
+            hi, want_end = lo, first
+        assert want_end == 0, cuts
+
+
+@pytest.mark.parametrize("down", [0, 2, 4])
+def test_phase_ranges_of_the_plain_order(lib, down):
+    """conv_first (2), the down stages (2 each), 30 parameters per RRDB, then trunk_conv / up-sampler / conv_last."""
+    l, _ = lib
+    nb = 5
+    c = _cfg(nb=nb, up=1 if down else 2, down=down)
+    n = l.srcgan_rddbnet_num_params(C.byref(c))
+    p_rdb0 = 2 + 2 * (down.bit_length() - 1 if down else 0)
+    assert l.srcgan_rddbnet_num_rrdb(C.byref(c)) == nb
+    for lo in range(nb + 1):
+        for hi in range(lo, nb + 1):
+            want = (0, 0 if lo == 0 else p_rdb0 + 30 * lo, n if hi == nb else p_rdb0 + 30 * hi)
+            assert _phase(l, c, lo, hi) == want, (lo, hi)
+
+
+def test_layout_functions_reject_bad_input(lib):
+    l, _ = lib
+    for c in (_cfg(nf=60), _cfg(legacy=4), _cfg(up=2, down=2)):
+        assert l.srcgan_rddbnet_ws_bytes(C.byref(c)) == 0
+        want = l.srcgan_last_error()
+        assert want
+        assert l.srcgan_rddbnet_num_rrdb(C.byref(c)) == -1 and l.srcgan_last_error() == want
+        assert _phase(l, c, 0, 1)[0] != 0 and l.srcgan_last_error() == want
+    ok = _cfg(nb=3, up=2)
+    for lo, hi in ((-1, 2), (2, 1), (0, 4), (4, 4)):
+        assert _phase(l, ok, lo, hi) == (1, -1, -1), (lo, hi)
+        assert b"outside [0,3)" in l.srcgan_last_error()
+    legacy = _cfg(up=2, legacy=2)                               # no trunk: [0, 0) is the only range
+    assert _phase(l, legacy, 0, 1)[0] != 0 and l.srcgan_last_error()
+    assert l.srcgan_rddbnet_phase_params(C.byref(ok), 0, 3, None, None) != 0 and l.srcgan_last_error()
