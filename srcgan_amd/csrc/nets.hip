@@ -3,8 +3,9 @@
 // conv_wgrad.hip and elementwise.hip on the caller's stream (no allocation, no synchronisation:
 // graph-capturable).
 //
-//   RDDBNet            reference src/model/rddb.py:48-114
-//   NLayerDiscriminator reference src/model/model.py:595-639
+//   RRDB generators (RDDBNet, RDDBNetA, RDDBNetB, legacy RDDBNet, SRDN)   reference src/model/rddb.py:48-114, model.py:347-440, srdn.py
+//   NLayerDiscriminator (PatchGAN, BatchNorm2d / InstanceNorm2d)          reference src/model/model.py:595-639
+//   op-list networks: ResDeconv, ESPCN, SRCNN, EDSR                        reference src/model/{resdeconv,espcn,srcnn,edsr}.py
 //
 // Memory design (HBM): activations live in NHWC.  Each ResidualDenseBlock_5 owns ONE dense buffer of
 // nf+4*gc channels; conv k reads the channel prefix [0, nf+(k-1)gc) and writes its own slice, so the
@@ -13,6 +14,7 @@
 // channels [0,nf) of the next block's dense buffer.  Backward mirrors this with a dense *gradient*
 // buffer per block that the dgrads of conv5..conv1 accumulate into in place.
 #include "common.h"
+#include <algorithm>
 #include <vector>
 #include <map>
 #include <string>
@@ -62,6 +64,17 @@ struct WLayout { long sr, sk, sty, stx, off; };
 static inline WLayout lay_fwd(int cin, int kh, int kw) { return {(long)cin * kh * kw, (long)kh * kw, kw, 1, 0}; }
 // Conv2d dgrad for stride 1: rows = ci, k = co, taps flipped
 static inline WLayout lay_dgrad_s1(int cin, int kh, int kw) { return {(long)kh * kw, (long)cin * kh * kw, -kw, -1, (long)kh * kw - 1}; }
+// Input gradient of a k x k stride-2 convolution with padding `pad`, by output parity a (0 / 1) along one axis:
+//   dx[2 j + a] = sum over the kernel rows ky == (a + pad) mod 2 of dy[j + (a + pad - ky) / 2] * w[ky]
+// -> a stride-1 sub-convolution with n taps; tap t (ascending dy row) uses ky = ky_max - 2 t and needs `lead` rows above row j.
+// (4x4 p1: 2 taps, ky_max 3 / 2, lead 1 / 0;  3x3 p1: 1 / 2 taps, lead 0;  7x7 p3: 3 / 4 taps)
+struct Par2 { int n, ky_max, lead; };
+static inline Par2 par2(int k, int pad, int a) {
+    int ky_max = k - 1;
+    if (((ky_max ^ (a + pad)) & 1) != 0) --ky_max;
+    Par2 r; r.ky_max = ky_max; r.n = ky_max >= 0 ? ky_max / 2 + 1 : 0; r.lead = (ky_max - a - pad) / 2;
+    return r;
+}
 
 struct Bump {   // workspace bump allocator (256-byte aligned)
     size_t off = 0;
@@ -105,6 +118,7 @@ struct PackList {
         sg_pack_job_finish(j, dtype, nblk);
         jobs.push_back(j);
     }
+    void add(const float* w, void* wp, int rows, int kdim, int tys, int txs, WLayout L) { add(w, wp, rows, kdim, tys, txs, L.sr, L.sk, L.sty, L.stx, L.off); }
     int run(const char* tag, const void* key_ptr, void* st, const unsigned long long* guard = nullptr) {
         if (jobs.empty()) return 0;
         int dev = 0;
@@ -144,6 +158,54 @@ static inline const unsigned long long* pack_guard(const srcgan_net_opts* o) {
     return (o && o->wpack && o->pack == 2) ? (const unsigned long long*)o->guard : nullptr;
 }
 
+// ---- the input gradient of a k x k, stride 2, padding `pad` convolution cin -> cout: four stride-1 sub-convolutions over dy, one
+// per output parity q = (a, b) = (q >> 1, q & 1), each with its own pack of par2() taps per axis (rows = cin, k = cout), made
+// from the canonical weight w [cout][cin][k][k]
+struct S2Dgrad {
+    int k, pad, cin, cout;
+    void plan(Bump& wb, int dtype, size_t wd[4]) const {
+        for (int q = 0; q < 4; ++q) wd[q] = wb.take(srcgan_packed_weight_bytes(cin, cout, par2(k, pad, q >> 1).n * par2(k, pad, q & 1).n, dtype));
+    }
+    void pack(PackList& packs, const float* w, char* wp, const size_t wd[4]) const {
+        const long kk = (long)k * k;
+        for (int q = 0; q < 4; ++q) {
+            const Par2 py = par2(k, pad, q >> 1), px = par2(k, pad, q & 1);
+            packs.add(w, wp + wd[q], cin, cout, py.n, px.n, kk, (long)cin * kk, -2 * k, -2, (long)py.ky_max * k + px.ky_max);
+        }
+    }
+    // dy [B, OH, OW, cout] -> dx [B, H, W, cin].  acc: dx already holds a contribution, add to it; mz: multiply by LeakyReLU' of
+    // this tensor (either may be TNULL).  fuse: all four parities from one staged dy tile in ONE launch (conv_par4.hip: 4x4 p1,
+    // equally spaced packs, 16-byte accessible operands) where that applies; SRCGAN_NO_PAR4 (diagnostic builds) keeps the four.
+    int run(int dt, TRef dy, int B, int OH, int OW, TRef dx, int H, int W, const char* wp, const size_t wd[4], TRef acc, TRef mz,
+            bool fuse, void* st) const {
+        static const bool no_par4 = sg_env("SRCGAN_NO_PAR4") != nullptr;
+        auto launch = [&](Conv& cv) {
+            if (acc.p) cv.res1(acc, cin, 1.f);
+            if (mz.p) cv.mask(mz, 0);
+            return cv.run(st);
+        };
+        const int vec = 16 / (dt == SRCGAN_F32 ? 4 : 2);
+        const size_t wstep = wd[1] - wd[0];
+        const bool even = wd[2] - wd[1] == wstep && wd[3] - wd[2] == wstep;
+        if (fuse && !no_par4 && k == 4 && pad == 1 && even && H >= 2 && W >= 2 && cin % vec == 0 && dx.cs % vec == 0) {
+            Conv cv(dt, 2, 2, 1);
+            cv.in(dy, B, OH, OW, cout).w(wp + wd[0]).out(dx, (H + 1) / 2, (W + 1) / 2, cin).scatter(2, 0, 0, H, W);
+            cv.d.npar = 4; cv.d.wpar_stride = (long)wstep;
+            return launch(cv);
+        }
+        for (int q = 0; q < 4; ++q) {
+            const int a = q >> 1, b = q & 1;
+            const int mh = (H - a + 1) / 2, mw = (W - b + 1) / 2;
+            if (mh <= 0 || mw <= 0) continue;
+            const Par2 py = par2(k, pad, a), px = par2(k, pad, b);
+            Conv cv(dt, py.n, px.n, 1);
+            cv.in(dy, B, OH, OW, cout).w(wp + wd[q]).out(dx, mh, mw, cin).pad(py.lead, px.lead).scatter(2, a, b, H, W);
+            SG_TRY(launch(cv));
+        }
+        return 0;
+    }
+};
+
 // ======================================================================================== RDDBNet
 // The generator families: the values of srcgan_rddbnet_cfg.legacy (include/srcgan_amd.h describes each)
 enum RddbFamily { RDDB_PLAIN = 0, RDDB_NETB = 1, RDDB_LEGACY = 2, RDDB_SRDN = 3 };
@@ -174,6 +236,7 @@ struct RddbPlan {
     // parameter indices
     int p_first_w, p_first_b, p_rdb0, p_trunk_w, p_trunk_b, p_up0, p_dn0, p_last_w;
     int ntail, nlw, p_lg[3], p_last_b;       // nearest-x2 tail: ops, shared weights and their parameters, conv_last's bias
+    S2Dgrad dn_dgrad() const { return S2Dgrad{3, 1, nf, nf}; }      // input gradient of a down stage of RDDBNetA (3x3 s2 p1, nf -> nf)
     int prdb(int r) const { return p_rdb0 + r * 10 + ((family == RDDB_SRDN && r >= 3 * nb) ? 2 : 0); }     // SRDN: trunk_conv's two parameters sit between the stacks
     struct TailOp { int conv, w, hin, win, hout, wout; } tail[16];     // conv: 1 = 3x3 conv w + LReLU, 0 = nearest x2
     size_t lw_f[3], lw_d[3];
@@ -237,7 +300,7 @@ static int rddb_plan(const srcgan_rddbnet_cfg* c, RddbPlan& P) {
     Bump wb;
     auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, c->dtype)); };
     P.w_first_f = pk(c->nf, P.in_cs, 9); P.w_first_d = pk(c->in_ch, c->nf, 9);
-    for (int s = 0; s < P.ndn; ++s) { P.w_dn_f[s] = pk(c->nf, c->nf, 9); for (int q = 0; q < 4; ++q) P.w_dn_d[s][q] = pk(c->nf, c->nf, 4); }
+    for (int s = 0; s < P.ndn; ++s) { P.w_dn_f[s] = pk(c->nf, c->nf, 9); P.dn_dgrad().plan(wb, c->dtype, P.w_dn_d[s]); }
     const int nrdb = (P.nrr ? P.nrr : c->nb) * 3;
     P.w_rdb_f.resize(nrdb * 5); P.w_rdb_d.resize(nrdb * 5);
     for (int i = 0; i < nrdb; ++i)
@@ -622,12 +685,12 @@ struct RddbBwd : RddbCall {
 int RddbBwd::pack_dgrad(bool pack_dx) const {
     PackList packs(dt, wp);
     const WLayout L = lay_dgrad_s1(nf, 3, 3);
-    packs.add(params[P.p_last_w], wp + P.w_last_d, nf, c->out_ch, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
+    packs.add(params[P.p_last_w], wp + P.w_last_d, nf, c->out_ch, 3, 3, L);
     for (int s = 0; s < P.nup; ++s)   // deconv dgrad = 2x2 s2 conv over dy: rows = ci, k = co, tap = (a,b)
         packs.add(params[P.p_up0 + s], wp + P.w_up_d[s], nf, nf, 2, 2, (long)nf * 4, 4, 2, 1, 0);
     for (int k = 0; k < P.nlw; ++k)
-        packs.add(params[P.p_lg[k]], wp + P.lw_d[k], nf, nf, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
-    if (P.family != RDDB_SRDN) packs.add(params[P.p_trunk_w], wp + P.w_trunk_d, nf, nf, 3, 3, L.sr, L.sk, L.sty, L.stx, L.off);
+        packs.add(params[P.p_lg[k]], wp + P.lw_d[k], nf, nf, 3, 3, L);
+    if (P.family != RDDB_SRDN) packs.add(params[P.p_trunk_w], wp + P.w_trunk_d, nf, nf, 3, 3, L);
     SG_TRY(sg_fill_zero_guarded(wp + P.w_rdb_d0, P.w_rdb_dsz, pack_guard(opt), (hipStream_t)st));
     for (int r = 0; r < P.nrr * 3; ++r) {
         const float a5 = (r % 3 == 2) ? 0.04f : 0.2f;       // d(x5)/d(block out), RDB3 carries the RRDB 0.2 too
@@ -641,18 +704,8 @@ int RddbBwd::pack_dgrad(bool pack_dx) const {
             }
         }
     }
-    for (int s = 0; s < P.ndn; ++s)
-        for (int q = 0; q < 4; ++q) {
-            // 3x3 s2 p1 dgrad, output parity (a,b): rows with ky = a+1 (mod 2).  a=0: ky=1 (1 tap); a=1: ky=2,0 (2 taps)
-            const int a = q >> 1, bb = q & 1;
-            const int ty = a ? 2 : 1, tx = bb ? 2 : 1;
-            const long off = (a ? 2 : 1) * 3 + (bb ? 2 : 1);
-            packs.add(params[P.p_dn0 + 2 * s], wp + P.w_dn_d[s][q], nf, nf, ty, tx, 9, (long)nf * 9, -6, -2, off);
-        }
-    if (pack_dx) {
-        const WLayout L0 = lay_dgrad_s1(c->in_ch, 3, 3);
-        packs.add(params[P.p_first_w], wp + P.w_first_d, c->in_ch, nf, 3, 3, L0.sr, L0.sk, L0.sty, L0.stx, L0.off);
-    }
+    for (int s = 0; s < P.ndn; ++s) P.dn_dgrad().pack(packs, params[P.p_dn0 + 2 * s], wp, P.w_dn_d[s]);
+    if (pack_dx) packs.add(params[P.p_first_w], wp + P.w_first_d, c->in_ch, nf, 3, 3, lay_dgrad_s1(c->in_ch, 3, 3));
     return packs.run((std::string(P.tag) + (pack_dx ? "_bwd_dx" : "_bwd")).c_str(), params[0], st, pack_guard(opt));
 }
 
@@ -826,14 +879,7 @@ int RddbBwd::input_side(float* dx_nchw) const {
         if (G(pw)) SG_TRY(wgrad_call(dt, dfea, ho, wo, nf, xin_s, B, hi, wi, nf, 3, 3, 2, 1, 1, lay_fwd(nf, 3, 3), 1.f, slab, G(pw), st, G(pw + 1)));
         else if (G(pw + 1)) SG_TRY(bias_grad(dt, dfea, (long)B * ho * wo, nf, 1.f, G(pw + 1), colscr, st));
         TRef dst = S_(Q.dfea_dn[s], nf);
-        for (int q = 0; q < 4; ++q) {           // dgrad by output parity (a,b): sub-kernel of 1 or 2 taps per axis
-            const int a = q >> 1, bb = q & 1;
-            const int mh = (hi - a + 1) / 2, mw = (wi - bb + 1) / 2;
-            Conv cv(dt, a ? 2 : 1, bb ? 2 : 1, 1);
-            cv.in(dfea, B, ho, wo, nf).w(wp + P.w_dn_d[s][q]).out(dst, mh, mw, nf).pad(0, 0).scatter(2, a, bb, hi, wi);
-            if (s > 0) cv.mask(xin_s, 0);
-            SG_TRY(cv.run(st));
-        }
+        SG_TRY(P.dn_dgrad().run(dt, dfea, B, ho, wo, dst, hi, wi, wp, P.w_dn_d[s], TNULL, s > 0 ? xin_s : TNULL, false, st));
         dfea = dst;
     }
     // conv_first
@@ -893,19 +939,29 @@ extern "C" int srcgan_rddbnet_backward(const srcgan_rddbnet_cfg* c, const float*
 
 // ======================================================================================== NLayerDiscriminator
 namespace {
+// One convolution layer as the kernels run it.  The first layer of an even-sized input runs in space-to-depth form (blocks of 2x2
+// pixels x 8 channels, srcgan_nchw_f32_to_s2d) and is described as what it then is: a 2x2 s1 p0 convolution over (H/2+1) x (W/2+1)
+// blocks of 32 channels with a folded weight.  Only the layout conversions, the folded pack jobs and the unfolding of the weight
+// gradient know the difference.
+enum DPost { D_LRELU, D_BNORM, D_INORM, D_FINAL };       // what follows the convolution (D_FINAL: nothing, the 1-channel prediction map)
+struct DLayer {
+    int k, stride, pad;
+    int H, W, Cin, in_cs;            // input; Cin: input channels of the weight as run; in_cs: channel stride = the forward's (zero-padded) reduction length
+    int OH, OW, Cout, out_cs;        // output; out_cs: channel stride = the input gradient's reduction length
+    DPost post;
+    bool folded;                     // the weight as run is the space-to-depth fold of the canonical [Cout][in_ch][4][4]
+    int pw, pb, pg, pbeta, bn_idx;   // parameter indices (-1 if absent); index among the BatchNorm layers
+    size_t X, Y, Z, stat;            // workspace: input, output, convolution output in front of a normalisation, its statistics
+    size_t wf, wf_bytes, wd[4], wd_bytes;       // packed weights: forward; input gradient (stride 1: wd[0], wd_bytes; stride 2: one per parity)
+    bool normed() const { return post == D_BNORM || post == D_INORM; }
+    S2Dgrad s2() const { return S2Dgrad{k, pad, Cin, Cout}; }
+};
 struct DPlan {
-    int dtype, esz, L;                 // L convs
-    int ch[8], hh[8], ww[8], st[8];    // ch[l] -> ch[l+1]; spatial dims of activation l (0 = input)
-    int in_cs, out_cs;
-    int nparams;
-    size_t xin, Y[8], Z[8], stat[8], out, colscr, wpk, total;      // stat: mean[C], var[C], rstd[C]
-    size_t wf[8], wd[8][4];
-    int pw[8], pb[8], pg[8], pbeta[8];   // parameter indices (-1 if absent)
-    int bn_idx[8];                       // index among BN layers (-1 if none)
-    int inorm;                           // norm_layer = InstanceNorm2d: the normalised layers are GroupNorm(G = C) without affine part
-    int nrm[8];                          // layer l is followed by a normalisation layer
-    size_t gnscr;                        // GroupNorm scratch (instance norm)
-    int s2d;                             // first layer in space-to-depth form (even H, W): 2x2 s1 over 32-channel blocks, K not padded
+    int esz, L, nparams, cmax;         // L convs; cmax: widest channel count (>= 8)
+    bool inorm;                        // norm_layer = InstanceNorm2d: the normalised layers are GroupNorm(G = C) without affine part
+    DLayer y[8];
+    size_t colscr, gnscr, wpk, total;  // gnscr: GroupNorm scratch (instance norm)
+    bool s2d() const { return y[0].folded; }
 };
 
 static int d_plan(const srcgan_nlayerd_cfg* c, DPlan& P) {
@@ -917,69 +973,56 @@ static int d_plan(const srcgan_nlayerd_cfg* c, DPlan& P) {
     SG_REQUIRE(c->B > 0 && c->H > 0 && c->W > 0, "nlayerd: bad B/H/W");
     SG_REQUIRE(c->norm == 0 || c->norm == 1, "nlayerd: norm must be 0 (BatchNorm2d) or 1 (InstanceNorm2d)");
     P.inorm = c->norm == 1;
-    P.dtype = c->dtype; P.esz = c->dtype == SRCGAN_F32 ? 4 : 2;
-    P.L = c->n_layers + 2;
-    P.ch[0] = c->in_ch; P.ch[1] = c->ndf;
-    for (int n = 1; n < c->n_layers; ++n) { int m = 1 << n; if (m > 8) m = 8; P.ch[n + 1] = c->ndf * m; }
-    { int m = 1 << c->n_layers; if (m > 8) m = 8; P.ch[c->n_layers + 1] = c->ndf * m; }
-    P.ch[P.L] = 1;
-    P.hh[0] = c->H; P.ww[0] = c->W;
+    P.esz = c->dtype == SRCGAN_F32 ? 4 : 2; P.L = c->n_layers + 2;
+    // the module's layers (model/model.py:612-634): 4x4 p1, stride 2 for the first n_layers, ndf * min(2^l, 8) channels, 1 at the end
+    int n = 0, nbn = 0, h = c->H, w = c->W, cin = c->in_ch;
+    P.cmax = 8;
     for (int l = 0; l < P.L; ++l) {
-        P.st[l] = l < c->n_layers ? 2 : 1;
-        P.hh[l + 1] = (P.hh[l] + 2 - 4) / P.st[l] + 1;
-        P.ww[l + 1] = (P.ww[l] + 2 - 4) / P.st[l] + 1;
-        SG_REQUIRE(P.hh[l + 1] > 0 && P.ww[l + 1] > 0, "nlayerd: input %dx%d too small for %d layers", c->H, c->W, c->n_layers);
-    }
-    P.in_cs = img_cs(c->in_ch); P.out_cs = 8;
-    const size_t e = P.esz, B = c->B;
-    static const bool no_s2d = sg_env("SRCGAN_NO_S2D") != nullptr;
-    P.s2d = !no_s2d && c->H % 2 == 0 && c->W % 2 == 0;
-    Bump b;
-    P.xin = b.take(P.s2d ? B * (c->H / 2 + 1) * (c->W / 2 + 1) * 32 * e : B * c->H * c->W * P.in_cs * e);
-    int n = 0, nbn = 0;
-    for (int l = 0; l < P.L; ++l) {
-        const bool nrm = (l >= 1 && l <= P.L - 2), bn = nrm && !P.inorm, bias = (l == 0 || l == P.L - 1 || (nrm && P.inorm));
-        P.nrm[l] = nrm;
-        P.pw[l] = n++;
-        P.pb[l] = bias ? n++ : -1;
-        P.pg[l] = bn ? n++ : -1;
-        P.pbeta[l] = bn ? n++ : -1;
-        P.bn_idx[l] = bn ? nbn++ : -1;
-        const size_t sz = B * P.hh[l + 1] * P.ww[l + 1] * (l == P.L - 1 ? P.out_cs : P.ch[l + 1]) * e;
-        if (l == P.L - 1) P.out = b.take(sz);
-        else {
-            P.Y[l] = b.take(sz);
-            if (nrm) {      // BatchNorm: mean[C], var[C], rstd[C]; instance norm: {mean, rstd}[B][C]
-                P.Z[l] = b.take(sz);
-                P.stat[l] = b.take((P.inorm ? (size_t)2 * B * P.ch[l + 1] : (size_t)3 * P.ch[l + 1]) * sizeof(float));
-            }
-        }
+        DLayer& y = P.y[l];
+        const bool last = l == P.L - 1, nrm = l >= 1 && !last, bn = nrm && !P.inorm;
+        y.k = 4; y.stride = l < c->n_layers ? 2 : 1; y.pad = 1; y.folded = false;
+        y.H = h; y.W = w; y.Cin = cin; y.in_cs = l == 0 ? img_cs(cin) : cin;
+        y.OH = (h + 2 - 4) / y.stride + 1; y.OW = (w + 2 - 4) / y.stride + 1;
+        SG_REQUIRE(y.OH > 0 && y.OW > 0, "nlayerd: input %dx%d too small for %d layers", c->H, c->W, c->n_layers);
+        y.Cout = last ? 1 : c->ndf * (l < 3 ? 1 << l : 8); y.out_cs = last ? 8 : y.Cout;
+        y.post = last ? D_FINAL : !nrm ? D_LRELU : P.inorm ? D_INORM : D_BNORM;
+        y.pw = n++;
+        y.pb = (!nrm || P.inorm) ? n++ : -1;
+        y.pg = bn ? n++ : -1;
+        y.pbeta = bn ? n++ : -1;
+        y.bn_idx = bn ? nbn++ : -1;
+        if (y.Cout > P.cmax) P.cmax = y.Cout;
+        h = y.OH; w = y.OW; cin = y.Cout;
     }
     P.nparams = n;
+    static const bool no_s2d = sg_env("SRCGAN_NO_S2D") != nullptr;
+    if (!no_s2d && c->H % 2 == 0 && c->W % 2 == 0) {
+        DLayer& y = P.y[0];
+        y.folded = true; y.k = 2; y.stride = 1; y.pad = 0; y.H = c->H / 2 + 1; y.W = c->W / 2 + 1; y.Cin = y.in_cs = 32;
+    }
+    const size_t e = P.esz, B = c->B;
+    Bump b, wb;      // activations; packed weights (forward: rows = Cout, k = in_cs; input gradient: rows = Cin, k = out_cs)
+    P.y[0].X = b.take(B * P.y[0].H * P.y[0].W * P.y[0].in_cs * e);
+    for (int l = 0; l < P.L; ++l) {
+        DLayer& y = P.y[l];
+        y.wf = wb.take(y.wf_bytes = srcgan_packed_weight_bytes(y.Cout, y.in_cs, y.k * y.k, c->dtype));
+        y.wd_bytes = y.stride == 1 ? srcgan_packed_weight_bytes(y.Cin, y.out_cs, y.k * y.k, c->dtype) : 0;     // stride 2: four packs, S2Dgrad
+        if (y.stride == 1) y.wd[0] = wb.take(y.wd_bytes); else y.s2().plan(wb, c->dtype, y.wd);
+        const size_t sz = B * y.OH * y.OW * y.out_cs * e;
+        y.Y = b.take(sz);
+        if (y.normed()) {      // BatchNorm: mean[C], var[C], rstd[C]; instance norm: {mean, rstd}[B][C]
+            y.Z = b.take(sz);
+            y.stat = b.take((P.inorm ? (size_t)2 * B * y.Cout : (size_t)3 * y.Cout) * sizeof(float));
+        }
+        if (l + 1 < P.L) P.y[l + 1].X = y.Y;
+    }
     P.gnscr = 0;
     if (P.inorm) {
-        int cmax = 8; for (int l = 1; l < P.L; ++l) if (P.ch[l] > cmax) cmax = P.ch[l];
-        SG_REQUIRE(cmax <= 1024 && cmax % (16 / (int)e) == 0 && 256 % (cmax / (16 / (int)e)) == 0, "nlayerd: InstanceNorm2d needs channel counts that are powers of two up to 1024");
-        P.gnscr = b.take(srcgan_gn_scratch_floats(c->B, cmax) * sizeof(float));
+        SG_REQUIRE(P.cmax <= 1024 && P.cmax % (16 / (int)e) == 0 && 256 % (P.cmax / (16 / (int)e)) == 0, "nlayerd: InstanceNorm2d needs channel counts that are powers of two up to 1024");
+        P.gnscr = b.take(srcgan_gn_scratch_floats(c->B, P.cmax) * sizeof(float));
     }
-    {
-        int cmax = 8; for (int l = 1; l < P.L; ++l) if (P.ch[l] > cmax) cmax = P.ch[l];
-        P.colscr = b.take((size_t)2 * srcgan_col_reduce_blocks((long)B * P.hh[1] * P.ww[1]) * cmax * sizeof(float));
-    }
+    P.colscr = b.take((size_t)2 * srcgan_col_reduce_blocks((long)B * P.y[0].OH * P.y[0].OW) * P.cmax * sizeof(float));
     P.wpk = b.off;
-    Bump wb;
-    for (int l = 0; l < P.L; ++l) {
-        const int cin_r = l == 0 ? P.in_cs : P.ch[l];
-        const int k_r = l == P.L - 1 ? P.out_cs : P.ch[l + 1];
-        if (l == 0 && P.s2d) {             // folded first layer: forward rows = Cout, k = 32, 4 taps; dgrad rows = 32, k = Cout
-            P.wf[l] = wb.take(srcgan_packed_weight_bytes(P.ch[1], 32, 4, c->dtype));
-            P.wd[l][0] = wb.take(srcgan_packed_weight_bytes(32, k_r, 4, c->dtype));
-            continue;
-        }
-        P.wf[l] = wb.take(srcgan_packed_weight_bytes(P.ch[l + 1], cin_r, 16, c->dtype));
-        if (P.st[l] == 1) P.wd[l][0] = wb.take(srcgan_packed_weight_bytes(P.ch[l], k_r, 16, c->dtype));
-        else for (int q = 0; q < 4; ++q) P.wd[l][q] = wb.take(srcgan_packed_weight_bytes(P.ch[l], k_r, 4, c->dtype));
-    }
     P.total = align_up(P.wpk + wb.off + 256, 256);
     return 0;
 }
@@ -987,37 +1030,185 @@ static int d_plan(const srcgan_nlayerd_cfg* c, DPlan& P) {
 struct DBwdPlan { size_t dO, g[2], dxin, slab, colscr, sums, gfold, gnscr, total; };
 static void d_bwd_plan(const srcgan_nlayerd_cfg* c, const DPlan& P, DBwdPlan& Q) {
     const size_t e = P.esz, B = c->B;
+    const DLayer& y0 = P.y[0]; const DLayer& yl = P.y[P.L - 1];
     Bump b;
-    Q.dO = b.take(B * P.hh[P.L] * P.ww[P.L] * P.out_cs * e);
-    size_t mx = 0;
-    for (int l = 0; l < P.L - 1; ++l) { size_t s = B * P.hh[l + 1] * P.ww[l + 1] * P.ch[l + 1] * e; if (s > mx) mx = s; }
-    Q.g[0] = b.take(mx); Q.g[1] = b.take(mx);
-    Q.dxin = b.take(P.s2d ? B * (c->H / 2 + 1) * (c->W / 2 + 1) * 32 * e : B * c->H * c->W * P.in_cs * e);
-    Q.gfold = b.take((size_t)P.ch[1] * 32 * 4 * sizeof(float));
-    size_t slab = 0;
+    Q.dO = b.take(B * yl.OH * yl.OW * yl.out_cs * e);
+    size_t mx = 0, slab = 0;       // largest gradient of a hidden activation (two buffers alternate); largest weight-gradient slab
     for (int l = 0; l < P.L; ++l) {
-        size_t s = (l == 0 && P.s2d) ? wgrad_slab(c->B, P.hh[1], P.ww[1], P.ch[1], 32, 2, 2, 1)
-                                     : wgrad_slab(c->B, P.hh[l + 1], P.ww[l + 1], P.ch[l + 1], P.ch[l], 4, 4, P.st[l]);
-        if (s > slab) slab = s;
+        const DLayer& y = P.y[l];
+        if (l < P.L - 1) mx = std::max(mx, B * y.OH * y.OW * y.Cout * e);
+        slab = std::max(slab, wgrad_slab(c->B, y.OH, y.OW, y.Cout, y.Cin, y.k, y.k, y.stride));
     }
+    Q.g[0] = b.take(mx); Q.g[1] = b.take(mx);
+    Q.dxin = b.take(B * y0.H * y0.W * y0.in_cs * e);
+    Q.gfold = b.take((size_t)y0.Cout * 32 * 4 * sizeof(float));
     Q.slab = b.take(slab);
-    int cmax = 8; for (int l = 1; l <= P.L; ++l) if (P.ch[l] > cmax) cmax = P.ch[l];
-    Q.colscr = b.take((size_t)2 * srcgan_col_reduce_blocks((long)B * P.hh[1] * P.ww[1]) * cmax * sizeof(float));
-    Q.sums = b.take((size_t)2 * cmax * sizeof(float));
-    Q.gnscr = P.inorm ? b.take(srcgan_gn_scratch_floats(c->B, cmax) * sizeof(float)) : 0;
+    Q.colscr = b.take((size_t)2 * srcgan_col_reduce_blocks((long)B * y0.OH * y0.OW) * P.cmax * sizeof(float));
+    Q.sums = b.take((size_t)2 * P.cmax * sizeof(float));
+    Q.gnscr = P.inorm ? b.take(srcgan_gn_scratch_floats(c->B, P.cmax) * sizeof(float)) : 0;
     Q.total = b.off + 256;
 }
+
+// ---- one native call on the discriminator, in named steps (a forward call has no scratch, gradients or backward plan)
+struct DCall {
+    const srcgan_nlayerd_cfg* c; const DPlan& P; const float* const* params; const srcgan_net_opts* opt; void* st;
+    const int dt, B;
+    char* w8;
+    char* wp;            // packed weights: a persistent buffer of the caller's or a region of this call's workspace
+    bool do_pack;
+    const DBwdPlan* Q; char* s8; float* const* grads;
+    DCall(const srcgan_nlayerd_cfg* c_, const DPlan& P_, const float* const* params_, void* ws, const srcgan_net_opts* opt_, void* st_,
+          const DBwdPlan* Q_ = nullptr, void* scratch = nullptr, float* const* grads_ = nullptr)
+        : c(c_), P(P_), params(params_), opt(opt_), st(st_), dt(c_->dtype), B(c_->B), w8((char*)ws),
+          wp((opt_ && opt_->wpack) ? (char*)opt_->wpack : (char*)ws + P_.wpk), do_pack(!(opt_ && opt_->wpack) || opt_->pack),
+          Q(Q_), s8((char*)scratch), grads(grads_) {}
+    TRef X(const DLayer& y) const { return tref(w8 + y.X, y.in_cs); }
+    TRef Y(const DLayer& y) const { return tref(w8 + y.Y, y.out_cs); }
+    float* W(size_t off) const { return (float*)(w8 + off); }
+    float* S(size_t off) const { return (float*)(s8 + off); }
+    int pack_forward() const {
+        PackList packs(dt, wp);
+        for (int l = 0; l < P.L; ++l) {
+            const DLayer& y = P.y[l];
+            if (y.folded) {
+                // W[co][c][2ty+dy][2tx+dx] -> k = (dy,dx,c8), taps (ty,tx): one part per (dy,dx); channels c >= Cin stay zero
+                SG_TRY(sg_fill_zero_guarded(wp + y.wf, y.wf_bytes, pack_guard(opt), (hipStream_t)st));
+                for (int q = 0; q < 4; ++q)
+                    packs.add(params[y.pw], wp + y.wf, y.Cout, c->in_ch, 2, 2, (long)c->in_ch * 16, 16, 8, 2, (q >> 1) * 4 + (q & 1), q * 8, 32);
+            } else
+                packs.add(params[y.pw], wp + y.wf, y.Cout, y.Cin, y.k, y.k, lay_fwd(y.Cin, y.k, y.k));
+        }
+        return packs.run(P.s2d() ? "d_fwd_s2d" : "d_fwd", params[0], st, pack_guard(opt));
+    }
+    // Z -> Y: BatchNorm2d (batch statistics in training mode, running statistics otherwise) or InstanceNorm2d, then LeakyReLU
+    int norm_forward(const DLayer& y, float* const* bn_running, int64_t* const* bn_nbt) const {
+        const int C = y.Cout, bi = y.bn_idx;
+        const long npix = (long)B * y.OH * y.OW;
+        if (y.post == D_INORM)          // no affine part, instance statistics in either mode
+            return srcgan_gn_forward(w8 + y.Z, C, nullptr, 0, w8 + y.Y, C, nullptr, nullptr, W(y.stat), B, (long)y.OH * y.OW, C, C, 1e-5f, 1, 0.2f, dt, W(P.gnscr), st);
+        float* mean = W(y.stat); float* var = mean + C; float* rstd = var + C;
+        if (c->training) {
+            SG_TRY(srcgan_col_reduce(3, w8 + y.Z, C, 0, nullptr, 0, 0, nullptr, nullptr, npix, C, 1.f, mean, var, W(P.colscr), dt, st));      // one pass: mean and variance
+            SG_TRY(srcgan_bn_finalize(mean, var, rstd, bn_running ? bn_running[2 * bi] : nullptr, bn_running ? bn_running[2 * bi + 1] : nullptr,
+                                      bn_nbt ? bn_nbt[bi] : nullptr, C, npix, 0.1f, 1e-5f, st));
+        } else {
+            SG_REQUIRE(bn_running, "srcgan_nlayerd_forward: eval mode needs running statistics");
+            SG_TRY(srcgan_bn_eval_rstd(bn_running[2 * bi + 1], rstd, C, 1e-5f, st));
+            mean = bn_running[2 * bi];
+        }
+        return srcgan_bn_apply_lrelu(w8 + y.Z, w8 + y.Y, mean, rstd, params[y.pg], params[y.pbeta], npix, C, C, 0.2f, dt, st);
+    }
+    int forward(const float* x_nchw, float* const* bn_running, int64_t* const* bn_nbt, float* y_nchw) const {
+        if (do_pack) SG_TRY(pack_forward());
+        const DLayer& y0 = P.y[0]; const DLayer& yl = P.y[P.L - 1];
+        if (P.s2d()) SG_TRY(srcgan_nchw_f32_to_s2d(x_nchw, w8 + y0.X, B, c->in_ch, c->H, c->W, dt, st));
+        else SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + y0.X, B, c->in_ch, c->H, c->W, y0.in_cs, dt, st));
+        for (int l = 0; l < P.L; ++l) {     // conv + bias + LeakyReLU, conv -> norm -> LeakyReLU ..., conv + bias (model/model.py:612-634)
+            const DLayer& y = P.y[l];
+            Conv cv(dt, y.k, y.k, y.stride);
+            cv.in(X(y), B, y.H, y.W, y.in_cs).w(wp + y.wf, y.pb >= 0 ? params[y.pb] : nullptr).pad(y.pad, y.pad);
+            cv.out(y.normed() ? tref(w8 + y.Z, y.Cout) : Y(y), y.OH, y.OW, y.Cout);
+            if (y.post == D_LRELU) cv.lrelu();
+            if (y.post == D_FINAL) SG_HIP(hipMemsetAsync(w8 + y.Y, 0, (size_t)B * y.OH * y.OW * y.out_cs * P.esz, (hipStream_t)st));     // padded with zeros to out_cs
+            SG_TRY(cv.run(st));
+            if (y.normed()) SG_TRY(norm_forward(y, bn_running, bn_nbt));
+        }
+        return srcgan_nhwc_to_nchw_f32(w8 + yl.Y, y_nchw, B, 1, yl.OH, yl.OW, yl.out_cs, 0, dt, st);
+    }
+    // ---- backward steps.  dcur = gradient w.r.t. a layer's output, already times LeakyReLU' of that output (the mask is fused in
+    // the input-gradient convolution that produced it).  Packed input-gradient weights: the first layer's only if someone may ask for dx
+    int pack_dgrad(bool pack_dx) const {
+        PackList packs(dt, wp);
+        for (int l = pack_dx ? 0 : 1; l < P.L; ++l) {
+            const DLayer& y = P.y[l];
+            if (y.folded) {
+                // dX'[j,i,(dy,dx,c)] = sum_{u,v,co} dY[j-1+u, i-1+v, co] * W[co][c][2(1-u)+dy][2(1-v)+dx]: rows (dy,dx,c8), k = co, 2x2 taps.
+                // The rows of one (dy,dx) are a strided slice of the weight: one part per (dy,dx) and per half of k (so that no part
+                // is a whole matrix, which would zero-fill all 32 rows of its view), written at row offset (dy*2+dx)*8.
+                const int cin = c->in_ch, cout = y.Cout, kce = 64 / P.esz;
+                SG_TRY(sg_fill_zero_guarded(wp + y.wd[0], y.wd_bytes, pack_guard(opt), (hipStream_t)st));
+                for (int q = 0; q < 4; ++q)
+                    for (int hk = 0; hk < 2; ++hk)
+                        packs.add(params[y.pw], wp + y.wd[0] + (size_t)q * 8 * kce * P.esz, cin, cout / 2, 2, 2, 16, (long)cin * 16, -8, -2,
+                                  10 + (q >> 1) * 4 + (q & 1) + (long)hk * (cout / 2) * cin * 16, hk * (cout / 2), cout);
+            } else if (y.stride == 1)
+                packs.add(params[y.pw], wp + y.wd[0], y.Cin, y.Cout, y.k, y.k, lay_dgrad_s1(y.Cin, y.k, y.k));
+            else
+                y.s2().pack(packs, params[y.pw], wp, y.wd);
+        }
+        return packs.run(P.s2d() ? (pack_dx ? "d_bwd_dx_s2d" : "d_bwd_s2d") : (pack_dx ? "d_bwd_dx" : "d_bwd"), params[0], st, pack_guard(opt));
+    }
+    // dcur: d/d(normalised output) -> d/d(convolution output), in place; BatchNorm's gamma and beta gradients
+    int norm_backward(const DLayer& y, TRef dcur) const {
+        const int C = y.Cout;
+        const long npix = (long)B * y.OH * y.OW;
+        if (y.post == D_INORM)          // per (image, channel)
+            return srcgan_gn_backward(dcur.p, dcur.cs, nullptr, 0, w8 + y.Z, C, nullptr, W(y.stat), dcur.p, dcur.cs, nullptr, 0, 0,
+                                      nullptr, nullptr, 0, 0.2f, B, (long)y.OH * y.OW, C, C, dt, S(Q->gnscr), st);
+        if (y.post != D_BNORM) return 0;
+        // BatchNorm (training mode): needs sum g, sum g*xhat
+        float* mean = W(y.stat); float* rstd = mean + 2 * C; float* sums = S(Q->sums);
+        SG_TRY(srcgan_col_reduce(2, dcur.p, dcur.cs, 0, w8 + y.Z, C, 0, mean, rstd, npix, C, 1.f, sums, sums + C, S(Q->colscr), dt, st));
+        if (grads[y.pbeta]) SG_HIP(hipMemcpyAsync(grads[y.pbeta], sums, C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)st));
+        if (grads[y.pg]) SG_HIP(hipMemcpyAsync(grads[y.pg], sums + C, C * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)st));
+        return srcgan_bn_bwd_apply(dcur.p, w8 + y.Z, dcur.p, mean, rstd, params[y.pg], sums, sums + C, npix, C, C, dt, st);
+    }
+    // weight and bias gradient (a folded weight's gradient is taken in the folded form, then unfolded to [Cout][in_ch][4][4])
+    int param_grads(const DLayer& y, TRef dcur) const {
+        if (grads[y.pw]) {
+            float* g = y.folded ? S(Q->gfold) : grads[y.pw];
+            SG_TRY(wgrad_call(dt, dcur, y.OH, y.OW, y.Cout, X(y), B, y.H, y.W, y.Cin, y.k, y.k, y.stride, y.pad, y.pad, lay_fwd(y.Cin, y.k, y.k), 1.f, S(Q->slab), g, st));
+            if (y.folded) SG_TRY(srcgan_s2d_wgrad_unfold(g, grads[y.pw], y.Cout, c->in_ch, 0, st));
+        }
+        if (y.pb >= 0 && grads[y.pb]) SG_TRY(bias_grad(dt, dcur, (long)B * y.OH * y.OW, y.Cout, 1.f, grads[y.pb], S(Q->colscr), st));
+        return 0;
+    }
+    // gradient of a layer's input into dst, times LeakyReLU' of mz (the input itself where it is a layer's post-activation, or TNULL)
+    int input_grad(const DLayer& y, TRef dcur, TRef dst, TRef mz) const {
+        if (y.stride == 2) return y.s2().run(dt, dcur, B, y.OH, y.OW, dst, y.H, y.W, wp, y.wd, TNULL, mz, true, st);
+        Conv cv(dt, y.k, y.k, 1);       // stride 1: the "full" convolution with the flipped kernel
+        cv.in(dcur, B, y.OH, y.OW, y.out_cs).w(wp + y.wd[0]).out(dst, y.H, y.W, y.Cin).pad(y.k - 1 - y.pad, y.k - 1 - y.pad);
+        if (mz.p) cv.mask(mz, 0);
+        return cv.run(st);
+    }
+    // the first layer's input gradient, in the input's layout, and from there to NCHW f32
+    int write_dx(TRef dcur, float* dx_nchw) const {
+        const DLayer& y = P.y[0];
+        TRef dxin = tref(s8 + Q->dxin, y.in_cs);
+        if (!P.s2d())       // NHWC: the padded image channels, which the convolution does not write (the space-to-depth form is written whole)
+            SG_HIP(hipMemsetAsync(dxin.p, 0, (size_t)B * y.H * y.W * y.in_cs * P.esz, (hipStream_t)st));
+        SG_TRY(input_grad(y, dcur, dxin, TNULL));
+        if (P.s2d()) return srcgan_s2d_to_nchw_f32(dxin.p, dx_nchw, B, c->in_ch, c->H, c->W, dt, st);
+        return srcgan_nhwc_to_nchw_f32(dxin.p, dx_nchw, B, c->in_ch, c->H, c->W, y.in_cs, 0, dt, st);
+    }
+    int backward(const float* dy_nchw, float* dx_nchw) const {
+        if (do_pack) SG_TRY(pack_dgrad(dx_nchw || (opt && opt->wpack)));       // a persistent pack serves later calls that may want dx
+        const DLayer& yl = P.y[P.L - 1];
+        TRef dcur = tref(s8 + Q->dO, yl.out_cs);        // dy -> NHWC (1 channel, padded with zeros to 8)
+        SG_TRY(srcgan_nchw_f32_to_nhwc(dy_nchw, dcur.p, B, 1, yl.OH, yl.OW, yl.out_cs, dt, st));
+        for (int l = P.L - 1; l > 0; --l) {
+            const DLayer& y = P.y[l];
+            TRef dst = tref(s8 + Q->g[l & 1], y.Cin);
+            SG_TRY(norm_backward(y, dcur));
+            SG_TRY(param_grads(y, dcur));
+            SG_TRY(input_grad(y, dcur, dst, X(y)));
+            dcur = dst;
+        }
+        SG_TRY(param_grads(P.y[0], dcur));      // the first layer has no normalisation, and its input gradient is dx
+        if (dx_nchw) SG_TRY(write_dx(dcur, dx_nchw));
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" int srcgan_nlayerd_num_params(const srcgan_nlayerd_cfg* c) { DPlan P; if (d_plan(c, P)) return -1; return P.nparams; }
 extern "C" int srcgan_nlayerd_out_hw(const srcgan_nlayerd_cfg* c, int* oh, int* ow) {
-    DPlan P; SG_TRY(d_plan(c, P)); if (oh) *oh = P.hh[P.L]; if (ow) *ow = P.ww[P.L]; return 0;
+    DPlan P; SG_TRY(d_plan(c, P)); if (oh) *oh = P.y[P.L - 1].OH; if (ow) *ow = P.y[P.L - 1].OW; return 0;
 }
 extern "C" size_t srcgan_nlayerd_ws_bytes(const srcgan_nlayerd_cfg* c) { DPlan P; if (d_plan(c, P)) return 0; return P.total; }
 extern "C" size_t srcgan_nlayerd_bwd_scratch_bytes(const srcgan_nlayerd_cfg* c) {
     DPlan P; if (d_plan(c, P)) return 0; DBwdPlan Q; d_bwd_plan(c, P, Q); return Q.total;
 }
-
 extern "C" size_t srcgan_nlayerd_wpack_bytes(const srcgan_nlayerd_cfg* c) { DPlan P; if (d_plan(c, P)) return 0; return P.total - P.wpk; }
 
 extern "C" int srcgan_nlayerd_forward(const srcgan_nlayerd_cfg* c, const float* x_nchw, const float* const* params,
@@ -1036,68 +1227,9 @@ extern "C" int srcgan_nlayerd_forward_ex(const srcgan_nlayerd_cfg* c, const floa
     SG_TRY(d_plan(c, P));
     SG_REQUIRE(x_nchw && params && ws && y_nchw, "srcgan_nlayerd_forward: null pointer");
     SG_REQUIRE(((uintptr_t)ws % 256) == 0, "srcgan_nlayerd_forward: workspace must be 256-byte aligned");
-    const int dt = c->dtype, B = c->B;
-    char* w8 = (char*)ws; char* wp = (opt && opt->wpack) ? (char*)opt->wpack : w8 + P.wpk;
-    SG_REQUIRE(((uintptr_t)wp % 256) == 0, "srcgan_nlayerd_forward: wpack must be 256-byte aligned");
-    if (!(opt && opt->wpack) || opt->pack) {
-        PackList packs(dt, wp);
-        for (int l = 0; l < P.L; ++l) {
-            if (l == 0 && P.s2d) {
-                // W[co][c][2ty+dy][2tx+dx] -> k = (dy,dx,c8), taps (ty,tx): one part per (dy,dx); channels c >= Cin stay zero
-                SG_TRY(sg_fill_zero_guarded(wp + P.wf[0], srcgan_packed_weight_bytes(P.ch[1], 32, 4, dt), pack_guard(opt), (hipStream_t)st));
-                for (int q = 0; q < 4; ++q)
-                    packs.add(params[P.pw[0]], wp + P.wf[0], P.ch[1], P.ch[0], 2, 2, (long)P.ch[0] * 16, 16, 8, 2, (q >> 1) * 4 + (q & 1), q * 8, 32);
-                continue;
-            }
-            packs.add(params[P.pw[l]], wp + P.wf[l], P.ch[l + 1], P.ch[l], 4, 4, (long)P.ch[l] * 16, 16, 4, 1, 0);
-        }
-        SG_TRY(packs.run(P.s2d ? "d_fwd_s2d" : "d_fwd", params[0], st, pack_guard(opt)));
-    }
-    if (P.s2d) SG_TRY(srcgan_nchw_f32_to_s2d(x_nchw, w8 + P.xin, B, c->in_ch, c->H, c->W, dt, st));
-    else SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, c->in_ch, c->H, c->W, P.in_cs, dt, st));
-    TRef cur = tref(w8 + P.xin, P.s2d ? 32 : P.in_cs);
-    for (int l = 0; l < P.L; ++l) {
-        const int cin_r = l == 0 ? P.in_cs : P.ch[l], cout = P.ch[l + 1];
-        const int oh = P.hh[l + 1], ow = P.ww[l + 1];
-        const long npix = (long)B * oh * ow;
-        Conv cv(dt, (l == 0 && P.s2d) ? 2 : 4, (l == 0 && P.s2d) ? 2 : 4, (l == 0 && P.s2d) ? 1 : P.st[l]);
-        if (l == 0 && P.s2d) cv.in(cur, B, c->H / 2 + 1, c->W / 2 + 1, 32).w(wp + P.wf[l], params[P.pb[l]]).pad(0, 0);
-        else cv.in(cur, B, P.hh[l], P.ww[l], cin_r).w(wp + P.wf[l], P.pb[l] >= 0 ? params[P.pb[l]] : nullptr).pad(1, 1);
-        if (l == 0) {                       // conv + bias + LeakyReLU (model/model.py:612)
-            TRef y = tref(w8 + P.Y[l], cout);
-            SG_TRY(cv.out(y, oh, ow, cout).lrelu().run(st));
-            cur = y;
-        } else if (l == P.L - 1) {          // final 1-channel prediction map (model/model.py:634)
-            SG_HIP(hipMemsetAsync(w8 + P.out, 0, (size_t)npix * P.out_cs * P.esz, (hipStream_t)st));
-            SG_TRY(cv.out(tref(w8 + P.out, P.out_cs), oh, ow, 1).run(st));
-        } else {                            // conv -> BatchNorm2d -> LeakyReLU (model/model.py:620-631)
-            TRef z = tref(w8 + P.Z[l], cout), y = tref(w8 + P.Y[l], cout);
-            SG_TRY(cv.out(z, oh, ow, cout).run(st));
-            if (P.inorm) {                  // InstanceNorm2d (no affine part, instance statistics in either mode) + LeakyReLU
-                SG_TRY(srcgan_gn_forward(z.p, cout, nullptr, 0, y.p, cout, nullptr, nullptr, (float*)(w8 + P.stat[l]), B, (long)oh * ow, cout, cout,
-                                         1e-5f, 1, 0.2f, dt, (float*)(w8 + P.gnscr), st));
-                cur = y;
-                continue;
-            }
-            float* mean = (float*)(w8 + P.stat[l]); float* var = mean + cout; float* rstd = var + cout;
-            const int bi = P.bn_idx[l];
-            const float* gamma = params[P.pg[l]]; const float* beta = params[P.pbeta[l]];
-            if (c->training) {
-                float* scr = (float*)(w8 + P.colscr);
-                SG_TRY(srcgan_col_reduce(3, z.p, cout, 0, nullptr, 0, 0, nullptr, nullptr, npix, cout, 1.f, mean, var, scr, dt, st));      // one pass: mean and variance
-                SG_TRY(srcgan_bn_finalize(mean, var, rstd, bn_running ? bn_running[2 * bi] : nullptr, bn_running ? bn_running[2 * bi + 1] : nullptr,
-                                          bn_nbt ? bn_nbt[bi] : nullptr, cout, npix, 0.1f, 1e-5f, st));
-                SG_TRY(srcgan_bn_apply_lrelu(z.p, y.p, mean, rstd, gamma, beta, npix, cout, cout, 0.2f, dt, st));
-            } else {
-                SG_REQUIRE(bn_running, "srcgan_nlayerd_forward: eval mode needs running statistics");
-                SG_TRY(srcgan_bn_eval_rstd(bn_running[2 * bi + 1], rstd, cout, 1e-5f, st));
-                SG_TRY(srcgan_bn_apply_lrelu(z.p, y.p, bn_running[2 * bi], rstd, gamma, beta, npix, cout, cout, 0.2f, dt, st));
-            }
-            cur = y;
-        }
-    }
-    SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + P.out, y_nchw, B, 1, P.hh[P.L], P.ww[P.L], P.out_cs, 0, dt, st));
-    return 0;
+    const DCall K(c, P, params, ws, opt, st);
+    SG_REQUIRE(((uintptr_t)K.wp % 256) == 0, "srcgan_nlayerd_forward: wpack must be 256-byte aligned");
+    return K.forward(x_nchw, bn_running, bn_nbt, y_nchw);
 }
 
 extern "C" int srcgan_nlayerd_backward_ex(const srcgan_nlayerd_cfg* c, const float* dy_nchw, const float* const* params,
@@ -1108,115 +1240,7 @@ extern "C" int srcgan_nlayerd_backward_ex(const srcgan_nlayerd_cfg* c, const flo
     SG_REQUIRE(dy_nchw && params && ws && scratch && grads, "srcgan_nlayerd_backward: null pointer");
     DBwdPlan Q;
     d_bwd_plan(c, P, Q);
-    const int dt = c->dtype, B = c->B;
-    char* w8 = (char*)ws; char* s8 = (char*)scratch; char* wp = (opt && opt->wpack) ? (char*)opt->wpack : w8 + P.wpk;
-    float* slab = (float*)(s8 + Q.slab); float* colscr = (float*)(s8 + Q.colscr); float* sums = (float*)(s8 + Q.sums);
-    // ---- packed dgrad weights
-    const bool pack_dx = dx_nchw || (opt && opt->wpack);       // a persistent pack serves later calls that may want dx
-    PackList packs(dt, wp);
-    for (int l = 0; l < P.L && (!(opt && opt->wpack) || opt->pack); ++l) {
-        if (l == 0 && !pack_dx) continue;
-        const int cin = P.ch[l], cout = P.ch[l + 1];
-        if (l == 0 && P.s2d) {
-            // dX'[j,i,(dy,dx,c)] = sum_{u,v,co} dY[j-1+u, i-1+v, co] * W[co][c][2(1-u)+dy][2(1-v)+dx]: rows (dy,dx,c8), k = co, 2x2 taps.
-            // The rows of one (dy,dx) are a strided slice of the weight: one part per (dy,dx) and per half of k (so that no part
-            // is a whole matrix, which would zero-fill all 32 rows of its view), written at row offset (dy*2+dx)*8.
-            const int kce = 64 / P.esz;
-            SG_TRY(sg_fill_zero_guarded(wp + P.wd[0][0], srcgan_packed_weight_bytes(32, cout, 4, dt), pack_guard(opt), (hipStream_t)st));
-            for (int q = 0; q < 4; ++q)
-                for (int hk = 0; hk < 2; ++hk)
-                    packs.add(params[P.pw[0]], wp + P.wd[0][0] + (size_t)q * 8 * kce * P.esz, cin, cout / 2, 2, 2, 16, (long)cin * 16, -8, -2,
-                              10 + (q >> 1) * 4 + (q & 1) + (long)hk * (cout / 2) * cin * 16, hk * (cout / 2), cout);
-            continue;
-        }
-        if (P.st[l] == 1)
-            packs.add(params[P.pw[l]], wp + P.wd[l][0], cin, cout, 4, 4, 16, (long)cin * 16, -4, -1, 15);
-        else
-            for (int q = 0; q < 4; ++q) {   // stride-2 dgrad by output parity (a,b): 2x2 sub-kernel, ky = (a?2:3) - 2*ty
-                const int a = q >> 1, bb = q & 1;
-                const long off = (a ? 2 : 3) * 4 + (bb ? 2 : 3);
-                packs.add(params[P.pw[l]], wp + P.wd[l][q], cin, cout, 2, 2, 16, (long)cin * 16, -8, -2, off);
-            }
-    }
-    SG_TRY(packs.run(P.s2d ? (pack_dx ? "d_bwd_dx_s2d" : "d_bwd_s2d") : (pack_dx ? "d_bwd_dx" : "d_bwd"), params[0], st, pack_guard(opt)));
-    // ---- dy -> NHWC (1 channel, padded with zeros to 8)
-    const int Lh = P.hh[P.L], Lw = P.ww[P.L];
-    TRef dcur = tref(s8 + Q.dO, P.out_cs);
-    SG_TRY(srcgan_nchw_f32_to_nhwc(dy_nchw, dcur.p, B, 1, Lh, Lw, P.out_cs, dt, st));
-    int dcur_c = P.out_cs;      // channels to read from dcur (padded)
-    for (int l = P.L - 1; l >= 0; --l) {
-        const int cin = P.ch[l], cout = P.ch[l + 1];
-        const int ih = P.hh[l], iw = P.ww[l], oh = P.hh[l + 1], ow = P.ww[l + 1];
-        const long npix = (long)B * oh * ow;
-        const bool bn = P.bn_idx[l] >= 0;
-        if (P.nrm[l] && P.inorm) {
-            // dcur = dL/dy * lrelu'(y) (mask fused in the producer); instance-norm backward per (image, channel), in place
-            TRef z = tref(w8 + P.Z[l], cout);
-            SG_TRY(srcgan_gn_backward(dcur.p, dcur.cs, nullptr, 0, z.p, cout, nullptr, (const float*)(w8 + P.stat[l]), dcur.p, dcur.cs, nullptr, 0, 0,
-                                      nullptr, nullptr, 0, 0.2f, B, (long)oh * ow, cout, cout, dt, (float*)(s8 + Q.gnscr), st));
-        }
-        if (bn) {
-            // dcur = dL/dy * lrelu'(y) (mask fused in the producer).  BN backward (train): needs sum g, sum g*xhat
-            float* mean = (float*)(w8 + P.stat[l]); float* rstd = mean + 2 * cout;
-            TRef z = tref(w8 + P.Z[l], cout);
-            SG_TRY(srcgan_col_reduce(2, dcur.p, dcur.cs, 0, z.p, cout, 0, mean, rstd, npix, cout, 1.f, sums, sums + cout, colscr, dt, st));
-            if (grads[P.pbeta[l]]) SG_HIP(hipMemcpyAsync(grads[P.pbeta[l]], sums, cout * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)st));
-            if (grads[P.pg[l]]) SG_HIP(hipMemcpyAsync(grads[P.pg[l]], sums + cout, cout * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)st));
-            SG_TRY(srcgan_bn_bwd_apply(dcur.p, z.p, dcur.p, mean, rstd, params[P.pg[l]], sums, sums + cout, npix, cout, cout, dt, st));
-        }
-        TRef xin_l = l == 0 ? tref(w8 + P.xin, P.s2d ? 32 : P.in_cs) : tref(w8 + P.Y[l - 1], cin);
-        if (grads[P.pw[l]]) {
-            if (l == 0 && P.s2d) {          // gradient of the folded weight, then back to [Cout][Cin][4][4]
-                float* gfold = (float*)(s8 + Q.gfold);
-                SG_TRY(wgrad_call(dt, dcur, oh, ow, cout, xin_l, B, c->H / 2 + 1, c->W / 2 + 1, 32, 2, 2, 1, 0, 0, lay_fwd(32, 2, 2), 1.f, slab, gfold, st));
-                SG_TRY(srcgan_s2d_wgrad_unfold(gfold, grads[P.pw[l]], cout, cin, 0, st));
-            } else
-            SG_TRY(wgrad_call(dt, dcur, oh, ow, cout, xin_l, B, ih, iw, cin, 4, 4, P.st[l], 1, 1, lay_fwd(cin, 4, 4), 1.f, slab, grads[P.pw[l]], st));
-        }
-        if (P.pb[l] >= 0 && grads[P.pb[l]]) SG_TRY(bias_grad(dt, dcur, npix, cout, 1.f, grads[P.pb[l]], colscr, st));
-        if (l == 0 && !dx_nchw) break;
-        // dgrad -> gradient of the layer input, times LeakyReLU' of that input (it is some layer's post-activation)
-        if (l == 0 && P.s2d) {              // one 2x2 "full" convolution into the space-to-depth gradient, then back to NCHW f32
-            TRef dst = tref(s8 + Q.dxin, 32);
-            SG_TRY(Conv(dt, 2, 2, 1).in(dcur, B, oh, ow, dcur_c).w(wp + P.wd[0][0]).out(dst, c->H / 2 + 1, c->W / 2 + 1, 32).pad(1, 1).run(st));
-            SG_TRY(srcgan_s2d_to_nchw_f32(dst.p, dx_nchw, B, c->in_ch, c->H, c->W, dt, st));
-            return 0;
-        }
-        TRef dst = l == 0 ? tref(s8 + Q.dxin, P.in_cs) : tref(s8 + Q.g[l & 1], cin);
-        if (l == 0) SG_HIP(hipMemsetAsync(dst.p, 0, (size_t)B * ih * iw * P.in_cs * P.esz, (hipStream_t)st));
-        TRef mz = l == 0 ? TNULL : tref(w8 + P.Y[l - 1], cin);
-        if (P.st[l] == 1) {
-            Conv cv(dt, 4, 4, 1);
-            cv.in(dcur, B, oh, ow, dcur_c).w(wp + P.wd[l][0]).out(dst, ih, iw, cin).pad(2, 2);
-            if (mz.p) cv.mask(mz, 0);
-            SG_TRY(cv.run(st));
-        } else {
-            // stride-2 layers: all four output parities of the input gradient from one staged dy tile (conv_par4.hip); the four
-            // parity packs are equally spaced.  (SRCGAN_NO_PAR4, diagnostic builds: the four separate 2x2 launches of rounds 1-2.)
-            static const bool no_par4 = sg_env("SRCGAN_NO_PAR4") != nullptr;
-            const long wstep = (long)(P.wd[l][1] - P.wd[l][0]);
-            const bool even = P.wd[l][2] - P.wd[l][1] == (size_t)wstep && P.wd[l][3] - P.wd[l][2] == (size_t)wstep;
-            if (!no_par4 && even && ih >= 2 && iw >= 2 && cin % (16 / P.esz) == 0 && dst.cs % (16 / P.esz) == 0) {
-                Conv cv(dt, 2, 2, 1);
-                cv.in(dcur, B, oh, ow, dcur_c).w(wp + P.wd[l][0]).out(dst, (ih + 1) / 2, (iw + 1) / 2, cin).scatter(2, 0, 0, ih, iw);
-                cv.d.npar = 4; cv.d.wpar_stride = wstep;
-                if (mz.p) cv.mask(mz, 0);
-                SG_TRY(cv.run(st));
-            } else
-            for (int q = 0; q < 4; ++q) {
-                const int a = q >> 1, bb = q & 1;
-                const int mh = (ih - a + 1) / 2, mw = (iw - bb + 1) / 2;
-                if (mh <= 0 || mw <= 0) continue;
-                Conv cv(dt, 2, 2, 1);
-                cv.in(dcur, B, oh, ow, dcur_c).w(wp + P.wd[l][q]).out(dst, mh, mw, cin).pad(a ? 0 : 1, bb ? 0 : 1).scatter(2, a, bb, ih, iw);
-                if (mz.p) cv.mask(mz, 0);
-                SG_TRY(cv.run(st));
-            }
-        }
-        dcur = dst; dcur_c = cin;
-    }
-    if (dx_nchw) SG_TRY(srcgan_nhwc_to_nchw_f32(s8 + Q.dxin, dx_nchw, B, c->in_ch, c->H, c->W, P.in_cs, 0, dt, st));
-    return 0;
+    return DCall(c, P, params, ws, opt, st, &Q, scratch, grads).backward(dy_nchw, dx_nchw);
 }
 
 // ======================================================================================== op-list networks
@@ -1232,17 +1256,6 @@ extern "C" int srcgan_nlayerd_backward_ex(const srcgan_nlayerd_cfg* c, const flo
 // convolution with a fused ReLU is the gradient w.r.t. its pre-activation: whoever writes it applies the mask (the consumer's
 // dgrad epilogue, or srcgan_mask_inplace for the gradient arriving from the loss).
 namespace {
-// Input gradient of a k x k stride-2 convolution with padding `pad`, by output parity a (0 / 1) along one axis:
-//   dx[2 j + a] = sum over the kernel rows ky == (a + pad) mod 2 of dy[j + (a + pad - ky) / 2] * w[ky]
-// -> a stride-1 sub-convolution with n taps; tap t (ascending dy row) uses ky = ky_max - 2 t and needs `lead` rows above row j.
-struct Par2 { int n, ky_max, lead; };
-static inline Par2 par2(int k, int pad, int a) {
-    int ky_max = k - 1;
-    if (((ky_max ^ (a + pad)) & 1) != 0) --ky_max;
-    Par2 r; r.ky_max = ky_max; r.n = ky_max >= 0 ? ky_max / 2 + 1 : 0; r.lead = (ky_max - a - pad) / 2;
-    return r;
-}
-
 struct RdT { int C, cs, H, W, act; size_t off; };       // act: produced by a convolution with a fused ReLU
 struct RdOp {
     int type;                 // 0 conv (+bias)(+ReLU), 1 GroupNorm(+res)(+ReLU), 2 ConvTranspose2d k2 s2, 3 PixelShuffle(r)
@@ -1251,6 +1264,7 @@ struct RdOp {
     int ngrp;                 // GroupNorm: groups (InstanceNorm2d: = channels)
     float slope;              // GroupNorm activation: 0 = ReLU, 0.2 = LeakyReLU (edsr.py:42)
     size_t wf[4], wd[4], stats;
+    S2Dgrad s2(int cin, int cout) const { return S2Dgrad{k, pad, cin, cout}; }      // input gradient of a stride-2 convolution with k > 1
 };
 struct RdPlan {
     int dtype, esz, B, H, W, in_ch, out_ch, in_cs, out_cs, nparams, maxC;
@@ -1326,11 +1340,9 @@ struct RdBuilder {
             const RdT ti = P.T[o.in], to = P.T[o.out];
             if (o.type == 0) {
                 o.wf[0] = pk(to.C, ti.C, o.k * o.k);
-                {       // (the input tensor's own gradient is produced on request: dx_nchw of the backward entry points)
-                    if (o.s == 1) o.wd[0] = pk(ti.C, to.C, o.k * o.k);
-                    else if (o.k == 1) o.wd[0] = pk(ti.C, to.C, 1);
-                    else for (int q = 0; q < 4; ++q) o.wd[q] = pk(ti.C, to.C, par2(o.k, o.pad, q >> 1).n * par2(o.k, o.pad, q & 1).n);
-                }
+                if (o.s == 1) o.wd[0] = pk(ti.C, to.C, o.k * o.k);
+                else if (o.k == 1) o.wd[0] = pk(ti.C, to.C, 1);
+                else o.s2(ti.C, to.C).plan(wb, dtype, o.wd);
             } else if (o.type == 2) {
                 for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.C, ti.C, 1);
                 o.wd[0] = pk(ti.C, to.C, 4);
@@ -1447,6 +1459,7 @@ static int sr_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
     return 0;
 }
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
+static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
 static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, const char* tag, void* st) {
     SG_REQUIRE(x_nchw && params && ws && y_nchw, "%s forward: null pointer", tag);
@@ -1505,14 +1518,9 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
         for (const RdOp& o : P.ops) {
             const RdT ti = P.T[o.in], to = P.T[o.out];
             if (o.type == 0 && (o.in != 0 || dx_nchw)) {
-                if (o.s == 1) { const WLayout L = lay_dgrad_s1(ti.C, o.k, o.k); packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, o.k, o.k, L.sr, L.sk, L.sty, L.stx, L.off); }
+                if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, o.k, o.k, lay_dgrad_s1(ti.C, o.k, o.k));
                 else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 1, 1, 1, (long)ti.C, 0, 0, 0);
-                else
-                    for (int q = 0; q < 4; ++q) {       // stride-2 dgrad by output parity (a,b): par2() taps per axis (3x3 p1: 1 or 2; 7x7 p3: 3 or 4)
-                        const Par2 py = par2(o.k, o.pad, q >> 1), px = par2(o.k, o.pad, q & 1);
-                        const long kk = (long)o.k * o.k;
-                        packs.add(params[o.w], wp + o.wd[q], ti.C, to.C, py.n, px.n, kk, (long)ti.C * kk, -2 * o.k, -2, (long)py.ky_max * o.k + px.ky_max);
-                    }
+                else o.s2(ti.C, to.C).pack(packs, params[o.w], wp, o.wd);
             } else if (o.type == 2) {
                 packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 2, 2, (long)to.C * 4, 4, 2, 1, 0);
             }
@@ -1566,17 +1574,8 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                     cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, to.H, to.W, ti.C).pad(0, 0).scatter(2, 0, 0, ti.H, ti.W);
                     if (acc) cv.res1(dx, ti.C, 1.f);
                     SG_TRY(cv.run(st));
-                } else {
-                    for (int q = 0; q < 4; ++q) {
-                        const int a = q >> 1, bb = q & 1;
-                        const int mh = (ti.H - a + 1) / 2, mw = (ti.W - bb + 1) / 2;
-                        const Par2 py = par2(o.k, o.pad, a), px = par2(o.k, o.pad, bb);
-                        Conv cv(dt, py.n, px.n, 1);
-                        cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[q]).out(dx, mh, mw, ti.C).pad(py.lead, px.lead).scatter(2, a, bb, ti.H, ti.W);
-                        if (acc) cv.res1(dx, ti.C, 1.f);
-                        SG_TRY(cv.run(st));
-                    }
-                }
+                } else
+                    SG_TRY(o.s2(ti.C, to.C).run(dt, dy, B, to.H, to.W, dx, ti.H, ti.W, wp, o.wd, acc ? dx : TNULL, TNULL, false, st));
                 written[o.in] = 1;
             }
         } else if (o.type == 1) {
@@ -1632,11 +1631,11 @@ extern "C" size_t srcgan_srnet_bwd_scratch_bytes(const srcgan_srnet_cfg* c) { Rd
 extern "C" int srcgan_srnet_forward(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
     RdPlan P;
     SG_TRY(sr_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind == 0 ? "espcn" : c->kind == 1 ? "srcnn" : "edsr", st);
+    return rd_forward(P, x_nchw, params, ws, y_nchw, sr_tag(c->kind), st);
 }
 extern "C" int srcgan_srnet_backward(const srcgan_srnet_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
                                      float* const* grads, float* dx_nchw, void* st) {
     RdPlan P;
     SG_TRY(sr_plan(c, P));
-    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, c->kind == 0 ? "espcn" : c->kind == 1 ? "srcnn" : "edsr", st);
+    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, sr_tag(c->kind), st);
 }
