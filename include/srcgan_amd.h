@@ -381,6 +381,24 @@ int srcgan_resdeconv_forward(const srcgan_resdeconv_cfg* c, const float* x_nchw,
 /* dx_nchw: gradient w.r.t. the input [B,3,H,W] f32, or NULL */
 int srcgan_resdeconv_backward(const srcgan_resdeconv_cfg* c, const float* dy_nchw, const float* const* params, void* ws,
                               void* scratch, float* const* grads, float* dx_nchw, void* stream);
+/* Inference forward (no backward can follow): the launches of srcgan_resdeconv_forward in the same order with the same arguments,
+ * on a workspace whose tensors share slots -- a slot is handed back after its tensor's last reader, an op's output never aliases its
+ * inputs.  The activation part (infer_act_bytes = infer_ws_bytes minus the packed weights) does not depend on `layers`.
+ * fold_tail = 0: bit-identical to srcgan_resdeconv_forward.  fold_tail = 1: deconv13 -> pred (resdeconv.py:194-195, linear: no bias,
+ * nothing between them) run as four parity 2x2 convolutions 64 -> tar_ch on the half-resolution tensor with composed weights
+ * (srcgan_fold_tail_pack); the 64-channel full-resolution tensor is never made.  Equal in real arithmetic, not bit for bit.
+ * infer_plan (for tests of the planner): per op k, ranges[6k..6k+5] = byte {offset, size} of its input, its residual operand
+ * (0, 0: none) and its output inside the workspace; writes at most `cap` ops, returns the op count or -1. */
+size_t srcgan_resdeconv_infer_ws_bytes(const srcgan_resdeconv_cfg* c, int fold_tail);
+size_t srcgan_resdeconv_infer_act_bytes(const srcgan_resdeconv_cfg* c, int fold_tail);
+int srcgan_resdeconv_infer_plan(const srcgan_resdeconv_cfg* c, int fold_tail, size_t* ranges, int cap);
+int srcgan_resdeconv_infer(const srcgan_resdeconv_cfg* c, const float* x_nchw, const float* const* params, void* ws,
+                           float* y_nchw, int fold_tail, void* stream);
+/* Composed weights of ConvTranspose2d(64, 64, k2 s2, no bias) [64,64,2,2] followed by Conv2d(64, tar, 3x3 p1, no bias) [tar,64,3,3]
+ * (tar <= 8), both f32: four packs Wp[parity a * 2 + b][chunk][tap dy * 2 + dx][row (32)][k] of the 2x2 stride-1 convolutions that
+ * give output pixel (2i + a, 2j + b) from the input pixels (i + a - 1 + dy, j + b - 1 + dx); rows >= tar are zero. */
+size_t srcgan_fold_tail_pack_bytes(int dtype);
+int srcgan_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int tar, int dtype, void* stream);
 
 /* SR networks selectable as --SRModel (trainCas.py:169): kind 0 = ESPCN (espcn.py:18-51; the CLI default), kind 1 = SRCNN
  * (srcnn.py:17-42), kind 2 = EDSR (edsr.py:37-110: GroupNorm residual blocks, [B,out_ch,H*up,W*up]).  [B,in_ch,H,W] f32 NCHW -> ESPCN [B,out_ch,H*up,W*up] / SRCNN [B,out_ch,H,W].  params/grads in state_dict
@@ -397,6 +415,12 @@ size_t srcgan_srnet_bwd_scratch_bytes(const srcgan_srnet_cfg* c);
 int srcgan_srnet_forward(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 int srcgan_srnet_backward(const srcgan_srnet_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
                           float* const* grads, float* dx_nchw, void* stream);
+/* Inference forward of ESPCN / SRCNN / EDSR: as srcgan_resdeconv_infer with fold_tail = 0 (bit-identical to srcgan_srnet_forward;
+ * the activation part does not depend on nres). */
+size_t srcgan_srnet_infer_ws_bytes(const srcgan_srnet_cfg* c);
+size_t srcgan_srnet_infer_act_bytes(const srcgan_srnet_cfg* c);
+int srcgan_srnet_infer_plan(const srcgan_srnet_cfg* c, size_t* ranges, int cap);
+int srcgan_srnet_infer(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
 /* nn.PixelShuffle(r) on NHWC (espcn.py:44,50): src [B,H,W,C*r*r] -> dst [B,H*r,W*r,C]; inverse = 1: the adjoint, src [B,H*r,W*r,C]
  * -> dst [B,H,W,C*r*r].  srcgan_mask_inplace: g *= (act > 0 ? 1 : slope) over n elements (ReLU' / LeakyReLU' on an incoming gradient). */

@@ -447,6 +447,51 @@ extern "C" int srcgan_pack_weight(const float* w, void* wp, int rows, int kdim, 
     return srcgan_pack_weight_part(w, wp, rows, kdim, tys, txs, sr, sk, sty, stx, off, 0, kdim, 1.f, dtype, stream);
 }
 
+// Folded tail of the ResDeconv colouriser (resdeconv.py:194-195): deconv13 = ConvTranspose2d(64, 64, k2 s2) feeds pred = Conv2d(64, tar, 3x3,
+// p1) with nothing between them and neither has a bias, so their composition is linear in the half-resolution tensor h:
+//   y[t][2i + a][2j + b] = sum over (dy, dx) in {0,1}^2, c:  h[c][i + a - 1 + dy][j + b - 1 + dx] * Wc[a][b][dy][dx][t][c]
+//   Wc[a][b][dy][dx][t][c] = sum over m and the 3x3 taps (u, v) with  floor((a + u - 1) / 2) == a - 1 + dy,  floor((b + v - 1) / 2) == b - 1 + dx:
+//                            pred[t][m][u][v] * deconv13[c][m][(a + u - 1) mod 2][(b + v - 1) mod 2]
+// (tap u of output row 2i + a reads full-resolution row 2i + a + u - 1 = sub-row p = (a + u - 1) mod 2 of half-resolution row
+// i + floor((a + u - 1) / 2); a half-resolution pixel outside the image stands for four zero-padding pixels of pred.)  One thread per element
+// of the four parity packs Wp[parity][chunk][tap dy * 2 + dx][row (32)][k (KCE)], rows >= tar zero; f32 accumulation of at most 4 x 64 products.
+template <typename T>
+__global__ __launch_bounds__(256) void fold_tail_pack_k(const float* __restrict__ wd, const float* __restrict__ wc, T* __restrict__ wp, int tar) {
+    constexpr int KCE = DT<T>::KCE, PER = 64 * 4 * 32;         // elements of one parity's pack
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= 4 * PER) return;
+    int q = e % PER;
+    const int par = e / PER, a = par >> 1, b = par & 1;
+    const int kl = q % KCE; q /= KCE;
+    const int t = q % 32; q /= 32;
+    const int tap = q % 4, c = (q / 4) * KCE + kl;
+    const int dy = tap >> 1, dx = tap & 1;
+    float s = 0.f;
+    if (t < tar) {
+        for (int u = 0; u < 3; ++u) {
+            const int hy = (a + u + 1) / 2 - 1, p = a + u - 1 - 2 * hy;      // floor((a + u - 1) / 2) for a + u - 1 >= -1
+            if (hy != a - 1 + dy) continue;
+            for (int v = 0; v < 3; ++v) {
+                const int hx = (b + v + 1) / 2 - 1, r = b + v - 1 - 2 * hx;
+                if (hx != b - 1 + dx) continue;
+                for (int m = 0; m < 64; ++m) s += wc[((t * 64 + m) * 3 + u) * 3 + v] * wd[((c * 64 + m) * 2 + p) * 2 + r];
+            }
+        }
+    }
+    wp[e] = from_f<T>(s);
+}
+int sg_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int tar, int dtype, hipStream_t st) {
+    SG_REQUIRE(w_deconv && w_conv && wp && tar >= 1 && tar <= 8, "fold_tail_pack: bad arguments");
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(fold_tail_pack_k<T>, dim3(4 * 64 * 4 * 32 / 256), dim3(256), 0, st, w_deconv, w_conv, (T*)wp, tar));
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" size_t srcgan_fold_tail_pack_bytes(int dtype) { return sg_dtype_ok(dtype) ? 4 * srcgan_packed_weight_bytes(8, 64, 4, dtype) : 0; }
+extern "C" int srcgan_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int tar, int dtype, void* stream) {
+    SG_REQUIRE(sg_dtype_ok(dtype), "srcgan_fold_tail_pack: bad dtype %d", dtype);
+    return sg_fold_tail_pack(w_deconv, w_conv, wp, tar, dtype, (hipStream_t)stream);
+}
+
 // --------------------------------------------------------------------------- column reductions
 // Block = 64 channel lanes x 4 pixel lanes.  Stage 1 writes partial[which][blk][c]; stage 2 sums
 // the blocks in index order.

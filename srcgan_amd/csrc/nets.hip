@@ -1258,9 +1258,11 @@ extern "C" int srcgan_nlayerd_backward_ex(const srcgan_nlayerd_cfg* c, const flo
 namespace {
 struct RdT { int C, cs, H, W, act; size_t off; };       // act: produced by a convolution with a fused ReLU
 struct RdOp {
-    int type;                 // 0 conv (+bias)(+ReLU), 1 GroupNorm(+res)(+ReLU), 2 ConvTranspose2d k2 s2, 3 PixelShuffle(r)
+    int type;                 // 0 conv (+bias)(+ReLU), 1 GroupNorm(+res)(+ReLU), 2 ConvTranspose2d k2 s2, 3 PixelShuffle(r),
+                              // 4 (inference plans only) ConvTranspose2d k2 s2 followed by a bias-free 3x3 conv, folded into four parity 2x2 convs
     int in, out, res, relu;
     int k, s, pad, w, bias;   // w: parameter index of the weight (GroupNorm: gamma, beta = w + 1; -1 = no affine part); bias: parameter index or -1
+    int w2;                   // type 4: parameter index of the 3x3 convolution's weight (w = the transposed convolution's)
     int ngrp;                 // GroupNorm: groups (InstanceNorm2d: = channels)
     float slope;              // GroupNorm activation: 0 = ReLU, 0.2 = LeakyReLU (edsr.py:42)
     size_t wf[4], wd[4], stats;
@@ -1270,6 +1272,7 @@ struct RdPlan {
     int dtype, esz, B, H, W, in_ch, out_ch, in_cs, out_cs, nparams, maxC;
     std::vector<RdT> T; std::vector<RdOp> ops;
     size_t xin, gnfwd, wpk, total, act_bytes;
+    size_t wpack;             // inference plans: bytes of the packed-weight part
     std::vector<size_t> g;    // backward: gradient buffer offsets (scratch), same shapes as T
     size_t slab, gnscr, colscr, bwd_total;
 };
@@ -1475,6 +1478,8 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
     }
     char key[64]; snprintf(key, sizeof(key), "%s_fwd", tag);
     SG_TRY(packs.run(key, params[0], st));
+    for (const RdOp& o : P.ops)      // composed weights of a folded tail: made from both sources on every call, like the packs above
+        if (o.type == 4) SG_TRY(sg_fold_tail_pack(params[o.w], params[o.w2], wp + o.wf[0], P.T[o.out].C, dt, (hipStream_t)st));
     SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, P.in_ch, P.H, P.W, P.in_cs, dt, st));
     float* gnscr = (float*)(w8 + P.gnfwd);
     for (const RdOp& o : P.ops) {
@@ -1496,13 +1501,111 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
             for (int q = 0; q < 4; ++q)
                 SG_TRY(Conv(dt, 1, 1, 1).in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[q]).out(out, ti.H, ti.W, to.C)
                            .scatter(2, q >> 1, q & 1, to.H, to.W).run(st));
-        } else {
+        } else if (o.type == 3) {
             SG_TRY(srcgan_pixel_shuffle_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, to.C, o.k, 0, dt, st));
+        } else {
+            // folded tail: output pixel (2i + a, 2j + b) = 2x2 window of the half-resolution input at (i + a - 1, j + b - 1) times the
+            // composed weights of parity (a, b) -- the geometry of the 4x4 stride-2 input gradient, so its four-parity kernel serves.
+            // All to.cs channels are written (the pack's rows >= to.C are zero): no memset of the padded channels.
+            Conv cv(dt, 2, 2, 1);
+            cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0]).out(out, ti.H, ti.W, to.cs).scatter(2, 0, 0, to.H, to.W);
+            cv.d.npar = 4; cv.d.wpar_stride = (long)(o.wf[1] - o.wf[0]);
+            SG_TRY(cv.run(st));
         }
     }
     const RdT& last = P.T.back();
     SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + last.off, y_nchw, B, P.out_ch, last.H, last.W, last.cs, 0, dt, st));
     return 0;
+}
+
+// ---- inference: the same op list on a liveness-planned workspace.  rd_forward walks whatever offsets the plan holds, so an
+// inference plan is the training plan with its addresses rewritten: a tensor's slot is handed back after its last reader (as `in`
+// or as `res`) and reused by later tensors of the same byte size -- one pool per size: a network's stages each cycle through a
+// handful of equal tensors, so the pool sizes do not depend on the depth.  An op's output slot is taken BEFORE its inputs are
+// handed back: it never aliases them (the kernels take __restrict__ pointers).  GroupNorm statistics share one region (nothing reads
+// them after the op), and only the forward packs are laid out.  fold: the trailing ConvTranspose2d k2 s2 -> bias-free 3x3 conv pair
+// becomes one op of type 4, and the full-resolution tensor between them gets no slot.
+static inline size_t rd_bytes(const RdPlan& P, const RdT& t) { return (size_t)P.B * t.H * t.W * t.cs * P.esz; }
+
+static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare = 0) {
+    if (fold) {
+        const int n = (int)P.ops.size();
+        SG_REQUIRE(n >= 2, "%s: no tail to fold", who);
+        const RdOp d = P.ops[n - 2], c = P.ops[n - 1];
+        SG_REQUIRE(d.type == 2 && c.type == 0 && c.in == d.out && c.k == 3 && c.s == 1 && c.pad == 1 && c.bias < 0 && !c.relu && c.res < 0 &&
+                   P.T[d.in].C == 64 && P.T[d.out].C == 64 && P.T[c.out].cs == 8,
+                   "%s: the tail is not ConvTranspose2d(64, 64, k2 s2) -> bias-free 3x3 convolution to <= 8 channels", who);
+        RdOp f; memset(&f, 0, sizeof(f));
+        f.type = 4; f.in = d.in; f.out = c.out; f.res = -1; f.k = 2; f.s = 1; f.w = d.w; f.w2 = c.w; f.bias = -1;
+        P.ops.resize(n - 2);
+        P.ops.push_back(f);
+    }
+    const int nops = (int)P.ops.size(), nt = (int)P.T.size();
+    std::vector<int> last(nt, -1);
+    for (int k = 0; k < nops; ++k) { last[P.ops[k].in] = k; if (P.ops[k].res >= 0) last[P.ops[k].res] = k; }
+    last[nt - 1] = nops;                                       // the output conversion reads the last tensor
+    Bump b;
+    std::map<size_t, std::vector<size_t>> pool;                // byte size -> free slots
+    auto get = [&](int t) {
+        const size_t sz = align_up(rd_bytes(P, P.T[t]), 256);
+        std::vector<size_t>& f = pool[sz];
+        if (f.empty()) P.T[t].off = b.take(sz);
+        else { P.T[t].off = f.back(); f.pop_back(); }
+    };
+    auto put = [&](int t) { pool[align_up(rd_bytes(P, P.T[t]), 256)].push_back(P.T[t].off); };
+    for (RdT& t : P.T) t.off = 0;
+    get(0);
+    P.xin = P.T[0].off;
+    for (int k = 0; k < nops; ++k) {
+        const RdOp& o = P.ops[k];
+        get(o.out);
+        if (last[o.in] == k) put(o.in);
+        if (o.res >= 0 && o.res != o.in && last[o.res] == k) put(o.res);
+    }
+    if (spare) b.take(spare);
+    size_t stats = 0;
+    for (const RdOp& o : P.ops) if (o.type == 1) stats = std::max(stats, (size_t)P.B * o.ngrp * 2 * sizeof(float));
+    const size_t stats_off = b.take(stats);
+    for (RdOp& o : P.ops) if (o.type == 1) o.stats = stats_off;
+    P.gnfwd = b.take(srcgan_gn_scratch_floats(P.B, P.maxC > 1024 ? 1024 : P.maxC) * sizeof(float));
+    P.act_bytes = b.off;
+    P.wpk = b.off;
+    Bump wb;
+    auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, P.dtype)); };
+    for (RdOp& o : P.ops) {
+        const RdT ti = P.T[o.in], to = P.T[o.out];
+        if (o.type == 0) o.wf[0] = pk(to.C, ti.C, o.k * o.k);
+        else if (o.type == 2) { for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.C, ti.C, 1); }
+        else if (o.type == 4) { for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.cs, ti.C, 4); }
+    }
+    P.wpack = wb.off;
+    P.total = align_up(P.wpk + wb.off + 256, 256);
+    return 0;
+}
+static int rd_infer_plan(const srcgan_resdeconv_cfg* c, int fold, RdPlan& P) {
+    SG_TRY(rd_plan(c, P));
+    SG_REQUIRE(fold == 0 || fold == 1, "resdeconv: fold_tail must be 0 or 1");
+    return rd_infer_replan(P, fold != 0, "resdeconv");
+}
+static int sr_infer_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
+    SG_TRY(sr_plan(c, P));
+    // EDSR with ONE residual block: its input is input_conv's output, which the global skip keeps alive anyway, so it needs one
+    // feature slot fewer than every deeper stack (4).  It gets the fourth as a spare: the activation part is then a function of
+    // the shapes alone, and a caller can size one workspace for a family of depths.
+    const size_t spare = (c->kind == 2 && c->nres == 1) ? (size_t)c->B * c->H * c->W * c->base * P.esz : 0;
+    return rd_infer_replan(P, false, "srnet", spare);
+}
+// per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
+static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
+    const int n = (int)P.ops.size();
+    for (int k = 0; k < n && k < cap && ranges; ++k) {
+        const RdOp& o = P.ops[k];
+        size_t* r = ranges + 6 * k;
+        r[0] = P.T[o.in].off; r[1] = rd_bytes(P, P.T[o.in]);
+        r[2] = o.res >= 0 ? P.T[o.res].off : 0; r[3] = o.res >= 0 ? rd_bytes(P, P.T[o.res]) : 0;
+        r[4] = P.T[o.out].off; r[5] = rd_bytes(P, P.T[o.out]);
+    }
+    return n;
 }
 
 static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, const float* const* params, void* ws, void* scratch, float* const* grads,
@@ -1638,4 +1741,34 @@ extern "C" int srcgan_srnet_backward(const srcgan_srnet_cfg* c, const float* dy_
     RdPlan P;
     SG_TRY(sr_plan(c, P));
     return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, sr_tag(c->kind), st);
+}
+
+// Inference forwards of the op-list networks: rd_forward on the liveness-planned workspace (same launches, same arguments apart from
+// buffer addresses -> the same bits), and for ResDeconv optionally the folded tail.  The job tables are cached under tags of their
+// own: the packs sit at other offsets than the training forward's (no dgrad packs between them).
+extern "C" size_t srcgan_resdeconv_infer_ws_bytes(const srcgan_resdeconv_cfg* c, int fold_tail) { RdPlan P; if (rd_infer_plan(c, fold_tail, P)) return 0; return P.total; }
+extern "C" size_t srcgan_resdeconv_infer_act_bytes(const srcgan_resdeconv_cfg* c, int fold_tail) { RdPlan P; if (rd_infer_plan(c, fold_tail, P)) return 0; return P.total - P.wpack; }
+extern "C" int srcgan_resdeconv_infer_plan(const srcgan_resdeconv_cfg* c, int fold_tail, size_t* ranges, int cap) {
+    RdPlan P;
+    if (rd_infer_plan(c, fold_tail, P)) return -1;
+    return rd_plan_ranges(P, ranges, cap);
+}
+extern "C" int srcgan_resdeconv_infer(const srcgan_resdeconv_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw,
+                                      int fold_tail, void* st) {
+    RdPlan P;
+    SG_TRY(rd_infer_plan(c, fold_tail, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, fold_tail ? "resdeconv_fold" : "resdeconv_infer", st);
+}
+extern "C" size_t srcgan_srnet_infer_ws_bytes(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_infer_plan(c, P)) return 0; return P.total; }
+extern "C" size_t srcgan_srnet_infer_act_bytes(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_infer_plan(c, P)) return 0; return P.total - P.wpack; }
+extern "C" int srcgan_srnet_infer_plan(const srcgan_srnet_cfg* c, size_t* ranges, int cap) {
+    RdPlan P;
+    if (sr_infer_plan(c, P)) return -1;
+    return rd_plan_ranges(P, ranges, cap);
+}
+extern "C" int srcgan_srnet_infer(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(sr_infer_plan(c, P));
+    char tag[32]; snprintf(tag, sizeof(tag), "%s_infer", sr_tag(c->kind));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, tag, st);
 }

@@ -410,25 +410,31 @@ class LegacyRDDBNet(RDDBNetB):
 
 
 # ------------------------------------------------------------------------------------------------ ResDeconv colouriser
+def _resdeconv_prepare(x, out_ch, dtype, layers, norm, params):
+    """Checks and conversions shared by the training forward and the inference call -> (x, cfg, plist)."""
+    N.require_cuda(x, "ResDeconv.forward")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f"ResDeconv's stem expects 3 channels, got {tuple(x.shape)}")
+    x = x.detach().contiguous().float()
+    B, _, H, W = x.shape
+    if H % 16 or W % 16:
+        raise ValueError(f"ResDeconv needs H and W to be multiples of 16 (four stride-2 stages), got {H}x{W}")
+    cfg = N.ResDeconvCfg(3, out_ch, B, H, W, dtype, (C.c_int * 4)(*layers), norm)
+    for p in params:
+        N.require_cuda(p, "ResDeconv parameter")
+    plist = [p.detach().contiguous() for p in params]
+    return x, cfg, plist
+
+
 class _ResDeconvFn(torch.autograd.Function):
     """One native forward / one native backward for the whole colouriser (resdeconv.py:164-195)."""
 
     @staticmethod
     def forward(ctx, x, out_ch, dtype, layers, norm, *params):
-        N.require_cuda(x, "ResDeconv.forward")
         lib = N.lib()
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise ValueError(f"ResDeconv's stem expects 3 channels, got {tuple(x.shape)}")
-        x = x.detach().contiguous().float()
-        B, _, H, W = x.shape
-        if H % 16 or W % 16:
-            raise ValueError(f"ResDeconv needs H and W to be multiples of 16 (four stride-2 stages), got {H}x{W}")
-        cfg = N.ResDeconvCfg(3, out_ch, B, H, W, dtype, (C.c_int * 4)(*layers), norm)
-        for p in params:
-            N.require_cuda(p, "ResDeconv parameter")
-        plist = [p.detach().contiguous() for p in params]
+        x, cfg, plist = _resdeconv_prepare(x, out_ch, dtype, layers, norm, params)
         ws = N.workspace(lib.srcgan_resdeconv_ws_bytes(C.byref(cfg)), x.device)
-        y = torch.empty(B, out_ch, H, W, dtype=torch.float32, device=x.device)
+        y = torch.empty(cfg.B, out_ch, cfg.H, cfg.W, dtype=torch.float32, device=x.device)
         N.check(lib.srcgan_resdeconv_forward(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(),
                                              N.stream_ptr(x.device)), "srcgan_resdeconv_forward")
         ctx.cfg, ctx.ws = cfg, ws
@@ -455,6 +461,19 @@ class _ResDeconvFn(torch.autograd.Function):
         if ctx.phase_hook is not None:
             ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
         return (dx, None, None, None, None, *grads)
+
+
+def _resdeconv_infer(x, out_ch, dtype, layers, norm, params, fold_tail=1):
+    """Forward under ``torch.no_grad()``: one native call on the slot-planned inference workspace (``srcgan_resdeconv_infer``),
+    released on return; no autograd node.  ``fold_tail=1``: deconv13 and pred run as four parity 2x2 convolutions with composed
+    weights, the 64-channel full-resolution tensor is never made.  ``fold_tail=0``: the training forward's launches, its bits."""
+    lib = N.lib()
+    x, cfg, plist = _resdeconv_prepare(x, out_ch, dtype, layers, norm, params)
+    ws = N.workspace(lib.srcgan_resdeconv_infer_ws_bytes(C.byref(cfg), fold_tail), x.device)
+    y = torch.empty(cfg.B, out_ch, cfg.H, cfg.W, dtype=torch.float32, device=x.device)
+    N.check(lib.srcgan_resdeconv_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), fold_tail,
+                                       N.stream_ptr(x.device)), "srcgan_resdeconv_infer")
+    return y
 
 
 class _BasicBlockHolder(_HolderOnly):
@@ -533,33 +552,42 @@ class ResDeconv(nn.Module):
     def forward(self, x):
         if self.src_ch == 1:
             x = torch.cat([x, x, x], dim=1)
-        return _ResDeconvFn.apply(x, self.tar_ch, N.dtype_id(self.compute_dtype), self.layers_cfg, 1 if self.BN == "IN" else 0, *self.parameters())
+        args = (self.tar_ch, N.dtype_id(self.compute_dtype), self.layers_cfg, 1 if self.BN == "IN" else 0)
+        if torch.is_grad_enabled():         # the rule of _rddb_forward: grad mode decides, eval() plays no part
+            return _ResDeconvFn.apply(x, *args, *self.parameters())
+        return _resdeconv_infer(x, *args, list(self.parameters()))
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
 
 
 # ------------------------------------------------------------------------------------------------ ESPCN / SRCNN
+def _srnet_prepare(x, cfg_items, params):
+    """Checks and conversions shared by the training forward and the inference call -> (x, cfg, plist, output shape)."""
+    N.require_cuda(x, "ESPCN/SRCNN forward")
+    kind, in_ch, out_ch, up, base, dtype = cfg_items[:6]
+    nres = cfg_items[6] if len(cfg_items) > 6 else 0
+    if x.dim() != 4 or x.shape[1] != in_ch:
+        raise ValueError(f"expected [B,{in_ch},H,W], got {tuple(x.shape)}")
+    x = x.detach().contiguous().float()
+    B, _, H, W = x.shape
+    cfg = N.SrNetCfg(kind, in_ch, out_ch, up, base, B, H, W, dtype, nres)
+    for p in params:
+        N.require_cuda(p, "parameter")
+    plist = [p.detach().contiguous() for p in params]
+    f = 1 if kind == 1 else up
+    return x, cfg, plist, (B, out_ch, H * f, W * f)
+
+
 class _SrNetFn(torch.autograd.Function):
     """One native forward / backward for the small --SRModel networks (kind 0 ESPCN, 1 SRCNN)."""
 
     @staticmethod
     def forward(ctx, x, cfg_items, *params):
-        N.require_cuda(x, "ESPCN/SRCNN forward")
         lib = N.lib()
-        kind, in_ch, out_ch, up, base, dtype = cfg_items[:6]
-        nres = cfg_items[6] if len(cfg_items) > 6 else 0
-        if x.dim() != 4 or x.shape[1] != in_ch:
-            raise ValueError(f"expected [B,{in_ch},H,W], got {tuple(x.shape)}")
-        x = x.detach().contiguous().float()
-        B, _, H, W = x.shape
-        cfg = N.SrNetCfg(kind, in_ch, out_ch, up, base, B, H, W, dtype, nres)
-        for p in params:
-            N.require_cuda(p, "parameter")
-        plist = [p.detach().contiguous() for p in params]
+        x, cfg, plist, yshape = _srnet_prepare(x, cfg_items, params)
         ws = N.workspace(lib.srcgan_srnet_ws_bytes(C.byref(cfg)), x.device)
-        f = 1 if kind == 1 else up
-        y = torch.empty(B, out_ch, H * f, W * f, dtype=torch.float32, device=x.device)
+        y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
         N.check(lib.srcgan_srnet_forward(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
                 "srcgan_srnet_forward")
         ctx.cfg, ctx.ws = cfg, ws
@@ -588,6 +616,20 @@ class _SrNetFn(torch.autograd.Function):
         return (dx, None, *grads)
 
 
+def _srnet_forward(x, cfg_items, params):
+    """Grad mode on: the autograd Function (workspace kept for backward).  Off: ``srcgan_srnet_infer`` on the slot-planned
+    workspace, released on return -- the same launches, hence the same bits."""
+    if torch.is_grad_enabled():
+        return _SrNetFn.apply(x, cfg_items, *params)
+    lib = N.lib()
+    x, cfg, plist, yshape = _srnet_prepare(x, cfg_items, params)
+    ws = N.workspace(lib.srcgan_srnet_infer_ws_bytes(C.byref(cfg)), x.device)
+    y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
+    N.check(lib.srcgan_srnet_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
+            "srcgan_srnet_infer")
+    return y
+
+
 class ESPCN(nn.Module):
     """Drop-in for reference ``model.ESPCN`` (src/model/espcn.py:18-51; the CLI default ``--SRModel``, trainCas.py:169):
     5x5, 3x3, 3x3 convolutions + ReLU, 3x3 to 64 r^2 channels, PixelShuffle(r), 3x3."""
@@ -607,7 +649,7 @@ class ESPCN(nn.Module):
         self.compute_dtype = N.dtype_name(dtype)
 
     def forward(self, x):
-        return _SrNetFn.apply(x, (*self._cfg, N.dtype_id(self.compute_dtype)), *self.parameters())
+        return _srnet_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
@@ -629,7 +671,7 @@ class SRCNN(nn.Module):
         self.compute_dtype = N.dtype_name(dtype)
 
     def forward(self, x):
-        return _SrNetFn.apply(x, (*self._cfg, N.dtype_id(self.compute_dtype)), *self.parameters())
+        return _srnet_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
@@ -664,7 +706,7 @@ class EDSR(nn.Module):
         self.compute_dtype = N.dtype_name(dtype)
 
     def forward(self, x):
-        return _SrNetFn.apply(x, (*self._cfg, N.dtype_id(self.compute_dtype), self._nres), *self.parameters())
+        return _srnet_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype), self._nres), list(self.parameters()))
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
