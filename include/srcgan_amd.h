@@ -115,7 +115,12 @@ typedef struct srcgan_conv_desc {
      * pack_q = wp + q * wpar_stride bytes (rows = the layer's Cin, k = its Cout, taps ky = (a?2:3) - 2ty, kx = (b?2:3) - 2tx).
      * OH / OW / pad / os / oa / ob are derived from YH, YW; epilogue operands (mz, r1, ...) are indexed like y.  npar == 0: plain.
      * npar == 4 with kh = kw = 1 (ConvTranspose2d k2 s2 as four 1x1 convolutions, rddb.py:28-38, in one launch): os = 2, oa = ob = 0;
-     *   y[2oy+a][2ox+b] = epilogue(x[oy][ox] * pack_q),  q = 2a + b,  pack_q = wp + q * wpar_stride bytes (Cout rows each). */
+     *   y[2oy+a][2ox+b] = epilogue(x[oy][ox] * pack_q),  q = 2a + b,  pack_q = wp + q * wpar_stride bytes (Cout rows each).
+     * npar == 4 with kh = kw = 3, stride = 2, pad 1 (ConvTranspose2d k3 s2 p1 output_padding 1, model/model.py:698-701, in one launch):
+     *   x [B,H,W,Cin], y [B,2H,2W,..], OH x OW = H x W, os = 2, oa = ob = 0;
+     *   y[2i+a][2j+b] = epilogue(sum_{wy <= a, wx <= b} x[i+wy][j+wx] * pack_q[tap wy * (b + 1) + wx]),  q = 2a + b (x = 0 past the edge),
+     * pack_q = wp + q * wpar_stride bytes: rows = Cout, k = Cin, (a + 1) x (b + 1) taps with ky = a ? 2 - 2 wy : 1, kx = b ? 2 - 2 wx : 1 of
+     * the canonical weight [Cin][Cout][3][3].  bias and act are fused; 16-byte accessible output channels are required. */
     int npar; long wpar_stride;
 } srcgan_conv_desc;
 int srcgan_conv_igemm(const srcgan_conv_desc* d, void* stream);
@@ -421,6 +426,35 @@ size_t srcgan_srnet_infer_ws_bytes(const srcgan_srnet_cfg* c);
 size_t srcgan_srnet_infer_act_bytes(const srcgan_srnet_cfg* c);
 int srcgan_srnet_infer_plan(const srcgan_srnet_cfg* c, size_t* ranges, int cap);
 int srcgan_srnet_infer(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
+/* SRDenseNetA (kind 0, LR -> HR) / SRDenseNetB (kind 1, HR -> LR), reference src/model/model.py:643-786: conv_first (in_ch -> 1),
+ * conv (1 -> growth * num_layers) + ReLU, num_blocks DenseBlocks of num_layers 3x3 layers with `growth` channels each, a 1x1 bottleneck
+ * to 256 + ReLU, the up-sampler ConvTranspose2d(256, 256, k3 s2 p1 output_padding 1) + ReLU (A) or the down-sampler Conv2d(256, 256,
+ * k3 s2 p1) + ReLU (B) applied once (up = 2: mode 'x2') or twice with the SAME weights (up = 4: 'x4'; their gradients add over the two
+ * uses), reconstruction (256 -> 1), conv_last (1 -> out_ch).  [B,in_ch,H,W] f32 NCHW -> A: [B,out_ch,H*up,W*up]; B: each stage maps n to
+ * (n + 1) / 2 (any H, W >= 2, odd sizes included).  params / grads in state_dict order: conv_first.{weight,bias}, conv.conv.*,
+ * dense_blocks.<i>.block.<j>.conv.*, bottleneck.0.*, deconv.0.*, reconstruction.*, conv_last.*.
+ * The dense blocks run concat-free in ONE buffer of growth * num_layers * (num_blocks + 1) channels (every block's output is the next
+ * block's input prefix), so a cfg is refused unless growth % 8 == 0 (a layer's slice is addressed in 16-byte pieces) and growth *
+ * num_layers is a multiple of the 64-byte K chunk (16 channels in f32, 32 in bf16 / f16: the slice offset of block i is growth *
+ * num_layers * (i + 1)).  The infer entry runs the forward's launches on a slot-planned workspace (same bits). */
+typedef struct srcgan_srdense_cfg {
+    int kind, in_ch, out_ch;
+    int B, H, W;
+    int dtype;
+    int growth, num_blocks, num_layers;
+    int up;                                /* 2 or 4 */
+} srcgan_srdense_cfg;
+int srcgan_srdense_num_params(const srcgan_srdense_cfg* c);
+int srcgan_srdense_out_hw(const srcgan_srdense_cfg* c, int* oh, int* ow);
+size_t srcgan_srdense_ws_bytes(const srcgan_srdense_cfg* c);
+size_t srcgan_srdense_bwd_scratch_bytes(const srcgan_srdense_cfg* c);
+int srcgan_srdense_forward(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+/* grads[i] may be NULL; dx_nchw: gradient w.r.t. the input [B,in_ch,H,W] f32, or NULL */
+int srcgan_srdense_backward(const srcgan_srdense_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                            float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_srdense_infer_ws_bytes(const srcgan_srdense_cfg* c);
+int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
 /* nn.PixelShuffle(r) on NHWC (espcn.py:44,50): src [B,H,W,C*r*r] -> dst [B,H*r,W*r,C]; inverse = 1: the adjoint, src [B,H*r,W*r,C]
  * -> dst [B,H,W,C*r*r].  srcgan_mask_inplace: g *= (act > 0 ? 1 : slope) over n elements (ReLU' / LeakyReLU' on an incoming gradient). */

@@ -99,6 +99,10 @@ class SrNetCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "in_ch", "out_ch", "up", "base", "B", "H", "W", "dtype", "nres")]
 
 
+class SrDenseCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kind", "in_ch", "out_ch", "B", "H", "W", "dtype", "growth", "num_blocks", "num_layers", "up")]
+
+
 class NLayerDCfg(C.Structure):
     _fields_ = [("in_ch", C.c_int), ("ndf", C.c_int), ("n_layers", C.c_int),
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int), ("training", C.c_int), ("norm", C.c_int)]
@@ -163,6 +167,14 @@ SIGNATURES = {
     "srcgan_srnet_infer_act_bytes": (_S, [C.POINTER(SrNetCfg)]),
     "srcgan_srnet_infer_plan": (_I, [C.POINTER(SrNetCfg), C.POINTER(C.c_size_t), _I]),
     "srcgan_srnet_infer": (_I, [C.POINTER(SrNetCfg), _P, _P, _P, _P, _P]),
+    "srcgan_srdense_num_params": (_I, [C.POINTER(SrDenseCfg)]),
+    "srcgan_srdense_out_hw": (_I, [C.POINTER(SrDenseCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "srcgan_srdense_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
+    "srcgan_srdense_bwd_scratch_bytes": (_S, [C.POINTER(SrDenseCfg)]),
+    "srcgan_srdense_forward": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
+    "srcgan_srdense_backward": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P, _P, _P]),
+    "srcgan_srdense_infer_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
+    "srcgan_srdense_infer": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
     "srcgan_pixel_shuffle_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_mask_inplace": (_I, [_P, _P, _F, _L, _I, _P]),
     "srcgan_metric_scratch_floats": (_I, [_I, _I, _I, _I]),

@@ -368,6 +368,7 @@ static int dispatch_shape(const ConvP& p, int kh, int kw, int s, int ctiles, hip
 
 int sg_conv3x3_dma(const ConvP& p, int dtype, hipStream_t st);      // conv3x3_dma.hip
 int sg_dgrad_s2k4(const ConvP& p, int dtype, hipStream_t st);       // conv_par4.hip
+int sg_deconv_k3s2(const ConvP& p, int dtype, hipStream_t st);      // deconv_k3s2.hip
 static const bool g_force_generic = sg_env("SRCGAN_GENERIC_3X3") != nullptr;   // A/B switch for benchmarking
 
 extern "C" int srcgan_conv_igemm(const srcgan_conv_desc* d, void* stream) {
@@ -434,7 +435,16 @@ extern "C" int srcgan_conv_igemm(const srcgan_conv_desc* d, void* stream) {
                   (!d->r2 || (p.r2plane < lim && p.r2pix < (1 << 20))) && (!d->mz || (p.mzplane < lim && p.mzpix < (1 << 20)));
     }
     hipStream_t st = (hipStream_t)stream;
-    if (d->npar && d->kh == 1 && d->kw == 1) {
+    if (d->npar && d->kh == 3) {
+        // ConvTranspose2d(k3, s2, p1, output_padding 1): the four output parities (1, 2, 2 and 4 taps) in one launch (deconv_k3s2.hip)
+        SG_REQUIRE(d->npar == 4 && d->kw == 3 && d->stride == 2 && d->pad_y == 1 && d->pad_x == 1 && d->os == 2 && d->oa == 0 && d->ob == 0 &&
+                   d->OH == d->H && d->OW == d->W && d->YH == 2 * d->H && d->YW == 2 * d->W && d->wpar_stride > 0 && d->wpar_stride % 16 == 0 &&
+                   !d->x_plane && !d->y_plane && !d->sign_in && !d->sign_out,
+                   "srcgan_conv_igemm: npar == 4 with a 3x3 kernel is the transposed stride-2 form: stride 2, pad 1, os 2, oa == ob == 0, OH x OW = H x W, "
+                   "YH x YW = 2H x 2W, the four parity packs wpar_stride bytes apart, interleaved tensors, no sign masks");
+        p.npar = 4; p.wpar = d->wpar_stride;
+        return sg_deconv_k3s2(p, d->dtype, st);
+    } else if (d->npar && d->kh == 1 && d->kw == 1) {
         // four output parities of a stride-2 scatter in one launch: parity q = (oa, ob) = (q >> 1, q & 1) uses the pack at wp + q * wpar_stride
         SG_REQUIRE(d->npar == 4 && d->stride == 1 && d->os == 2 && d->oa == 0 && d->ob == 0 && d->wpar_stride > 0 && d->wpar_stride % 16 == 0 &&
                    !d->sign_in, "srcgan_conv_igemm: npar == 4 with a 1x1 kernel needs os == 2, oa == ob == 0 and the four packs wpar_stride bytes apart");

@@ -177,11 +177,11 @@ struct S2Dgrad {
     // this tensor (either may be TNULL).  fuse: all four parities from one staged dy tile in ONE launch (conv_par4.hip: 4x4 p1,
     // equally spaced packs, 16-byte accessible operands) where that applies; SRCGAN_NO_PAR4 (diagnostic builds) keeps the four.
     int run(int dt, TRef dy, int B, int OH, int OW, TRef dx, int H, int W, const char* wp, const size_t wd[4], TRef acc, TRef mz,
-            bool fuse, void* st) const {
+            bool fuse, void* st, float mslope = 0.2f) const {
         static const bool no_par4 = sg_env("SRCGAN_NO_PAR4") != nullptr;
         auto launch = [&](Conv& cv) {
             if (acc.p) cv.res1(acc, cin, 1.f);
-            if (mz.p) cv.mask(mz, 0);
+            if (mz.p) { cv.mask(mz, 0); cv.d.mslope = mslope; }
             return cv.run(st);
         };
         const int vec = 16 / (dt == SRCGAN_F32 ? 4 : 2);
@@ -1260,7 +1260,10 @@ struct RdT { int C, cs, H, W, act; size_t off; };       // act: produced by a co
 struct RdOp {
     int type;                 // 0 conv (+bias)(+ReLU), 1 GroupNorm(+res)(+ReLU), 2 ConvTranspose2d k2 s2, 3 PixelShuffle(r),
                               // 4 (inference plans only) ConvTranspose2d k2 s2 followed by a bias-free 3x3 conv, folded into four parity 2x2 convs
+                              // 5 ConvTranspose2d k3 s2 p1 output_padding 1 + bias + ReLU (deconv_k3s2.hip)
     int in, out, res, relu;
+    int icoff, iC, ocoff, oC; // type 0 on a dense buffer: reads channels [icoff, icoff + iC) of `in`, writes [ocoff, ocoff + oC) of `out` (iC / oC == 0: the whole tensor)
+    int share;                // != 0: a module applied a second time -- op share - 1 owns the packs, this op's weight and bias gradients add to its
     int k, s, pad, w, bias;   // w: parameter index of the weight (GroupNorm: gamma, beta = w + 1; -1 = no affine part); bias: parameter index or -1
     int w2;                   // type 4: parameter index of the 3x3 convolution's weight (w = the transposed convolution's)
     int ngrp;                 // GroupNorm: groups (InstanceNorm2d: = channels)
@@ -1268,13 +1271,22 @@ struct RdOp {
     size_t wf[4], wd[4], stats;
     S2Dgrad s2(int cin, int cout) const { return S2Dgrad{k, pad, cin, cout}; }      // input gradient of a stride-2 convolution with k > 1
 };
+static inline int rd_cin(const RdOp& o, const RdT& ti) { return o.iC ? o.iC : ti.C; }
+static inline int rd_cout(const RdOp& o, const RdT& to) { return o.oC ? o.oC : to.C; }
+// ConvTranspose2d weight [ci][co][3][3], output parity q = (a, b): rows = co, k = ci, taps (wy, wx) in [0, a] x [0, b] with ky = a ? 2 - 2 wy : 1
+static inline void deconv3_pack(PackList& packs, const float* w, char* wp, const size_t wf[4], int cin, int cout) {
+    for (int q = 0; q < 4; ++q) {
+        const int a = q >> 1, b = q & 1;
+        packs.add(w, wp + wf[q], cout, cin, a + 1, b + 1, 9, (long)cout * 9, -6, -2, (a ? 2 : 1) * 3 + (b ? 2 : 1));
+    }
+}
 struct RdPlan {
     int dtype, esz, B, H, W, in_ch, out_ch, in_cs, out_cs, nparams, maxC;
     std::vector<RdT> T; std::vector<RdOp> ops;
     size_t xin, gnfwd, wpk, total, act_bytes;
     size_t wpack;             // inference plans: bytes of the packed-weight part
     std::vector<size_t> g;    // backward: gradient buffer offsets (scratch), same shapes as T
-    size_t slab, gnscr, colscr, bwd_total;
+    size_t slab, gnscr, colscr, btmp, bwd_total;      // btmp: a bias gradient on its way to being added (second use of a shared module)
 };
 
 struct RdBuilder {
@@ -1289,6 +1301,25 @@ struct RdBuilder {
         o.type = 0; o.in = in; o.res = -1; o.k = k; o.s = s; o.pad = pad; o.relu = relu; o.w = np++; o.bias = bias ? np++ : -1;
         o.out = tensor(cout, cout < 8 ? 8 : cout, oh, ow, relu);
         P.ops.push_back(o); return o.out;
+    }
+    // convolution between channel slices of dense buffers (the concat-free dense blocks of SRDenseNet)
+    void conv_slice(int in, int icoff, int iC, int out, int ocoff, int oC, int k, int pad) {
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 0; o.in = in; o.out = out; o.res = -1; o.k = k; o.s = 1; o.pad = pad; o.relu = 1; o.w = np++; o.bias = np++;
+        o.icoff = icoff; o.iC = iC; o.ocoff = ocoff; o.oC = oC;
+        P.ops.push_back(o);
+    }
+    int deconv3(int in, int cout) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 5; o.in = in; o.out = tensor(cout, cout, 2 * ti.H, 2 * ti.W, 1); o.res = -1; o.k = 3; o.s = 2; o.pad = 1; o.relu = 1; o.w = np++; o.bias = np++;
+        P.ops.push_back(o); return o.out;
+    }
+    // the last op applies the module of op `first` again (same parameters, same packs)
+    void share_last(int first) {
+        RdOp& o = P.ops.back();
+        o.w = P.ops[first].w; o.bias = P.ops[first].bias; o.share = first + 1;
+        np -= 2;
     }
     int gn(int in, int res, int relu) {
         const RdT ti = P.T[in];
@@ -1341,14 +1372,21 @@ struct RdBuilder {
         auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, dtype)); };
         for (RdOp& o : P.ops) {
             const RdT ti = P.T[o.in], to = P.T[o.out];
-            if (o.type == 0) {
-                o.wf[0] = pk(to.C, ti.C, o.k * o.k);
-                if (o.s == 1) o.wd[0] = pk(ti.C, to.C, o.k * o.k);
-                else if (o.k == 1) o.wd[0] = pk(ti.C, to.C, 1);
-                else o.s2(ti.C, to.C).plan(wb, dtype, o.wd);
+            const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
+            if (o.share) {
+                memcpy(o.wf, P.ops[o.share - 1].wf, sizeof(o.wf)); memcpy(o.wd, P.ops[o.share - 1].wd, sizeof(o.wd));
+            } else if (o.type == 0) {
+                o.wf[0] = pk(cout, cin, o.k * o.k);
+                if (o.s == 1) o.wd[0] = pk(cin, cout, o.k * o.k);
+                else if (o.k == 1) o.wd[0] = pk(cin, cout, 1);
+                else o.s2(cin, cout).plan(wb, dtype, o.wd);
             } else if (o.type == 2) {
                 for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.C, ti.C, 1);
                 o.wd[0] = pk(ti.C, to.C, 4);
+            } else if (o.type == 5) {       // four parity packs, equally spaced (the 4-tap pack's size)
+                const size_t step = srcgan_packed_weight_bytes(to.C, ti.C, 4, dtype), w0 = wb.take(4 * step);
+                for (int q = 0; q < 4; ++q) o.wf[q] = w0 + q * step;
+                o.wd[0] = pk(ti.C, to.C, 9);
             }
         }
         P.total = align_up(P.wpk + wb.off + 256, 256);
@@ -1364,13 +1402,16 @@ struct RdBuilder {
         for (const RdOp& o : P.ops) {
             const RdT ti = P.T[o.in], to = P.T[o.out];
             size_t v = 0;
-            if (o.type == 0) v = wgrad_slab(B, to.H, to.W, to.C, ti.C, o.k, o.k, o.s);
+            if (o.type == 0) v = wgrad_slab(B, to.H, to.W, rd_cout(o, to), rd_cin(o, ti), o.k, o.k, o.s);
             else if (o.type == 2) v = wgrad_slab(B, ti.H, ti.W, ti.C, to.C, 2, 2, 2);
+            else if (o.type == 5) v = wgrad_slab(B, ti.H, ti.W, ti.C, to.C, 3, 3, 2);
             if (v > slab) slab = v;
         }
         P.slab = s.take(slab);
         P.gnscr = s.take(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC) * sizeof(float));
         P.colscr = s.take((size_t)2 * srcgan_col_reduce_blocks(maxpix) * P.maxC * sizeof(float));
+        P.btmp = 0;           // only plans that apply a module twice carry it (the others keep their size)
+        for (const RdOp& o : P.ops) if (o.share && !P.btmp) P.btmp = s.take((size_t)P.maxC * sizeof(float));
         P.bwd_total = s.off + 256;
     }
 };
@@ -1461,6 +1502,52 @@ static int sr_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
     nb.finish(c->dtype);
     return 0;
 }
+// SRDenseNetA (kind 0, LR -> HR) / SRDenseNetB (kind 1, HR -> LR) -- reference src/model/model.py:643-786.  conv_first (in -> 1
+// channel) -> conv (1 -> g L) + ReLU -> num_blocks DenseBlocks -> 1x1 bottleneck to 256 + ReLU -> the shared up- / down-sampler once
+// ('x2') or twice ('x4') -> reconstruction (256 -> 1) -> conv_last.  state_dict order = the order the ops are built in.
+//
+// Concat-free dense blocks, in-place prefixing: DenseBlock i maps its input x (C_i = g L (i + 1) channels) to cat[x, c_1 .. c_L], and
+// that is exactly the next block's input, so ALL blocks share ONE buffer of g L (num_blocks + 1) channels: the block's first layer reads
+// the prefix [0, C_i), layer j > 1 reads [C_i, C_i + g (j - 1)) (the block-local concatenation: model.py:666-669 does not feed x to its
+// DenseLayers), each writes its own g-channel slice, and the bottleneck reads the whole buffer.  No copy, no torch.cat, no CatBackward.
+// Backward: the bottleneck's input gradient is the first writer of the whole gradient buffer; every layer's dgrad adds to the
+// slice range it read through the epilogue's in-place residual, masked by ReLU' of the stored activation.
+static int sd_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srdense: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srdense"));
+    SG_REQUIRE(c->kind == 0 || c->kind == 1, "srdense: kind must be 0 (SRDenseNetA) or 1 (SRDenseNetB)");
+    SG_REQUIRE(c->in_ch > 0 && c->in_ch <= 8 && c->out_ch > 0 && c->out_ch <= 8, "srdense: in/out channels must be in 1..8");
+    SG_REQUIRE(c->num_blocks >= 1 && c->num_layers >= 1 && c->growth >= 1, "srdense: growth_rate, num_blocks and num_layers must be positive");
+    SG_REQUIRE(c->up == 2 || c->up == 4, "srdense: mode must be 'x2' or 'x4' (up = 2 or 4)");
+    SG_REQUIRE(c->growth % 8 == 0, "srdense: growth_rate must be a multiple of 8 (growth_rate = %d): every layer writes a growth_rate-channel slice, and slices are "
+               "addressed in 16-byte pieces", c->growth);
+    const int g = c->growth, L = c->num_layers, nB = c->num_blocks, gL = g * L, kce = 64 / P.esz;
+    SG_REQUIRE(gL % kce == 0, "srdense: growth_rate * num_layers = %d must be a multiple of the 64-byte K chunk (%d channels in this dtype): a dense block's "
+               "slice offset growth_rate * num_layers * (i + 1) has to start a chunk", gL, kce);
+    SG_REQUIRE(c->kind == 0 || (c->H >= 2 && c->W >= 2), "srdense: SRDenseNetB needs H, W >= 2");
+    SG_REQUIRE((long)gL * (nB + 1) <= 8192, "srdense: more than 8192 concatenated channels");
+    RdBuilder nb(P, c->B);
+    nb.input(c->in_ch, c->H, c->W);
+    const int t1 = nb.conv(0, 1, 3, 1, 1, true, false);                      // conv_first
+    const int Ctot = gL * (nB + 1);
+    const int D = nb.tensor(Ctot, Ctot, c->H, c->W, 1);
+    nb.conv_slice(t1, 0, 0, D, 0, gL, 3, 1);                                 // conv
+    for (int i = 0; i < nB; ++i) {
+        const int Ci = gL * (i + 1);
+        nb.conv_slice(D, 0, Ci, D, Ci, g, 3, 1);                             // ConvLayer: the whole block input
+        for (int j = 1; j < L; ++j) nb.conv_slice(D, Ci, g * j, D, Ci + g * j, g, 3, 1);     // DenseLayer j: c_1 .. c_j
+    }
+    int t = nb.conv(D, 256, 1, 1, 0, true, true);                            // bottleneck
+    int first = -1;
+    for (int f = 1; f < c->up; f *= 2) {                                     // deconv: ONE module, applied once or twice
+        t = c->kind == 0 ? nb.deconv3(t, 256) : nb.conv(t, 256, 3, 2, 1, true, true);
+        if (first < 0) first = (int)P.ops.size() - 1; else nb.share_last(first);
+    }
+    t = nb.conv(t, 1, 3, 1, 1, true, false);                                 // reconstruction
+    nb.conv(t, c->out_ch, 3, 1, 1, true, false);                             // conv_last
+    nb.finish(c->dtype);
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -1472,9 +1559,12 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
     PackList packs(dt, wp);
     for (const RdOp& o : P.ops) {
         const RdT ti = P.T[o.in], to = P.T[o.out];
-        if (o.type == 0) packs.add(params[o.w], wp + o.wf[0], to.C, ti.C, o.k, o.k, (long)ti.C * o.k * o.k, (long)o.k * o.k, o.k, 1, 0);
+        const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
+        if (o.share) continue;          // packed by the module's first use
+        if (o.type == 0) packs.add(params[o.w], wp + o.wf[0], cout, cin, o.k, o.k, (long)cin * o.k * o.k, (long)o.k * o.k, o.k, 1, 0);
         else if (o.type == 2)
             for (int q = 0; q < 4; ++q) packs.add(params[o.w], wp + o.wf[q], to.C, ti.C, 1, 1, 4, (long)to.C * 4, 0, 0, q);
+        else if (o.type == 5) deconv3_pack(packs, params[o.w], wp, o.wf, ti.C, to.C);
     }
     char key[64]; snprintf(key, sizeof(key), "%s_fwd", tag);
     SG_TRY(packs.run(key, params[0], st));
@@ -1488,7 +1578,8 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
         if (o.type == 0) {
             if (to.C < to.cs) SG_HIP(hipMemsetAsync(out.p, 0, (size_t)B * to.H * to.W * to.cs * P.esz, (hipStream_t)st));
             Conv cv(dt, o.k, o.k, o.s);
-            cv.in(xin, B, ti.H, ti.W, ti.C < 8 ? ti.cs : ti.C).w(wp + o.wf[0], o.bias >= 0 ? params[o.bias] : nullptr).out(out, to.H, to.W, to.C).pad(o.pad, o.pad);
+            cv.in(sl(xin, o.icoff), B, ti.H, ti.W, ti.C < 8 ? ti.cs : rd_cin(o, ti)).w(wp + o.wf[0], o.bias >= 0 ? params[o.bias] : nullptr)
+                .out(sl(out, o.ocoff), to.H, to.W, rd_cout(o, to)).pad(o.pad, o.pad);
             if (o.relu) { cv.lrelu(); cv.d.slope = 0.f; }
             if (o.res >= 0) cv.res1(rd_t(w8, P.T[o.res]), to.C, 1.f);          // y = conv(x) + res (edsr.py:97-98)
             SG_TRY(cv.run(st));
@@ -1503,6 +1594,12 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
                            .scatter(2, q >> 1, q & 1, to.H, to.W).run(st));
         } else if (o.type == 3) {
             SG_TRY(srcgan_pixel_shuffle_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, to.C, o.k, 0, dt, st));
+        } else if (o.type == 5) {
+            // output pixel (2i + a, 2j + b) = the 1, 2, 2 or 4 taps of parity (a, b) over x[i..i+1][j..j+1]: all four in one launch
+            Conv cv(dt, 3, 3, 2);
+            cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0], params[o.bias]).out(out, ti.H, ti.W, to.C).pad(1, 1).scatter(2, 0, 0, to.H, to.W).lrelu();
+            cv.d.slope = 0.f; cv.d.npar = 4; cv.d.wpar_stride = (long)(o.wf[1] - o.wf[0]);
+            SG_TRY(cv.run(st));
         } else {
             // folded tail: output pixel (2i + a, 2j + b) = 2x2 window of the half-resolution input at (i + a - 1, j + b - 1) times the
             // composed weights of parity (a, b) -- the geometry of the 4x4 stride-2 input gradient, so its four-parity kernel serves.
@@ -1554,11 +1651,12 @@ static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare =
     };
     auto put = [&](int t) { pool[align_up(rd_bytes(P, P.T[t]), 256)].push_back(P.T[t].off); };
     for (RdT& t : P.T) t.off = 0;
-    get(0);
+    std::vector<char> have(nt, 0);          // a dense buffer is the output of many ops: it takes its slot at the first
+    get(0); have[0] = 1;
     P.xin = P.T[0].off;
     for (int k = 0; k < nops; ++k) {
         const RdOp& o = P.ops[k];
-        get(o.out);
+        if (!have[o.out]) { get(o.out); have[o.out] = 1; }
         if (last[o.in] == k) put(o.in);
         if (o.res >= 0 && o.res != o.in && last[o.res] == k) put(o.res);
     }
@@ -1574,9 +1672,14 @@ static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare =
     auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, P.dtype)); };
     for (RdOp& o : P.ops) {
         const RdT ti = P.T[o.in], to = P.T[o.out];
-        if (o.type == 0) o.wf[0] = pk(to.C, ti.C, o.k * o.k);
+        if (o.share) memcpy(o.wf, P.ops[o.share - 1].wf, sizeof(o.wf));
+        else if (o.type == 0) o.wf[0] = pk(rd_cout(o, to), rd_cin(o, ti), o.k * o.k);
         else if (o.type == 2) { for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.C, ti.C, 1); }
         else if (o.type == 4) { for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.cs, ti.C, 4); }
+        else if (o.type == 5) {
+            const size_t step = srcgan_packed_weight_bytes(to.C, ti.C, 4, P.dtype), w0 = wb.take(4 * step);
+            for (int q = 0; q < 4; ++q) o.wf[q] = w0 + q * step;
+        }
     }
     P.wpack = wb.off;
     P.total = align_up(P.wpk + wb.off + 256, 256);
@@ -1594,6 +1697,10 @@ static int sr_infer_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
     // the shapes alone, and a caller can size one workspace for a family of depths.
     const size_t spare = (c->kind == 2 && c->nres == 1) ? (size_t)c->B * c->H * c->W * c->base * P.esz : 0;
     return rd_infer_replan(P, false, "srnet", spare);
+}
+static int sd_infer_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
+    SG_TRY(sd_plan(c, P));
+    return rd_infer_replan(P, false, "srdense");
 }
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -1620,12 +1727,16 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
         PackList packs(dt, wp);
         for (const RdOp& o : P.ops) {
             const RdT ti = P.T[o.in], to = P.T[o.out];
+            const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
+            if (o.share) continue;
             if (o.type == 0 && (o.in != 0 || dx_nchw)) {
-                if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, o.k, o.k, lay_dgrad_s1(ti.C, o.k, o.k));
-                else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 1, 1, 1, (long)ti.C, 0, 0, 0);
-                else o.s2(ti.C, to.C).pack(packs, params[o.w], wp, o.wd);
+                if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));
+                else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, 1, 1, 1, (long)cin, 0, 0, 0);
+                else o.s2(cin, cout).pack(packs, params[o.w], wp, o.wd);
             } else if (o.type == 2) {
                 packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 2, 2, (long)to.C * 4, 4, 2, 1, 0);
+            } else if (o.type == 5) {       // the input gradient is a 3x3 s2 p1 convolution of dy: rows = ci, k = co, taps as stored
+                packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 3, 3, lay_fwd(to.C, 3, 3));
             }
         }
         char key[64]; snprintf(key, sizeof(key), "%s_bwd", tag);
@@ -1644,10 +1755,19 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
         const RdOp& o = P.ops[k];
         const RdT ti = P.T[o.in], to = P.T[o.out];
         SG_REQUIRE(written[o.out], "%s backward: internal error (gradient of tensor %d missing)", tag, o.out);
-        TRef xin = rd_t(w8, ti), dy = gt(o.out);
+        const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
+        TRef xin = sl(rd_t(w8, ti), o.icoff), dy = sl(gt(o.out), o.ocoff);
         const bool need_dx = o.in != 0 || dx_nchw;
-        TRef dx = need_dx ? gt(o.in) : TNULL;
+        TRef dx = need_dx ? sl(gt(o.in), o.icoff) : TNULL;
         bool acc = need_dx && written[o.in];
+        // a module applied twice (SRDenseNet's shared up- / down-sampler): the later use's parameter gradients add to the earlier one's
+        const int pacc0 = (o.type == 0 || o.type == 5) ? seen_param[o.w] : 0;
+        auto bias_sum = [&](TRef g, long npix, int C, float* out) -> int {
+            if (!pacc0) return bias_grad(dt, g, npix, C, 1.f, out, colscr, st);
+            float* tmp = (float*)(s8 + P.btmp);
+            SG_TRY(bias_grad(dt, g, npix, C, 1.f, tmp, colscr, st));
+            return srcgan_add_inplace(out, C, 0, tmp, C, 0, nullptr, 0, 0, 0.f, 1, C, SRCGAN_F32, st);
+        };
         if (o.type == 0) {
             if (o.res >= 0) {       // y = conv(x) + res: the residual's gradient is dy itself
                 const RdT tr = P.T[o.res];
@@ -1659,16 +1779,19 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             }
             const bool fused_bias = o.bias >= 0 && o.k == 3 && G(o.w);
             if (G(o.w))
-                SG_TRY(wgrad_call(dt, dy, to.H, to.W, to.C, xin, B, ti.H, ti.W, ti.C, o.k, o.k, o.s, o.pad, o.pad, lay_fwd(ti.C, o.k, o.k), 1.f, slab, G(o.w), st,
-                                  fused_bias ? G(o.bias) : nullptr));
-            if (o.bias >= 0 && G(o.bias) && !fused_bias) SG_TRY(bias_grad(dt, dy, (long)B * to.H * to.W, to.C, 1.f, G(o.bias), colscr, st));
+                SG_TRY(wgrad_call(dt, dy, to.H, to.W, cout, xin, B, ti.H, ti.W, cin, o.k, o.k, o.s, o.pad, o.pad, lay_fwd(cin, o.k, o.k), 1.f, slab, G(o.w), st,
+                                  fused_bias ? G(o.bias) : nullptr, pacc0));
+            if (o.bias >= 0 && G(o.bias) && !fused_bias) SG_TRY(bias_sum(dy, (long)B * to.H * to.W, cout, G(o.bias)));
+            seen_param[o.w] = 1;
             if (need_dx) {
-                SG_REQUIRE(!(acc && ti.act), "%s backward: internal error (activated tensor with two consumers)", tag);
-                if (o.in == 0 && !acc) SG_HIP(hipMemsetAsync(dx.p, 0, (size_t)B * ti.H * ti.W * ti.cs * P.esz, (hipStream_t)st));    // padded image channels
+                // (a slice of a dense buffer has several consumers: every contribution is masked by the same ReLU', and the mask of a sum
+                //  that already holds masked terms leaves them as they are)
+                SG_REQUIRE(!(acc && ti.act) || o.iC, "%s backward: internal error (activated tensor with two consumers)", tag);
+                if ((o.in == 0 || ti.C < ti.cs) && !acc) SG_HIP(hipMemsetAsync(dx.p, 0, (size_t)B * ti.H * ti.W * ti.cs * P.esz, (hipStream_t)st));    // padded image channels
                 if (o.s == 1) {
                     Conv cv(dt, o.k, o.k, 1);
-                    cv.in(dy, B, to.H, to.W, to.C < 8 ? to.cs : to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(o.k - 1 - o.pad, o.k - 1 - o.pad);
-                    if (acc) cv.res1(dx, ti.C, 1.f);
+                    cv.in(dy, B, to.H, to.W, to.C < 8 ? to.cs : cout).w(wp + o.wd[0]).out(dx, ti.H, ti.W, cin).pad(o.k - 1 - o.pad, o.k - 1 - o.pad);
+                    if (acc) cv.res1(dx, cin, 1.f);
                     if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
                     SG_TRY(cv.run(st));
                 } else if (o.k == 1) {
@@ -1678,7 +1801,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                     if (acc) cv.res1(dx, ti.C, 1.f);
                     SG_TRY(cv.run(st));
                 } else
-                    SG_TRY(o.s2(ti.C, to.C).run(dt, dy, B, to.H, to.W, dx, ti.H, ti.W, wp, o.wd, acc ? dx : TNULL, TNULL, false, st));
+                    SG_TRY(o.s2(ti.C, to.C).run(dt, dy, B, to.H, to.W, dx, ti.H, ti.W, wp, o.wd, acc ? dx : TNULL, ti.act ? xin : TNULL, false, st, 0.f));
                 written[o.in] = 1;
             }
         } else if (o.type == 1) {
@@ -1698,6 +1821,19 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                 SG_TRY(wgrad_call(dt, xin, ti.H, ti.W, ti.C, dy, B, to.H, to.W, to.C, 2, 2, 2, 0, 0, WLayout{(long)to.C * 4, 4, 2, 1, 0}, 1.f, slab, G(o.w), st));
             SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (deconvolution input)", tag);
             SG_TRY(Conv(dt, 2, 2, 2).in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(0, 0).run(st));
+            written[o.in] = 1;
+        } else if (o.type == 5) {
+            // dW[ci][co][ky][kx] = sum x[i][j][ci] * dy[2i + ky - 1][2j + kx - 1][co]: the stride-2 wgrad with the roles of x and dy exchanged
+            if (G(o.w))
+                SG_TRY(wgrad_call(dt, xin, ti.H, ti.W, ti.C, dy, B, to.H, to.W, to.C, 3, 3, 2, 1, 1, lay_fwd(to.C, 3, 3), 1.f, slab, G(o.w), st, nullptr, pacc0));
+            if (G(o.bias)) SG_TRY(bias_sum(dy, (long)B * to.H * to.W, to.C, G(o.bias)));
+            seen_param[o.w] = 1;
+            SG_REQUIRE(!acc, "%s backward: internal error (transposed convolution input with two consumers)", tag);
+            // dx[i][j][ci] = sum dy[2i + ky - 1][2j + kx - 1][co] * W[ci][co][ky][kx]: the forward 3x3 stride-2 pad-1 convolution
+            Conv cv(dt, 3, 3, 2);
+            cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(1, 1);
+            if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
+            SG_TRY(cv.run(st));
             written[o.in] = 1;
         } else {
             SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (PixelShuffle input)", tag);
@@ -1771,4 +1907,33 @@ extern "C" int srcgan_srnet_infer(const srcgan_srnet_cfg* c, const float* x_nchw
     SG_TRY(sr_infer_plan(c, P));
     char tag[32]; snprintf(tag, sizeof(tag), "%s_infer", sr_tag(c->kind));
     return rd_forward(P, x_nchw, params, ws, y_nchw, tag, st);
+}
+
+// SRDenseNetA / SRDenseNetB on the op-list executor (sd_plan); the inference entry runs the same launches on the slot-planned workspace.
+extern "C" int srcgan_srdense_num_params(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_plan(c, P)) return -1; return P.nparams; }
+extern "C" size_t srcgan_srdense_ws_bytes(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_plan(c, P)) return 0; return P.total; }
+extern "C" size_t srcgan_srdense_bwd_scratch_bytes(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_plan(c, P)) return 0; return P.bwd_total; }
+extern "C" int srcgan_srdense_out_hw(const srcgan_srdense_cfg* c, int* oh, int* ow) {
+    RdPlan P;
+    SG_TRY(sd_plan(c, P));
+    SG_REQUIRE(oh && ow, "srcgan_srdense_out_hw: null pointer");
+    *oh = P.T.back().H; *ow = P.T.back().W;
+    return 0;
+}
+extern "C" int srcgan_srdense_forward(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(sd_plan(c, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind ? "srdenseB" : "srdenseA", st);
+}
+extern "C" int srcgan_srdense_backward(const srcgan_srdense_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                                       float* const* grads, float* dx_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(sd_plan(c, P));
+    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, c->kind ? "srdenseB" : "srdenseA", st);
+}
+extern "C" size_t srcgan_srdense_infer_ws_bytes(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_infer_plan(c, P)) return 0; return P.total; }
+extern "C" int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(sd_infer_plan(c, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind ? "srdenseB_infer" : "srdenseA_infer", st);
 }

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
            "get_deconv_params"]
 
 
@@ -736,6 +736,157 @@ class SRDN(nn.Module):
 
     def extra_repr(self):
         return f"native gfx950, compute_dtype={self.compute_dtype}"
+
+
+# ------------------------------------------------------------------------------------------------ SRDenseNetA / SRDenseNetB
+def _srdense_prepare(x, cfg_items, params):
+    """Checks and conversions shared by the training forward and the inference call -> (x, cfg, plist, output shape)."""
+    N.require_cuda(x, "SRDenseNet forward")
+    kind, in_ch, out_ch, growth, nblocks, nlayers, up, dtype = cfg_items
+    if x.dim() != 4 or x.shape[1] != in_ch:
+        raise ValueError(f"expected [B,{in_ch},H,W], got {tuple(x.shape)}")
+    x = x.detach().contiguous().float()
+    B, _, H, W = x.shape
+    cfg = N.SrDenseCfg(kind, in_ch, out_ch, B, H, W, dtype, growth, nblocks, nlayers, up)
+    for p in params:
+        N.require_cuda(p, "parameter")
+    plist = [p.detach().contiguous() for p in params]
+    oh, ow = C.c_int(), C.c_int()
+    N.check(N.lib().srcgan_srdense_out_hw(C.byref(cfg), C.byref(oh), C.byref(ow)), "srcgan_srdense_out_hw")
+    return x, cfg, plist, (B, out_ch, oh.value, ow.value)
+
+
+class _SrDenseFn(torch.autograd.Function):
+    """One native forward / backward for SRDenseNetA (kind 0) / SRDenseNetB (kind 1)."""
+
+    @staticmethod
+    def forward(ctx, x, cfg_items, *params):
+        lib = N.lib()
+        x, cfg, plist, yshape = _srdense_prepare(x, cfg_items, params)
+        ws = N.workspace(lib.srcgan_srdense_ws_bytes(C.byref(cfg)), x.device)
+        y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
+        N.check(lib.srcgan_srdense_forward(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
+                "srcgan_srdense_forward")
+        ctx.cfg, ctx.ws = cfg, ws
+        ctx.save_for_backward(*plist)
+        ctx.phase_hook = _phase_hooks.get("srdense")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = N.lib()
+        params = list(ctx.saved_tensors)
+        cfg = ctx.cfg
+        if ctx.ws is None:
+            raise RuntimeError("backward called twice (activations were released)")
+        need_dx = ctx.needs_input_grad[0]
+        dy = dy.contiguous().float()
+        dx = torch.empty(cfg.B, cfg.in_ch, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if need_dx else None
+        arena = _GradArena(params, [ctx.needs_input_grad[2 + i] for i in range(len(params))])
+        grads = arena.views
+        scratch = N.workspace(lib.srcgan_srdense_bwd_scratch_bytes(C.byref(cfg)), dy.device)
+        N.check(lib.srcgan_srdense_backward(C.byref(cfg), dy.data_ptr(), N.ptr_array(params), ctx.ws.data_ptr(), scratch.data_ptr(),
+                                            N.ptr_array(grads), dx.data_ptr() if need_dx else None, N.stream_ptr(dy.device)), "srcgan_srdense_backward")
+        ctx.ws = None
+        if ctx.phase_hook is not None:
+            ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
+        return (dx, None, *grads)
+
+
+def _srdense_forward(x, cfg_items, params):
+    """Grad mode on: the autograd Function (workspace kept for backward).  Off: ``srcgan_srdense_infer`` on the slot-planned
+    workspace, released on return -- the same launches, hence the same bits."""
+    if torch.is_grad_enabled():
+        return _SrDenseFn.apply(x, cfg_items, *params)
+    lib = N.lib()
+    x, cfg, plist, yshape = _srdense_prepare(x, cfg_items, params)
+    ws = N.workspace(lib.srcgan_srdense_infer_ws_bytes(C.byref(cfg)), x.device)
+    y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
+    N.check(lib.srcgan_srdense_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
+            "srcgan_srdense_infer")
+    return y
+
+
+class _SrDenseConv(_HolderOnly):
+    """Parameter holder of model/model.py:643-660 ConvLayer / DenseLayer: one convolution under the key ``conv``."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super().__init__()
+        self.conv = nn.Conv2d(in_channels, out_channels, kernel_size=kernel_size, padding=kernel_size // 2)
+        self.relu = nn.ReLU(inplace=True)
+
+
+class _SrDenseBlock(_HolderOnly):
+    """Parameter holder of model/model.py:663-672 DenseBlock: ``block.<j>.conv``; layer 0 takes the block input, layer j > 0 the
+    block-local concatenation of the j earlier outputs."""
+
+    def __init__(self, in_channels, growth_rate, num_layers):
+        super().__init__()
+        layers = [_SrDenseConv(in_channels, growth_rate, 3)]
+        for i in range(num_layers - 1):
+            layers.append(_SrDenseConv(growth_rate * (i + 1), growth_rate, 3))
+        self.block = nn.Sequential(*layers)
+
+
+class SRDenseNetA(nn.Module):
+    """LR -> HR SRDenseNet, drop-in for reference ``model.model.SRDenseNetA`` (model/model.py:675-729; train.py:165-168):
+    ``SRDenseNetA(in_nc, out_nc, nb_channel=1, growth_rate=16, num_blocks=8, num_layers=8, mode='x2')``.  conv_first (to 1 channel) ->
+    conv + ReLU -> dense blocks -> 1x1 bottleneck to 256 + ReLU -> ``deconv`` = ConvTranspose2d(256, 256, k3 s2 p1 output_padding 1) +
+    ReLU once ('x2') or twice with the same weights ('x4') -> reconstruction -> conv_last.  ``forward(x[B,in_nc,H,W]) ->
+    [B,out_nc,H*up,W*up]``, any H, W >= 1.  ``nb_channel`` must be 1 (the reference's own conv_first fixes it); any other mode leaves
+    the resolution unchanged in the reference and is refused here."""
+
+    _kind = 0
+
+    def __init__(self, in_nc, out_nc, nb_channel=1, growth_rate=16, num_blocks=8, num_layers=8, mode="x2", dtype=None):
+        super().__init__()
+        if nb_channel != 1:
+            raise NotImplementedError(f"{type(self).__name__}: nb_channel must be 1 -- conv_first always produces one channel "
+                                      "(model/model.py:679,683), any other value fails in the reference's own forward")
+        if mode not in ("x2", "x4"):
+            raise NotImplementedError(f"{type(self).__name__}: mode {mode!r} is not supported (use 'x2' or 'x4')")
+        self.mode = mode
+        self.compute_dtype = N.dtype_name(dtype)
+        self._cfg = (self._kind, in_nc, out_nc, growth_rate, num_blocks, num_layers, _MODES[mode])
+        # the native planner owns the alignment rules: ask it (host code, no GPU needed) before any parameter is created
+        probe = N.SrDenseCfg(self._kind, in_nc, out_nc, 1, 2, 2, N.dtype_id(self.compute_dtype), growth_rate, num_blocks, num_layers, _MODES[mode])
+        if N.lib().srcgan_srdense_num_params(C.byref(probe)) < 0:
+            raise ValueError(f"{type(self).__name__}: " + (N.lib().srcgan_last_error() or b"").decode())
+        # creation order == the reference's
+        self.conv_first = nn.Conv2d(in_nc, 1, 3, 1, 1, bias=True)
+        self.conv = _SrDenseConv(nb_channel, growth_rate * num_layers, 3)
+        self.dense_blocks = nn.Sequential(*[_SrDenseBlock(growth_rate * num_layers * (i + 1), growth_rate, num_layers) for i in range(num_blocks)])
+        self.bottleneck = nn.Sequential(nn.Conv2d(growth_rate * num_layers * (num_blocks + 1), 256, kernel_size=1), nn.ReLU(inplace=True))
+        self.deconv = nn.Sequential(self._sampler(), nn.ReLU(inplace=True))
+        self.reconstruction = nn.Conv2d(256, nb_channel, kernel_size=3, padding=1)
+        self.conv_last = nn.Conv2d(1, out_nc, 3, 1, 1, bias=True)
+        # model.py:710-715: kaiming-normal (fan_in, relu) on every Conv2d / ConvTranspose2d weight in modules() order, zero biases
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+                nn.init.kaiming_normal_(m.weight.data, nonlinearity="relu")
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias.data)
+
+    @staticmethod
+    def _sampler():
+        return nn.ConvTranspose2d(256, 256, kernel_size=3, stride=2, padding=1, output_padding=1)
+
+    def forward(self, x):
+        return _srdense_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
+
+    def extra_repr(self):
+        return f"native gfx950, mode={self.mode}, compute_dtype={self.compute_dtype}"
+
+
+class SRDenseNetB(SRDenseNetA):
+    """HR -> LR SRDenseNet, drop-in for reference ``model.model.SRDenseNetB`` (model/model.py:732-786): as SRDenseNetA with
+    ``deconv`` = Conv2d(256, 256, k3 s2 p1) + ReLU, so each stage maps n to (n + 1) // 2: any H, W >= 2, odd sizes included."""
+
+    _kind = 1
+
+    @staticmethod
+    def _sampler():
+        return nn.Conv2d(256, 256, kernel_size=3, stride=2, padding=1)
 
 
 class _NLayerDFn(torch.autograd.Function):

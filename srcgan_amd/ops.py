@@ -121,6 +121,38 @@ def conv_igemm(x: torch.Tensor, wp: torch.Tensor, y: torch.Tensor, *, kh: int, k
     return y
 
 
+def pack_deconv3x3s2(w: torch.Tensor, dtype=None):
+    """The four parity packs of a ConvTranspose2d weight [Cin,Cout,3,3] ((a + 1) x (b + 1) taps for output parity (a, b)), one 4-tap
+    pack size apart in one buffer -> (buffer, bytes between packs)."""
+    N.require_cuda(w, "pack_deconv3x3s2")
+    lib = N.lib()
+    dt = N.dtype_id(dtype)
+    cin, cout = w.shape[:2]
+    w = w.contiguous().float()
+    step = lib.srcgan_packed_weight_bytes(cout, cin, 4, dt)
+    wp = torch.zeros(4 * step, dtype=torch.uint8, device=w.device)
+    for q in range(4):
+        a, b = q >> 1, q & 1
+        N.check(lib.srcgan_pack_weight(w.data_ptr(), wp.data_ptr() + q * step, cout, cin, a + 1, b + 1, 9, cout * 9, -6, -2,
+                                       (2 if a else 1) * 3 + (2 if b else 1), dt, N.stream_ptr(w.device)), "srcgan_pack_weight")
+    return wp, step
+
+
+def deconv3x3s2(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False, packed=None,
+                y: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ConvTranspose2d(k3, s2, p1, output_padding 1) (+ bias)(+ ReLU) as ONE launch of the four-parity kernel.
+    x: NHWC [B,H,W,Cin] of the compute dtype; w: canonical f32 [Cin,Cout,3,3]; bias: f32 [Cout] -> NHWC [B,2H,2W,Cout].
+    packed: the result of pack_deconv3x3s2(w, x.dtype), to keep the packing out of a timed loop."""
+    N.require_cuda(x, "deconv3x3s2")
+    B, H, W, _ = x.shape
+    cout = w.shape[1]
+    wp, step = packed if packed is not None else pack_deconv3x3s2(w, x.dtype)
+    if y is None:
+        y = torch.empty(B, 2 * H, 2 * W, cout, dtype=x.dtype, device=x.device)
+    return conv_igemm(x, wp, y, kh=3, kw=3, stride=2, Cout=cout, OH=H, OW=W, pad=(1, 1), bias=bias, act=relu, slope=0.0, os=2,
+                      npar=4, wpar_stride=step)
+
+
 def conv_wgrad(dy: torch.Tensor, x: torch.Tensor, grad: torch.Tensor, *, kh: int, kw: int, stride: int = 1, Cout: int, Cin: int,
                dy_coff: int = 0, x_coff: int = 0, pad: Tuple[int, int] = (0, 0), layout: Tuple[int, int, int, int, int],
                alpha: float = 1.0, nsplit: Optional[int] = None, accumulate: bool = False,

@@ -22,7 +22,7 @@ import torch.nn as nn
 
 from . import ops
 from .losses import GANLoss, L1Loss, PSNRLoss
-from .model import EDSR, ESPCN, SRCNN, SRDN, NLayerDiscriminator, RDDBNet, RDDBNetA, RDDBNetB, ResDeconv
+from .model import EDSR, ESPCN, SRCNN, SRDN, NLayerDiscriminator, RDDBNet, RDDBNetA, RDDBNetB, ResDeconv, SRDenseNetA, SRDenseNetB
 from .optim import Adam
 
 __all__ = ["PairedSRGAN", "StackedSR", "SRCycleGAN", "CycleParams", "ImagePool", "CasSRC", "CasSRCConst", "CasSRCLAB", "CasSRCConstLAB", "CasParams",
@@ -328,7 +328,8 @@ class CasParams:
 
 
 # name -> constructor(in_ch, out_ch, up) ; the reference resolves these with eval() (trainCas.py:30-31)
-MODEL_REGISTRY = {"RDDBNet": RDDBNet, "ESPCN": ESPCN, "SRCNN": SRCNN, "EDSR": EDSR, "SRDN": SRDN, "ResDeconv": ResDeconv}
+MODEL_REGISTRY = {"RDDBNet": RDDBNet, "ESPCN": ESPCN, "SRCNN": SRCNN, "EDSR": EDSR, "SRDN": SRDN, "ResDeconv": ResDeconv,
+                  "SRDenseNetA": SRDenseNetA, "SRDenseNetB": SRDenseNetB}
 
 
 class CasSRC:
