@@ -256,6 +256,12 @@ int srcgan_bilinear_down(const float* src, float* dst, int B, int C, int H, int 
 int srcgan_nearest_resize(const float* src, float* dst, int B, int C, int H, int W, int OH, int OW, void* stream);
 /* bilinear x up (integer, align_corners=False): the second half of the blur of trainCasConst.py:89-92 */
 int srcgan_bilinear_up(const float* src, float* dst, int B, int C, int H, int W, int up, void* stream);
+/* Gray-path preprocessing of the cycle step (train.py:251-260), NCHW f32, s = 2 or 4:
+ *   gray_nearest_down: y[B,1,H/s,W/s], y[b,0,oy,ox] = gray(rgb[b,:,oy*s,ox*s])  == nearest x(1/s) of srcgan_rgb_to_gray (s | H, W)
+ *   rep3_nearest_up:   y[B,3,s*h,s*w], y[b,c,Y,X]   = x[b,0,Y/s,X/s]            == nearest x s of cat([x, x, x], 1)
+ * Each is one pass over the low-resolution side; no full-resolution gray image and no 3-channel low-resolution tensor is made. */
+int srcgan_gray_nearest_down(const float* rgb, float* y, int B, int H, int W, int s, void* stream);
+int srcgan_rep3_nearest_up(const float* x, float* y, int B, int h, int w, int s, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Whole-network passes (C++ sequencing of the kernels above; one call per

@@ -1014,12 +1014,19 @@ extern "C" int srcgan_psnr_from_mse(const float* mse, float* out, void* stream) 
 }
 
 // --------------------------------------------------------------------------- preprocessing
+// the one gray expression of the library: same association as the reference expression (trainCas.py:85-87, train.py:252).
+// Contraction is off: left to the compiler, the two loop versions it makes of ONE kernel fuse different products into
+// multiply-adds, so a pixel's value would depend on the image size and on which kernel computed it.
+__device__ __forceinline__ float sg_gray(float r, float g, float b) {
+#pragma clang fp contract(off)
+    return (0.2125f * r + 0.7154f * g) + 0.0721f * b;
+}
+
 __global__ __launch_bounds__(256) void rgb_to_gray_k(const float* __restrict__ rgb, float* __restrict__ gray, long HW, long total) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long b = e / HW, p = e % HW;
         const float* s = rgb + (size_t)b * 3 * HW + p;
-        // same association as the reference expression (trainCas.py:85-87)
-        gray[e] = (0.2125f * s[0] + 0.7154f * s[HW]) + 0.0721f * s[2 * HW];
+        gray[e] = sg_gray(s[0], s[HW], s[2 * HW]);
     }
 }
 extern "C" int srcgan_rgb_to_gray(const float* rgb, float* gray, int B, int H, int W, void* stream) {
@@ -1172,6 +1179,90 @@ extern "C" int srcgan_nearest_resize(const float* src, float* dst, int B, int C,
     SG_REQUIRE(src && dst && B > 0 && C > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "srcgan_nearest_resize: bad arguments");
     const long total = (long)B * C * OH * OW;
     hipLaunchKernelGGL(nearest_resize_k, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, src, dst, H, W, OH, OW, total);
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- gray-path preprocessing of the cycle step (train.py:251-260), each fused into one pass over the SMALL side.
+// Memory-bound and tiny: a grid-stride loop over at most 2048 blocks.
+static inline int pre_blocks(long n) {
+    const long b = cdivl(n, 256);
+    return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
+}
+
+// y[b,0,oy,ox] = gray(x[b,:,oy*s,ox*s]): torch's nearest rule for scale 1/s with s | H, W (src = floor(dst * s)).  One thread per
+// OUTPUT pixel reads the three source values it needs; the full-resolution gray image is never formed.
+__global__ __launch_bounds__(256) void gray_nearest_down_k(const float* __restrict__ rgb, float* __restrict__ y, int H, int W, int s, long total) {
+    const int OH = H / s, OW = W / s;
+    const long HW = (long)H * W;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int ox = (int)(e % OW); const long q = e / OW;
+        const int oy = (int)(q % OH); const long b = q / OH;
+        const float* p = rgb + b * 3 * HW + (long)oy * s * W + (long)ox * s;
+        y[e] = sg_gray(p[0], p[HW], p[2 * HW]);
+    }
+}
+extern "C" int srcgan_gray_nearest_down(const float* rgb, float* y, int B, int H, int W, int s, void* stream) {
+    SG_REQUIRE(rgb && y && B > 0 && H > 0 && W > 0, "srcgan_gray_nearest_down: bad arguments");
+    SG_REQUIRE((s == 2 || s == 4) && H % s == 0 && W % s == 0, "srcgan_gray_nearest_down: s must be 2 or 4 and divide H and W (s=%d H=%d W=%d)", s, H, W);
+    const long total = (long)B * (H / s) * (W / s);
+    hipLaunchKernelGGL(gray_nearest_down_k, dim3(pre_blocks(total)), dim3(256), 0, (hipStream_t)stream, rgb, y, H, W, s, total);
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
+// y[b,c,Y,X] = x[b,0,Y/S,X/S], c = 0..2: cat([x, x, x], 1) followed by nearest x S, without the 3-channel low-resolution tensor.
+// Vector form (S*w a multiple of 4, so that every output row starts on a 16-byte boundary): one thread per 16 bytes of an output
+// row loads the 4/S source pixels under it once and stores the vector to S rows of 3 planes.
+template <int S>
+__global__ __launch_bounds__(256) void rep3_nearest_up_v4_k(const float* __restrict__ x, float* __restrict__ y, int h, int w, long total) {
+    typedef __attribute__((ext_vector_type(4))) float f4;
+    const int OW = S * w, nvx = OW / 4;
+    const long plane = (long)S * h * OW;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int vx = (int)(e % nvx); const long q = e / nvx;
+        const int iy = (int)(q % h); const long b = q / h;
+        const float* p = x + (b * h + iy) * (long)w + vx * (4 / S);
+        const float a0 = p[0], a1 = S == 2 ? p[1] : a0;
+        const f4 v = {a0, a0, a1, a1};
+        float* o = y + b * 3 * plane + (long)iy * S * OW + vx * 4;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < S; ++r) *(f4*)(o + c * plane + (long)r * OW) = v;
+    }
+}
+// Scalar form (S*w not a multiple of 4: rows are not 16-byte aligned): one thread per SOURCE pixel, 3*S*S scalar stores.
+template <int S>
+__global__ __launch_bounds__(256) void rep3_nearest_up_s_k(const float* __restrict__ x, float* __restrict__ y, int h, int w, long total) {
+    const int OW = S * w;
+    const long plane = (long)S * h * OW;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int ix = (int)(e % w); const long q = e / w;
+        const int iy = (int)(q % h); const long b = q / h;
+        const float v = x[e];
+        float* o = y + b * 3 * plane + (long)iy * S * OW + ix * S;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int r = 0; r < S; ++r)
+#pragma unroll
+                for (int t = 0; t < S; ++t) o[c * plane + (long)r * OW + t] = v;
+    }
+}
+extern "C" int srcgan_rep3_nearest_up(const float* x, float* y, int B, int h, int w, int s, void* stream) {
+    SG_REQUIRE(x && y && B > 0 && h > 0 && w > 0, "srcgan_rep3_nearest_up: bad arguments");
+    SG_REQUIRE(s == 2 || s == 4, "srcgan_rep3_nearest_up: s must be 2 or 4 (s=%d)", s);
+    hipStream_t st = (hipStream_t)stream;
+    if (((long)s * w) % 4 == 0 && ((uintptr_t)y % 16) == 0) {
+        const long total = (long)B * h * (s * w / 4);
+        if (s == 2) hipLaunchKernelGGL(rep3_nearest_up_v4_k<2>, dim3(pre_blocks(total)), dim3(256), 0, st, x, y, h, w, total);
+        else hipLaunchKernelGGL(rep3_nearest_up_v4_k<4>, dim3(pre_blocks(total)), dim3(256), 0, st, x, y, h, w, total);
+    } else {
+        const long total = (long)B * h * w;
+        if (s == 2) hipLaunchKernelGGL(rep3_nearest_up_s_k<2>, dim3(pre_blocks(total)), dim3(256), 0, st, x, y, h, w, total);
+        else hipLaunchKernelGGL(rep3_nearest_up_s_k<4>, dim3(pre_blocks(total)), dim3(256), 0, st, x, y, h, w, total);
+    }
     SG_LAUNCH_CHECK();
     return 0;
 }

@@ -8,7 +8,7 @@
 * ``.pth`` naming and round trip: ``{SRModel}_A2C_x{up}_{epoch:04d}.pth`` / ``{CModel}_C2B_x{up}_{epoch:04d}.pth`` written
   every 25 epochs (src/trainCas.py:221-225) and parsed back by the test script to rebuild the two networks
   (src/testCas.py:41-56).  Files hold ``torch.save(net.state_dict())`` with the reference's key names, so they load into
-  either implementation.
+  either implementation.  The cycle harness's pair is ``netG_A2B_SRtask_{mode}_{epoch:04d}.pth`` / ``netG_B2A_...`` (src/train.py:407-408).
 
 There is no CPU fallback: the conversions run in libsrcgan_amd.so (csrc/colour.hip).
 """
@@ -238,6 +238,34 @@ def save_checkpoints(model, opt, epoch: int, root: str = "./checkpoints") -> Tup
     pb = os.path.join(root, checkpoint_name(opt.CModel, "C2B", opt.up, epoch))
     torch.save(model.netG_A2C.state_dict(), pa)
     torch.save(model.netG_C2B.state_dict(), pb)
+    return pa, pb
+
+
+def cycle_checkpoint_name(direction: str, mode: str, epoch: int) -> str:
+    """File name of train.py:407-408: ``netG_A2B_SRtask_<mode>_<epoch:04d>.pth`` (G_A) / ``netG_B2A_...`` (G_B)."""
+    if direction not in ("A2B", "B2A"):
+        raise ValueError(f"cycle_checkpoint_name: direction must be 'A2B' or 'B2A', got {direction!r}")
+    if mode not in ("x2", "x4"):
+        raise ValueError(f"cycle_checkpoint_name: mode must be 'x2' or 'x4', got {mode!r}")
+    return "netG_%s_SRtask_%s_%04d.pth" % (direction, mode, epoch)
+
+
+def parse_cycle_checkpoint_name(path: str) -> Tuple[str, str, int]:
+    """(direction, mode, epoch) from a cycle checkpoint path; refuses anything ``cycle_checkpoint_name`` cannot have written."""
+    parts = os.path.basename(path).split(".pth")[0].split("_")
+    if (len(parts) != 5 or parts[0] != "netG" or parts[1] not in ("A2B", "B2A") or parts[2] != "SRtask" or parts[3] not in ("x2", "x4")
+            or not parts[4].isdigit()):
+        raise ValueError(f"parse_cycle_checkpoint_name: {path!r} is not 'netG_<A2B|B2A>_SRtask_<x2|x4>_<epoch>.pth'")
+    return parts[1], parts[3], int(parts[4])
+
+
+def save_cycle_checkpoints(model, opt, epoch: int, root: str = "./checkpoints") -> Tuple[str, str]:
+    """The save of train.py:406-410 for a cycle harness (``netG_A`` / ``netG_B``): two state_dict files."""
+    os.makedirs(root, exist_ok=True)
+    pa = os.path.join(root, cycle_checkpoint_name("A2B", opt.mode, epoch))
+    pb = os.path.join(root, cycle_checkpoint_name("B2A", opt.mode, epoch))
+    torch.save(model.netG_A.state_dict(), pa)
+    torch.save(model.netG_B.state_dict(), pb)
     return pa, pb
 
 

@@ -261,6 +261,42 @@ def nearest_resize(x: torch.Tensor, scale_factor: float) -> torch.Tensor:
     return out
 
 
+def _check_scale(x: torch.Tensor, s, channels: int, what: str) -> int:
+    if isinstance(s, bool) or not isinstance(s, int) or s not in (2, 4):
+        raise ValueError(f"{what}: s must be 2 or 4, got {s!r}")
+    if x.dim() != 4 or x.shape[1] != channels:
+        raise ValueError(f"{what} expects [B,{channels},H,W], got {tuple(x.shape)}")
+    return s
+
+
+def gray_nearest_down(x: torch.Tensor, s: int) -> torch.Tensor:
+    """``F.interpolate(gray(x), scale_factor=1/s)`` of train.py:252-253 in one pass: x [B,3,H,W] -> [B,1,H/s,W/s], reading only the
+    pixels the nearest rule keeps.  Acts on data: the input is detached and the result has no grad_fn."""
+    s = _check_scale(x, s, 3, "gray_nearest_down")
+    B, _, H, W = x.shape
+    if H % s or W % s:
+        raise ValueError(f"gray_nearest_down: s={s} must divide H and W, got {tuple(x.shape)}")
+    N.require_cuda(x, "gray_nearest_down")
+    x = x.detach().contiguous().float()
+    out = torch.empty(B, 1, H // s, W // s, dtype=torch.float32, device=x.device)
+    N.check(N.lib().srcgan_gray_nearest_down(x.data_ptr(), out.data_ptr(), B, H, W, s, N.stream_ptr(x.device)), "srcgan_gray_nearest_down")
+    return out
+
+
+def rep3_nearest_up(x: torch.Tensor, s: int) -> torch.Tensor:
+    """``F.interpolate(torch.cat([x, x, x], 1), scale_factor=s)`` of train.py:257-258 in one pass: x [B,1,h,w] -> [B,3,s*h,s*w].
+    Acts on data: the input is detached and the result has no grad_fn."""
+    s = _check_scale(x, s, 1, "rep3_nearest_up")
+    B, _, h, w = x.shape
+    if h < 1 or w < 1:
+        raise ValueError(f"rep3_nearest_up: empty image {tuple(x.shape)}")
+    N.require_cuda(x, "rep3_nearest_up")
+    x = x.detach().contiguous().float()
+    out = torch.empty(B, 3, s * h, s * w, dtype=torch.float32, device=x.device)
+    N.check(N.lib().srcgan_rep3_nearest_up(x.data_ptr(), out.data_ptr(), B, h, w, s, N.stream_ptr(x.device)), "srcgan_rep3_nearest_up")
+    return out
+
+
 def group_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, G: int = 32, *, res: Optional[torch.Tensor] = None,
                relu: bool = False, eps: float = 1e-5, slope: float = 0.0):
     """GroupNorm (+ residual + (Leaky)ReLU) on NHWC [B,H,W,C].  Returns (y, stats[B,G,2] = {mean, rstd})."""

@@ -209,7 +209,9 @@ class ImagePool:
 
 
 class CycleParams:
-    """train.py:344-361 defaults (net == '1': 3-channel images on both sides)."""
+    """train.py:344-361 defaults (net == '1': 3-channel images on both sides).  ``net`` selects the configuration of
+    train.py:166-180: '1' (default), 'SRdens' (SRDenseNetA / SRDenseNetB on gray LR <-> RGB HR) or anything else (the RRDB
+    generators on gray LR <-> RGB HR)."""
 
     def __init__(self, device="cuda"):
         self.device = torch.device(device)
@@ -225,6 +227,7 @@ class CycleParams:
         self.mode = "x2"
         self.net = "1"
         self.nf, self.nb, self.gc, self.ndf, self.n_layers = 64, 3, 32, 64, 2
+        self.num_blocks, self.num_layers = 2, 2          # net == 'SRdens' (train.py:167-168)
         self.dtype = None
         # G_A class: "RDDBNetB" is what reference train.py:172,177 constructs (legacy nearest-up-sampling generator,
         # model/model.py:394); "RDDBNet" (rddb.py, deconv up-sampler) is the generator BASELINE.json's configs name.
@@ -232,21 +235,32 @@ class CycleParams:
 
 
 class SRCycleGAN(_DataParallel):
-    """Full cycle step of reference src/train.py:145-340.  G_A = RDDBNet (LR->HR), G_B = RDDBNetA (HR->LR,
-    build-defined), D_A on HR images, D_B on LR images."""
+    """Full cycle step of reference src/train.py:145-340, in the three configurations ``opt.net`` selects (train.py:166-180):
+
+      '1'       3-channel images on both sides: G_A = RDDBNet (LR->HR), G_B = RDDBNetA (HR->LR, build-defined), D_A on HR, D_B on LR.
+      'SRdens'  gray LR <-> RGB HR: G_A = SRDenseNetA(1, 3), G_B = SRDenseNetB(3, 1), D_A on 3 channels, D_B on 1.
+      other     gray LR <-> RGB HR with the RRDB generators: G_A(1, 3) by ``opt.G_A`` as for '1', G_B = RDDBNetA(3, 1)."""
 
     def __init__(self, opt: CycleParams):
         self.opt = opt
         up = 2 if opt.mode == "x2" else 4
         self.up = up
         dev = opt.device
-        if getattr(opt, "G_A", "RDDBNet") == "RDDBNetB":
-            self.netG_A = RDDBNetB(3, 3, opt.nf, nb=opt.nb, gc=opt.gc, mode=opt.mode, dtype=opt.dtype).to(dev)
+        self.net = str(getattr(opt, "net", "1"))
+        self.gray = self.net != "1"                      # train.py:241,251: every other value takes the gray path
+        lr_ch = 1 if self.gray else 3
+        if self.net == "SRdens":
+            nbl, nly = getattr(opt, "num_blocks", 2), getattr(opt, "num_layers", 2)
+            self.netG_A = SRDenseNetA(1, 3, mode=opt.mode, num_blocks=nbl, num_layers=nly, dtype=opt.dtype).to(dev)
+            self.netG_B = SRDenseNetB(3, 1, mode=opt.mode, num_blocks=nbl, num_layers=nly, dtype=opt.dtype).to(dev)
         else:
-            self.netG_A = RDDBNet(3, 3, up, nf=opt.nf, nb=opt.nb, gc=opt.gc, dtype=opt.dtype).to(dev)
-        self.netG_B = RDDBNetA(3, 3, up, nf=opt.nf, nb=opt.nb, gc=opt.gc, dtype=opt.dtype).to(dev)
+            if getattr(opt, "G_A", "RDDBNet") == "RDDBNetB":
+                self.netG_A = RDDBNetB(lr_ch, 3, opt.nf, nb=opt.nb, gc=opt.gc, mode=opt.mode, dtype=opt.dtype).to(dev)
+            else:
+                self.netG_A = RDDBNet(lr_ch, 3, up, nf=opt.nf, nb=opt.nb, gc=opt.gc, dtype=opt.dtype).to(dev)
+            self.netG_B = RDDBNetA(3, lr_ch, up, nf=opt.nf, nb=opt.nb, gc=opt.gc, dtype=opt.dtype).to(dev)
         self.netD_A = NLayerDiscriminator(3, opt.ndf, opt.n_layers, dtype=opt.dtype).to(dev)
-        self.netD_B = NLayerDiscriminator(3, opt.ndf, opt.n_layers, dtype=opt.dtype).to(dev)
+        self.netD_B = NLayerDiscriminator(lr_ch, opt.ndf, opt.n_layers, dtype=opt.dtype).to(dev)
         self.fake_A_pool = ImagePool(opt.pool_size)
         self.fake_B_pool = ImagePool(opt.pool_size)
         self.criterionGAN = GANLoss("lsgan", device=dev)
@@ -262,15 +276,23 @@ class SRCycleGAN(_DataParallel):
 
     set_requires_grad = staticmethod(set_requires_grad)
 
-    def forward(self, realA, realB):                                     # train.py:228-249 (net == '1')
+    def forward(self, realA, realB):                                     # train.py:228-260
+        if self.gray:
+            s = self.up
+            if (realA.dim() != 4 or realB.dim() != 4 or realA.shape[1] != 1 or realB.shape[1] != 3 or realA.shape[0] != realB.shape[0]
+                    or tuple(realB.shape[2:]) != (s * realA.shape[2], s * realA.shape[3])):
+                raise ValueError(f"SRCycleGAN(net={self.net!r}, mode={self.opt.mode!r}) expects realA [B,1,h,w] and realB [B,3,{s}h,{s}w], "
+                                 f"got realA {tuple(realA.shape)} and realB {tuple(realB.shape)}")
         self.real_A, self.real_B = realA, realB
         self.fake_B = self.netG_A(self.real_A)
         self.recl_A = self.netG_B(self.fake_B)
         self.fake_A = self.netG_B(self.real_B)
         self.recl_B = self.netG_A(self.fake_A)
-        self.real_B_Gray = ops.nearest_resize(self.real_B, 1.0 / self.up)
+        # net == '1' (train.py:241-250): nearest resize of the 3-channel images; otherwise (train.py:251-260) gray + nearest down and
+        # cat([A, A, A]) + nearest up, each one fused launch
+        self.real_B_Gray = ops.gray_nearest_down(self.real_B, self.up) if self.gray else ops.nearest_resize(self.real_B, 1.0 / self.up)
         self.iden_A = self.netG_A(self.real_B_Gray)
-        self.real_A_RGB = ops.nearest_resize(self.real_A, self.up)
+        self.real_A_RGB = ops.rep3_nearest_up(self.real_A, self.up) if self.gray else ops.nearest_resize(self.real_A, self.up)
         self.iden_B = self.netG_B(self.real_A_RGB)
 
     def backward_D_basic(self, netD, real, fake):                        # train.py:262-280
