@@ -507,6 +507,30 @@ int srcgan_s2d_wgrad_unfold(const float* gfold, float* grad, int Cout, int Cin, 
 int srcgan_u8rgb_to_planes(const unsigned char* rgb, float* dst, int B, long hw, int mode, void* stream);
 int srcgan_lab_planes_to_u8rgb(const float* lab, unsigned char* rgb, int B, long hw, void* stream);
 
+/* ---- whole-scene inference: tile gather / write-back (csrc/tiles.hip, srcgan_amd/infer.py) ----
+ * A scene stays on the device; tiles of ONE common shape are gathered into an NCHW f32 batch, the network runs on the batch, and its
+ * HR tiles are written back.  Tile origins and rectangles are HOST arrays: they travel in the kernel arguments (no device allocation,
+ * no host-to-device copy), chunked internally when T exceeds what one launch carries.
+ *
+ * srcgan_tile_gather: dst[t][c][ty][tx] = scene(c, min(y0_t + ty, H - 1), min(x0_t + tx, W - 1)) -- a tile that passes the right /
+ *   bottom edge is filled by edge replication and nothing outside the scene is read.  src_u8 = 1: the scene is u8 HWC (C = 1 or 3),
+ *   mapped v / 255 exactly as srcgan_u8rgb_to_planes mode 1; src_u8 = 0: f32 planes [C][H][W], C <= 8.  origins_yx: T pairs (y0, x0)
+ *   inside the scene.  16-byte accesses along W where tw, the origin, W and the pointers allow, scalar otherwise (same bits).
+ * srcgan_tile_scatter: tiles [T][C][th*up][tw*up] -> scene [C][H*up][W*up].  rects: 10 ints per tile, in LR pixels:
+ *   y0, x0 (tile origin), sy0, sy1, sx0, sx1 (the write-back rectangle: inside the tile and inside the scene, so the replicated
+ *   excess of a tile is dropped), ny_lo, ny_hi, nx_lo, nx_hi (ramp lengths at the low / high end of the rectangle).
+ *   feather = 0: scene = tile on the rectangle (rectangles must be disjoint; ramps must be 0).
+ *   feather = 1: scene = fma(wy * wx, tile, scene); w = (j + 0.5) / n rising over a low ramp of n HR pixels, 1 - (j + 0.5) / n over a
+ *   high ramp, 1 between (f32).  The caller zeroes the scene first.  No atomics: one launch per tile, so a pixel receives its
+ *   contributions in tile order on `stream` and the result is bitwise reproducible.
+ * srcgan_planes_to_u8hwc: dst[px][c] = floor(clamp(src[c][px], 0, 1) * 255) -- the reference's tensor2image for in-range values;
+ *   out-of-range values saturate instead of wrapping.  C <= 8. */
+int srcgan_tile_gather(const void* src, int src_u8, int C, int H, int W, float* dst, int T, int th, int tw,
+                       const int* origins_yx, void* stream);
+int srcgan_tile_scatter(const float* tiles, float* dst, int C, int H, int W, int up, int T, int th, int tw,
+                        const int* rects, int feather, void* stream);
+int srcgan_planes_to_u8hwc(const float* src, unsigned char* dst, int C, long hw, void* stream);
+
 /* Fused multi-tensor Adam (torch.optim.Adam.step() of trainCas.py:38-41,143-150 / train.py:191-192,331-340; torch's
  * single-tensor arithmetic, default flags: no weight decay, no amsgrad).  tensors_dev: device array of records
  * {float* p; const float* g; float* m; float* v;} (32 bytes); chunks_dev: device array of nchunks records

@@ -189,6 +189,9 @@ SIGNATURES = {
     "srcgan_s2d_wgrad_unfold": (_I, [_P, _P, _I, _I, _I, _P]),
     "srcgan_u8rgb_to_planes": (_I, [_P, _P, _I, _L, _I, _P]),
     "srcgan_lab_planes_to_u8rgb": (_I, [_P, _P, _I, _L, _P]),
+    "srcgan_tile_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_int), _P]),
+    "srcgan_tile_scatter": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), _I, _P]),
+    "srcgan_planes_to_u8hwc": (_I, [_P, _P, _I, _L, _P]),
     "srcgan_adam_step": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _L, _P]),
     "srcgan_params_fingerprint": (_I, [_P, _I, _L, _P, _P]),
     "srcgan_prof_enable": (_I, [_I]),

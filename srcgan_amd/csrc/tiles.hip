@@ -1,0 +1,221 @@
+// Whole-scene inference plumbing (srcgan_amd/infer.py): a scene too large for one forward stays on the device, tiles of one common
+// shape are gathered with a halo into an NCHW f32 batch, and the network's HR tiles are written back by crop or by a feathered blend.
+// Three memory-bound copies; no arithmetic intensity to speak of, so the only levers are coalescing and access width:
+//   * consecutive threads take consecutive 4-pixel units of one row, a unit is one 16-byte load / store where the row start, the row
+//     pitch and the base pointer are 16-byte aligned, and four scalar accesses otherwise (same values either way: these are copies);
+//   * tile origins / write-back rectangles travel in the kernel arguments (no device allocation, no host-to-device copy per launch);
+//     a launch carries SG_GATHER_CHUNK / SG_SCATTER_CHUNK tiles and the entry points chunk above that;
+//   * no atomics: crop rectangles are disjoint, and the feathered blend adds one tile per launch, so the additions to a pixel happen
+//     in tile order on the stream and the result is the same bits run after run.
+#include "common.h"
+
+namespace {
+constexpr int SG_GATHER_CHUNK = 128;        // 128 x 8 B  = 1 KiB of kernel arguments
+constexpr int SG_SCATTER_CHUNK = 64;        // 64 x 40 B = 2.5 KiB (the limit is 4 KiB)
+constexpr int SG_TILE_MAX_SIDE = 16384;     // per-tile extent (LR for gather, HR for scatter): grid.x stays far below 2^31
+
+struct GatherArgs { int yx[SG_GATHER_CHUNK][2]; };
+// One HR write-back rectangle ("support") per tile, in LR pixels: the core widened by half a ramp on every blended side.
+// ny_lo / ny_hi / nx_lo / nx_hi: ramp lengths in LR pixels at the low / high end of the support (0 = no ramp on that side).
+struct ScatterTile { int y0, x0, sy0, sy1, sx0, sx1, ny_lo, ny_hi, nx_lo, nx_hi; };
+struct ScatterArgs { ScatterTile t[SG_SCATTER_CHUNK]; };
+
+// u8 -> f32 exactly as data.arr2rgb / srcgan_u8rgb_to_planes mode 1: the quotient in double, one rounding to float
+__device__ __forceinline__ float u8_unit(unsigned char v) { return (float)((double)v / 255.0); }
+
+// dst[t][c][ty][tx] = src(c, min(y0 + ty, H - 1), min(x0 + tx, W - 1)).  VEC = 4: tw % 4 == 0 and dst 16-byte aligned (host-checked).
+// grid: x = units of one (tile, channel) plane, y = channel (f32) or 1 (u8: a thread converts all C channels of its pixels), z = tile.
+template <int VEC, bool U8>
+__global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ src_, float* __restrict__ dst, int C, int H, int W,
+                                                     int th, int tw, int src_vec_ok, GatherArgs a) {
+    const int upr = tw / VEC;                                   // units per row
+    const long unit = (long)blockIdx.x * 256 + threadIdx.x;
+    if (unit >= (long)th * upr) return;
+    const int ty = (int)(unit / upr), tx = (int)(unit - (long)ty * upr) * VEC;
+    const int y0 = a.yx[blockIdx.z][0], x0 = a.yx[blockIdx.z][1];
+    const int sy = min(y0 + ty, H - 1);
+    const size_t plane = (size_t)th * tw;
+    float* d = dst + (size_t)blockIdx.z * C * plane + (size_t)ty * tw + tx;
+    if constexpr (U8) {
+        const unsigned char* row = (const unsigned char*)src_ + (size_t)sy * W * C;
+        for (int c = 0; c < C; ++c) {
+            float v[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) v[i] = u8_unit(row[(size_t)min(x0 + tx + i, W - 1) * C + c]);
+            if constexpr (VEC == 4) store4<float>(d + c * plane, v);
+            else d[c * plane] = v[0];
+        }
+    } else {
+        const int c = blockIdx.y;
+        const float* row = (const float*)src_ + ((size_t)c * H + sy) * W;
+        float v[VEC];
+        if constexpr (VEC == 4) {
+            if (src_vec_ok && !(x0 & 3) && x0 + tx + 3 < W) {
+                load4<float>(row + x0 + tx, v);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) v[i] = row[min(x0 + tx + i, W - 1)];
+            }
+            store4<float>(d + c * plane, v);
+        } else {
+            d[c * plane] = row[min(x0 + tx, W - 1)];
+        }
+    }
+}
+
+// ramp weight of HR position j inside a support of n HR pixels: (j + 0.5) / n_lo rising over the first n_lo, 1 - (jj + 0.5) / n_hi
+// falling over the last n_hi, 1 between (infer.py TilePlan.axis_weights is the same arithmetic in torch f32)
+__device__ __forceinline__ float ramp_w(int j, int n, int n_lo, int n_hi) {
+    if (j < n_lo) return ((float)j + 0.5f) / (float)n_lo;
+    const int jj = j - (n - n_hi);
+    if (jj >= 0) return 1.0f - ((float)jj + 0.5f) / (float)n_hi;
+    return 1.0f;
+}
+
+// feather == 0: dst = tile on the support.  feather == 1: dst = fma(wy * wx, tile, dst) (ONE tile per launch, see the entry point).
+// VEC = 4 is chosen per tile: `vec_ok` (dst pitch / pointers / tile pitch aligned) and the support's HR x-range 4-aligned in both.
+__global__ __launch_bounds__(256) void tile_scatter_k(const float* __restrict__ tiles, float* __restrict__ dst, int C, int SH, int SW,
+                                                      int TH, int TW, int up, int feather, int vec_ok, ScatterArgs a) {
+    const ScatterTile t = a.t[blockIdx.z];
+    const int hx0 = t.sx0 * up, hy0 = t.sy0 * up, hw = (t.sx1 - t.sx0) * up, hh = (t.sy1 - t.sy0) * up;
+    const int ox = hx0 - t.x0 * up, oy = hy0 - t.y0 * up;                      // support origin inside the HR tile
+    const bool vec = vec_ok && !(hx0 & 3) && !(hw & 3) && !(ox & 3);
+    const int V = vec ? 4 : 1, upr = hw / V;
+    const long unit = (long)blockIdx.x * 256 + threadIdx.x;
+    if (unit >= (long)hh * upr) return;
+    const int j = (int)(unit / upr), i = (int)(unit - (long)j * upr) * V;
+    const int c = blockIdx.y;
+    const float* s = tiles + (((size_t)blockIdx.z * C + c) * TH + oy + j) * TW + ox + i;
+    float* d = dst + ((size_t)c * SH + hy0 + j) * SW + hx0 + i;
+    const float wy = feather ? ramp_w(j, hh, t.ny_lo * up, t.ny_hi * up) : 1.0f;
+    if (vec) {
+        float v[4];
+        load4<float>(s, v);
+        if (feather) {
+            float o[4];
+            load4<float>(d, o);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = __fmaf_rn(wy * ramp_w(i + k, hw, t.nx_lo * up, t.nx_hi * up), v[k], o[k]);
+        }
+        store4<float>(d, v);
+    } else {
+        *d = feather ? __fmaf_rn(wy * ramp_w(i, hw, t.nx_lo * up, t.nx_hi * up), *s, *d) : *s;
+    }
+}
+
+// dst[px][c] = floor(clamp(src[c][px], 0, 1) * 255).  WORD: hw * C % 4 == 0 and dst 4-byte aligned -- a thread makes one aligned word
+// (4 consecutive bytes of the HWC stream; the lanes of a wave read runs of consecutive pixels from each plane); else one byte.
+__device__ __forceinline__ unsigned int unit_to_u8(float v) { return (unsigned int)floorf(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); }
+
+template <bool WORD>
+__global__ __launch_bounds__(256) void planes_to_u8hwc_k(const float* __restrict__ src, unsigned char* __restrict__ dst, int C, long hw) {
+    const long nunit = WORD ? hw * C / 4 : hw * C;
+    for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < nunit; u += (long)gridDim.x * 256) {
+        if constexpr (WORD) {
+            unsigned int word = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const long b = 4 * u + q, px = b / C;
+                word |= unit_to_u8(src[(size_t)(b - px * C) * hw + px]) << (8 * q);
+            }
+            ((unsigned int*)dst)[u] = word;
+        } else {
+            const long px = u / C;
+            dst[u] = (unsigned char)unit_to_u8(src[(size_t)(u - px * C) * hw + px]);
+        }
+    }
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+}   // namespace
+
+extern "C" int srcgan_tile_gather(const void* src, int src_u8, int C, int H, int W, float* dst, int T, int th, int tw,
+                                  const int* origins_yx, void* stream) {
+    SG_REQUIRE(src && dst && origins_yx, "srcgan_tile_gather: null pointer");
+    SG_REQUIRE(src_u8 ? (C == 1 || C == 3) : (C >= 1 && C <= 8), "srcgan_tile_gather: C = %d (u8 HWC scenes: 1 or 3 channels; f32 planes: 1..8)", C);
+    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_gather: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
+    SG_REQUIRE(th <= SG_TILE_MAX_SIDE && tw <= SG_TILE_MAX_SIDE, "srcgan_tile_gather: tile %dx%d is larger than the launch limit of %d per side", th, tw, SG_TILE_MAX_SIDE);
+    for (int t = 0; t < T; ++t)
+        SG_REQUIRE(origins_yx[2 * t] >= 0 && origins_yx[2 * t] < H && origins_yx[2 * t + 1] >= 0 && origins_yx[2 * t + 1] < W,
+                   "srcgan_tile_gather: origin (%d, %d) of tile %d is outside the %dx%d scene", origins_yx[2 * t], origins_yx[2 * t + 1], t, H, W);
+    const bool vec = (tw % 4 == 0) && aligned16(dst);
+    const int src_vec_ok = !src_u8 && (W % 4 == 0) && aligned16(src);
+    const int upr = vec ? tw / 4 : tw;
+    const unsigned gx = (unsigned)cdivl((long)th * upr, 256);
+    const size_t per_tile = (size_t)C * th * tw;
+    for (int t0 = 0; t0 < T; t0 += SG_GATHER_CHUNK) {
+        const int n = T - t0 < SG_GATHER_CHUNK ? T - t0 : SG_GATHER_CHUNK;
+        GatherArgs a;
+        memset(&a, 0, sizeof(a));
+        memcpy(a.yx, origins_yx + 2 * t0, sizeof(int) * 2 * n);
+        const dim3 grid(gx, src_u8 ? 1 : C, n);
+        float* d = dst + (size_t)t0 * per_tile;             // per_tile * 4 bytes is a multiple of 16 whenever tw % 4 == 0
+        if (src_u8) {
+            if (vec) hipLaunchKernelGGL((tile_gather_k<4, true>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, 0, a);
+            else hipLaunchKernelGGL((tile_gather_k<1, true>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, 0, a);
+        } else {
+            if (vec) hipLaunchKernelGGL((tile_gather_k<4, false>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, src_vec_ok, a);
+            else hipLaunchKernelGGL((tile_gather_k<1, false>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, 0, a);
+        }
+        SG_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int srcgan_tile_scatter(const float* tiles, float* dst, int C, int H, int W, int up, int T, int th, int tw,
+                                   const int* rects, int feather, void* stream) {
+    SG_REQUIRE(tiles && dst && rects, "srcgan_tile_scatter: null pointer");
+    SG_REQUIRE(C >= 1 && C <= 8, "srcgan_tile_scatter: C = %d (1..8 planes)", C);
+    SG_REQUIRE(up >= 1, "srcgan_tile_scatter: up = %d (must be >= 1)", up);
+    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_scatter: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
+    SG_REQUIRE((long)th * up <= SG_TILE_MAX_SIDE && (long)tw * up <= SG_TILE_MAX_SIDE && (long)H * up < (1L << 30) && (long)W * up < (1L << 30),
+               "srcgan_tile_scatter: HR tile %ldx%ld is larger than the launch limit of %d per side", (long)th * up, (long)tw * up, SG_TILE_MAX_SIDE);
+    feather = feather ? 1 : 0;
+    long max_units = 0;
+    for (int t = 0; t < T; ++t) {
+        const int* r = rects + 10 * t;
+        const int y0 = r[0], x0 = r[1], sy0 = r[2], sy1 = r[3], sx0 = r[4], sx1 = r[5];
+        // the support lies inside the scene AND inside the tile: nothing outside either is ever touched
+        SG_REQUIRE(sy0 >= 0 && sy0 < sy1 && sy1 <= H && sx0 >= 0 && sx0 < sx1 && sx1 <= W && sy0 >= y0 && sy1 <= y0 + th && sx0 >= x0 && sx1 <= x0 + tw,
+                   "srcgan_tile_scatter: write-back rectangle [%d,%d)x[%d,%d) of tile %d (origin %d,%d, %dx%d) leaves the tile or the %dx%d scene",
+                   sy0, sy1, sx0, sx1, t, y0, x0, th, tw, H, W);
+        SG_REQUIRE(r[6] >= 0 && r[7] >= 0 && r[8] >= 0 && r[9] >= 0 && r[6] + r[7] <= sy1 - sy0 && r[8] + r[9] <= sx1 - sx0,
+                   "srcgan_tile_scatter: ramps of tile %d overlap inside its write-back rectangle", t);
+        SG_REQUIRE(feather || (r[6] | r[7] | r[8] | r[9]) == 0, "srcgan_tile_scatter: crop mode takes no ramps (tile %d)", t);
+        const long units = (long)(sy1 - sy0) * up * (sx1 - sx0) * up;
+        if (units > max_units) max_units = units;
+    }
+    const int SH = H * up, SW = W * up, TH = th * up, TW = tw * up;
+    const int vec_ok = (SW % 4 == 0) && (TW % 4 == 0) && aligned16(dst) && aligned16(tiles) && (((size_t)C * TH * TW) % 4 == 0);
+    // crop: disjoint rectangles, one launch per chunk.  feather: one tile per launch -- stream order is the order of the additions.
+    const int step = feather ? 1 : SG_SCATTER_CHUNK;
+    for (int t0 = 0; t0 < T; t0 += step) {
+        const int n = T - t0 < step ? T - t0 : step;
+        ScatterArgs a;
+        memset(&a, 0, sizeof(a));
+        long units = 0;
+        for (int k = 0; k < n; ++k) {
+            const int* r = rects + 10 * (t0 + k);
+            a.t[k] = ScatterTile{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9]};
+            const long u = (long)(r[3] - r[2]) * up * (r[5] - r[4]) * up;
+            if (u > units) units = u;
+        }
+        const dim3 grid((unsigned)cdivl(units, 256), C, n);              // sized for the scalar path; vector tiles leave threads idle
+        hipLaunchKernelGGL(tile_scatter_k, grid, dim3(256), 0, (hipStream_t)stream, tiles + (size_t)t0 * C * TH * TW, dst, C, SH, SW, TH, TW, up,
+                           feather, vec_ok, a);
+        SG_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int srcgan_planes_to_u8hwc(const float* src, unsigned char* dst, int C, long hw, void* stream) {
+    SG_REQUIRE(src && dst, "srcgan_planes_to_u8hwc: null pointer");
+    SG_REQUIRE(C >= 1 && C <= 8, "srcgan_planes_to_u8hwc: C = %d (1..8 planes)", C);
+    SG_REQUIRE(hw > 0, "srcgan_planes_to_u8hwc: hw = %ld", hw);
+    const bool word = ((hw * C) % 4 == 0) && (((uintptr_t)dst & 3) == 0);
+    long nb = cdivl(word ? hw * C / 4 : hw * C, 256); if (nb > 16384) nb = 16384;
+    if (word) hipLaunchKernelGGL(planes_to_u8hwc_k<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, dst, C, hw);
+    else hipLaunchKernelGGL(planes_to_u8hwc_k<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, dst, C, hw);
+    SG_LAUNCH_CHECK();
+    return 0;
+}

@@ -1,0 +1,339 @@
+"""Whole-scene inference: super-resolve (and colourise) an image too large, or too oddly sized, for one forward.
+
+The scene stays on the device (u8 HWC or f32 NCHW).  ``plan_tiles`` cuts it into cores that partition it, each read with a halo;
+``srcgan_tile_gather`` collects up to ``batch`` tiles of one shape into an NCHW f32 batch, the generators run on it under
+``no_grad`` (their inference workspaces, sized by the tile batch and not by the scene), and ``srcgan_tile_scatter`` writes the HR
+tiles back -- by crop, or by a feathered blend whose ramps the plan defines.  Everything on the hot path is native (csrc/tiles.hip
+and the generators' own kernels); there is no CPU fallback.
+
+Two modes:
+  exact    ``halo=None``: the halo is the receptive radius of the chain (``receptive_halo``), tiles are cropped to their cores, and
+           the result is the whole-image forward's (networks without normalisation layers only).
+  blended  an explicit ``halo`` and ``blend="feather"``: for chains with per-image statistics (ResDeconv's GroupNorm), where no halo
+           makes tiles exact; neighbouring tiles are cross-faded over ``2 * min(halo, tile // 2)`` pixels around each core boundary.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _native as N
+from . import model as M
+
+__all__ = ["plan_tiles", "receptive_halo", "upscale_scene", "TilePlan", "Tile"]
+
+
+# ------------------------------------------------------------------------------------------------ the plan (pure Python)
+@dataclass(frozen=True)
+class Tile:
+    """One tile, in LR pixels.  ``y0, x0, th, tw``: the gathered rectangle (it may pass the right / bottom edge: the gather replicates
+    the edge there).  ``core`` = (cy0, cy1, cx0, cx1): the cores of all tiles partition the scene.  ``support`` = (sy0, sy1, sx0, sx1):
+    what a feathered write-back touches, the core widened by half a ramp on every side that has a neighbour.  ``ramps`` = (ny_lo, ny_hi,
+    nx_lo, nx_hi): the ramp lengths at the low / high end of the support (0 at the scene border)."""
+    y0: int
+    x0: int
+    th: int
+    tw: int
+    core: Tuple[int, int, int, int]
+    support: Tuple[int, int, int, int]
+    ramps: Tuple[int, int, int, int]
+
+
+@dataclass
+class TilePlan:
+    """``tiles``: every tile, ordered class by class (classes in order of first appearance, row-major inside a class) -- the order
+    ``upscale_scene`` runs and blends them in, so "tile order" below always means the index into this list.  ``classes``: tile shape
+    (th, tw) -> indices into ``tiles``."""
+    H: int
+    W: int
+    tile: int
+    halo: int
+    multiple: int
+    tiles: List[Tile] = field(default_factory=list)
+    classes: Dict[Tuple[int, int], List[int]] = field(default_factory=dict)
+
+    @property
+    def overruns(self) -> bool:
+        """Some tile passes the right / bottom edge (possible with ``multiple > 1`` only)."""
+        return any(t.y0 + t.th > self.H or t.x0 + t.tw > self.W for t in self.tiles)
+
+    @staticmethod
+    def axis_weights(n: int, n_lo: int, n_hi: int) -> torch.Tensor:
+        """f32 weights of one axis of a support of ``n`` (HR) pixels: ``(j + 0.5) / n_lo`` over the first ``n_lo``, ``1 - (j + 0.5) /
+        n_hi`` over the last ``n_hi``, 1 between -- the arithmetic of the scatter kernel, rounding for rounding."""
+        w = torch.ones(n, dtype=torch.float32)
+        if n_lo:
+            w[:n_lo] = (torch.arange(n_lo, dtype=torch.float32) + 0.5) / float(n_lo)
+        if n_hi:
+            w[n - n_hi:] = 1.0 - (torch.arange(n_hi, dtype=torch.float32) + 0.5) / float(n_hi)
+        return w
+
+    def weights(self, t: Tile, up: int = 1) -> torch.Tensor:
+        """[support height * up, support width * up] f32 feather weights of one tile: the outer product of its two axis ramps.  Over
+        all tiles they sum to 1 at every pixel (a partition of unity up to f32 rounding)."""
+        sy0, sy1, sx0, sx1 = t.support
+        wy = self.axis_weights((sy1 - sy0) * up, t.ramps[0] * up, t.ramps[1] * up)
+        wx = self.axis_weights((sx1 - sx0) * up, t.ramps[2] * up, t.ramps[3] * up)
+        return wy[:, None] * wx[None, :]
+
+    def rects(self, idx: Sequence[int], feather: bool):
+        """The 10-int records ``srcgan_tile_scatter`` takes (crop mode: the core, no ramps)."""
+        out = []
+        for i in idx:
+            t = self.tiles[i]
+            out += [t.y0, t.x0, *(t.support if feather else t.core), *(t.ramps if feather else (0, 0, 0, 0))]
+        return out
+
+
+def _axis(L: int, tile: int, halo: int, multiple: int):
+    """One axis: [(start, extent, core0, core1, support0, support1, ramp_lo, ramp_hi)].  The ramp between two neighbours is centred on
+    their core boundary B and spans [B - r, B + r), r = min(halo, tile // 2, length of the following core): inside both tiles (r <=
+    halo), inside the scene, and never meeting the next boundary's ramp (every core that has ramps at both ends is a full one, and
+    tile >= 2 (tile // 2)) -- so at most two tiles per axis carry weight at any pixel."""
+    cores = [(c0, min(c0 + tile, L)) for c0 in range(0, L, tile)]
+    r = [min(halo, tile // 2, cores[k + 1][1] - cores[k + 1][0]) for k in range(len(cores) - 1)]
+    out = []
+    for k, (c0, c1) in enumerate(cores):
+        s = max(c0 - halo, 0)
+        n = min(c1 + halo, L) - s
+        n = -(-n // multiple) * multiple
+        r_lo = r[k - 1] if k > 0 else 0
+        r_hi = r[k] if k < len(cores) - 1 else 0
+        out.append((s, n, c0, c1, c0 - r_lo, c1 + r_hi, 2 * r_lo, 2 * r_hi))
+    return out
+
+
+def plan_tiles(H: int, W: int, tile: int, halo: int, multiple: int = 1) -> TilePlan:
+    """Cut an H x W scene into tiles.  Cores of ``tile`` x ``tile`` pixels (ragged at the right / bottom) partition the scene; a tile is
+    its core plus ``halo`` on every side, clipped at the scene border -- a clipped side sees the network's own zero padding, exactly
+    as the whole image does.  ``multiple > 1`` rounds every tile extent up to that multiple (towards the right / bottom); where that
+    passes the edge the gather replicates the edge pixel and the scatter drops the excess."""
+    if min(H, W, tile, multiple) < 1 or halo < 0:
+        raise ValueError(f"plan_tiles: need H, W, tile, multiple >= 1 and halo >= 0, got {(H, W, tile, halo, multiple)}")
+    plan = TilePlan(H, W, tile, halo, multiple)
+    by_class: Dict[Tuple[int, int], List[Tile]] = {}
+    for (y0, th, cy0, cy1, sy0, sy1, ny_lo, ny_hi) in _axis(H, tile, halo, multiple):
+        for (x0, tw, cx0, cx1, sx0, sx1, nx_lo, nx_hi) in _axis(W, tile, halo, multiple):
+            by_class.setdefault((th, tw), []).append(
+                Tile(y0, x0, th, tw, (cy0, cy1, cx0, cx1), (sy0, sy1, sx0, sx1), (ny_lo, ny_hi, nx_lo, nx_hi)))
+    for shape, ts in by_class.items():
+        plan.classes[shape] = list(range(len(plan.tiles), len(plan.tiles) + len(ts)))
+        plan.tiles += ts
+    return plan
+
+
+# ------------------------------------------------------------------------------------------------ receptive radii
+def _cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def _scale(net) -> Optional[int]:
+    """Output pixels per input pixel of a known generator (None: unknown module)."""
+    if isinstance(net, (M.RDDBNetA, M.SRDenseNetB)):
+        return None                                     # HR -> LR networks: not an up-scaling chain
+    if isinstance(net, M.SRDenseNetA):
+        return M._MODES[net.mode]
+    if isinstance(net, M.RDDBNetB):                     # and LegacyRDDBNet
+        return M._MODES[net.mode]
+    if isinstance(net, M.RDDBNet):
+        return int(net.upscale_factor)
+    if isinstance(net, (M.ESPCN, M.EDSR)):
+        return int(net._cfg[3])
+    if isinstance(net, (M.SRCNN, M.SRDN, M.ResDeconv)):
+        return 1
+    return None
+
+
+def receptive_halo(net) -> int:
+    """Receptive radius of a generator in INPUT pixels: the halo at which a cropped tile equals the whole-image forward.
+
+    Every 3x3 p1 convolution spreads 1 pixel at its own resolution (k x k: k // 2); LeakyReLU / ReLU, 1x1 convolutions, the k2 s2
+    transposed convolutions, PixelShuffle and nearest up-sampling spread nothing; r pixels at a resolution ``s`` times the input's
+    cost ceil(r / s) input pixels.  Citations are into the reference (src/model/...):
+
+      RDDBNet        15 nb + 3      conv_first (rddb.py:89) 1; five 3x3 per dense block (rddb.py:52-58), three blocks per RRDB
+                                    (rddb.py:71-82): 15 per RRDB; trunk_conv (rddb.py:91) 1; deconv k2 s2 + LeakyReLU (rddb.py:28-38,
+                                    93-97) 0; conv_last at HR (rddb.py:98): 1 HR pixel = 1 input pixel
+      RDDBNetB       15 nb + 8 (x2), 15 nb + 5 (x4)
+                                    conv_first, trunk, trunk_conv (model.py:400-402, 418-424) 15 nb + 2; x2: nearest x2, upconv1 twice
+                                    (model.py:429-430), HRconv eight times and conv_last (model.py:431-439): 11 HR pixels = 6 input
+                                    pixels; x4: upconv1 at 2x (model.py:426) 1, then upconv2, 8 HRconv, conv_last at 4x: 10 -> 5 at 2x,
+                                    6 at 2x in all = 3 input pixels
+      LegacyRDDBNet  3 (x2, x4), 5 (x1)
+                                    the trunk is computed and discarded (model.py:381-382): conv_first (model.py:352) 1; x2: upconv,
+                                    HRconv twice, conv_last at 2x (model.py:386, 390-391): 4 -> 2; x4: upconv at 2x, then upconv, 2 HRconv,
+                                    conv_last at 4x (model.py:383-384): 4 -> 2 at 2x, 3 at 2x in all -> 2; x1 (model.py:388): 4 at 1x
+      ESPCN          6              conv1 5x5 (espcn.py:27) 2; conv2, conv3, conv4 3x3 (espcn.py:29-33) 3; PixelShuffle (espcn.py:35) 0;
+                                    conv5 3x3 at HR (espcn.py:36): 1 HR pixel = 1 input pixel
+      SRCNN          6              conv1 9x9 (srcnn.py:25) 4; conv2 1x1 (srcnn.py:27) 0; conv3 5x5 (srcnn.py:29) 2
+      SRDenseNetA    blocks * layers + 4
+                                    conv_first (model.py:679) 1; conv (model.py:643-646) 1; one 3x3 per dense layer (model.py:653-672);
+                                    bottleneck 1x1 (model.py:693) 0; ConvTranspose2d k3 s2 p1 op1 (model.py:699): output 2i reads input i,
+                                    output 2i + 1 reads i and i + 1; reconstruction and conv_last at HR (model.py:704-706) 2 HR pixels:
+                                    HR [2c - 2, 2c + 3] reads inputs [c - 1, c + 2] (x4, the sampler applied twice: [c - 1, c + 2] too): 2
+      SRDenseNetB    blocks * layers + 7 (x2), + 13 (x4)
+                                    as A up to the bottleneck: blocks * layers + 2; Conv2d k3 s2 p1 (model.py:756): output o reads inputs
+                                    2o - 1 .. 2o + 1; reconstruction and conv_last (model.py:761-763) 2 output pixels: x2 2 * 2 + 1 = 5
+                                    input pixels, x4 2 * (2 * 2 + 1) + 1 = 11.  (An HR -> LR network: ``upscale_scene`` does not run it.)
+
+    Networks with normalisation layers (ResDeconv, EDSR: GroupNorm / InstanceNorm statistics are taken over the whole image) and
+    unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
+    name = type(net).__name__
+    if isinstance(net, (M.ResDeconv, M.EDSR)):
+        raise ValueError(f"receptive_halo: {name} has normalisation layers whose per-image statistics make tiles inexact at any halo; "
+                         "pass halo= explicitly (and blend='feather')")
+    if isinstance(net, M.LegacyRDDBNet):
+        return 5 if net.mode == "x1" else 3
+    if isinstance(net, M.RDDBNetB):
+        return 15 * net.nb + (8 if net.mode == "x2" else 5)
+    if isinstance(net, M.SRDenseNetA):                  # and SRDenseNetB
+        _, _, _, growth, nblocks, nlayers, up = net._cfg
+        trunk = nblocks * nlayers
+        if isinstance(net, M.SRDenseNetB):
+            return trunk + (7 if up == 2 else 13)
+        return trunk + 4
+    if isinstance(net, M.RDDBNet) and not isinstance(net, M.RDDBNetA):
+        return 15 * net._cfg[4] + 3
+    if isinstance(net, (M.ESPCN, M.SRCNN)):
+        return 6
+    raise ValueError(f"receptive_halo: no receptive radius is known for {name} (an unknown module may hold per-image statistics, which "
+                     "make tiles inexact); pass halo= explicitly")
+
+
+def _chain_halo(nets) -> int:
+    """Summed receptive radius of a chain in pixels of its input: a later network's radius shrinks by the scale in front of it."""
+    total, scale = 0, 1
+    for net in nets:
+        r = receptive_halo(net)
+        total += _cdiv(r, scale)
+        s = _scale(net)
+        if s is None:
+            raise ValueError(f"upscale_scene: {type(net).__name__} is not an up-scaling generator")
+        scale *= s
+    return total
+
+
+# ------------------------------------------------------------------------------------------------ native calls
+def _int_array(values):
+    return (C.c_int * len(values))(*values)
+
+
+def tile_gather(scene: torch.Tensor, origins, th: int, tw: int) -> torch.Tensor:
+    """``srcgan_tile_gather``: scene u8 [H,W,C] / [H,W] or f32 [C,H,W] / [1,C,H,W] on the device, origins [(y0, x0)] -> f32
+    [T,C,th,tw]; coordinates are clamped to the scene (edge replication past the right / bottom edge)."""
+    N.require_cuda(scene, "tile_gather")
+    if scene.dtype == torch.uint8:
+        s = scene if scene.dim() == 3 else scene[:, :, None]
+        H, W, Cc = s.shape
+        u8 = 1
+    elif scene.dtype == torch.float32:
+        s = scene if scene.dim() == 3 else scene[0]
+        Cc, H, W = s.shape
+        u8 = 0
+    else:
+        raise TypeError(f"tile_gather: the scene must be uint8 (HWC) or float32 (NCHW), got {scene.dtype}")
+    if not s.is_contiguous():
+        raise ValueError("tile_gather: the scene must be contiguous")
+    T = len(origins)
+    out = torch.empty(T, Cc, th, tw, dtype=torch.float32, device=scene.device)
+    flat = _int_array([int(v) for yx in origins for v in yx])
+    N.check(N.lib().srcgan_tile_gather(s.data_ptr(), u8, Cc, H, W, out.data_ptr(), T, th, tw, flat, N.stream_ptr(scene.device)),
+            "srcgan_tile_gather")
+    return out
+
+
+def tile_scatter(tiles: torch.Tensor, dst: torch.Tensor, up: int, rects, feather: bool) -> None:
+    """``srcgan_tile_scatter``: tiles f32 [T,C,th*up,tw*up] into dst f32 [C,H*up,W*up]; ``rects`` as ``TilePlan.rects`` builds them.
+    Feather mode adds into ``dst`` (zero it first), tile after tile in the order given."""
+    N.require_cuda(tiles, "tile_scatter")
+    N.require_cuda(dst, "tile_scatter")
+    if tiles.dtype != torch.float32 or dst.dtype != torch.float32 or not tiles.is_contiguous() or not dst.is_contiguous():
+        raise TypeError("tile_scatter: tiles and destination must be contiguous float32")
+    d = dst if dst.dim() == 3 else dst[0]
+    T, Cc, TH, TW = tiles.shape
+    if up < 1 or TH % up or TW % up or d.shape[0] != Cc or d.shape[1] % up or d.shape[2] % up:
+        raise ValueError(f"tile_scatter: tiles {tuple(tiles.shape)} / scene {tuple(d.shape)} do not fit up = {up}")
+    if len(rects) != 10 * T:
+        raise ValueError("tile_scatter: 10 integers per tile expected")
+    N.check(N.lib().srcgan_tile_scatter(tiles.data_ptr(), d.data_ptr(), Cc, d.shape[1] // up, d.shape[2] // up, up, T, TH // up, TW // up,
+                                        _int_array([int(v) for v in rects]), int(bool(feather)), N.stream_ptr(dst.device)),
+            "srcgan_tile_scatter")
+
+
+def planes_to_u8hwc(planes: torch.Tensor) -> torch.Tensor:
+    """f32 [C,H,W] / [1,C,H,W] on the device -> u8 [H,W,C]: ``floor(clamp(v, 0, 1) * 255)``.  For values in [0, 1] this is the
+    reference's ``tensor2image`` (test.py:38, visCas.py:28: ``* 255`` then ``astype(uint8)``).  Deviation: out-of-range values
+    SATURATE (below 0 -> 0, above 1 -> 255) where the reference's uint8 cast wraps around."""
+    N.require_cuda(planes, "planes_to_u8hwc")
+    p = planes if planes.dim() == 3 else planes[0]
+    if p.dtype != torch.float32 or not p.is_contiguous():
+        raise TypeError("planes_to_u8hwc: contiguous float32 planes expected")
+    Cc, H, W = p.shape
+    out = torch.empty(H, W, Cc, dtype=torch.uint8, device=p.device)
+    N.check(N.lib().srcgan_planes_to_u8hwc(p.data_ptr(), out.data_ptr(), Cc, H * W, N.stream_ptr(p.device)), "srcgan_planes_to_u8hwc")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the driver
+def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: Optional[int] = None, batch: int = 1,
+                  blend: str = "crop", out: str = "f32", multiple: int = 1) -> torch.Tensor:
+    """Run ``nets`` (a module, or a sequence applied in order, e.g. ``[sr, colouriser]``) over a whole scene, tile by tile.
+
+    ``scene``: a device tensor, u8 [H,W,C] (C = 1 or 3; mapped v / 255 like ``data.arr2rgb``) or f32 [1,C,H,W].  ``up``: output pixels
+    per scene pixel of the whole chain.  ``tile``: core size; ``halo``: context read around each core -- ``None`` means EXACT mode: the
+    summed receptive radius of the chain (``receptive_halo``), which needs ``blend="crop"`` and a chain without normalisation layers,
+    and then equals the whole-image forward.  ``blend``: "crop" (each tile writes its core) or "feather" (neighbours are cross-faded
+    over linear ramps, accumulated in f32 in tile order: bitwise reproducible).  ``multiple``: round tile extents up to a multiple (16
+    / up of the first stage for a ResDeconv behind it).  ``out``: "f32" -> [1,C',H*up,W*up], "u8" -> u8 [H*up,W*up,C']
+    (``planes_to_u8hwc``).
+
+    Runs under ``no_grad`` with the modules in ``eval()``.  Extra memory: one tile batch's inference workspace and its input / output
+    tensors, next to the input and output scenes -- independent of the scene size."""
+    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    if not nets or not all(isinstance(n, nn.Module) for n in nets):
+        raise TypeError("upscale_scene: nets must be a module or a sequence of modules")
+    if blend not in ("crop", "feather"):
+        raise ValueError(f"upscale_scene: blend must be 'crop' or 'feather', got {blend!r}")
+    if out not in ("f32", "u8"):
+        raise ValueError(f"upscale_scene: out must be 'f32' or 'u8', got {out!r}")
+    if up < 1 or batch < 1:
+        raise ValueError("upscale_scene: up and batch must be >= 1")
+    exact = halo is None
+    if exact:
+        if blend != "crop":
+            raise ValueError("upscale_scene: halo=None is the exact mode and needs blend='crop'")
+        halo = _chain_halo(nets)                        # ValueError for chains with normalisation layers / unknown modules
+    N.require_cuda(scene, "upscale_scene")
+    if scene.dtype == torch.uint8 and scene.dim() in (2, 3):
+        H, W = scene.shape[:2]
+    elif scene.dtype == torch.float32 and scene.dim() == 4 and scene.shape[0] == 1:
+        H, W = scene.shape[2:]
+    else:
+        raise ValueError(f"upscale_scene: the scene must be u8 [H,W,C] or f32 [1,C,H,W], got {scene.dtype} {tuple(scene.shape)}")
+    plan = plan_tiles(H, W, tile, halo, multiple)
+    if exact and plan.overruns:
+        raise ValueError("upscale_scene: with this `multiple` a tile passes the scene's edge and sees replicated pixels where the whole "
+                         "image sees zero padding, so exact mode would not be exact; use multiple=1 or pass halo= explicitly")
+    feather = blend == "feather"
+    scene = scene.contiguous()
+    result = None
+    with torch.no_grad():
+        for net in nets:
+            net.eval()
+        for (th, tw), idx in plan.classes.items():
+            for b0 in range(0, len(idx), batch):
+                ids = idx[b0:b0 + batch]
+                x = tile_gather(scene, [(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids], th, tw)
+                for net in nets:
+                    x = net(x)
+                if x.dim() != 4 or x.shape[0] != len(ids) or tuple(x.shape[2:]) != (th * up, tw * up):
+                    raise ValueError(f"upscale_scene: the chain maps a {th}x{tw} tile to {tuple(x.shape)}, not to {th * up}x{tw * up} (up = {up})")
+                if result is None:
+                    alloc = torch.zeros if feather else torch.empty
+                    result = alloc(1, x.shape[1], H * up, W * up, dtype=torch.float32, device=scene.device)
+                tile_scatter(x.contiguous().float(), result, up, plan.rects(ids, feather), feather)
+    return planes_to_u8hwc(result) if out == "u8" else result
