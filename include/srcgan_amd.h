@@ -531,6 +531,25 @@ int srcgan_tile_scatter(const float* tiles, float* dst, int C, int H, int W, int
                         const int* rects, int feather, void* stream);
 int srcgan_planes_to_u8hwc(const float* src, unsigned char* dst, int C, long hw, void* stream);
 
+/* ---- cascade inference without scene-sized f32 intermediates (infer.py cascade_scene) ----
+ * srcgan_tile_gather_ex: srcgan_tile_gather of a scene that is converted and up-sampled while it is read.
+ *   src_kind 0: f32 planes [C][H][W], C <= 8; 1: u8 HWC (C = 1 or 3), v / 255; 2: u8 [H][W][3] -> ONE gray plane, the arithmetic of
+ *   srcgan_u8rgb_to_planes mode 0 (C = 3 is the source's channel count; dst holds one plane per tile).
+ *   s >= 1: dst[t][c][ty][tx] = U(c, min(y0_t + ty, H s - 1), min(x0_t + tx, W s - 1)), U = the converted scene up-sampled s times
+ *   bilinearly (align_corners = False) exactly as srcgan_bilinear_up computes it; s = 1: no interpolation.  Origins are on the
+ *   up-sampled grid, inside [0, H s) x [0, W s).  Every sample is evaluated from in-scene reads by the device functions the
+ *   materialising kernels use, so the result is bit-identical to srcgan_tile_gather of the materialised scene; with s = 1 and
+ *   src_kind 0 / 1 the call IS srcgan_tile_gather.
+ * srcgan_tile_scatter_u8: crop-mode write-back into an 8-bit RGB scene dst [H*up][W*up][3], the conversion fused into the store.
+ *   rects as srcgan_tile_scatter (disjoint rectangles, ramps 0).  mode 0: tiles_a [T][3][th*up][tw*up] RGB planes, tiles_b NULL,
+ *   Cb = 0; bytes as srcgan_planes_to_u8hwc.  mode 1: tiles_a [T][1][..] the L plane, tiles_b [T][2][..] the chroma planes (normalised
+ *   LAB); bytes as srcgan_lab_planes_to_u8rgb.  Aligned 12-byte stores of 4 pixels in the interior of a rectangle row, byte stores at
+ *   its ends; no read-modify-write, no atomics, any W. */
+int srcgan_tile_gather_ex(const void* src, int src_kind, int C, int H, int W, int s, float* dst, int T, int th, int tw,
+                          const int* origins_yx, void* stream);
+int srcgan_tile_scatter_u8(const float* tiles_a, int Ca, const float* tiles_b, int Cb, unsigned char* dst_u8hwc, int H, int W, int up,
+                           int T, int th, int tw, const int* rects, int mode, void* stream);
+
 /* Fused multi-tensor Adam (torch.optim.Adam.step() of trainCas.py:38-41,143-150 / train.py:191-192,331-340; torch's
  * single-tensor arithmetic, default flags: no weight decay, no amsgrad).  tensors_dev: device array of records
  * {float* p; const float* g; float* m; float* v;} (32 bytes); chunks_dev: device array of nchunks records

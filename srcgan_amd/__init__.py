@@ -7,8 +7,8 @@ Everything computes in libsrcgan_amd.so (hand-written HIP for gfx950); there is 
 from ._native import set_default_dtype, LIB_PATH
 from .model import RDDBNet, RDDBNetA, RDDBNetB, LegacyRDDBNet, ResDeconv, ESPCN, SRCNN, EDSR, SRDN, SRDenseNetA, SRDenseNetB, NLayerDiscriminator, ResidualDenseBlock_5, RRDB
 from .losses import L1Loss, MSELoss, PSNRLoss, GANLoss, DSSIMLoss
-from .infer import plan_tiles, receptive_halo, upscale_scene
+from .infer import plan_tiles, receptive_halo, upscale_scene, cascade_scene
 
 __all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB",
-           "L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "plan_tiles", "receptive_halo", "upscale_scene", "set_default_dtype", "LIB_PATH"]
+           "L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "plan_tiles", "receptive_halo", "upscale_scene", "cascade_scene", "set_default_dtype", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -192,6 +192,8 @@ SIGNATURES = {
     "srcgan_tile_gather": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_int), _P]),
     "srcgan_tile_scatter": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), _I, _P]),
     "srcgan_planes_to_u8hwc": (_I, [_P, _P, _I, _L, _P]),
+    "srcgan_tile_gather_ex": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_int), _P]),
+    "srcgan_tile_scatter_u8": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), _I, _P]),
     "srcgan_adam_step": (_I, [_P, _P, _I, C.c_double, C.c_double, C.c_double, C.c_double, _L, _P]),
     "srcgan_params_fingerprint": (_I, [_P, _I, _L, _P, _P]),
     "srcgan_prof_enable": (_I, [_I]),

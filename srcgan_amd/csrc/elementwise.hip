@@ -4,6 +4,7 @@
 // All reductions are two-stage and order-fixed (deterministic); wavefront (64-lane) shuffles do
 // the in-wave part.
 #include "common.h"
+#include "pixel_ops.h"
 
 static thread_local char g_err[512] = "";
 void srcgan_set_error(const char* fmt, ...) {
@@ -1138,21 +1139,16 @@ extern "C" int srcgan_sum2x2_nhwc(const void* src, int s_cs, void* dst, int d_cs
 }
 
 // bilinear x up (integer), align_corners=False, as F.interpolate(scale_factor=up, mode="bilinear") in trainCasConst.py:91-92:
-// src coordinate = (dst + 0.5) / up - 0.5 clamped at 0, neighbour index clamped at the border
+// src coordinate = (dst + 0.5) / up - 0.5 clamped at 0, neighbour index clamped at the border.  The sample is pixel_ops.h's
+// sg_bilinear_sample, which the whole-scene tile gather evaluates on the fly and must reproduce bit for bit.
 __global__ __launch_bounds__(256) void bilinear_up_k(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int up, long total) {
     const int OH = H * up, OW = W * up;
-    const float inv = 1.f / (float)up;
+    const float inv = sg_bilinear_inv(up);
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const int ox = (int)(e % OW); const long q = e / OW;
         const int oy = (int)(q % OH); const long bc = q / OH;
-        float sy = ((float)oy + 0.5f) * inv - 0.5f, sx = ((float)ox + 0.5f) * inv - 0.5f;
-        sy = sy < 0.f ? 0.f : sy; sx = sx < 0.f ? 0.f : sx;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-        const float ly = sy - (float)y0, lx = sx - (float)x0;
         const float* s = src + (size_t)bc * H * W;
-        dst[e] = (1.f - ly) * ((1.f - lx) * s[(size_t)y0 * W + x0] + lx * s[(size_t)y0 * W + x1]) +
-                 ly * ((1.f - lx) * s[(size_t)y1 * W + x0] + lx * s[(size_t)y1 * W + x1]);
+        dst[e] = sg_bilinear_sample([&](int y, int x) { return s[(size_t)y * W + x]; }, H, W, inv, oy, ox);
     }
 }
 extern "C" int srcgan_bilinear_up(const float* src, float* dst, int B, int C, int H, int W, int up, void* stream) {

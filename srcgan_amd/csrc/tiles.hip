@@ -7,7 +7,12 @@
 //     a launch carries SG_GATHER_CHUNK / SG_SCATTER_CHUNK tiles and the entry points chunk above that;
 //   * no atomics: crop rectangles are disjoint, and the feathered blend adds one tile per launch, so the additions to a pixel happen
 //     in tile order on the stream and the result is the same bits run after run.
+// The cascade driver (infer.py cascade_scene) adds two fused forms, so that no f32 scene is ever made: srcgan_tile_gather_ex converts
+// (u8 RGB -> gray) and up-samples (bilinear x s) the scene while it gathers, with pixel_ops.h's per-sample functions, and is thereby
+// bit-identical to gathering from the materialised scene; srcgan_tile_scatter_u8 converts the network's tiles (RGB planes, or L + ab
+// planes) to 8-bit RGB while it writes their cores back.
 #include "common.h"
+#include "pixel_ops.h"
 
 namespace {
 constexpr int SG_GATHER_CHUNK = 128;        // 128 x 8 B  = 1 KiB of kernel arguments
@@ -19,9 +24,6 @@ struct GatherArgs { int yx[SG_GATHER_CHUNK][2]; };
 // ny_lo / ny_hi / nx_lo / nx_hi: ramp lengths in LR pixels at the low / high end of the support (0 = no ramp on that side).
 struct ScatterTile { int y0, x0, sy0, sy1, sx0, sx1, ny_lo, ny_hi, nx_lo, nx_hi; };
 struct ScatterArgs { ScatterTile t[SG_SCATTER_CHUNK]; };
-
-// u8 -> f32 exactly as data.arr2rgb / srcgan_u8rgb_to_planes mode 1: the quotient in double, one rounding to float
-__device__ __forceinline__ float u8_unit(unsigned char v) { return (float)((double)v / 255.0); }
 
 // dst[t][c][ty][tx] = src(c, min(y0 + ty, H - 1), min(x0 + tx, W - 1)).  VEC = 4: tw % 4 == 0 and dst 16-byte aligned (host-checked).
 // grid: x = units of one (tile, channel) plane, y = channel (f32) or 1 (u8: a thread converts all C channels of its pixels), z = tile.
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ sr
         for (int c = 0; c < C; ++c) {
             float v[VEC];
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) v[i] = u8_unit(row[(size_t)min(x0 + tx + i, W - 1) * C + c]);
+            for (int i = 0; i < VEC; ++i) v[i] = sg_u8_unit(row[(size_t)min(x0 + tx + i, W - 1) * C + c]);
             if constexpr (VEC == 4) store4<float>(d + c * plane, v);
             else d[c * plane] = v[0];
         }
@@ -60,6 +62,48 @@ __global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ sr
         } else {
             d[c * plane] = row[min(x0 + tx, W - 1)];
         }
+    }
+}
+
+// One sample of the CONVERTED scene at (c, y, x), 0 <= y < H, 0 <= x < W.  KIND 0: f32 planes; 1: u8 HWC, v / 255; 2: u8 RGB -> gray.
+template <int KIND>
+__device__ __forceinline__ float scene_at(const void* __restrict__ src, int C, int H, int W, int c, int y, int x) {
+    if constexpr (KIND == 0) {
+        return ((const float*)src)[((size_t)c * H + y) * W + x];
+    } else {
+        const unsigned char* p = (const unsigned char*)src + ((size_t)y * W + x) * C;
+        if constexpr (KIND == 1) return sg_u8_unit(p[c]);
+        else return sg_gray_u8(p[0], p[1], p[2]);
+    }
+}
+
+// dst[t][c][ty][tx] = U(c, min(y0 + ty, H s - 1), min(x0 + tx, W s - 1)), U = the converted scene up-sampled x s (s == 1: the converted
+// scene itself), evaluated per sample: every tap is an in-scene read.  Grid as tile_gather_k; a u8 thread writes all planes of its pixels.
+template <int VEC, int KIND>
+__global__ __launch_bounds__(256) void tile_gather_up_k(const void* __restrict__ src, float* __restrict__ dst, int C, int H, int W, int s,
+                                                        int th, int tw, GatherArgs a) {
+    const int upr = tw / VEC;
+    const long unit = (long)blockIdx.x * 256 + threadIdx.x;
+    if (unit >= (long)th * upr) return;
+    const int ty = (int)(unit / upr), tx = (int)(unit - (long)ty * upr) * VEC;
+    const int y0 = a.yx[blockIdx.z][0], x0 = a.yx[blockIdx.z][1];
+    const int OH = H * s, OW = W * s;
+    const int oy = min(y0 + ty, OH - 1);
+    const float inv = sg_bilinear_inv(s);
+    const int Cd = KIND == 2 ? 1 : C;                           // planes written
+    const int c_lo = KIND == 0 ? (int)blockIdx.y : 0, c_hi = KIND == 0 ? c_lo + 1 : Cd;
+    const size_t plane = (size_t)th * tw;
+    float* d = dst + (size_t)blockIdx.z * Cd * plane + (size_t)ty * tw + tx;
+    for (int c = c_lo; c < c_hi; ++c) {
+        float v[VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const int ox = min(x0 + tx + i, OW - 1);
+            v[i] = s == 1 ? scene_at<KIND>(src, C, H, W, c, oy, ox)
+                          : sg_bilinear_sample([&](int y, int x) { return scene_at<KIND>(src, C, H, W, c, y, x); }, H, W, inv, oy, ox);
+        }
+        if constexpr (VEC == 4) store4<float>(d + c * plane, v);
+        else d[c * plane] = v[0];
     }
 }
 
@@ -122,6 +166,63 @@ __global__ __launch_bounds__(256) void planes_to_u8hwc_k(const float* __restrict
         } else {
             const long px = u / C;
             dst[u] = (unsigned char)unit_to_u8(src[(size_t)(u - px * C) * hw + px]);
+        }
+    }
+}
+
+// Crop-mode write-back fused with the 8-bit conversion: dst u8 [SH][SW][3].  MODE 0: ta = 3 RGB planes, floor(clamp(v, 0, 1) * 255) as
+// planes_to_u8hwc_k.  MODE 1: ta = the L plane, tb = the two chroma planes, sg_lab_to_u8rgb as lab_planes_to_u8rgb_k.
+// A thread owns one GROUP: the pixels of one rectangle row whose linear index p = y * SW + x lies in [4 g, 4 g + 4) -- 12 bytes that
+// start at byte 12 g, 4-byte aligned whatever SW is.  A group that lies wholly inside the row is stored as three words; a group cut
+// by the rectangle's left / right end (its other pixels belong to a neighbouring tile, or to the previous / next scene row) stores
+// only its own pixels, byte by byte: nothing outside the rectangle is read or written, so disjoint rectangles never race.
+// A row of hw pixels touches at most hw / 4 + 2 groups; that bound sizes the grid and threads past a row's last group exit.
+template <int MODE>
+__global__ __launch_bounds__(256) void tile_scatter_u8_k(const float* __restrict__ ta, const float* __restrict__ tb, unsigned char* __restrict__ dst,
+                                                         int SW, int TH, int TW, int up, int word_ok, ScatterArgs a) {
+    const ScatterTile t = a.t[blockIdx.z];
+    const int hx0 = t.sx0 * up, hy0 = t.sy0 * up, hw = (t.sx1 - t.sx0) * up, hh = (t.sy1 - t.sy0) * up;
+    const int ox = hx0 - t.x0 * up, oy = hy0 - t.y0 * up;                      // rectangle origin inside the HR tile
+    const int gpr = hw / 4 + 2;
+    const long unit = (long)blockIdx.x * 256 + threadIdx.x;
+    if (unit >= (long)hh * gpr) return;
+    const int j = (int)(unit / gpr), k = (int)(unit - (long)j * gpr);
+    const long p0 = (long)(hy0 + j) * SW + hx0, p1 = p0 + hw;                  // this row of the rectangle, in linear pixel indices
+    const long q = ((p0 >> 2) + k) * 4;                                        // first pixel of the group
+    if (q >= p1) return;
+    const size_t plane = (size_t)TH * TW, row = (size_t)(oy + j) * TW + ox;
+    const float* sa = ta + (size_t)blockIdx.z * (MODE == 0 ? 3 : 1) * plane + row;
+    const float* sb = MODE == 0 ? nullptr : tb + (size_t)blockIdx.z * 2 * plane + row;
+    unsigned int b[4][3];
+    bool in[4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n) {
+        in[n] = q + n >= p0 && q + n < p1;
+        b[n][0] = b[n][1] = b[n][2] = 0;
+        if (!in[n]) continue;
+        const long i = q + n - p0;                                             // 0 <= i < hw
+        if constexpr (MODE == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) b[n][c] = unit_to_u8(sa[c * plane + i]);
+        } else {
+            unsigned char rgb[3];
+            sg_lab_to_u8rgb(sa[i], sb[i], sb[plane + i], rgb);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) b[n][c] = rgb[c];
+        }
+    }
+    unsigned char* d = dst + (size_t)q * 3;
+    if (word_ok && in[0] && in[3]) {
+        unsigned int* w = (unsigned int*)d;
+        w[0] = b[0][0] | b[0][1] << 8 | b[0][2] << 16 | b[1][0] << 24;
+        w[1] = b[1][1] | b[1][2] << 8 | b[2][0] << 16 | b[2][1] << 24;
+        w[2] = b[2][2] | b[3][0] << 8 | b[3][1] << 16 | b[3][2] << 24;
+    } else {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+            if (!in[n]) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d[3 * n + c] = (unsigned char)b[n][c];
         }
     }
 }
@@ -217,5 +318,87 @@ extern "C" int srcgan_planes_to_u8hwc(const float* src, unsigned char* dst, int 
     if (word) hipLaunchKernelGGL(planes_to_u8hwc_k<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, dst, C, hw);
     else hipLaunchKernelGGL(planes_to_u8hwc_k<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, src, dst, C, hw);
     SG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int srcgan_tile_gather_ex(const void* src, int src_kind, int C, int H, int W, int s, float* dst, int T, int th, int tw,
+                                     const int* origins_yx, void* stream) {
+    SG_REQUIRE(src && dst && origins_yx, "srcgan_tile_gather_ex: null pointer");
+    SG_REQUIRE(src_kind >= 0 && src_kind <= 2, "srcgan_tile_gather_ex: src_kind = %d (0 f32 planes, 1 u8 HWC, 2 u8 RGB -> gray)", src_kind);
+    SG_REQUIRE(src_kind == 0 ? (C >= 1 && C <= 8) : src_kind == 1 ? (C == 1 || C == 3) : C == 3,
+               "srcgan_tile_gather_ex: C = %d (f32 planes: 1..8; u8 HWC: 1 or 3; u8 RGB -> gray: 3)", C);
+    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_gather_ex: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
+    SG_REQUIRE(s >= 1 && (long)H * s < (1L << 30) && (long)W * s < (1L << 30), "srcgan_tile_gather_ex: s = %d (must be >= 1, and the up-sampled scene below 2^30 per side)", s);
+    SG_REQUIRE(th <= SG_TILE_MAX_SIDE && tw <= SG_TILE_MAX_SIDE, "srcgan_tile_gather_ex: tile %dx%d is larger than the launch limit of %d per side", th, tw, SG_TILE_MAX_SIDE);
+    const int OH = H * s, OW = W * s;
+    for (int t = 0; t < T; ++t)
+        SG_REQUIRE(origins_yx[2 * t] >= 0 && origins_yx[2 * t] < OH && origins_yx[2 * t + 1] >= 0 && origins_yx[2 * t + 1] < OW,
+                   "srcgan_tile_gather_ex: origin (%d, %d) of tile %d is outside the %dx%d scene", origins_yx[2 * t], origins_yx[2 * t + 1], t, OH, OW);
+    if (s == 1 && src_kind <= 1)                                // a plain copy: the existing kernels, vector loads included
+        return srcgan_tile_gather(src, src_kind, C, H, W, dst, T, th, tw, origins_yx, stream);
+    const bool vec = (tw % 4 == 0) && aligned16(dst);
+    const int upr = vec ? tw / 4 : tw;
+    const unsigned gx = (unsigned)cdivl((long)th * upr, 256);
+    const size_t per_tile = (size_t)(src_kind == 2 ? 1 : C) * th * tw;
+    for (int t0 = 0; t0 < T; t0 += SG_GATHER_CHUNK) {
+        const int n = T - t0 < SG_GATHER_CHUNK ? T - t0 : SG_GATHER_CHUNK;
+        GatherArgs a;
+        memset(&a, 0, sizeof(a));
+        memcpy(a.yx, origins_yx + 2 * t0, sizeof(int) * 2 * n);
+        const dim3 grid(gx, src_kind == 0 ? C : 1, n);
+        float* d = dst + (size_t)t0 * per_tile;             // per_tile * 4 bytes is a multiple of 16 whenever tw % 4 == 0
+#define SG_GATHER_UP(V, K) hipLaunchKernelGGL((tile_gather_up_k<V, K>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, s, th, tw, a)
+        if (src_kind == 0) { if (vec) SG_GATHER_UP(4, 0); else SG_GATHER_UP(1, 0); }
+        else if (src_kind == 1) { if (vec) SG_GATHER_UP(4, 1); else SG_GATHER_UP(1, 1); }
+        else { if (vec) SG_GATHER_UP(4, 2); else SG_GATHER_UP(1, 2); }
+#undef SG_GATHER_UP
+        SG_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" int srcgan_tile_scatter_u8(const float* tiles_a, int Ca, const float* tiles_b, int Cb, unsigned char* dst, int H, int W, int up,
+                                      int T, int th, int tw, const int* rects, int mode, void* stream) {
+    SG_REQUIRE(tiles_a && dst && rects, "srcgan_tile_scatter_u8: null pointer");
+    SG_REQUIRE(mode == 0 || mode == 1, "srcgan_tile_scatter_u8: mode = %d (0 RGB planes, 1 L + ab planes)", mode);
+    SG_REQUIRE(mode == 0 ? (Ca == 3 && !tiles_b && Cb == 0) : (Ca == 1 && tiles_b && Cb == 2),
+               "srcgan_tile_scatter_u8: mode %d takes %s, got Ca = %d, Cb = %d", mode,
+               mode == 0 ? "Ca = 3 and no second tensor (tiles_b null, Cb = 0)" : "Ca = 1 (L) and Cb = 2 (ab)", Ca, Cb);
+    SG_REQUIRE(up >= 1, "srcgan_tile_scatter_u8: up = %d (must be >= 1)", up);
+    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_scatter_u8: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
+    SG_REQUIRE((long)th * up <= SG_TILE_MAX_SIDE && (long)tw * up <= SG_TILE_MAX_SIDE && (long)H * up < (1L << 30) && (long)W * up < (1L << 30),
+               "srcgan_tile_scatter_u8: HR tile %ldx%ld is larger than the launch limit of %d per side", (long)th * up, (long)tw * up, SG_TILE_MAX_SIDE);
+    for (int t = 0; t < T; ++t) {
+        const int* r = rects + 10 * t;
+        const int y0 = r[0], x0 = r[1], sy0 = r[2], sy1 = r[3], sx0 = r[4], sx1 = r[5];
+        // the rectangle lies inside the scene AND inside the tile: nothing outside either is ever touched
+        SG_REQUIRE(sy0 >= 0 && sy0 < sy1 && sy1 <= H && sx0 >= 0 && sx0 < sx1 && sx1 <= W && sy0 >= y0 && sy1 <= y0 + th && sx0 >= x0 && sx1 <= x0 + tw,
+                   "srcgan_tile_scatter_u8: write-back rectangle [%d,%d)x[%d,%d) of tile %d (origin %d,%d, %dx%d) leaves the tile or the %dx%d scene",
+                   sy0, sy1, sx0, sx1, t, y0, x0, th, tw, H, W);
+        SG_REQUIRE((r[6] | r[7] | r[8] | r[9]) == 0, "srcgan_tile_scatter_u8: crop mode takes no ramps (tile %d)", t);
+    }
+    const int SW = W * up, TH = th * up, TW = tw * up;
+    const int word_ok = ((uintptr_t)dst & 3) == 0;
+    for (int t0 = 0; t0 < T; t0 += SG_SCATTER_CHUNK) {
+        const int n = T - t0 < SG_SCATTER_CHUNK ? T - t0 : SG_SCATTER_CHUNK;
+        ScatterArgs a;
+        memset(&a, 0, sizeof(a));
+        long units = 0;
+        for (int k = 0; k < n; ++k) {
+            const int* r = rects + 10 * (t0 + k);
+            a.t[k] = ScatterTile{r[0], r[1], r[2], r[3], r[4], r[5], 0, 0, 0, 0};
+            const long u = (long)(r[3] - r[2]) * up * ((long)(r[5] - r[4]) * up / 4 + 2);       // rows x groups per row
+            if (u > units) units = u;
+        }
+        const dim3 grid((unsigned)cdivl(units, 256), 1, n);
+        const size_t plane = (size_t)TH * TW;
+        if (mode == 0)
+            hipLaunchKernelGGL(tile_scatter_u8_k<0>, grid, dim3(256), 0, (hipStream_t)stream, tiles_a + (size_t)t0 * 3 * plane, (const float*)nullptr,
+                               dst, SW, TH, TW, up, word_ok, a);
+        else
+            hipLaunchKernelGGL(tile_scatter_u8_k<1>, grid, dim3(256), 0, (hipStream_t)stream, tiles_a + (size_t)t0 * plane, tiles_b + (size_t)t0 * 2 * plane,
+                               dst, SW, TH, TW, up, word_ok, a);
+        SG_LAUNCH_CHECK();
+    }
     return 0;
 }

@@ -6,6 +6,12 @@ The scene stays on the device (u8 HWC or f32 NCHW).  ``plan_tiles`` cuts it into
 tiles back -- by crop, or by a feathered blend whose ramps the plan defines.  Everything on the hot path is native (csrc/tiles.hip
 and the generators' own kernels); there is no CPU fallback.
 
+``cascade_scene`` is the reference's product, the gray LR scene -> super-resolution -> colourisation -> 8-bit RGB cascade of
+testCas.py / testCasConst.py / testCasLAB.py / testCasConstLAB.py, on the same plan: the gray conversion of a colour scene and the
+Const variants' bilinear up-sampling happen inside the gather (``srcgan_tile_gather_ex``), the LAB variants keep the L tile of the
+first network next to the ab tile of the second, and in crop mode the 8-bit conversion happens inside the write-back
+(``srcgan_tile_scatter_u8``) -- no f32 scene is made on the way.
+
 Two modes:
   exact    ``halo=None``: the halo is the receptive radius of the chain (``receptive_halo``), tiles are cropped to their cores, and
            the result is the whole-image forward's (networks without normalisation layers only).
@@ -24,7 +30,7 @@ import torch.nn as nn
 from . import _native as N
 from . import model as M
 
-__all__ = ["plan_tiles", "receptive_halo", "upscale_scene", "TilePlan", "Tile"]
+__all__ = ["plan_tiles", "receptive_halo", "upscale_scene", "cascade_scene", "TilePlan", "Tile"]
 
 
 # ------------------------------------------------------------------------------------------------ the plan (pure Python)
@@ -337,3 +343,169 @@ def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: 
                     result = alloc(1, x.shape[1], H * up, W * up, dtype=torch.float32, device=scene.device)
                 tile_scatter(x.contiguous().float(), result, up, plan.rects(ids, feather), feather)
     return planes_to_u8hwc(result) if out == "u8" else result
+
+
+# ------------------------------------------------------------------------------------------------ the cascade
+_KINDS = {"f32": 0, "u8": 1, "u8rgb2gray": 2}
+
+
+def tile_gather_ex(scene: torch.Tensor, kind: str, s: int, origins, th: int, tw: int) -> torch.Tensor:
+    """``srcgan_tile_gather_ex``: ``tile_gather`` of the scene converted (``kind``: "f32" planes, "u8" HWC v / 255, "u8rgb2gray" u8
+    [H,W,3] -> one gray plane as ``data.arr2gray``) and up-sampled ``s`` times bilinearly (as ``ops.bilinear_up``), evaluated on the
+    fly; origins are on the up-sampled grid.  Bit-identical to ``tile_gather`` of the materialised scene."""
+    N.require_cuda(scene, "tile_gather_ex")
+    if kind not in _KINDS:
+        raise ValueError(f"tile_gather_ex: kind must be one of {sorted(_KINDS)}, got {kind!r}")
+    if kind == "f32":
+        if scene.dtype != torch.float32 or scene.dim() not in (3, 4) or (scene.dim() == 4 and scene.shape[0] != 1):
+            raise TypeError(f"tile_gather_ex: kind 'f32' takes float32 [C,H,W] / [1,C,H,W], got {scene.dtype} {tuple(scene.shape)}")
+        sc = scene if scene.dim() == 3 else scene[0]
+        Cc, H, W = sc.shape
+        planes = Cc
+    else:
+        if scene.dtype != torch.uint8 or scene.dim() not in (2, 3):
+            raise TypeError(f"tile_gather_ex: kind {kind!r} takes uint8 [H,W] / [H,W,C], got {scene.dtype} {tuple(scene.shape)}")
+        sc = scene if scene.dim() == 3 else scene[:, :, None]
+        H, W, Cc = sc.shape
+        planes = 1 if kind == "u8rgb2gray" else Cc
+    if not sc.is_contiguous():
+        raise ValueError("tile_gather_ex: the scene must be contiguous")
+    T = len(origins)
+    out = torch.empty(T, planes, th, tw, dtype=torch.float32, device=scene.device)
+    flat = _int_array([int(v) for yx in origins for v in yx])
+    N.check(N.lib().srcgan_tile_gather_ex(sc.data_ptr(), _KINDS[kind], Cc, H, W, int(s), out.data_ptr(), T, th, tw, flat,
+                                          N.stream_ptr(scene.device)), "srcgan_tile_gather_ex")
+    return out
+
+
+def tile_scatter_u8(tiles_a: torch.Tensor, tiles_b: Optional[torch.Tensor], dst: torch.Tensor, up: int, rects) -> None:
+    """``srcgan_tile_scatter_u8``: crop-mode write-back into dst u8 [H*up,W*up,3] with the conversion fused into the store.
+    ``tiles_b is None``: ``tiles_a`` f32 [T,3,th*up,tw*up] RGB planes, bytes as ``planes_to_u8hwc``; else ``tiles_a`` [T,1,..] is L and
+    ``tiles_b`` [T,2,..] is ab (normalised LAB), bytes as ``data.lab2img``.  ``rects``: ``TilePlan.rects(idx, False)``."""
+    N.require_cuda(tiles_a, "tile_scatter_u8")
+    N.require_cuda(dst, "tile_scatter_u8")
+    for t in (tiles_a, tiles_b):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous()):
+            raise TypeError("tile_scatter_u8: tiles must be contiguous float32 [T,C,TH,TW]")
+    if dst.dtype != torch.uint8 or dst.dim() != 3 or dst.shape[2] != 3 or not dst.is_contiguous():
+        raise TypeError("tile_scatter_u8: the destination must be contiguous uint8 [H,W,3]")
+    T, Ca, TH, TW = tiles_a.shape
+    Cb = 0 if tiles_b is None else tiles_b.shape[1]
+    if tiles_b is not None and (tiles_b.shape[0], tiles_b.shape[2], tiles_b.shape[3]) != (T, TH, TW):
+        raise ValueError(f"tile_scatter_u8: L tiles {tuple(tiles_a.shape)} and ab tiles {tuple(tiles_b.shape)} do not match")
+    if up < 1 or TH % up or TW % up or dst.shape[0] % up or dst.shape[1] % up:
+        raise ValueError(f"tile_scatter_u8: tiles {tuple(tiles_a.shape)} / scene {tuple(dst.shape)} do not fit up = {up}")
+    if len(rects) != 10 * T:
+        raise ValueError("tile_scatter_u8: 10 integers per tile expected")
+    N.check(N.lib().srcgan_tile_scatter_u8(tiles_a.data_ptr(), Ca, None if tiles_b is None else tiles_b.data_ptr(), Cb, dst.data_ptr(),
+                                           dst.shape[0] // up, dst.shape[1] // up, up, T, TH // up, TW // up,
+                                           _int_array([int(v) for v in rects]), 0 if tiles_b is None else 1, N.stream_ptr(dst.device)),
+            "srcgan_tile_scatter_u8")
+
+
+def _cascade_plan(netG_A2C, netG_C2B, H: int, W: int, *, up: int, const: bool, tile: int, halo: Optional[int], multiple: int) -> TilePlan:
+    """The plan ``cascade_scene`` runs (pure Python).  ``const``: the first network is size-preserving and sees the scene up-sampled
+    by ``up`` inside the gather, so the plan -- tiles, halo, ``multiple`` -- is made on the H*up x W*up grid and the chain's own scale
+    is 1; the interpolation reads the scene itself and adds nothing to the halo.  Otherwise the plan is on the scene's own grid, as in
+    ``upscale_scene``.  ``halo=None``: the summed receptive radius of both networks (refused for normalisation layers)."""
+    if const and _scale(netG_A2C) != 1:
+        raise ValueError(f"cascade_scene: const=True needs a size-preserving netG_A2C (SRCNN, SRDN), got {type(netG_A2C).__name__}"
+                         + ("" if _scale(netG_A2C) is None else f" with scale {_scale(netG_A2C)}"))
+    exact = halo is None
+    if exact:
+        halo = _chain_halo([netG_A2C, netG_C2B])        # ValueError for chains with normalisation layers / unknown modules
+    plan = plan_tiles(H * up, W * up, tile, halo, multiple) if const else plan_tiles(H, W, tile, halo, multiple)
+    if exact and plan.overruns:
+        raise ValueError("cascade_scene: with this `multiple` a tile passes the scene's edge and sees replicated pixels where the whole "
+                         "image sees zero padding, so exact mode would not be exact; use multiple=1 or pass halo= explicitly")
+    return plan
+
+
+def cascade_scene(netG_A2C, netG_C2B, scene: torch.Tensor, *, up: int, space: str = "rgb", const: bool = False, tile: int = 512,
+                  halo: Optional[int] = None, batch: int = 1, blend: str = "crop", out: str = "u8", multiple: int = 1) -> torch.Tensor:
+    """The reference's cascade over a whole LR scene: gray -> ``netG_A2C`` (super-resolution) -> ``netG_C2B`` (colourisation) -> picture.
+
+        testCas.py          cascade_scene(sr, col, scene, up=up)
+        testCasLAB.py       cascade_scene(sr, col, scene, up=up, space="lab")
+        testCasConst.py     cascade_scene(sr, col, scene, up=up, const=True)
+        testCasConstLAB.py  cascade_scene(sr, col, scene, up=up, const=True, space="lab")
+
+    (The test scripts make their LR input by down-sampling the HR target; here ``scene`` IS the LR input.)
+
+    ``scene``: a device tensor -- u8 [H,W] / [H,W,1] gray (v / 255), u8 [H,W,3] colour (converted to gray with the arithmetic of
+    ``data.arr2gray``) or f32 [1,1,H,W].  ``const``: ``netG_A2C`` is size-preserving and sees the gray scene up-sampled bilinearly by
+    ``up`` (trainCasConst.py:89-92); the up-sampling happens inside the tile gather and tiles, halo and ``multiple`` are planned on the
+    H*up x W*up grid.  ``space``: "rgb" -- ``netG_C2B`` returns the 3 image planes; "lab" -- it returns the 2 chroma planes and the
+    image is normalised LAB, cat(L tile of ``netG_A2C``, ab tile), converted as ``data.lab2img`` for ``out="u8"``.  ``out``: "u8" ->
+    u8 [H*up,W*up,3] RGB; "f32" -> f32 [1,3,H*up,W*up], RGB planes or normalised LAB planes.  ``tile, halo, batch, blend, multiple``:
+    as in ``upscale_scene`` (``halo=None``: exact mode over both networks' receptive radii, crop only, no normalisation layers).
+
+    Memory: with ``blend="crop", out="u8"`` nothing scene-sized is allocated but the u8 result (the conversion is fused into the
+    write-back); ``blend="feather"`` accumulates in ONE f32 [3,H*up,W*up] buffer (L into plane 0, ab into planes 1-2) converted once at
+    the end; ``out="f32"`` allocates the f32 result.  Everything else follows the tile batch."""
+    if not isinstance(netG_A2C, nn.Module) or not isinstance(netG_C2B, nn.Module):
+        raise TypeError("cascade_scene: netG_A2C and netG_C2B must be modules")
+    if space not in ("rgb", "lab"):
+        raise ValueError(f"cascade_scene: space must be 'rgb' or 'lab', got {space!r}")
+    if blend not in ("crop", "feather"):
+        raise ValueError(f"cascade_scene: blend must be 'crop' or 'feather', got {blend!r}")
+    if out not in ("f32", "u8"):
+        raise ValueError(f"cascade_scene: out must be 'f32' or 'u8', got {out!r}")
+    if up < 1 or batch < 1:
+        raise ValueError("cascade_scene: up and batch must be >= 1")
+    if halo is None and blend != "crop":
+        raise ValueError("cascade_scene: halo=None is the exact mode and needs blend='crop'")
+    if scene.dtype == torch.uint8 and (scene.dim() == 2 or (scene.dim() == 3 and scene.shape[2] in (1, 3))):
+        H, W = scene.shape[:2]
+        kind = "u8rgb2gray" if scene.dim() == 3 and scene.shape[2] == 3 else "u8"
+    elif scene.dtype == torch.float32 and scene.dim() == 4 and scene.shape[0] == 1 and scene.shape[1] == 1:
+        H, W = scene.shape[2:]
+        kind = "f32"
+    else:
+        raise ValueError(f"cascade_scene: the scene must be u8 [H,W], [H,W,1], [H,W,3] or f32 [1,1,H,W], got {scene.dtype} {tuple(scene.shape)}")
+    plan = _cascade_plan(netG_A2C, netG_C2B, H, W, up=up, const=const, tile=tile, halo=halo, multiple=multiple)
+    N.require_cuda(scene, "cascade_scene")
+    s, cu = (up, 1) if const else (1, up)               # up-sampling inside the gather; scale of the chain on the plan's grid
+    lab, feather, fused = space == "lab", blend == "feather", blend == "crop" and out == "u8"
+    want = 2 if lab else 3
+    scene = scene.contiguous()
+    result = None
+    with torch.no_grad():
+        netG_A2C.eval()
+        netG_C2B.eval()
+        for (th, tw), idx in plan.classes.items():
+            for b0 in range(0, len(idx), batch):
+                ids = idx[b0:b0 + batch]
+                x = tile_gather_ex(scene, kind, s, [(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids], th, tw)
+                l = netG_A2C(x)
+                if l.dim() != 4 or l.shape[0] != len(ids) or tuple(l.shape[2:]) != (th * cu, tw * cu):
+                    raise ValueError(f"cascade_scene: netG_A2C maps a {th}x{tw} tile to {tuple(l.shape)}, not to {th * cu}x{tw * cu} "
+                                     f"(up = {up}, const = {const})")
+                if lab and l.shape[1] != 1:
+                    raise ValueError(f"cascade_scene: space='lab' needs a 1-plane netG_A2C (L), got {l.shape[1]} planes")
+                c = netG_C2B(l)
+                if c.dim() != 4 or c.shape[0] != len(ids) or tuple(c.shape[2:]) != tuple(l.shape[2:]):
+                    raise ValueError(f"cascade_scene: netG_C2B maps {tuple(l.shape)} to {tuple(c.shape)}; a size-preserving colouriser is expected")
+                if c.shape[1] != want:
+                    raise ValueError(f"cascade_scene: space={space!r} needs a colouriser with {want} output planes, got {c.shape[1]}")
+                l, c = l.contiguous().float(), c.contiguous().float()
+                rects = plan.rects(ids, feather)
+                if fused:
+                    if result is None:
+                        result = torch.empty(H * up, W * up, 3, dtype=torch.uint8, device=scene.device)
+                    tile_scatter_u8(l if lab else c, c if lab else None, result, cu, rects)
+                    continue
+                if result is None:
+                    alloc = torch.zeros if feather else torch.empty
+                    result = alloc(1, 3, H * up, W * up, dtype=torch.float32, device=scene.device)
+                if lab:                                 # L -> plane 0, ab -> planes 1-2 of the same buffer, through offset pointers
+                    tile_scatter(l, result[0, 0:1], cu, rects, feather)
+                    tile_scatter(c, result[0, 1:3], cu, rects, feather)
+                else:
+                    tile_scatter(c, result, cu, rects, feather)
+    if fused or out == "f32":
+        return result
+    if lab:
+        from .data import lab2img
+        return lab2img(result[0])
+    return planes_to_u8hwc(result)
