@@ -177,7 +177,7 @@ int srcgan_wgrad_dense(const srcgan_wgrad_dense_desc* d, void* stream);
  * Column reductions over pixels (deterministic two-stage):
  *   mode 0: out0[c] = scale * sum a[p,c]                         (bias grad; BN mean)
  *   mode 1: out0[c] = scale * sum (a[p,c]-m[c])^2                (BN variance)
- *   mode 2: out0[c] = sum g[p,c] ; out1[c] = sum g[p,c]*(z[p,c]-m[c])*rstd[c]   (BN backward)
+ *   mode 2: out0[c] = scale * sum g[p,c] ; out1[c] = scale * sum g[p,c]*(z[p,c]-m[c])*rstd[c]   (BN backward; a = g)
  *   mode 3: out0[c] = mean of a[p,c] ; out1[c] = its biased variance -- ONE pass over a (per-thread shifted sums, partials
  *           combined exactly in a fixed order); `scale` and `m` are not used                       (BN statistics, training)
  * scratch: 2*nblk*C floats, nblk = srcgan_col_reduce_blocks(npix).
@@ -190,7 +190,12 @@ int srcgan_col_reduce(int mode, const void* a, int a_cs, int a_coff, const void*
 /* BatchNorm2d(train)+LeakyReLU (model/model.py:622-623,630-631), NHWC.
  * bn_finalize: mean/var -> rstd, running-stat update (momentum .1, unbiased var), nbt++.
  * bn_apply:    y = lrelu(gamma*(z-mean)*rstd+beta)
- * bn_bwd_apply:dz = gamma*rstd*(g - sum_g/N - xhat*sum_gx/N)   (g already holds dy*lrelu'(y)) */
+ * bn_bwd_apply:dz = gamma*rstd*(g - sum_g/N - xhat*sum_gx/N)   (g already holds dy*lrelu'(y))
+ * Shape constraints of bn_apply_lrelu and bn_bwd_apply (anything else is refused with an error, nothing is launched): the tensors
+ * are dense NHWC, cs == C; C is a multiple of epp = 4 (f32) or 8 (bf16 / fp16), i.e. of one 16-byte vector; C/epp divides 256
+ * (a thread owns one vector of channels and 256/(C/epp) threads share a pixel column), so C <= 1024 (f32) / 2048 (16-bit).
+ * bn_bwd_apply may run in place, dz == g: a thread reads the elements it writes, and no others, before it writes them; the result
+ * has the same bits as the out-of-place call.  z must not alias dz. */
 int srcgan_bn_finalize(const float* mean, const float* var, float* rstd, float* running_mean,
                        float* running_var, int64_t* num_batches_tracked, int C, long count,
                        float momentum, float eps, void* stream);

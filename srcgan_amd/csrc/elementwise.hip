@@ -1294,7 +1294,13 @@ extern "C" int srcgan_pixel_shuffle_nhwc(const void* src, int s_cs, void* dst, i
 template <typename T>
 __global__ __launch_bounds__(256) void mask_inplace_k(T* __restrict__ g, const T* __restrict__ act, float slope, long n) {
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256)
-        if (!(to_f(act[e]) > 0.f)) g[e] = from_f<T>(to_f(g[e]) * slope);
+        if (!(to_f(act[e]) > 0.f)) {
+            // The product stays an f32 multiply: for _Float16 the compiler otherwise forms v_fma_mixlo_f16 (g * slope + 0.0), and the
+            // +0.0 addend turns a product of -0.0 (a negative g under slope 0, the ReLU case) into +0.0.
+            float p = to_f(g[e]) * slope;
+            asm volatile("" : "+v"(p));
+            g[e] = from_f<T>(p);
+        }
 }
 extern "C" int srcgan_mask_inplace(void* g, const void* act, float slope, long n, int dtype, void* stream) {
     SG_REQUIRE(g && act && n > 0, "srcgan_mask_inplace: bad arguments");
