@@ -555,6 +555,22 @@ int srcgan_tile_gather_ex(const void* src, int src_kind, int C, int H, int W, in
 int srcgan_tile_scatter_u8(const float* tiles_a, int Ca, const float* tiles_b, int Cb, unsigned char* dst_u8hwc, int H, int W, int up,
                            int T, int th, int tw, const int* rects, int mode, void* stream);
 
+/* ---- whole-scene scoring (csrc/scene_score.hip, metrics.py score_scene) ----
+ * MSE, PSNR, AE, SSIM and CS of metrics.py:10-144 for ONE image pair of any size, in one pass and without scene-sized intermediates.
+ *   pred / truth: kind 0 = f32 planes [C][H][W] (taken as is), kind 1 = u8 [H][W][C] (v / 255 as srcgan_tile_gather kind 1; any byte
+ *   alignment of the base and of W * C).  C = 1 or 3; H, W >= 11.  The SSIM dynamic range follows the prediction: 1 for a u8
+ *   prediction, from a stream-ordered min / max pass for an f32 one.
+ *   srcgan_scene_score_tile:     T, the edge of a workgroup's tile of SSIM positions (host only).
+ *   srcgan_scene_score_ws_bytes: workspace size (host only); 0 and srcgan_last_error() for bad arguments.  16 bytes per tile plus
+ *                                a fixed part of at most 8 KiB: at most H * W * C / 16 for scenes of 256 x 256 and more.
+ *   srcgan_scene_score:          out5 (device, 5 doubles) = MSE, PSNR (+inf for MSE 0), AE in degrees, SSIM, CS.  One tile kernel
+ *                                + a two-stage f64 fold of fixed order: bitwise reproducible, no atomics, no host synchronisation.
+ *                                workspace: 16-byte aligned device memory of ws_bytes. */
+int srcgan_scene_score_tile(void);
+size_t srcgan_scene_score_ws_bytes(long H, long W, int C);
+int srcgan_scene_score(const void* pred, int pred_kind, const void* truth, int truth_kind, long H, long W, int C,
+                       double* out5, void* workspace, void* stream);
+
 /* Fused multi-tensor Adam (torch.optim.Adam.step() of trainCas.py:38-41,143-150 / train.py:191-192,331-340; torch's
  * single-tensor arithmetic, default flags: no weight decay, no amsgrad).  tensors_dev: device array of records
  * {float* p; const float* g; float* m; float* v;} (32 bytes); chunks_dev: device array of nchunks records

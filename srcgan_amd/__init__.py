@@ -8,7 +8,8 @@ from ._native import set_default_dtype, LIB_PATH
 from .model import RDDBNet, RDDBNetA, RDDBNetB, LegacyRDDBNet, ResDeconv, ESPCN, SRCNN, EDSR, SRDN, SRDenseNetA, SRDenseNetB, NLayerDiscriminator, ResidualDenseBlock_5, RRDB
 from .losses import L1Loss, MSELoss, PSNRLoss, GANLoss, DSSIMLoss
 from .infer import plan_tiles, receptive_halo, upscale_scene, cascade_scene
+from .metrics import score_scene
 
 __all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB",
-           "L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "plan_tiles", "receptive_halo", "upscale_scene", "cascade_scene", "set_default_dtype", "LIB_PATH"]
+           "L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "plan_tiles", "receptive_halo", "upscale_scene", "cascade_scene", "score_scene", "set_default_dtype", "LIB_PATH"]
 __version__ = "0.1.0"

@@ -11,7 +11,7 @@ from . import _native as N
 from . import ops
 from .losses import MSELoss, PSNRLoss
 
-__all__ = ["AE", "MSE", "PSNR", "SSIM", "evaluate_cascade"]
+__all__ = ["AE", "MSE", "PSNR", "SSIM", "evaluate_cascade", "score_scene"]
 
 
 def _prep(y_pred, y_true, who):
@@ -111,3 +111,52 @@ def evaluate_cascade(netG_A2C: torch.nn.Module, netG_C2B: torch.nn.Module, batch
         for i, ev in enumerate(evaluators):
             performs[i].append(ev(fake_BB.detach(), realB.detach()).item())     # testCas.py:82 (AE: batch of one image)
     return {repr(e): sum(p) / len(p) for e, p in zip(evaluators, performs)}, (fake_AB, fake_BB)
+
+
+def _scene_arg(x, who, name):
+    """-> (kind, H, W, C) of one score_scene argument: u8 [H,W] / [H,W,C] is kind 1, f32 [1,C,H,W] is kind 0."""
+    if not isinstance(x, torch.Tensor):
+        raise ValueError(f"{who}: {name} must be a tensor, got {type(x).__name__}")
+    if x.dtype == torch.uint8 and x.dim() in (2, 3):
+        H, W = int(x.shape[0]), int(x.shape[1])
+        return 1, H, W, (int(x.shape[2]) if x.dim() == 3 else 1)
+    if x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] == 1:
+        return 0, int(x.shape[2]), int(x.shape[3]), int(x.shape[1])
+    raise ValueError(f"{who}: {name} must be u8 [H,W] / [H,W,C] or f32 [1,C,H,W], got {x.dtype} {tuple(x.shape)}")
+
+
+def score_scene(pred, target, *, full=False) -> Dict[str, torch.Tensor]:
+    """MSE, PSNR, AE and SSIM (and CS with ``full=True``) of one whole scene against its target in ONE pass, without scene-sized
+    intermediates: what the reference's test scripts compute with ``metrics.MSE / PSNR / AE / SSIM`` for a batch of one image.
+
+    ``pred`` and ``target`` are device tensors of the same H, W and C (C = 1 or 3; H, W >= 11); each is either u8 ``[H,W]`` /
+    ``[H,W,C]`` (value = v / 255, e.g. what ``cascade_scene(..., out="u8")`` returns) or f32 ``[1,C,H,W]`` (taken as is).  The SSIM
+    dynamic range follows the prediction as in the reference: 1 for a u8 prediction, from a min / max pass for an f32 one.
+    Returns 0-dim float64 device tensors; nothing synchronises with the host until the caller reads one (``.item()``)."""
+    who = "score_scene"
+    kp, H, W, Cc = _scene_arg(pred, who, "pred")
+    kt, Ht, Wt, Ct = _scene_arg(target, who, "target")
+    if (H, W, Cc) != (Ht, Wt, Ct):
+        raise ValueError(f"{who}: pred is {H}x{W}x{Cc} but target is {Ht}x{Wt}x{Ct}")
+    if Cc not in (1, 3):
+        raise ValueError(f"{who}: C must be 1 or 3, got {Cc}")
+    if H < 11 or W < 11:
+        raise ValueError(f"{who}: scenes must be at least 11x11 (valid 11x11 windows), got {H}x{W}")
+    try:
+        N.require_cuda(pred, who)
+        N.require_cuda(target, who)
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    if pred.device != target.device:
+        raise ValueError(f"{who}: pred is on {pred.device} but target is on {target.device}")
+    p, t = pred.detach().contiguous(), target.detach().contiguous()
+    lib = N.lib()
+    with torch.cuda.device(p.device):
+        ws = N.workspace(lib.srcgan_scene_score_ws_bytes(H, W, Cc), p.device)
+        out = torch.empty(5, dtype=torch.float64, device=p.device)
+        N.check(lib.srcgan_scene_score(p.data_ptr(), kp, t.data_ptr(), kt, H, W, Cc, out.data_ptr(), ws.data_ptr(), N.stream_ptr(p.device)),
+                "srcgan_scene_score")
+    ret = {"MSE": out[0], "PSNR": out[1], "AE": out[2], "SSIM": out[3]}
+    if full:
+        ret["CS"] = out[4]
+    return ret
