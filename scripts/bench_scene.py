@@ -8,7 +8,8 @@ before the call (torch.cuda.max_memory_allocated):
   exact    upscale_scene(tile=1024, halo=None): halo = the receptive radius 15 nb + 3, crop; the relative difference to `whole`
   feather  upscale_scene(tile=512, halo=32, blend="feather")
 then a --big x --big scene (which the whole-image path cannot hold) in feather mode, and the yardstick of the gather / scatter
-kernels: the same copies done with torch slicing in this process, side by side.  A measurement tool only: no test runs it and no
+kernels: the same copies done with torch slicing in this process, side by side (and the cascade's fused gather, which has no torch
+twin).  A measurement tool only: no test runs it and no
 gate is set on its numbers.  One JSON line per measurement, echoed to --out."""
 import argparse
 import json
@@ -89,6 +90,11 @@ def main():
     ms_torch, _, g2 = timed(lambda: torch.stack([x[0, :, t.y0:t.y0 + th, t.x0:t.x0 + tw] for t in tiles]), 5)
     emit(run="gather", tiles=len(idx), shape=[th, tw], native_ms=round(ms_native, 3), torch_slicing_ms=round(ms_torch, 3), equal=bool(torch.equal(g, g2)))
     del g, g2
+    # the fused gather of the cascade: a u8 RGB scene -> gray, up-sampled x2 inside the gather, on the same plan
+    rgb = torch.randint(0, 256, (S // 2, S // 2, 3), dtype=torch.uint8, device="cuda")
+    ms_native, _, g = timed(lambda: infer.tile_gather_ex(rgb, "u8rgb2gray", 2, org, th, tw), 5)
+    emit(run="gather_fused", kind="u8rgb2gray", s=2, tiles=len(idx), shape=[th, tw], native_ms=round(ms_native, 3))
+    del g, rgb
     hr = torch.rand(len(idx), 3, th * up, tw * up, device="cuda")
     dst = torch.zeros(1, 3, S * up, S * up, device="cuda")
 

@@ -261,6 +261,21 @@ def require_cuda(t: torch.Tensor, what: str) -> None:
             "there is no CPU fallback (move the module and its inputs to 'cuda').")
 
 
+def scene_layout(x):
+    """The layouts a whole scene comes in -> (kind, 3-D view, C, H, W): uint8 [H,W] / [H,W,C] is kind "u8" with the view [H,W,C];
+    float32 [C,H,W] / [1,C,H,W] is kind "f32" with the view [C,H,W].  None for anything else.  The view shares ``x``'s memory (it is
+    contiguous whenever ``x`` is); callers narrow the layouts further and word their own errors."""
+    if not isinstance(x, torch.Tensor):
+        return None
+    if x.dtype == torch.uint8 and x.dim() in (2, 3):
+        v = x if x.dim() == 3 else x[:, :, None]
+        return "u8", v, int(v.shape[2]), int(v.shape[0]), int(v.shape[1])
+    if x.dtype == torch.float32 and (x.dim() == 3 or (x.dim() == 4 and x.shape[0] == 1)):
+        v = x if x.dim() == 3 else x[0]
+        return "f32", v, int(v.shape[0]), int(v.shape[1]), int(v.shape[2])
+    return None
+
+
 def ptr_array(tensors: Sequence[Optional[torch.Tensor]]):
     arr = (C.c_void_p * len(tensors))()
     for i, t in enumerate(tensors):

@@ -7,10 +7,12 @@
 //     a launch carries SG_GATHER_CHUNK / SG_SCATTER_CHUNK tiles and the entry points chunk above that;
 //   * no atomics: crop rectangles are disjoint, and the feathered blend adds one tile per launch, so the additions to a pixel happen
 //     in tile order on the stream and the result is the same bits run after run.
-// The cascade driver (infer.py cascade_scene) adds two fused forms, so that no f32 scene is ever made: srcgan_tile_gather_ex converts
-// (u8 RGB -> gray) and up-samples (bilinear x s) the scene while it gathers, with pixel_ops.h's per-sample functions, and is thereby
-// bit-identical to gathering from the materialised scene; srcgan_tile_scatter_u8 converts the network's tiles (RGB planes, or L + ab
-// planes) to 8-bit RGB while it writes their cores back.
+// There is ONE gather, tile_gather_k<VEC, KIND, UP>, behind both srcgan_tile_gather (kind from the dtype, s = 1) and
+// srcgan_tile_gather_ex: it converts (KIND: f32 as is, u8 -> v / 255, u8 RGB -> gray) and, with UP, up-samples (bilinear x s) the
+// scene while it gathers, with pixel_ops.h's per-sample functions, and is thereby bit-identical to gathering from the materialised
+// scene -- so the cascade driver (infer.py cascade_scene) never makes an f32 scene.  Its other fused form, srcgan_tile_scatter_u8,
+// converts the network's tiles (RGB planes, or L + ab planes) to 8-bit RGB while it writes their cores back; it shares the
+// rectangle checks and the argument chunking with srcgan_tile_scatter, not the kernel.
 #include "common.h"
 #include "pixel_ops.h"
 
@@ -25,46 +27,6 @@ struct GatherArgs { int yx[SG_GATHER_CHUNK][2]; };
 struct ScatterTile { int y0, x0, sy0, sy1, sx0, sx1, ny_lo, ny_hi, nx_lo, nx_hi; };
 struct ScatterArgs { ScatterTile t[SG_SCATTER_CHUNK]; };
 
-// dst[t][c][ty][tx] = src(c, min(y0 + ty, H - 1), min(x0 + tx, W - 1)).  VEC = 4: tw % 4 == 0 and dst 16-byte aligned (host-checked).
-// grid: x = units of one (tile, channel) plane, y = channel (f32) or 1 (u8: a thread converts all C channels of its pixels), z = tile.
-template <int VEC, bool U8>
-__global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ src_, float* __restrict__ dst, int C, int H, int W,
-                                                     int th, int tw, int src_vec_ok, GatherArgs a) {
-    const int upr = tw / VEC;                                   // units per row
-    const long unit = (long)blockIdx.x * 256 + threadIdx.x;
-    if (unit >= (long)th * upr) return;
-    const int ty = (int)(unit / upr), tx = (int)(unit - (long)ty * upr) * VEC;
-    const int y0 = a.yx[blockIdx.z][0], x0 = a.yx[blockIdx.z][1];
-    const int sy = min(y0 + ty, H - 1);
-    const size_t plane = (size_t)th * tw;
-    float* d = dst + (size_t)blockIdx.z * C * plane + (size_t)ty * tw + tx;
-    if constexpr (U8) {
-        const unsigned char* row = (const unsigned char*)src_ + (size_t)sy * W * C;
-        for (int c = 0; c < C; ++c) {
-            float v[VEC];
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) v[i] = sg_u8_unit(row[(size_t)min(x0 + tx + i, W - 1) * C + c]);
-            if constexpr (VEC == 4) store4<float>(d + c * plane, v);
-            else d[c * plane] = v[0];
-        }
-    } else {
-        const int c = blockIdx.y;
-        const float* row = (const float*)src_ + ((size_t)c * H + sy) * W;
-        float v[VEC];
-        if constexpr (VEC == 4) {
-            if (src_vec_ok && !(x0 & 3) && x0 + tx + 3 < W) {
-                load4<float>(row + x0 + tx, v);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = row[min(x0 + tx + i, W - 1)];
-            }
-            store4<float>(d + c * plane, v);
-        } else {
-            d[c * plane] = row[min(x0 + tx, W - 1)];
-        }
-    }
-}
-
 // One sample of the CONVERTED scene at (c, y, x), 0 <= y < H, 0 <= x < W.  KIND 0: f32 planes; 1: u8 HWC, v / 255; 2: u8 RGB -> gray.
 template <int KIND>
 __device__ __forceinline__ float scene_at(const void* __restrict__ src, int C, int H, int W, int c, int y, int x) {
@@ -77,30 +39,40 @@ __device__ __forceinline__ float scene_at(const void* __restrict__ src, int C, i
     }
 }
 
-// dst[t][c][ty][tx] = U(c, min(y0 + ty, H s - 1), min(x0 + tx, W s - 1)), U = the converted scene up-sampled x s (s == 1: the converted
-// scene itself), evaluated per sample: every tap is an in-scene read.  Grid as tile_gather_k; a u8 thread writes all planes of its pixels.
-template <int VEC, int KIND>
-__global__ __launch_bounds__(256) void tile_gather_up_k(const void* __restrict__ src, float* __restrict__ dst, int C, int H, int W, int s,
-                                                        int th, int tw, GatherArgs a) {
-    const int upr = tw / VEC;
+// dst[t][c][ty][tx] = U(c, min(y0 + ty, OH - 1), min(x0 + tx, OW - 1)), U = the converted scene (UP: up-sampled x s, s > 1, OH x OW =
+// H s x W s; else s is unused and OH x OW = H x W), evaluated per sample: every tap is an in-scene read.  VEC = 4: tw % 4 == 0 and dst
+// 16-byte aligned (host-checked); a unit of f32 planes taken as they are is one 16-byte load where `src_vec_ok` (row pitch and base
+// aligned) and the unit is aligned and inside the row -- the same values either way.
+// grid: x = units of one (tile, channel) plane, y = channel (f32) or 1 (u8: a thread writes all planes of its pixels), z = tile.
+template <int VEC, int KIND, bool UP>
+__global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ src, float* __restrict__ dst, int C, int H, int W, int s,
+                                                     int th, int tw, int src_vec_ok, GatherArgs a) {
+    const int upr = tw / VEC;                                   // units per row
     const long unit = (long)blockIdx.x * 256 + threadIdx.x;
     if (unit >= (long)th * upr) return;
     const int ty = (int)(unit / upr), tx = (int)(unit - (long)ty * upr) * VEC;
     const int y0 = a.yx[blockIdx.z][0], x0 = a.yx[blockIdx.z][1];
-    const int OH = H * s, OW = W * s;
+    const int OH = UP ? H * s : H, OW = UP ? W * s : W;
     const int oy = min(y0 + ty, OH - 1);
-    const float inv = sg_bilinear_inv(s);
+    const float inv = UP ? sg_bilinear_inv(s) : 1.f;
     const int Cd = KIND == 2 ? 1 : C;                           // planes written
     const int c_lo = KIND == 0 ? (int)blockIdx.y : 0, c_hi = KIND == 0 ? c_lo + 1 : Cd;
     const size_t plane = (size_t)th * tw;
     float* d = dst + (size_t)blockIdx.z * Cd * plane + (size_t)ty * tw + tx;
     for (int c = c_lo; c < c_hi; ++c) {
         float v[VEC];
+        if constexpr (KIND == 0 && !UP && VEC == 4) {
+            if (src_vec_ok && !(x0 & 3) && x0 + tx + 3 < W) {
+                load4<float>((const float*)src + ((size_t)c * H + oy) * W + x0 + tx, v);
+                store4<float>(d + c * plane, v);
+                return;                                         // KIND 0: this thread's only plane
+            }
+        }
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
             const int ox = min(x0 + tx + i, OW - 1);
-            v[i] = s == 1 ? scene_at<KIND>(src, C, H, W, c, oy, ox)
-                          : sg_bilinear_sample([&](int y, int x) { return scene_at<KIND>(src, C, H, W, c, y, x); }, H, W, inv, oy, ox);
+            if constexpr (UP) v[i] = sg_bilinear_sample([&](int y, int x) { return scene_at<KIND>(src, C, H, W, c, y, x); }, H, W, inv, oy, ox);
+            else v[i] = scene_at<KIND>(src, C, H, W, c, oy, ox);
         }
         if constexpr (VEC == 4) store4<float>(d + c * plane, v);
         else d[c * plane] = v[0];
@@ -228,64 +200,97 @@ __global__ __launch_bounds__(256) void tile_scatter_u8_k(const float* __restrict
 }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-}   // namespace
 
-extern "C" int srcgan_tile_gather(const void* src, int src_u8, int C, int H, int W, float* dst, int T, int th, int tw,
-                                  const int* origins_yx, void* stream) {
-    SG_REQUIRE(src && dst && origins_yx, "srcgan_tile_gather: null pointer");
-    SG_REQUIRE(src_u8 ? (C == 1 || C == 3) : (C >= 1 && C <= 8), "srcgan_tile_gather: C = %d (u8 HWC scenes: 1 or 3 channels; f32 planes: 1..8)", C);
-    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_gather: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
-    SG_REQUIRE(th <= SG_TILE_MAX_SIDE && tw <= SG_TILE_MAX_SIDE, "srcgan_tile_gather: tile %dx%d is larger than the launch limit of %d per side", th, tw, SG_TILE_MAX_SIDE);
+// The gather behind both entry points: `who` names the caller in the messages.
+int tile_gather(const char* who, const void* src, int src_kind, int C, int H, int W, int s, float* dst, int T, int th, int tw,
+                const int* origins_yx, void* stream) {
+    SG_REQUIRE(src && dst && origins_yx, "%s: null pointer", who);
+    SG_REQUIRE(src_kind >= 0 && src_kind <= 2, "%s: src_kind = %d (0 f32 planes, 1 u8 HWC, 2 u8 RGB -> gray)", who, src_kind);
+    SG_REQUIRE(src_kind == 0 ? (C >= 1 && C <= 8) : src_kind == 1 ? (C == 1 || C == 3) : C == 3,
+               "%s: C = %d (f32 planes: 1..8; u8 HWC: 1 or 3; u8 RGB -> gray: 3)", who, C);
+    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "%s: bad extents (scene %dx%d, %d tiles of %dx%d)", who, H, W, T, th, tw);
+    SG_REQUIRE(s >= 1 && (long)H * s < (1L << 30) && (long)W * s < (1L << 30), "%s: s = %d (must be >= 1, and the up-sampled scene below 2^30 per side)", who, s);
+    SG_REQUIRE(th <= SG_TILE_MAX_SIDE && tw <= SG_TILE_MAX_SIDE, "%s: tile %dx%d is larger than the launch limit of %d per side", who, th, tw, SG_TILE_MAX_SIDE);
+    const int OH = H * s, OW = W * s;
     for (int t = 0; t < T; ++t)
-        SG_REQUIRE(origins_yx[2 * t] >= 0 && origins_yx[2 * t] < H && origins_yx[2 * t + 1] >= 0 && origins_yx[2 * t + 1] < W,
-                   "srcgan_tile_gather: origin (%d, %d) of tile %d is outside the %dx%d scene", origins_yx[2 * t], origins_yx[2 * t + 1], t, H, W);
+        SG_REQUIRE(origins_yx[2 * t] >= 0 && origins_yx[2 * t] < OH && origins_yx[2 * t + 1] >= 0 && origins_yx[2 * t + 1] < OW,
+                   "%s: origin (%d, %d) of tile %d is outside the %dx%d scene", who, origins_yx[2 * t], origins_yx[2 * t + 1], t, OH, OW);
     const bool vec = (tw % 4 == 0) && aligned16(dst);
-    const int src_vec_ok = !src_u8 && (W % 4 == 0) && aligned16(src);
+    const int src_vec_ok = src_kind == 0 && (W % 4 == 0) && aligned16(src);
     const int upr = vec ? tw / 4 : tw;
     const unsigned gx = (unsigned)cdivl((long)th * upr, 256);
-    const size_t per_tile = (size_t)C * th * tw;
+    const size_t per_tile = (size_t)(src_kind == 2 ? 1 : C) * th * tw;
+    static constexpr decltype(&tile_gather_k<1, 0, false>) kernels[2][3][2] = {                 // [vec][src_kind][s > 1]
+        {{tile_gather_k<1, 0, false>, tile_gather_k<1, 0, true>}, {tile_gather_k<1, 1, false>, tile_gather_k<1, 1, true>},
+         {tile_gather_k<1, 2, false>, tile_gather_k<1, 2, true>}},
+        {{tile_gather_k<4, 0, false>, tile_gather_k<4, 0, true>}, {tile_gather_k<4, 1, false>, tile_gather_k<4, 1, true>},
+         {tile_gather_k<4, 2, false>, tile_gather_k<4, 2, true>}}};
+    const auto kernel = kernels[vec][src_kind][s > 1];
     for (int t0 = 0; t0 < T; t0 += SG_GATHER_CHUNK) {
         const int n = T - t0 < SG_GATHER_CHUNK ? T - t0 : SG_GATHER_CHUNK;
         GatherArgs a;
         memset(&a, 0, sizeof(a));
         memcpy(a.yx, origins_yx + 2 * t0, sizeof(int) * 2 * n);
-        const dim3 grid(gx, src_u8 ? 1 : C, n);
+        const dim3 grid(gx, src_kind == 0 ? C : 1, n);
         float* d = dst + (size_t)t0 * per_tile;             // per_tile * 4 bytes is a multiple of 16 whenever tw % 4 == 0
-        if (src_u8) {
-            if (vec) hipLaunchKernelGGL((tile_gather_k<4, true>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, 0, a);
-            else hipLaunchKernelGGL((tile_gather_k<1, true>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, 0, a);
-        } else {
-            if (vec) hipLaunchKernelGGL((tile_gather_k<4, false>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, src_vec_ok, a);
-            else hipLaunchKernelGGL((tile_gather_k<1, false>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, th, tw, 0, a);
-        }
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, s, th, tw, src_vec_ok, a);
         SG_LAUNCH_CHECK();
     }
     return 0;
 }
 
-extern "C" int srcgan_tile_scatter(const float* tiles, float* dst, int C, int H, int W, int up, int T, int th, int tw,
-                                   const int* rects, int feather, void* stream) {
-    SG_REQUIRE(tiles && dst && rects, "srcgan_tile_scatter: null pointer");
-    SG_REQUIRE(C >= 1 && C <= 8, "srcgan_tile_scatter: C = %d (1..8 planes)", C);
-    SG_REQUIRE(up >= 1, "srcgan_tile_scatter: up = %d (must be >= 1)", up);
-    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_scatter: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
+// What both write-backs check alike: the extents, and every 10-int rectangle (`allow_ramps`: the feathered f32 write-back only).
+int scatter_check(const char* who, const int* rects, int T, int th, int tw, int H, int W, int up, bool allow_ramps) {
+    SG_REQUIRE(up >= 1, "%s: up = %d (must be >= 1)", who, up);
+    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "%s: bad extents (scene %dx%d, %d tiles of %dx%d)", who, H, W, T, th, tw);
     SG_REQUIRE((long)th * up <= SG_TILE_MAX_SIDE && (long)tw * up <= SG_TILE_MAX_SIDE && (long)H * up < (1L << 30) && (long)W * up < (1L << 30),
-               "srcgan_tile_scatter: HR tile %ldx%ld is larger than the launch limit of %d per side", (long)th * up, (long)tw * up, SG_TILE_MAX_SIDE);
-    feather = feather ? 1 : 0;
-    long max_units = 0;
+               "%s: HR tile %ldx%ld is larger than the launch limit of %d per side", who, (long)th * up, (long)tw * up, SG_TILE_MAX_SIDE);
     for (int t = 0; t < T; ++t) {
         const int* r = rects + 10 * t;
         const int y0 = r[0], x0 = r[1], sy0 = r[2], sy1 = r[3], sx0 = r[4], sx1 = r[5];
-        // the support lies inside the scene AND inside the tile: nothing outside either is ever touched
+        // the rectangle lies inside the scene AND inside the tile: nothing outside either is ever touched
         SG_REQUIRE(sy0 >= 0 && sy0 < sy1 && sy1 <= H && sx0 >= 0 && sx0 < sx1 && sx1 <= W && sy0 >= y0 && sy1 <= y0 + th && sx0 >= x0 && sx1 <= x0 + tw,
-                   "srcgan_tile_scatter: write-back rectangle [%d,%d)x[%d,%d) of tile %d (origin %d,%d, %dx%d) leaves the tile or the %dx%d scene",
-                   sy0, sy1, sx0, sx1, t, y0, x0, th, tw, H, W);
+                   "%s: write-back rectangle [%d,%d)x[%d,%d) of tile %d (origin %d,%d, %dx%d) leaves the tile or the %dx%d scene",
+                   who, sy0, sy1, sx0, sx1, t, y0, x0, th, tw, H, W);
         SG_REQUIRE(r[6] >= 0 && r[7] >= 0 && r[8] >= 0 && r[9] >= 0 && r[6] + r[7] <= sy1 - sy0 && r[8] + r[9] <= sx1 - sx0,
-                   "srcgan_tile_scatter: ramps of tile %d overlap inside its write-back rectangle", t);
-        SG_REQUIRE(feather || (r[6] | r[7] | r[8] | r[9]) == 0, "srcgan_tile_scatter: crop mode takes no ramps (tile %d)", t);
-        const long units = (long)(sy1 - sy0) * up * (sx1 - sx0) * up;
-        if (units > max_units) max_units = units;
+                   "%s: ramps of tile %d overlap inside its write-back rectangle", who, t);
+        SG_REQUIRE(allow_ramps || (r[6] | r[7] | r[8] | r[9]) == 0, "%s: crop mode takes no ramps (tile %d)", who, t);
     }
+    return 0;
+}
+
+// Rectangles [t0, t0 + n) into the kernel arguments; returns the largest units(hh, hw) over them, hh x hw = a rectangle in HR pixels.
+template <typename Units>
+long scatter_chunk(ScatterArgs& a, const int* rects, int t0, int n, int up, Units units) {
+    memset(&a, 0, sizeof(a));
+    long most = 0;
+    for (int k = 0; k < n; ++k) {
+        const int* r = rects + 10 * (t0 + k);
+        a.t[k] = ScatterTile{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9]};
+        const long u = units((long)(r[3] - r[2]) * up, (long)(r[5] - r[4]) * up);
+        if (u > most) most = u;
+    }
+    return most;
+}
+}   // namespace
+
+extern "C" int srcgan_tile_gather(const void* src, int src_u8, int C, int H, int W, float* dst, int T, int th, int tw,
+                                  const int* origins_yx, void* stream) {
+    return tile_gather("srcgan_tile_gather", src, src_u8 ? 1 : 0, C, H, W, 1, dst, T, th, tw, origins_yx, stream);
+}
+
+extern "C" int srcgan_tile_gather_ex(const void* src, int src_kind, int C, int H, int W, int s, float* dst, int T, int th, int tw,
+                                     const int* origins_yx, void* stream) {
+    return tile_gather("srcgan_tile_gather_ex", src, src_kind, C, H, W, s, dst, T, th, tw, origins_yx, stream);
+}
+
+extern "C" int srcgan_tile_scatter(const float* tiles, float* dst, int C, int H, int W, int up, int T, int th, int tw,
+                                   const int* rects, int feather, void* stream) {
+    const char* who = "srcgan_tile_scatter";
+    SG_REQUIRE(tiles && dst && rects, "%s: null pointer", who);
+    SG_REQUIRE(C >= 1 && C <= 8, "%s: C = %d (1..8 planes)", who, C);
+    feather = feather ? 1 : 0;
+    SG_TRY(scatter_check(who, rects, T, th, tw, H, W, up, feather));
     const int SH = H * up, SW = W * up, TH = th * up, TW = tw * up;
     const int vec_ok = (SW % 4 == 0) && (TW % 4 == 0) && aligned16(dst) && aligned16(tiles) && (((size_t)C * TH * TW) % 4 == 0);
     // crop: disjoint rectangles, one launch per chunk.  feather: one tile per launch -- stream order is the order of the additions.
@@ -293,14 +298,7 @@ extern "C" int srcgan_tile_scatter(const float* tiles, float* dst, int C, int H,
     for (int t0 = 0; t0 < T; t0 += step) {
         const int n = T - t0 < step ? T - t0 : step;
         ScatterArgs a;
-        memset(&a, 0, sizeof(a));
-        long units = 0;
-        for (int k = 0; k < n; ++k) {
-            const int* r = rects + 10 * (t0 + k);
-            a.t[k] = ScatterTile{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9]};
-            const long u = (long)(r[3] - r[2]) * up * (r[5] - r[4]) * up;
-            if (u > units) units = u;
-        }
+        const long units = scatter_chunk(a, rects, t0, n, up, [](long hh, long hw) { return hh * hw; });
         const dim3 grid((unsigned)cdivl(units, 256), C, n);              // sized for the scalar path; vector tiles leave threads idle
         hipLaunchKernelGGL(tile_scatter_k, grid, dim3(256), 0, (hipStream_t)stream, tiles + (size_t)t0 * C * TH * TW, dst, C, SH, SW, TH, TW, up,
                            feather, vec_ok, a);
@@ -321,42 +319,6 @@ extern "C" int srcgan_planes_to_u8hwc(const float* src, unsigned char* dst, int 
     return 0;
 }
 
-extern "C" int srcgan_tile_gather_ex(const void* src, int src_kind, int C, int H, int W, int s, float* dst, int T, int th, int tw,
-                                     const int* origins_yx, void* stream) {
-    SG_REQUIRE(src && dst && origins_yx, "srcgan_tile_gather_ex: null pointer");
-    SG_REQUIRE(src_kind >= 0 && src_kind <= 2, "srcgan_tile_gather_ex: src_kind = %d (0 f32 planes, 1 u8 HWC, 2 u8 RGB -> gray)", src_kind);
-    SG_REQUIRE(src_kind == 0 ? (C >= 1 && C <= 8) : src_kind == 1 ? (C == 1 || C == 3) : C == 3,
-               "srcgan_tile_gather_ex: C = %d (f32 planes: 1..8; u8 HWC: 1 or 3; u8 RGB -> gray: 3)", C);
-    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_gather_ex: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
-    SG_REQUIRE(s >= 1 && (long)H * s < (1L << 30) && (long)W * s < (1L << 30), "srcgan_tile_gather_ex: s = %d (must be >= 1, and the up-sampled scene below 2^30 per side)", s);
-    SG_REQUIRE(th <= SG_TILE_MAX_SIDE && tw <= SG_TILE_MAX_SIDE, "srcgan_tile_gather_ex: tile %dx%d is larger than the launch limit of %d per side", th, tw, SG_TILE_MAX_SIDE);
-    const int OH = H * s, OW = W * s;
-    for (int t = 0; t < T; ++t)
-        SG_REQUIRE(origins_yx[2 * t] >= 0 && origins_yx[2 * t] < OH && origins_yx[2 * t + 1] >= 0 && origins_yx[2 * t + 1] < OW,
-                   "srcgan_tile_gather_ex: origin (%d, %d) of tile %d is outside the %dx%d scene", origins_yx[2 * t], origins_yx[2 * t + 1], t, OH, OW);
-    if (s == 1 && src_kind <= 1)                                // a plain copy: the existing kernels, vector loads included
-        return srcgan_tile_gather(src, src_kind, C, H, W, dst, T, th, tw, origins_yx, stream);
-    const bool vec = (tw % 4 == 0) && aligned16(dst);
-    const int upr = vec ? tw / 4 : tw;
-    const unsigned gx = (unsigned)cdivl((long)th * upr, 256);
-    const size_t per_tile = (size_t)(src_kind == 2 ? 1 : C) * th * tw;
-    for (int t0 = 0; t0 < T; t0 += SG_GATHER_CHUNK) {
-        const int n = T - t0 < SG_GATHER_CHUNK ? T - t0 : SG_GATHER_CHUNK;
-        GatherArgs a;
-        memset(&a, 0, sizeof(a));
-        memcpy(a.yx, origins_yx + 2 * t0, sizeof(int) * 2 * n);
-        const dim3 grid(gx, src_kind == 0 ? C : 1, n);
-        float* d = dst + (size_t)t0 * per_tile;             // per_tile * 4 bytes is a multiple of 16 whenever tw % 4 == 0
-#define SG_GATHER_UP(V, K) hipLaunchKernelGGL((tile_gather_up_k<V, K>), grid, dim3(256), 0, (hipStream_t)stream, src, d, C, H, W, s, th, tw, a)
-        if (src_kind == 0) { if (vec) SG_GATHER_UP(4, 0); else SG_GATHER_UP(1, 0); }
-        else if (src_kind == 1) { if (vec) SG_GATHER_UP(4, 1); else SG_GATHER_UP(1, 1); }
-        else { if (vec) SG_GATHER_UP(4, 2); else SG_GATHER_UP(1, 2); }
-#undef SG_GATHER_UP
-        SG_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
 extern "C" int srcgan_tile_scatter_u8(const float* tiles_a, int Ca, const float* tiles_b, int Cb, unsigned char* dst, int H, int W, int up,
                                       int T, int th, int tw, const int* rects, int mode, void* stream) {
     SG_REQUIRE(tiles_a && dst && rects, "srcgan_tile_scatter_u8: null pointer");
@@ -364,32 +326,13 @@ extern "C" int srcgan_tile_scatter_u8(const float* tiles_a, int Ca, const float*
     SG_REQUIRE(mode == 0 ? (Ca == 3 && !tiles_b && Cb == 0) : (Ca == 1 && tiles_b && Cb == 2),
                "srcgan_tile_scatter_u8: mode %d takes %s, got Ca = %d, Cb = %d", mode,
                mode == 0 ? "Ca = 3 and no second tensor (tiles_b null, Cb = 0)" : "Ca = 1 (L) and Cb = 2 (ab)", Ca, Cb);
-    SG_REQUIRE(up >= 1, "srcgan_tile_scatter_u8: up = %d (must be >= 1)", up);
-    SG_REQUIRE(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "srcgan_tile_scatter_u8: bad extents (scene %dx%d, %d tiles of %dx%d)", H, W, T, th, tw);
-    SG_REQUIRE((long)th * up <= SG_TILE_MAX_SIDE && (long)tw * up <= SG_TILE_MAX_SIDE && (long)H * up < (1L << 30) && (long)W * up < (1L << 30),
-               "srcgan_tile_scatter_u8: HR tile %ldx%ld is larger than the launch limit of %d per side", (long)th * up, (long)tw * up, SG_TILE_MAX_SIDE);
-    for (int t = 0; t < T; ++t) {
-        const int* r = rects + 10 * t;
-        const int y0 = r[0], x0 = r[1], sy0 = r[2], sy1 = r[3], sx0 = r[4], sx1 = r[5];
-        // the rectangle lies inside the scene AND inside the tile: nothing outside either is ever touched
-        SG_REQUIRE(sy0 >= 0 && sy0 < sy1 && sy1 <= H && sx0 >= 0 && sx0 < sx1 && sx1 <= W && sy0 >= y0 && sy1 <= y0 + th && sx0 >= x0 && sx1 <= x0 + tw,
-                   "srcgan_tile_scatter_u8: write-back rectangle [%d,%d)x[%d,%d) of tile %d (origin %d,%d, %dx%d) leaves the tile or the %dx%d scene",
-                   sy0, sy1, sx0, sx1, t, y0, x0, th, tw, H, W);
-        SG_REQUIRE((r[6] | r[7] | r[8] | r[9]) == 0, "srcgan_tile_scatter_u8: crop mode takes no ramps (tile %d)", t);
-    }
+    SG_TRY(scatter_check("srcgan_tile_scatter_u8", rects, T, th, tw, H, W, up, false));
     const int SW = W * up, TH = th * up, TW = tw * up;
     const int word_ok = ((uintptr_t)dst & 3) == 0;
     for (int t0 = 0; t0 < T; t0 += SG_SCATTER_CHUNK) {
         const int n = T - t0 < SG_SCATTER_CHUNK ? T - t0 : SG_SCATTER_CHUNK;
         ScatterArgs a;
-        memset(&a, 0, sizeof(a));
-        long units = 0;
-        for (int k = 0; k < n; ++k) {
-            const int* r = rects + 10 * (t0 + k);
-            a.t[k] = ScatterTile{r[0], r[1], r[2], r[3], r[4], r[5], 0, 0, 0, 0};
-            const long u = (long)(r[3] - r[2]) * up * ((long)(r[5] - r[4]) * up / 4 + 2);       // rows x groups per row
-            if (u > units) units = u;
-        }
+        const long units = scatter_chunk(a, rects, t0, n, up, [](long hh, long hw) { return hh * (hw / 4 + 2); });   // rows x groups per row
         const dim3 grid((unsigned)cdivl(units, 256), 1, n);
         const size_t plane = (size_t)TH * TW;
         if (mode == 0)

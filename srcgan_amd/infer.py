@@ -8,7 +8,8 @@ and the generators' own kernels); there is no CPU fallback.
 
 ``cascade_scene`` is the reference's product, the gray LR scene -> super-resolution -> colourisation -> 8-bit RGB cascade of
 testCas.py / testCasConst.py / testCasLAB.py / testCasConstLAB.py, on the same plan: the gray conversion of a colour scene and the
-Const variants' bilinear up-sampling happen inside the gather (``srcgan_tile_gather_ex``), the LAB variants keep the L tile of the
+Const variants' bilinear up-sampling happen inside the gather (``srcgan_tile_gather_ex``, the one gather both drivers call: the
+plain ``srcgan_tile_gather`` is its ``s = 1`` case with the kind taken from the dtype), the LAB variants keep the L tile of the
 first network next to the ab tile of the second, and in crop mode the 8-bit conversion happens inside the write-back
 (``srcgan_tile_scatter_u8``) -- no f32 scene is made on the way.
 
@@ -228,28 +229,44 @@ def _int_array(values):
     return (C.c_int * len(values))(*values)
 
 
+_KINDS = {"f32": 0, "u8": 1, "u8rgb2gray": 2}
+
+
+def _gather(who: str, scene: torch.Tensor, lay, kind: str, s: int, origins, th: int, tw: int) -> torch.Tensor:
+    """The one native gather call; ``lay`` = ``N.scene_layout(scene)``, already checked against ``kind`` by the caller."""
+    _, sc, Cc, H, W = lay
+    if not sc.is_contiguous():
+        raise ValueError(f"{who}: the scene must be contiguous")
+    T = len(origins)
+    out = torch.empty(T, 1 if kind == "u8rgb2gray" else Cc, th, tw, dtype=torch.float32, device=scene.device)
+    flat = _int_array([int(v) for yx in origins for v in yx])
+    N.check(N.lib().srcgan_tile_gather_ex(sc.data_ptr(), _KINDS[kind], Cc, H, W, int(s), out.data_ptr(), T, th, tw, flat,
+                                          N.stream_ptr(scene.device)), who)
+    return out
+
+
 def tile_gather(scene: torch.Tensor, origins, th: int, tw: int) -> torch.Tensor:
     """``srcgan_tile_gather``: scene u8 [H,W,C] / [H,W] or f32 [C,H,W] / [1,C,H,W] on the device, origins [(y0, x0)] -> f32
     [T,C,th,tw]; coordinates are clamped to the scene (edge replication past the right / bottom edge)."""
     N.require_cuda(scene, "tile_gather")
-    if scene.dtype == torch.uint8:
-        s = scene if scene.dim() == 3 else scene[:, :, None]
-        H, W, Cc = s.shape
-        u8 = 1
-    elif scene.dtype == torch.float32:
-        s = scene if scene.dim() == 3 else scene[0]
-        Cc, H, W = s.shape
-        u8 = 0
-    else:
-        raise TypeError(f"tile_gather: the scene must be uint8 (HWC) or float32 (NCHW), got {scene.dtype}")
-    if not s.is_contiguous():
-        raise ValueError("tile_gather: the scene must be contiguous")
-    T = len(origins)
-    out = torch.empty(T, Cc, th, tw, dtype=torch.float32, device=scene.device)
-    flat = _int_array([int(v) for yx in origins for v in yx])
-    N.check(N.lib().srcgan_tile_gather(s.data_ptr(), u8, Cc, H, W, out.data_ptr(), T, th, tw, flat, N.stream_ptr(scene.device)),
-            "srcgan_tile_gather")
-    return out
+    lay = N.scene_layout(scene)
+    if lay is None:
+        raise TypeError(f"tile_gather: the scene must be uint8 (HWC) or float32 (NCHW), got {scene.dtype} {tuple(scene.shape)}")
+    return _gather("tile_gather", scene, lay, lay[0], 1, origins, th, tw)
+
+
+def tile_gather_ex(scene: torch.Tensor, kind: str, s: int, origins, th: int, tw: int) -> torch.Tensor:
+    """``srcgan_tile_gather_ex``: ``tile_gather`` of the scene converted (``kind``: "f32" planes, "u8" HWC v / 255, "u8rgb2gray" u8
+    [H,W,3] -> one gray plane as ``data.arr2gray``) and up-sampled ``s`` times bilinearly (as ``ops.bilinear_up``), evaluated on the
+    fly; origins are on the up-sampled grid.  Bit-identical to ``tile_gather`` of the materialised scene."""
+    N.require_cuda(scene, "tile_gather_ex")
+    if kind not in _KINDS:
+        raise ValueError(f"tile_gather_ex: kind must be one of {sorted(_KINDS)}, got {kind!r}")
+    lay = N.scene_layout(scene)
+    if lay is None or lay[0] != ("f32" if kind == "f32" else "u8"):
+        raise TypeError(f"tile_gather_ex: kind {kind!r} takes " + ("float32 [C,H,W] / [1,C,H,W]" if kind == "f32" else "uint8 [H,W] / [H,W,C]")
+                        + f", got {scene.dtype} {tuple(scene.shape)}")
+    return _gather("tile_gather_ex", scene, lay, kind, s, origins, th, tw)
 
 
 def tile_scatter(tiles: torch.Tensor, dst: torch.Tensor, up: int, rects, feather: bool) -> None:
@@ -284,100 +301,6 @@ def planes_to_u8hwc(planes: torch.Tensor) -> torch.Tensor:
     return out
 
 
-# ------------------------------------------------------------------------------------------------ the driver
-def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: Optional[int] = None, batch: int = 1,
-                  blend: str = "crop", out: str = "f32", multiple: int = 1) -> torch.Tensor:
-    """Run ``nets`` (a module, or a sequence applied in order, e.g. ``[sr, colouriser]``) over a whole scene, tile by tile.
-
-    ``scene``: a device tensor, u8 [H,W,C] (C = 1 or 3; mapped v / 255 like ``data.arr2rgb``) or f32 [1,C,H,W].  ``up``: output pixels
-    per scene pixel of the whole chain.  ``tile``: core size; ``halo``: context read around each core -- ``None`` means EXACT mode: the
-    summed receptive radius of the chain (``receptive_halo``), which needs ``blend="crop"`` and a chain without normalisation layers,
-    and then equals the whole-image forward.  ``blend``: "crop" (each tile writes its core) or "feather" (neighbours are cross-faded
-    over linear ramps, accumulated in f32 in tile order: bitwise reproducible).  ``multiple``: round tile extents up to a multiple (16
-    / up of the first stage for a ResDeconv behind it).  ``out``: "f32" -> [1,C',H*up,W*up], "u8" -> u8 [H*up,W*up,C']
-    (``planes_to_u8hwc``).
-
-    Runs under ``no_grad`` with the modules in ``eval()``.  Extra memory: one tile batch's inference workspace and its input / output
-    tensors, next to the input and output scenes -- independent of the scene size."""
-    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
-    if not nets or not all(isinstance(n, nn.Module) for n in nets):
-        raise TypeError("upscale_scene: nets must be a module or a sequence of modules")
-    if blend not in ("crop", "feather"):
-        raise ValueError(f"upscale_scene: blend must be 'crop' or 'feather', got {blend!r}")
-    if out not in ("f32", "u8"):
-        raise ValueError(f"upscale_scene: out must be 'f32' or 'u8', got {out!r}")
-    if up < 1 or batch < 1:
-        raise ValueError("upscale_scene: up and batch must be >= 1")
-    exact = halo is None
-    if exact:
-        if blend != "crop":
-            raise ValueError("upscale_scene: halo=None is the exact mode and needs blend='crop'")
-        halo = _chain_halo(nets)                        # ValueError for chains with normalisation layers / unknown modules
-    N.require_cuda(scene, "upscale_scene")
-    if scene.dtype == torch.uint8 and scene.dim() in (2, 3):
-        H, W = scene.shape[:2]
-    elif scene.dtype == torch.float32 and scene.dim() == 4 and scene.shape[0] == 1:
-        H, W = scene.shape[2:]
-    else:
-        raise ValueError(f"upscale_scene: the scene must be u8 [H,W,C] or f32 [1,C,H,W], got {scene.dtype} {tuple(scene.shape)}")
-    plan = plan_tiles(H, W, tile, halo, multiple)
-    if exact and plan.overruns:
-        raise ValueError("upscale_scene: with this `multiple` a tile passes the scene's edge and sees replicated pixels where the whole "
-                         "image sees zero padding, so exact mode would not be exact; use multiple=1 or pass halo= explicitly")
-    feather = blend == "feather"
-    scene = scene.contiguous()
-    result = None
-    with torch.no_grad():
-        for net in nets:
-            net.eval()
-        for (th, tw), idx in plan.classes.items():
-            for b0 in range(0, len(idx), batch):
-                ids = idx[b0:b0 + batch]
-                x = tile_gather(scene, [(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids], th, tw)
-                for net in nets:
-                    x = net(x)
-                if x.dim() != 4 or x.shape[0] != len(ids) or tuple(x.shape[2:]) != (th * up, tw * up):
-                    raise ValueError(f"upscale_scene: the chain maps a {th}x{tw} tile to {tuple(x.shape)}, not to {th * up}x{tw * up} (up = {up})")
-                if result is None:
-                    alloc = torch.zeros if feather else torch.empty
-                    result = alloc(1, x.shape[1], H * up, W * up, dtype=torch.float32, device=scene.device)
-                tile_scatter(x.contiguous().float(), result, up, plan.rects(ids, feather), feather)
-    return planes_to_u8hwc(result) if out == "u8" else result
-
-
-# ------------------------------------------------------------------------------------------------ the cascade
-_KINDS = {"f32": 0, "u8": 1, "u8rgb2gray": 2}
-
-
-def tile_gather_ex(scene: torch.Tensor, kind: str, s: int, origins, th: int, tw: int) -> torch.Tensor:
-    """``srcgan_tile_gather_ex``: ``tile_gather`` of the scene converted (``kind``: "f32" planes, "u8" HWC v / 255, "u8rgb2gray" u8
-    [H,W,3] -> one gray plane as ``data.arr2gray``) and up-sampled ``s`` times bilinearly (as ``ops.bilinear_up``), evaluated on the
-    fly; origins are on the up-sampled grid.  Bit-identical to ``tile_gather`` of the materialised scene."""
-    N.require_cuda(scene, "tile_gather_ex")
-    if kind not in _KINDS:
-        raise ValueError(f"tile_gather_ex: kind must be one of {sorted(_KINDS)}, got {kind!r}")
-    if kind == "f32":
-        if scene.dtype != torch.float32 or scene.dim() not in (3, 4) or (scene.dim() == 4 and scene.shape[0] != 1):
-            raise TypeError(f"tile_gather_ex: kind 'f32' takes float32 [C,H,W] / [1,C,H,W], got {scene.dtype} {tuple(scene.shape)}")
-        sc = scene if scene.dim() == 3 else scene[0]
-        Cc, H, W = sc.shape
-        planes = Cc
-    else:
-        if scene.dtype != torch.uint8 or scene.dim() not in (2, 3):
-            raise TypeError(f"tile_gather_ex: kind {kind!r} takes uint8 [H,W] / [H,W,C], got {scene.dtype} {tuple(scene.shape)}")
-        sc = scene if scene.dim() == 3 else scene[:, :, None]
-        H, W, Cc = sc.shape
-        planes = 1 if kind == "u8rgb2gray" else Cc
-    if not sc.is_contiguous():
-        raise ValueError("tile_gather_ex: the scene must be contiguous")
-    T = len(origins)
-    out = torch.empty(T, planes, th, tw, dtype=torch.float32, device=scene.device)
-    flat = _int_array([int(v) for yx in origins for v in yx])
-    N.check(N.lib().srcgan_tile_gather_ex(sc.data_ptr(), _KINDS[kind], Cc, H, W, int(s), out.data_ptr(), T, th, tw, flat,
-                                          N.stream_ptr(scene.device)), "srcgan_tile_gather_ex")
-    return out
-
-
 def tile_scatter_u8(tiles_a: torch.Tensor, tiles_b: Optional[torch.Tensor], dst: torch.Tensor, up: int, rects) -> None:
     """``srcgan_tile_scatter_u8``: crop-mode write-back into dst u8 [H*up,W*up,3] with the conversion fused into the store.
     ``tiles_b is None``: ``tiles_a`` f32 [T,3,th*up,tw*up] RGB planes, bytes as ``planes_to_u8hwc``; else ``tiles_a`` [T,1,..] is L and
@@ -403,6 +326,92 @@ def tile_scatter_u8(tiles_a: torch.Tensor, tiles_b: Optional[torch.Tensor], dst:
             "srcgan_tile_scatter_u8")
 
 
+# ------------------------------------------------------------------------------------------------ the drivers
+def _check_options(who: str, up: int, batch: int, blend: str, out: str, halo: Optional[int]) -> None:
+    if blend not in ("crop", "feather"):
+        raise ValueError(f"{who}: blend must be 'crop' or 'feather', got {blend!r}")
+    if out not in ("f32", "u8"):
+        raise ValueError(f"{who}: out must be 'f32' or 'u8', got {out!r}")
+    if up < 1 or batch < 1:
+        raise ValueError(f"{who}: up and batch must be >= 1")
+    if halo is None and blend != "crop":
+        raise ValueError(f"{who}: halo=None is the exact mode and needs blend='crop'")
+
+
+def _scene_plan(who: str, nets, H: int, W: int, tile: int, halo: Optional[int], multiple: int) -> TilePlan:
+    """The plan of an H x W grid.  ``halo=None`` is the exact mode: the summed receptive radius of ``nets`` (ValueError for chains with
+    normalisation layers / unknown modules), refused where a tile would pass the edge."""
+    exact = halo is None
+    plan = plan_tiles(H, W, tile, _chain_halo(nets) if exact else halo, multiple)
+    if exact and plan.overruns:
+        raise ValueError(f"{who}: with this `multiple` a tile passes the scene's edge and sees replicated pixels where the whole "
+                         "image sees zero padding, so exact mode would not be exact; use multiple=1 or pass halo= explicitly")
+    return plan
+
+
+def _run_tiles(nets, plan: TilePlan, batch: int, feather: bool, gather, forward, sink, hr, u8: bool = False) -> torch.Tensor:
+    """The tile loop of both drivers, class by class in batches of ``batch``: ``gather(origins, th, tw)`` -> the input batch;
+    ``forward(x, th, tw)`` -> the tensors to write back (shape-checked by the caller); ``sink(tensors, result, rects)`` writes them.
+    The result is made when the first batch is there: f32 [1, planes of all written tensors, *hr], or u8 [*hr, 3] with ``u8``; zeroed
+    for a feathered blend, which adds into it.  Under ``no_grad`` with ``nets`` in ``eval()``."""
+    result = None
+    with torch.no_grad():
+        for net in nets:
+            net.eval()
+        for (th, tw), idx in plan.classes.items():
+            for b0 in range(0, len(idx), batch):
+                ids = idx[b0:b0 + batch]
+                x = gather([(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids], th, tw)
+                tensors = [t.contiguous().float() for t in forward(x, th, tw)]
+                if result is None:
+                    shape = (*hr, 3) if u8 else (1, sum(t.shape[1] for t in tensors), *hr)
+                    result = (torch.zeros if feather else torch.empty)(shape, dtype=torch.uint8 if u8 else torch.float32, device=x.device)
+                sink(tensors, result, plan.rects(ids, feather))
+                del x, tensors                          # nothing of this batch is held while the next one runs
+    return result
+
+
+def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: Optional[int] = None, batch: int = 1,
+                  blend: str = "crop", out: str = "f32", multiple: int = 1) -> torch.Tensor:
+    """Run ``nets`` (a module, or a sequence applied in order, e.g. ``[sr, colouriser]``) over a whole scene, tile by tile.
+
+    ``scene``: a device tensor, u8 [H,W,C] (C = 1 or 3; mapped v / 255 like ``data.arr2rgb``) or f32 [1,C,H,W].  ``up``: output pixels
+    per scene pixel of the whole chain.  ``tile``: core size; ``halo``: context read around each core -- ``None`` means EXACT mode: the
+    summed receptive radius of the chain (``receptive_halo``), which needs ``blend="crop"`` and a chain without normalisation layers,
+    and then equals the whole-image forward.  ``blend``: "crop" (each tile writes its core) or "feather" (neighbours are cross-faded
+    over linear ramps, accumulated in f32 in tile order: bitwise reproducible).  ``multiple``: round tile extents up to a multiple (16
+    / up of the first stage for a ResDeconv behind it).  ``out``: "f32" -> [1,C',H*up,W*up], "u8" -> u8 [H*up,W*up,C']
+    (``planes_to_u8hwc``).
+
+    Runs under ``no_grad`` with the modules in ``eval()``.  Extra memory: one tile batch's inference workspace and its input / output
+    tensors, next to the input and output scenes -- independent of the scene size."""
+    nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
+    if not nets or not all(isinstance(n, nn.Module) for n in nets):
+        raise TypeError("upscale_scene: nets must be a module or a sequence of modules")
+    _check_options("upscale_scene", up, batch, blend, out, halo)
+    lay = N.scene_layout(scene)
+    if lay is None or (lay[0] == "f32" and scene.dim() != 4):
+        raise ValueError(f"upscale_scene: the scene must be u8 [H,W,C] or f32 [1,C,H,W], got {scene.dtype} {tuple(scene.shape)}")
+    kind, _, _, H, W = lay
+    plan = _scene_plan("upscale_scene", nets, H, W, tile, halo, multiple)
+    N.require_cuda(scene, "upscale_scene")
+    feather = blend == "feather"
+    scene = scene.contiguous()
+
+    def forward(x, th, tw):
+        n = x.shape[0]
+        for net in nets:
+            x = net(x)
+        if x.dim() != 4 or x.shape[0] != n or tuple(x.shape[2:]) != (th * up, tw * up):
+            raise ValueError(f"upscale_scene: the chain maps a {th}x{tw} tile to {tuple(x.shape)}, not to {th * up}x{tw * up} (up = {up})")
+        return [x]
+
+    result = _run_tiles(nets, plan, batch, feather, lambda org, th, tw: tile_gather_ex(scene, kind, 1, org, th, tw), forward,
+                        lambda ts, res, rects: tile_scatter(ts[0], res, up, rects, feather), (H * up, W * up))
+    return planes_to_u8hwc(result) if out == "u8" else result
+
+
+# ------------------------------------------------------------------------------------------------ the cascade
 def _cascade_plan(netG_A2C, netG_C2B, H: int, W: int, *, up: int, const: bool, tile: int, halo: Optional[int], multiple: int) -> TilePlan:
     """The plan ``cascade_scene`` runs (pure Python).  ``const``: the first network is size-preserving and sees the scene up-sampled
     by ``up`` inside the gather, so the plan -- tiles, halo, ``multiple`` -- is made on the H*up x W*up grid and the chain's own scale
@@ -411,14 +420,8 @@ def _cascade_plan(netG_A2C, netG_C2B, H: int, W: int, *, up: int, const: bool, t
     if const and _scale(netG_A2C) != 1:
         raise ValueError(f"cascade_scene: const=True needs a size-preserving netG_A2C (SRCNN, SRDN), got {type(netG_A2C).__name__}"
                          + ("" if _scale(netG_A2C) is None else f" with scale {_scale(netG_A2C)}"))
-    exact = halo is None
-    if exact:
-        halo = _chain_halo([netG_A2C, netG_C2B])        # ValueError for chains with normalisation layers / unknown modules
-    plan = plan_tiles(H * up, W * up, tile, halo, multiple) if const else plan_tiles(H, W, tile, halo, multiple)
-    if exact and plan.overruns:
-        raise ValueError("cascade_scene: with this `multiple` a tile passes the scene's edge and sees replicated pixels where the whole "
-                         "image sees zero padding, so exact mode would not be exact; use multiple=1 or pass halo= explicitly")
-    return plan
+    g = up if const else 1
+    return _scene_plan("cascade_scene", [netG_A2C, netG_C2B], H * g, W * g, tile, halo, multiple)
 
 
 def cascade_scene(netG_A2C, netG_C2B, scene: torch.Tensor, *, up: int, space: str = "rgb", const: bool = False, tile: int = 512,
@@ -447,62 +450,47 @@ def cascade_scene(netG_A2C, netG_C2B, scene: torch.Tensor, *, up: int, space: st
         raise TypeError("cascade_scene: netG_A2C and netG_C2B must be modules")
     if space not in ("rgb", "lab"):
         raise ValueError(f"cascade_scene: space must be 'rgb' or 'lab', got {space!r}")
-    if blend not in ("crop", "feather"):
-        raise ValueError(f"cascade_scene: blend must be 'crop' or 'feather', got {blend!r}")
-    if out not in ("f32", "u8"):
-        raise ValueError(f"cascade_scene: out must be 'f32' or 'u8', got {out!r}")
-    if up < 1 or batch < 1:
-        raise ValueError("cascade_scene: up and batch must be >= 1")
-    if halo is None and blend != "crop":
-        raise ValueError("cascade_scene: halo=None is the exact mode and needs blend='crop'")
-    if scene.dtype == torch.uint8 and (scene.dim() == 2 or (scene.dim() == 3 and scene.shape[2] in (1, 3))):
-        H, W = scene.shape[:2]
-        kind = "u8rgb2gray" if scene.dim() == 3 and scene.shape[2] == 3 else "u8"
-    elif scene.dtype == torch.float32 and scene.dim() == 4 and scene.shape[0] == 1 and scene.shape[1] == 1:
-        H, W = scene.shape[2:]
-        kind = "f32"
-    else:
+    _check_options("cascade_scene", up, batch, blend, out, halo)
+    lay = N.scene_layout(scene)
+    if lay is None or not (lay[2] in (1, 3) if lay[0] == "u8" else scene.dim() == 4 and lay[2] == 1):
         raise ValueError(f"cascade_scene: the scene must be u8 [H,W], [H,W,1], [H,W,3] or f32 [1,1,H,W], got {scene.dtype} {tuple(scene.shape)}")
+    kind, _, Cc, H, W = lay
+    if Cc == 3:
+        kind = "u8rgb2gray"
     plan = _cascade_plan(netG_A2C, netG_C2B, H, W, up=up, const=const, tile=tile, halo=halo, multiple=multiple)
     N.require_cuda(scene, "cascade_scene")
     s, cu = (up, 1) if const else (1, up)               # up-sampling inside the gather; scale of the chain on the plan's grid
     lab, feather, fused = space == "lab", blend == "feather", blend == "crop" and out == "u8"
     want = 2 if lab else 3
     scene = scene.contiguous()
-    result = None
-    with torch.no_grad():
-        netG_A2C.eval()
-        netG_C2B.eval()
-        for (th, tw), idx in plan.classes.items():
-            for b0 in range(0, len(idx), batch):
-                ids = idx[b0:b0 + batch]
-                x = tile_gather_ex(scene, kind, s, [(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids], th, tw)
-                l = netG_A2C(x)
-                if l.dim() != 4 or l.shape[0] != len(ids) or tuple(l.shape[2:]) != (th * cu, tw * cu):
-                    raise ValueError(f"cascade_scene: netG_A2C maps a {th}x{tw} tile to {tuple(l.shape)}, not to {th * cu}x{tw * cu} "
-                                     f"(up = {up}, const = {const})")
-                if lab and l.shape[1] != 1:
-                    raise ValueError(f"cascade_scene: space='lab' needs a 1-plane netG_A2C (L), got {l.shape[1]} planes")
-                c = netG_C2B(l)
-                if c.dim() != 4 or c.shape[0] != len(ids) or tuple(c.shape[2:]) != tuple(l.shape[2:]):
-                    raise ValueError(f"cascade_scene: netG_C2B maps {tuple(l.shape)} to {tuple(c.shape)}; a size-preserving colouriser is expected")
-                if c.shape[1] != want:
-                    raise ValueError(f"cascade_scene: space={space!r} needs a colouriser with {want} output planes, got {c.shape[1]}")
-                l, c = l.contiguous().float(), c.contiguous().float()
-                rects = plan.rects(ids, feather)
-                if fused:
-                    if result is None:
-                        result = torch.empty(H * up, W * up, 3, dtype=torch.uint8, device=scene.device)
-                    tile_scatter_u8(l if lab else c, c if lab else None, result, cu, rects)
-                    continue
-                if result is None:
-                    alloc = torch.zeros if feather else torch.empty
-                    result = alloc(1, 3, H * up, W * up, dtype=torch.float32, device=scene.device)
-                if lab:                                 # L -> plane 0, ab -> planes 1-2 of the same buffer, through offset pointers
-                    tile_scatter(l, result[0, 0:1], cu, rects, feather)
-                    tile_scatter(c, result[0, 1:3], cu, rects, feather)
-                else:
-                    tile_scatter(c, result, cu, rects, feather)
+
+    def forward(x, th, tw):
+        l = netG_A2C(x)
+        if l.dim() != 4 or l.shape[0] != x.shape[0] or tuple(l.shape[2:]) != (th * cu, tw * cu):
+            raise ValueError(f"cascade_scene: netG_A2C maps a {th}x{tw} tile to {tuple(l.shape)}, not to {th * cu}x{tw * cu} "
+                             f"(up = {up}, const = {const})")
+        if lab and l.shape[1] != 1:
+            raise ValueError(f"cascade_scene: space='lab' needs a 1-plane netG_A2C (L), got {l.shape[1]} planes")
+        c = netG_C2B(l)
+        if c.dim() != 4 or c.shape[0] != x.shape[0] or tuple(c.shape[2:]) != tuple(l.shape[2:]):
+            raise ValueError(f"cascade_scene: netG_C2B maps {tuple(l.shape)} to {tuple(c.shape)}; a size-preserving colouriser is expected")
+        if c.shape[1] != want:
+            raise ValueError(f"cascade_scene: space={space!r} needs a colouriser with {want} output planes, got {c.shape[1]}")
+        return [l, c] if lab else [c]
+
+    if fused:
+        def sink(ts, res, rects):
+            tile_scatter_u8(ts[0], ts[1] if lab else None, res, cu, rects)
+    elif lab:                                           # L -> plane 0, ab -> planes 1-2 of the same buffer, through offset pointers
+        def sink(ts, res, rects):
+            tile_scatter(ts[0], res[0, 0:1], cu, rects, feather)
+            tile_scatter(ts[1], res[0, 1:3], cu, rects, feather)
+    else:
+        def sink(ts, res, rects):
+            tile_scatter(ts[0], res, cu, rects, feather)
+
+    result = _run_tiles([netG_A2C, netG_C2B], plan, batch, feather, lambda org, th, tw: tile_gather_ex(scene, kind, s, org, th, tw), forward,
+                        sink, (H * up, W * up), u8=fused)
     if fused or out == "f32":
         return result
     if lab:

@@ -114,15 +114,13 @@ def evaluate_cascade(netG_A2C: torch.nn.Module, netG_C2B: torch.nn.Module, batch
 
 
 def _scene_arg(x, who, name):
-    """-> (kind, H, W, C) of one score_scene argument: u8 [H,W] / [H,W,C] is kind 1, f32 [1,C,H,W] is kind 0."""
-    if not isinstance(x, torch.Tensor):
-        raise ValueError(f"{who}: {name} must be a tensor, got {type(x).__name__}")
-    if x.dtype == torch.uint8 and x.dim() in (2, 3):
-        H, W = int(x.shape[0]), int(x.shape[1])
-        return 1, H, W, (int(x.shape[2]) if x.dim() == 3 else 1)
-    if x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] == 1:
-        return 0, int(x.shape[2]), int(x.shape[3]), int(x.shape[1])
-    raise ValueError(f"{who}: {name} must be u8 [H,W] / [H,W,C] or f32 [1,C,H,W], got {x.dtype} {tuple(x.shape)}")
+    """-> (native kind, H, W, C) of one score_scene argument: u8 [H,W] / [H,W,C] is kind 1, f32 [1,C,H,W] is kind 0."""
+    lay = N.scene_layout(x)
+    if lay is None or (lay[0] == "f32" and x.dim() != 4):
+        got = f"{x.dtype} {tuple(x.shape)}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise ValueError(f"{who}: {name} must be a u8 [H,W] / [H,W,C] or f32 [1,C,H,W] tensor, got {got}")
+    kind, _, Cc, H, W = lay
+    return int(kind == "u8"), H, W, Cc
 
 
 def score_scene(pred, target, *, full=False) -> Dict[str, torch.Tensor]:

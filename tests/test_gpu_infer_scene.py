@@ -84,6 +84,23 @@ def test_gather_u8_mapping_is_arr2rgb(infer):
     assert torch.equal(infer.tile_gather(off, [(16, 16), (48, 44)], 24, 24), infer.tile_gather(off.clone(), [(16, 16), (48, 44)], 24, 24))
 
 
+def test_gather_f32_vector_load_path(infer):
+    """The f32, s = 1 gather takes a unit as one 16-byte load where the scene is aligned (base and pitch), x0 % 4 == 0 and the unit
+    lies inside the row: x0 = 0, 4 take it, x0 = 3 does not, x0 = 20 takes it for the first unit of a row and replicates the edge in
+    the second (20 + 4 + 3 >= W = 24); the same scene one float further on never takes it.  All equal torch slicing, bit for bit,
+    through ``tile_gather`` and through ``tile_gather_ex``."""
+    C, H, W, T = 3, 20, 24, 8
+    base = torch.rand(C * H * W + 1, generator=torch.Generator().manual_seed(7)) * 2 - 0.5
+    origins = [(0, 0), (5, 4), (13, 3), (12, 20)]                                    # y0 = 13: the last row is replicated too
+    for off in (0, 1):
+        planes = base[off:off + C * H * W].view(C, H, W)
+        scene = base.cuda()[off:off + C * H * W].view(C, H, W)
+        assert (scene.data_ptr() % 16 == 0) == (off == 0) and scene.is_contiguous()
+        ref = torch.stack([_ref_tile(planes, type("T", (), dict(y0=y0, x0=x0, th=T, tw=T))) for y0, x0 in origins])
+        assert torch.equal(infer.tile_gather(scene, origins, T, T).cpu(), ref), off
+        assert torch.equal(infer.tile_gather_ex(scene, "f32", 1, origins, T, T).cpu(), ref), off
+
+
 def _hr_tiles(plan, idx, C, up, seed, ones=False):
     th, tw = plan.tiles[idx[0]].th, plan.tiles[idx[0]].tw
     if ones:

@@ -181,3 +181,44 @@ def test_native_entry_points_reject_bad_arguments():
     refused(lib.srcgan_planes_to_u8hwc(p, None, 3, 64, None), "null")
     refused(lib.srcgan_planes_to_u8hwc(p, p, 0, 64, None), "C = 0")
     refused(lib.srcgan_planes_to_u8hwc(p, p, 9, 64, None), "C = 9")
+
+
+def test_native_entry_points_share_their_checks():
+    """One bad argument list is refused by both write-back symbols, and one by both gather symbols, in the same words after each
+    symbol's own name.  Nothing launches: the dummy pointer is never dereferenced."""
+    from srcgan_amd import _native as N, build
+    build.build(verbose=False)
+    lib = N.lib()
+    p = 4096
+
+    def message(rc):
+        assert rc != 0
+        name, _, text = lib.srcgan_last_error().decode().partition(": ")
+        return name, text
+
+    # 8x8 scene, up = 2, one 4x4 tile at (2, 2); a rectangle is (y0, x0, sy0, sy1, sx0, sx1, ny_lo, ny_hi, nx_lo, nx_hi)
+    for rect, word in [((2, 2, 2, 6, 2, 7, 0, 0, 0, 0), "leaves"),                   # one column past the tile
+                       ((2, 2, 1, 6, 2, 6, 0, 0, 0, 0), "leaves"),                   # one row above the tile
+                       ((6, 6, 6, 9, 6, 8, 0, 0, 0, 0), "leaves"),                   # inside the tile, one row below the scene
+                       ((2, 2, 2, 6, 2, 6, 3, 2, 0, 0), "overlap"),                  # 3 + 2 ramp rows in a rectangle of 4
+                       ((2, 2, 2, 6, 2, 6, 0, 0, -1, 0), "overlap"),
+                       ((2, 2, 2, 6, 2, 6, 2, 0, 0, 0), "no ramps")]:                # crop mode
+        r = (C.c_int * 10)(*rect)
+        f32 = message(lib.srcgan_tile_scatter(p, p, 3, 8, 8, 2, 1, 4, 4, r, 0, None))
+        u8 = message(lib.srcgan_tile_scatter_u8(p, 3, None, 0, p, 8, 8, 2, 1, 4, 4, r, 0, None))
+        assert (f32[0], u8[0]) == ("srcgan_tile_scatter", "srcgan_tile_scatter_u8") and f32[1] == u8[1] and word in f32[1], (rect, f32, u8)
+    for args, word in [(dict(up=0), "up = 0"), (dict(H=0), "bad extents"), (dict(th=1 << 14), "launch limit")]:
+        H, up, th = ({"H": 8, "up": 2, "th": 4, **args}[k] for k in ("H", "up", "th"))
+        r = (C.c_int * 10)(0, 0, 0, 4, 0, 4, 0, 0, 0, 0)
+        f32 = message(lib.srcgan_tile_scatter(p, p, 3, H, 8, up, 1, th, 4, r, 0, None))
+        u8 = message(lib.srcgan_tile_scatter_u8(p, 3, None, 0, p, H, 8, up, 1, th, 4, r, 0, None))
+        assert f32[1] == u8[1] and word in f32[1], (args, f32, u8)
+
+    # the gather, s = 1: (kind = src_u8, C, H, th, origins)
+    org = (C.c_int * 2)(0, 0)
+    for kind, Cc, H, th, o, word in [(0, 3, 8, 4, None, "null"), (0, 9, 8, 4, org, "C = 9"), (1, 2, 8, 4, org, "C = 2"), (0, 3, 0, 4, org, "bad extents"),
+                                     (1, 3, 8, 1 << 20, org, "launch limit"), (0, 3, 8, 4, (C.c_int * 2)(0, 8), "outside"),
+                                     (1, 1, 8, 4, (C.c_int * 2)(-1, 0), "outside")]:
+        plain = message(lib.srcgan_tile_gather(p, kind, Cc, H, 8, p, 1, th, 4, o, None))
+        ex = message(lib.srcgan_tile_gather_ex(p, kind, Cc, H, 8, 1, p, 1, th, 4, o, None))
+        assert (plain[0], ex[0]) == ("srcgan_tile_gather", "srcgan_tile_gather_ex") and plain[1] == ex[1] and word in plain[1], (word, plain, ex)
