@@ -134,7 +134,7 @@ int srcgan_conv_igemm(const srcgan_conv_desc* d, void* stream);
  * ------------------------------------------------------------------------- */
 typedef struct srcgan_wgrad_desc {
     const void* dy; const void* x; float* slab; float* grad;
-    float* bias_grad;                       /* optional: alpha * sum_p dy[p,co], fused (3x3 kernels only) */
+    float* bias_grad;                       /* optional: bias_grad[co] (=|+=, as `accumulate` says) alpha * sum_p dy[p,co], fused (3x3 kernels only) */
     int dtype;
     int kh, kw, stride;
     int B, H, W, Cin, x_cs, x_coff;         /* x tensor; Cin = true input channels */
