@@ -46,7 +46,7 @@ def main():
         def infer(fold):
             def run():
                 with torch.no_grad():
-                    return M._resdeconv_infer(x3, *args, params, fold_tail=fold)
+                    return M._oplist_forward(x3, M._RESDECONV, args, params, extra=(fold,))
             return run
 
         modes = [("grad", lambda: net(x)), ("fold_tail=0", infer(0)), ("fold_tail=1", infer(1))]

@@ -141,14 +141,12 @@ class GradSync:
 
     # ---- in-backward form -------------------------------------------------------------------------------------------
     def attach(self) -> "GradSync":
-        """Average gradients inside every native backward of this package's networks (see the module docstring).  The hook table
-        is process-wide: a second GradSync cannot be attached while another one is."""
+        """Average gradients inside every native backward of this package's networks (see the module docstring).  The hook slot
+        (``model._phase_hook``) is process-wide: a second GradSync cannot be attached while another one is."""
         from . import model
-        other = [h for h in model._phase_hooks.values() if h is not self]
-        if other:
-            raise RuntimeError("srcgan_amd.dist: another GradSync is attached; detach() it first (the backward hooks are process-wide)")
-        for kind in ("rddb", "nlayerd", "resdeconv", "srnet"):
-            model._phase_hooks[kind] = self
+        if model._phase_hook is not None and model._phase_hook is not self:
+            raise RuntimeError("srcgan_amd.dist: another GradSync is attached; detach() it first (the backward hook is process-wide)")
+        model._phase_hook = self
         self.attached = True
         return self
 
@@ -165,9 +163,8 @@ class GradSync:
 
     def detach(self) -> None:
         from . import model
-        for kind, h in list(model._phase_hooks.items()):
-            if h is self:
-                del model._phase_hooks[kind]
+        if model._phase_hook is self:
+            model._phase_hook = None
         self.attached = False
 
     def cuts(self, cfg, nrr: int, params=()) -> List[int]:

@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 import functools
 import math
-from typing import List, Optional
+from typing import Callable, NamedTuple
 
 import torch
 import torch.nn as nn
@@ -149,16 +149,62 @@ class _GradArena:
             self.offsets.append(off)          # offsets[i] .. offsets[i + 1] = parameter i
 
 
+# Data-parallel hook (srcgan_amd.dist.GradSync.attach sets it, detach clears it): an object with ``cuts(cfg, nrr, params) -> [rrdb
+# indices]`` (phase boundaries of the generator's backward) and ``phase_done(arena, params, first, end, last)``, called right after
+# the native call that finalised the gradients of the parameters [first, end) (``srcgan_rddbnet_phase_params``; ``last``: the
+# backward is complete) was queued: the hook launches their all-reduce on its side stream while the next phase computes.  One slot
+# for every native network: each Function reads it at FORWARD time and its backward uses what it read.
+_phase_hook = None
+
+
+# ---- operand handling every native forward / backward shares
+def _check_input(x, name, in_ch, expects):
+    """The network input must be on the GPU (RuntimeError) and [B,in_ch,H,W] (ValueError, ``expects``: the family's wording)."""
+    N.require_cuda(x, f"{name}.forward")
+    if x.dim() != 4 or x.shape[1] != in_ch:
+        raise ValueError(f"{expects}, got {tuple(x.shape)}")
+
+
+def _input(x, name, in_ch, expects):
+    """-> the checked input as the native code reads it: off the graph, contiguous, f32."""
+    _check_input(x, name, in_ch, expects)
+    return x.detach().contiguous().float()
+
+
+def _params(params, name):
+    """-> the parameters as the native code reads them (``const float*``): on the GPU, off the graph, contiguous, f32."""
+    for p in params:
+        N.require_cuda(p, f"{name} parameter")
+    plist = [p.detach().contiguous() for p in params]
+    if any(p.dtype != torch.float32 for p in plist):
+        raise TypeError(f"{name} parameters must be float32 (canonical weights stay f32)")
+    return plist
+
+
+def _backward_operands(ctx, dy, first, scratch_bytes, name):
+    """What a native backward needs besides the forward's workspace -> (dy, params, arena, grads, scratch, dx).  ``first``: index
+    of the first parameter in ``ctx.needs_input_grad``; ``scratch_bytes``: the family's ``*_bwd_scratch_bytes``.  For all three
+    Functions: no arena (and ``None`` gradients: the native call gets the same null pointers as from an arena without elements,
+    and a hook's ``phase_done`` ignores either) when no parameter needs a gradient; ``dx`` is None when the input needs none."""
+    if ctx.ws is None:
+        raise RuntimeError(f"{name} backward called twice (activations were released)")
+    cfg, params = ctx.cfg, list(ctx.saved_tensors)
+    dy = dy.contiguous().float()
+    needs = [ctx.needs_input_grad[first + i] for i in range(len(params))]
+    arena = _GradArena(params, needs) if any(needs) else None
+    grads = arena.views if arena is not None else [None] * len(params)
+    scratch = N.workspace(scratch_bytes(C.byref(cfg)), dy.device)
+    dx = torch.empty(cfg.B, cfg.in_ch, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if ctx.needs_input_grad[0] else None
+    return dy, params, arena, grads, scratch, dx
+
+
 def _rddb_prepare(x, cfg_items, params):
     """Checks and allocations both generator forwards (autograd Function, inference) share.
     -> (x, None, None, pstate, layout, empty output) for an empty batch, else (x, cfg, plist, pstate, layout, y)."""
-    N.require_cuda(x, "RDDBNet.forward")
     in_ch, out_ch, up, nf, nb, gc, dtype, down = cfg_items[:8]
     legacy = cfg_items[8] if len(cfg_items) > 8 else 0
     pstate = cfg_items[9] if len(cfg_items) > 9 else None
-    if x.dim() != 4 or x.shape[1] != in_ch:
-        raise ValueError(f"RDDBNet expects [B,{in_ch},H,W], got {tuple(x.shape)}")
-    x = x.detach().contiguous().float()
+    x = _input(x, "RDDBNet", in_ch, f"RDDBNet expects [B,{in_ch},H,W]")
     B, _, H, W = x.shape
     f = (up if down == 0 else 1)
     HO, WO = (H * f, W * f) if down <= 1 else (H // down, W // down)
@@ -166,11 +212,7 @@ def _rddb_prepare(x, cfg_items, params):
     if B == 0:          # an empty batch yields an empty output and zero gradients, as aten::convolution does
         return x, None, None, pstate, layout, x.new_zeros((0, out_ch, HO, WO))
     cfg = N.RddbCfg(in_ch, out_ch, up, nf, nb, gc, B, H, W, dtype, down, legacy)
-    for p in params:
-        N.require_cuda(p, "RDDBNet parameter")
-    plist = [p.detach().contiguous() for p in params]
-    if any(p.dtype != torch.float32 for p in plist):
-        raise TypeError("RDDBNet parameters must be float32 (canonical weights stay f32)")
+    plist = _params(params, "RDDBNet")
     y = torch.empty(B, out_ch, HO, WO, dtype=torch.float32, device=x.device)
     return x, cfg, plist, pstate, layout, y
 
@@ -195,24 +237,17 @@ class _RddbFn(torch.autograd.Function):
         ctx.cfg, ctx.ws, ctx.n = cfg, ws, len(plist)
         ctx.pstate, ctx.layout = pstate, layout
         ctx.save_for_backward(*plist)
-        ctx.phase_hook = _phase_hooks.get("rddb")
+        ctx.phase_hook = _phase_hook
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = N.lib()
-        params = list(ctx.saved_tensors)
         if ctx.empty:
-            return (None, None, *[torch.zeros_like(p) if ctx.needs_input_grad[2 + i] else None for i, p in enumerate(params)])
+            return (None, None, *[torch.zeros_like(p) if ctx.needs_input_grad[2 + i] else None for i, p in enumerate(ctx.saved_tensors)])
         cfg = ctx.cfg
-        if ctx.ws is None:
-            raise RuntimeError("RDDBNet backward called twice (activations were released)")
-        dy = dy.contiguous().float()
-        need_dx = ctx.needs_input_grad[0]
-        arena = _GradArena(params, [ctx.needs_input_grad[2 + i] for i in range(len(params))])
-        grads = arena.views
-        scratch = N.workspace(lib.srcgan_rddbnet_bwd_scratch_bytes(C.byref(cfg)), dy.device)
-        dx = torch.empty(cfg.B, cfg.in_ch, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if need_dx else None
+        dy, params, arena, grads, scratch, dx = _backward_operands(ctx, dy, 2, lib.srcgan_rddbnet_bwd_scratch_bytes, "RDDBNet")
+        need_dx = dx is not None
         pstate = ctx.pstate
         opt = pstate.opts(lib.srcgan_rddbnet_wpack_bytes, cfg, params, ctx.layout, True, dy.device) if pstate is not None else N.NetOpts(None, 0, 0, 0, None)
         gptr, pptr = N.ptr_array(grads), N.ptr_array(params)
@@ -264,14 +299,15 @@ def _rddb_forward(x, cfg_items, params):
     return _rddb_infer(x, cfg_items, params)
 
 
-# Data-parallel hooks (srcgan_amd.dist.GradSync.attach): an object with ``cuts(nrr) -> [rrdb indices]`` (phase boundaries of the
-# generator's backward) and ``phase_done(arena, params, first, end, last)``, called right after the native call that finalised the
-# gradients of the parameters [first, end) (``srcgan_rddbnet_phase_params``; ``last``: the backward is complete) was queued: the hook
-# launches their all-reduce on its side stream while the next phase computes.
-_phase_hooks = {}
+class _NativeRepr:
+    """Method-only mixin of the native networks: what ``repr()`` says about them."""
+    _repr_mode = False          # True in the classes whose ``mode`` (up-sampling factor) belongs in the repr
+
+    def extra_repr(self):
+        return "native gfx950, " + (f"mode={self.mode}, " if self._repr_mode else "") + f"compute_dtype={self.compute_dtype}"
 
 
-class RDDBNet(nn.Module):
+class RDDBNet(_NativeRepr, nn.Module):
     """RRDB generator, drop-in for reference ``model.RDDBNet`` (rddb.py:85-114).
 
     ``forward(x[B,in_ch,H,W] f32 NCHW) -> [B,ou_ch,H*up,W*up]``.  ``dtype``: 'fp32' (default; exact
@@ -305,9 +341,6 @@ class RDDBNet(nn.Module):
         cfg = (*self._cfg, N.dtype_id(self.compute_dtype), self._down(), 0, self._pack)
         # parameters in state_dict order == the order the native planner assumes
         return _rddb_forward(x, cfg, list(self.parameters()))
-
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"
 
 
 class RDDBNetA(RDDBNet):
@@ -349,7 +382,7 @@ class _LegacyRRDB(_HolderOnly):
 _MODES = {"x1": 1, "x2": 2, "x4": 4}
 
 
-class RDDBNetB(nn.Module):
+class RDDBNetB(_NativeRepr, nn.Module):
     """Legacy nearest-up-sampling generator, drop-in for reference ``model.model.RDDBNetB`` (model/model.py:394-440; G_A of
     train.py:172,177).  ``RDDBNetB(in_nc, out_nc, nf, nb=3, gc=32, mode='x2')``; forward: conv_first -> RRDB trunk ->
     trunk_conv + skip -> [nearest x2 -> upconv -> LeakyReLU] (x4: upconv1 then upconv2; x2: upconv1 twice, the second
@@ -358,6 +391,7 @@ class RDDBNetB(nn.Module):
 
     _legacy = 1
     _tail = ("upconv1", "upconv2", "HRconv")
+    _repr_mode = True
 
     def __init__(self, in_nc, out_nc, nf, nb=3, gc=32, mode="x2", dtype=None):
         super().__init__()
@@ -384,9 +418,6 @@ class RDDBNetB(nn.Module):
             ps = [p.detach() if id(p) in skip else p for p in ps]
         return _rddb_forward(x, cfg, ps)
 
-    def extra_repr(self):
-        return f"native gfx950, mode={self.mode}, compute_dtype={self.compute_dtype}"
-
 
 class LegacyRDDBNet(RDDBNetB):
     """Drop-in for the *legacy* ``model.model.RDDBNet`` (model/model.py:347-391; not the rddb.py class that
@@ -409,73 +440,99 @@ class LegacyRDDBNet(RDDBNetB):
         return _rddb_forward(x, cfg, ps)
 
 
-# ------------------------------------------------------------------------------------------------ ResDeconv colouriser
-def _resdeconv_prepare(x, out_ch, dtype, layers, norm, params):
-    """Checks and conversions shared by the training forward and the inference call -> (x, cfg, plist)."""
-    N.require_cuda(x, "ResDeconv.forward")
-    if x.dim() != 4 or x.shape[1] != 3:
-        raise ValueError(f"ResDeconv's stem expects 3 channels, got {tuple(x.shape)}")
-    x = x.detach().contiguous().float()
+# ------------------------------------------------------------------------------------------------ op-list networks
+class _OpList(NamedTuple):
+    """One network family of the native op-list executor (``rd_forward`` / ``rd_backward`` in csrc/nets.hip).  Its C entry points
+    are ``<stem>_ws_bytes`` / ``_forward`` / ``_bwd_scratch_bytes`` / ``_backward`` / ``_infer_ws_bytes`` / ``_infer``."""
+    name: str                 # in messages
+    stem: str                 # C symbol stem
+    make_cfg: Callable        # (x, items) -> (config struct, output shape); checks x (_check_input) and what else the family requires
+
+
+def _resdeconv_cfg(x, items):
+    out_ch, dtype, layers, norm = items
+    _check_input(x, "ResDeconv", 3, "ResDeconv's stem expects 3 channels")
     B, _, H, W = x.shape
     if H % 16 or W % 16:
         raise ValueError(f"ResDeconv needs H and W to be multiples of 16 (four stride-2 stages), got {H}x{W}")
-    cfg = N.ResDeconvCfg(3, out_ch, B, H, W, dtype, (C.c_int * 4)(*layers), norm)
-    for p in params:
-        N.require_cuda(p, "ResDeconv parameter")
-    plist = [p.detach().contiguous() for p in params]
-    return x, cfg, plist
+    return N.ResDeconvCfg(3, out_ch, B, H, W, dtype, (C.c_int * 4)(*layers), norm), (B, out_ch, H, W)
 
 
-class _ResDeconvFn(torch.autograd.Function):
-    """One native forward / one native backward for the whole colouriser (resdeconv.py:164-195)."""
+def _srnet_cfg(x, items):
+    kind, in_ch, out_ch, up, base, dtype = items[:6]
+    nres = items[6] if len(items) > 6 else 0
+    _check_input(x, "ESPCN/SRCNN/EDSR", in_ch, f"expected [B,{in_ch},H,W]")
+    B, _, H, W = x.shape
+    f = 1 if kind == 1 else up
+    return N.SrNetCfg(kind, in_ch, out_ch, up, base, B, H, W, dtype, nres), (B, out_ch, H * f, W * f)
+
+
+def _srdense_cfg(x, items):
+    kind, in_ch, out_ch, growth, nblocks, nlayers, up, dtype = items
+    _check_input(x, "SRDenseNet", in_ch, f"expected [B,{in_ch},H,W]")
+    B, _, H, W = x.shape
+    cfg = N.SrDenseCfg(kind, in_ch, out_ch, B, H, W, dtype, growth, nblocks, nlayers, up)
+    oh, ow = C.c_int(), C.c_int()
+    N.check(N.lib().srcgan_srdense_out_hw(C.byref(cfg), C.byref(oh), C.byref(ow)), "srcgan_srdense_out_hw")
+    return cfg, (B, out_ch, oh.value, ow.value)
+
+
+# ResDeconv's inference entry points take one more argument, ``fold_tail``.  1: deconv13 and pred run as four parity 2x2 convolutions
+# with composed weights, the 64-channel full-resolution tensor is never made.  0: the training forward's launches, its bits.
+_RESDECONV = _OpList("ResDeconv", "srcgan_resdeconv", _resdeconv_cfg)       # resdeconv.py:164-195
+_SRNET = _OpList("ESPCN/SRCNN/EDSR", "srcgan_srnet", _srnet_cfg)            # kind 0 ESPCN, 1 SRCNN, 2 EDSR
+_SRDENSE = _OpList("SRDenseNet", "srcgan_srdense", _srdense_cfg)            # kind 0 SRDenseNetA, 1 SRDenseNetB
+
+
+def _oplist_run(x, family, items, params, entry, extra=()):
+    """One native forward, ``entry`` "forward" (training workspace) or "infer" (slot-planned workspace; ``extra``: the family's
+    trailing inference arguments) -> (y, cfg, plist, workspace)."""
+    lib = N.lib()
+    cfg, yshape = family.make_cfg(x, items)
+    x = x.detach().contiguous().float()
+    plist = _params(params, family.name)
+    ws_bytes = getattr(lib, f"{family.stem}_ws_bytes" if entry == "forward" else f"{family.stem}_infer_ws_bytes")
+    ws = N.workspace(ws_bytes(C.byref(cfg), *extra), x.device)
+    y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
+    what = f"{family.stem}_{entry}"
+    N.check(getattr(lib, what)(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), *extra, N.stream_ptr(x.device)), what)
+    return y, cfg, plist, ws
+
+
+class _OpListFn(torch.autograd.Function):
+    """One native forward / one native backward for a whole op-list network."""
 
     @staticmethod
-    def forward(ctx, x, out_ch, dtype, layers, norm, *params):
-        lib = N.lib()
-        x, cfg, plist = _resdeconv_prepare(x, out_ch, dtype, layers, norm, params)
-        ws = N.workspace(lib.srcgan_resdeconv_ws_bytes(C.byref(cfg)), x.device)
-        y = torch.empty(cfg.B, out_ch, cfg.H, cfg.W, dtype=torch.float32, device=x.device)
-        N.check(lib.srcgan_resdeconv_forward(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(),
-                                             N.stream_ptr(x.device)), "srcgan_resdeconv_forward")
-        ctx.cfg, ctx.ws = cfg, ws
+    def forward(ctx, x, family, items, *params):
+        y, ctx.cfg, plist, ctx.ws = _oplist_run(x, family, items, params, "forward")
+        ctx.family = family
         ctx.save_for_backward(*plist)
-        ctx.phase_hook = _phase_hooks.get("resdeconv")       # one rule for every network: the hook in force at FORWARD time
+        ctx.phase_hook = _phase_hook
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = N.lib()
-        params = list(ctx.saved_tensors)
-        cfg = ctx.cfg
-        if ctx.ws is None:
-            raise RuntimeError("ResDeconv backward called twice (activations were released)")
-        need_dx = ctx.needs_input_grad[0]
-        dy = dy.contiguous().float()
-        dx = torch.empty(cfg.B, 3, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if need_dx else None
-        arena = _GradArena(params, [ctx.needs_input_grad[5 + i] for i in range(len(params))])
-        grads = arena.views
-        scratch = N.workspace(lib.srcgan_resdeconv_bwd_scratch_bytes(C.byref(cfg)), dy.device)
-        N.check(lib.srcgan_resdeconv_backward(C.byref(cfg), dy.data_ptr(), N.ptr_array(params), ctx.ws.data_ptr(), scratch.data_ptr(),
-                                              N.ptr_array(grads), dx.data_ptr() if need_dx else None, N.stream_ptr(dy.device)), "srcgan_resdeconv_backward")
+        lib, family = N.lib(), ctx.family
+        dy, params, arena, grads, scratch, dx = _backward_operands(ctx, dy, 3, getattr(lib, f"{family.stem}_bwd_scratch_bytes"), family.name)
+        what = f"{family.stem}_backward"
+        N.check(getattr(lib, what)(C.byref(ctx.cfg), dy.data_ptr(), N.ptr_array(params), ctx.ws.data_ptr(), scratch.data_ptr(),
+                                   N.ptr_array(grads), dx.data_ptr() if dx is not None else None, N.stream_ptr(dy.device)), what)
         ctx.ws = None
         if ctx.phase_hook is not None:
             ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
-        return (dx, None, None, None, None, *grads)
+        return (dx, None, None, *grads)
 
 
-def _resdeconv_infer(x, out_ch, dtype, layers, norm, params, fold_tail=1):
-    """Forward under ``torch.no_grad()``: one native call on the slot-planned inference workspace (``srcgan_resdeconv_infer``),
-    released on return; no autograd node.  ``fold_tail=1``: deconv13 and pred run as four parity 2x2 convolutions with composed
-    weights, the 64-channel full-resolution tensor is never made.  ``fold_tail=0``: the training forward's launches, its bits."""
-    lib = N.lib()
-    x, cfg, plist = _resdeconv_prepare(x, out_ch, dtype, layers, norm, params)
-    ws = N.workspace(lib.srcgan_resdeconv_infer_ws_bytes(C.byref(cfg), fold_tail), x.device)
-    y = torch.empty(cfg.B, out_ch, cfg.H, cfg.W, dtype=torch.float32, device=x.device)
-    N.check(lib.srcgan_resdeconv_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), fold_tail,
-                                       N.stream_ptr(x.device)), "srcgan_resdeconv_infer")
-    return y
+def _oplist_forward(x, family, items, params, extra=()):
+    """The rule of _rddb_forward: grad mode decides, eval() plays no part.  On: the autograd Function (workspace kept for backward).
+    Off: ``<stem>_infer`` on the slot-planned workspace, released on return; no autograd node.  ``extra`` (the family's trailing
+    inference arguments) applies to the second branch only: the training forward has no such arguments."""
+    if torch.is_grad_enabled():
+        return _OpListFn.apply(x, family, items, *params)
+    return _oplist_run(x, family, items, params, "infer", extra)[0]
 
 
+# ------------------------------------------------------------------------------------------------ ResDeconv colouriser
 class _BasicBlockHolder(_HolderOnly):
     """Parameter holder of resdeconv.py:56-76 BasicBlock (attribute order = the reference's state_dict order)."""
     expansion = 1
@@ -492,7 +549,7 @@ class _BasicBlockHolder(_HolderOnly):
         self.stride = stride
 
 
-class ResDeconv(nn.Module):
+class ResDeconv(_NativeRepr, nn.Module):
     """Colouriser, drop-in for reference ``model.ResDeconv`` (src/model/resdeconv.py:99-195):
     ``ResDeconv(src_ch=1, tar_ch=3, block=None, layers=[2, 2, 2, 2], BN='GN')`` -- the reference's positional signature
     (resdeconv.py:107).  ``block``: BasicBlock, the only block the reference defines.  ``layers``: BasicBlocks per stage, any
@@ -552,85 +609,12 @@ class ResDeconv(nn.Module):
     def forward(self, x):
         if self.src_ch == 1:
             x = torch.cat([x, x, x], dim=1)
-        args = (self.tar_ch, N.dtype_id(self.compute_dtype), self.layers_cfg, 1 if self.BN == "IN" else 0)
-        if torch.is_grad_enabled():         # the rule of _rddb_forward: grad mode decides, eval() plays no part
-            return _ResDeconvFn.apply(x, *args, *self.parameters())
-        return _resdeconv_infer(x, *args, list(self.parameters()))
-
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"
+        items = (self.tar_ch, N.dtype_id(self.compute_dtype), self.layers_cfg, 1 if self.BN == "IN" else 0)
+        return _oplist_forward(x, _RESDECONV, items, list(self.parameters()), extra=(1,))      # under no_grad: fold_tail = 1
 
 
 # ------------------------------------------------------------------------------------------------ ESPCN / SRCNN
-def _srnet_prepare(x, cfg_items, params):
-    """Checks and conversions shared by the training forward and the inference call -> (x, cfg, plist, output shape)."""
-    N.require_cuda(x, "ESPCN/SRCNN forward")
-    kind, in_ch, out_ch, up, base, dtype = cfg_items[:6]
-    nres = cfg_items[6] if len(cfg_items) > 6 else 0
-    if x.dim() != 4 or x.shape[1] != in_ch:
-        raise ValueError(f"expected [B,{in_ch},H,W], got {tuple(x.shape)}")
-    x = x.detach().contiguous().float()
-    B, _, H, W = x.shape
-    cfg = N.SrNetCfg(kind, in_ch, out_ch, up, base, B, H, W, dtype, nres)
-    for p in params:
-        N.require_cuda(p, "parameter")
-    plist = [p.detach().contiguous() for p in params]
-    f = 1 if kind == 1 else up
-    return x, cfg, plist, (B, out_ch, H * f, W * f)
-
-
-class _SrNetFn(torch.autograd.Function):
-    """One native forward / backward for the small --SRModel networks (kind 0 ESPCN, 1 SRCNN)."""
-
-    @staticmethod
-    def forward(ctx, x, cfg_items, *params):
-        lib = N.lib()
-        x, cfg, plist, yshape = _srnet_prepare(x, cfg_items, params)
-        ws = N.workspace(lib.srcgan_srnet_ws_bytes(C.byref(cfg)), x.device)
-        y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
-        N.check(lib.srcgan_srnet_forward(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
-                "srcgan_srnet_forward")
-        ctx.cfg, ctx.ws = cfg, ws
-        ctx.save_for_backward(*plist)
-        ctx.phase_hook = _phase_hooks.get("srnet")
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = N.lib()
-        params = list(ctx.saved_tensors)
-        cfg = ctx.cfg
-        if ctx.ws is None:
-            raise RuntimeError("backward called twice (activations were released)")
-        need_dx = ctx.needs_input_grad[0]
-        dy = dy.contiguous().float()
-        dx = torch.empty(cfg.B, cfg.in_ch, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if need_dx else None
-        arena = _GradArena(params, [ctx.needs_input_grad[2 + i] for i in range(len(params))])
-        grads = arena.views
-        scratch = N.workspace(lib.srcgan_srnet_bwd_scratch_bytes(C.byref(cfg)), dy.device)
-        N.check(lib.srcgan_srnet_backward(C.byref(cfg), dy.data_ptr(), N.ptr_array(params), ctx.ws.data_ptr(), scratch.data_ptr(),
-                                          N.ptr_array(grads), dx.data_ptr() if need_dx else None, N.stream_ptr(dy.device)), "srcgan_srnet_backward")
-        ctx.ws = None
-        if ctx.phase_hook is not None:
-            ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
-        return (dx, None, *grads)
-
-
-def _srnet_forward(x, cfg_items, params):
-    """Grad mode on: the autograd Function (workspace kept for backward).  Off: ``srcgan_srnet_infer`` on the slot-planned
-    workspace, released on return -- the same launches, hence the same bits."""
-    if torch.is_grad_enabled():
-        return _SrNetFn.apply(x, cfg_items, *params)
-    lib = N.lib()
-    x, cfg, plist, yshape = _srnet_prepare(x, cfg_items, params)
-    ws = N.workspace(lib.srcgan_srnet_infer_ws_bytes(C.byref(cfg)), x.device)
-    y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
-    N.check(lib.srcgan_srnet_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
-            "srcgan_srnet_infer")
-    return y
-
-
-class ESPCN(nn.Module):
+class ESPCN(_NativeRepr, nn.Module):
     """Drop-in for reference ``model.ESPCN`` (src/model/espcn.py:18-51; the CLI default ``--SRModel``, trainCas.py:169):
     5x5, 3x3, 3x3 convolutions + ReLU, 3x3 to 64 r^2 channels, PixelShuffle(r), 3x3."""
 
@@ -649,13 +633,10 @@ class ESPCN(nn.Module):
         self.compute_dtype = N.dtype_name(dtype)
 
     def forward(self, x):
-        return _srnet_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
-
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"
+        return _oplist_forward(x, _SRNET, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
-class SRCNN(nn.Module):
+class SRCNN(_NativeRepr, nn.Module):
     """Drop-in for reference ``model.SRCNN`` (src/model/srcnn.py:17-42): 9x9, 1x1, 5x5 convolutions, each followed by ReLU;
     the output has the input's size (``upscale_factor`` is stored and unused, as in the reference); torch default init."""
 
@@ -671,10 +652,7 @@ class SRCNN(nn.Module):
         self.compute_dtype = N.dtype_name(dtype)
 
     def forward(self, x):
-        return _srnet_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
-
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"
+        return _oplist_forward(x, _SRNET, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class _EdsrBlock(_HolderOnly):
@@ -688,7 +666,7 @@ class _EdsrBlock(_HolderOnly):
         self.activation = nn.LeakyReLU(negative_slope=0.2, inplace=True)
 
 
-class EDSR(nn.Module):
+class EDSR(_NativeRepr, nn.Module):
     """Drop-in for reference ``model.EDSR`` (src/model/edsr.py:68-110): ``EDSR(in_ch, ou_ch, upscale_factor=2, base_channel=64,
     num_residuals=50)``."""
 
@@ -706,13 +684,10 @@ class EDSR(nn.Module):
         self.compute_dtype = N.dtype_name(dtype)
 
     def forward(self, x):
-        return _srnet_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype), self._nres), list(self.parameters()))
-
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"
+        return _oplist_forward(x, _SRNET, (*self._cfg, N.dtype_id(self.compute_dtype), self._nres), list(self.parameters()))
 
 
-class SRDN(nn.Module):
+class SRDN(_NativeRepr, nn.Module):
     """Drop-in for reference ``model.SRDN`` (src/model/srdn.py:56-74): conv_first -> RRDB_encoder (nb RRDBs) -> + skip ->
     RRDB_decoder (nb RRDBs) -> + skip -> conv_last; same resolution in and out (``upscale_factor`` is stored and unused, and
     ``trunk_conv`` exists in the state_dict but is never applied -- it receives no gradient, as in the reference)."""
@@ -734,79 +709,8 @@ class SRDN(nn.Module):
         skip = {id(self.trunk_conv.weight), id(self.trunk_conv.bias)}
         return _rddb_forward(x, cfg, [p.detach() if id(p) in skip else p for p in self.parameters()])
 
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"
-
 
 # ------------------------------------------------------------------------------------------------ SRDenseNetA / SRDenseNetB
-def _srdense_prepare(x, cfg_items, params):
-    """Checks and conversions shared by the training forward and the inference call -> (x, cfg, plist, output shape)."""
-    N.require_cuda(x, "SRDenseNet forward")
-    kind, in_ch, out_ch, growth, nblocks, nlayers, up, dtype = cfg_items
-    if x.dim() != 4 or x.shape[1] != in_ch:
-        raise ValueError(f"expected [B,{in_ch},H,W], got {tuple(x.shape)}")
-    x = x.detach().contiguous().float()
-    B, _, H, W = x.shape
-    cfg = N.SrDenseCfg(kind, in_ch, out_ch, B, H, W, dtype, growth, nblocks, nlayers, up)
-    for p in params:
-        N.require_cuda(p, "parameter")
-    plist = [p.detach().contiguous() for p in params]
-    oh, ow = C.c_int(), C.c_int()
-    N.check(N.lib().srcgan_srdense_out_hw(C.byref(cfg), C.byref(oh), C.byref(ow)), "srcgan_srdense_out_hw")
-    return x, cfg, plist, (B, out_ch, oh.value, ow.value)
-
-
-class _SrDenseFn(torch.autograd.Function):
-    """One native forward / backward for SRDenseNetA (kind 0) / SRDenseNetB (kind 1)."""
-
-    @staticmethod
-    def forward(ctx, x, cfg_items, *params):
-        lib = N.lib()
-        x, cfg, plist, yshape = _srdense_prepare(x, cfg_items, params)
-        ws = N.workspace(lib.srcgan_srdense_ws_bytes(C.byref(cfg)), x.device)
-        y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
-        N.check(lib.srcgan_srdense_forward(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
-                "srcgan_srdense_forward")
-        ctx.cfg, ctx.ws = cfg, ws
-        ctx.save_for_backward(*plist)
-        ctx.phase_hook = _phase_hooks.get("srdense")
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = N.lib()
-        params = list(ctx.saved_tensors)
-        cfg = ctx.cfg
-        if ctx.ws is None:
-            raise RuntimeError("backward called twice (activations were released)")
-        need_dx = ctx.needs_input_grad[0]
-        dy = dy.contiguous().float()
-        dx = torch.empty(cfg.B, cfg.in_ch, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if need_dx else None
-        arena = _GradArena(params, [ctx.needs_input_grad[2 + i] for i in range(len(params))])
-        grads = arena.views
-        scratch = N.workspace(lib.srcgan_srdense_bwd_scratch_bytes(C.byref(cfg)), dy.device)
-        N.check(lib.srcgan_srdense_backward(C.byref(cfg), dy.data_ptr(), N.ptr_array(params), ctx.ws.data_ptr(), scratch.data_ptr(),
-                                            N.ptr_array(grads), dx.data_ptr() if need_dx else None, N.stream_ptr(dy.device)), "srcgan_srdense_backward")
-        ctx.ws = None
-        if ctx.phase_hook is not None:
-            ctx.phase_hook.phase_done(arena, params, 0, len(params), True)
-        return (dx, None, *grads)
-
-
-def _srdense_forward(x, cfg_items, params):
-    """Grad mode on: the autograd Function (workspace kept for backward).  Off: ``srcgan_srdense_infer`` on the slot-planned
-    workspace, released on return -- the same launches, hence the same bits."""
-    if torch.is_grad_enabled():
-        return _SrDenseFn.apply(x, cfg_items, *params)
-    lib = N.lib()
-    x, cfg, plist, yshape = _srdense_prepare(x, cfg_items, params)
-    ws = N.workspace(lib.srcgan_srdense_infer_ws_bytes(C.byref(cfg)), x.device)
-    y = torch.empty(*yshape, dtype=torch.float32, device=x.device)
-    N.check(lib.srcgan_srdense_infer(C.byref(cfg), x.data_ptr(), N.ptr_array(plist), ws.data_ptr(), y.data_ptr(), N.stream_ptr(x.device)),
-            "srcgan_srdense_infer")
-    return y
-
-
 class _SrDenseConv(_HolderOnly):
     """Parameter holder of model/model.py:643-660 ConvLayer / DenseLayer: one convolution under the key ``conv``."""
 
@@ -828,7 +732,7 @@ class _SrDenseBlock(_HolderOnly):
         self.block = nn.Sequential(*layers)
 
 
-class SRDenseNetA(nn.Module):
+class SRDenseNetA(_NativeRepr, nn.Module):
     """LR -> HR SRDenseNet, drop-in for reference ``model.model.SRDenseNetA`` (model/model.py:675-729; train.py:165-168):
     ``SRDenseNetA(in_nc, out_nc, nb_channel=1, growth_rate=16, num_blocks=8, num_layers=8, mode='x2')``.  conv_first (to 1 channel) ->
     conv + ReLU -> dense blocks -> 1x1 bottleneck to 256 + ReLU -> ``deconv`` = ConvTranspose2d(256, 256, k3 s2 p1 output_padding 1) +
@@ -837,6 +741,7 @@ class SRDenseNetA(nn.Module):
     the resolution unchanged in the reference and is refused here."""
 
     _kind = 0
+    _repr_mode = True
 
     def __init__(self, in_nc, out_nc, nb_channel=1, growth_rate=16, num_blocks=8, num_layers=8, mode="x2", dtype=None):
         super().__init__()
@@ -872,10 +777,7 @@ class SRDenseNetA(nn.Module):
         return nn.ConvTranspose2d(256, 256, kernel_size=3, stride=2, padding=1, output_padding=1)
 
     def forward(self, x):
-        return _srdense_forward(x, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
-
-    def extra_repr(self):
-        return f"native gfx950, mode={self.mode}, compute_dtype={self.compute_dtype}"
+        return _oplist_forward(x, _SRDENSE, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class SRDenseNetB(SRDenseNetA):
@@ -892,16 +794,13 @@ class SRDenseNetB(SRDenseNetA):
 class _NLayerDFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, cfg_items, running, nbt, *params):
-        N.require_cuda(x, "NLayerDiscriminator.forward")
         lib = N.lib()
         in_ch, ndf, n_layers, dtype, training, pstate = cfg_items[:6]
         norm = cfg_items[6] if len(cfg_items) > 6 else 0
-        if x.dim() != 4 or x.shape[1] != in_ch:
-            raise ValueError(f"NLayerDiscriminator expects [B,{in_ch},H,W], got {tuple(x.shape)}")
-        x = x.detach().contiguous().float()
+        x = _input(x, "NLayerDiscriminator", in_ch, f"NLayerDiscriminator expects [B,{in_ch},H,W]")
         B, _, H, W = x.shape
         cfg = N.NLayerDCfg(in_ch, ndf, n_layers, B, H, W, dtype, int(training), norm)
-        plist = [p.detach().contiguous() for p in params]
+        plist = _params(params, "NLayerDiscriminator")
         oh, ow = C.c_int(), C.c_int()
         N.check(lib.srcgan_nlayerd_out_hw(C.byref(cfg), C.byref(oh), C.byref(ow)), "srcgan_nlayerd_out_hw")
         ws = N.workspace(lib.srcgan_nlayerd_ws_bytes(C.byref(cfg)), x.device)
@@ -915,26 +814,16 @@ class _NLayerDFn(torch.autograd.Function):
         ctx.cfg, ctx.ws = cfg, ws
         ctx.pstate, ctx.layout = pstate, layout
         ctx.save_for_backward(*plist)
-        ctx.phase_hook = _phase_hooks.get("nlayerd")
+        ctx.phase_hook = _phase_hook
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = N.lib()
-        params = list(ctx.saved_tensors)
-        cfg = ctx.cfg
-        if ctx.ws is None:
-            raise RuntimeError("NLayerDiscriminator backward called twice (activations were released)")
-        dy = dy.contiguous().float()
-        need_dx = ctx.needs_input_grad[0]
-        needs = [ctx.needs_input_grad[4 + i] for i in range(len(params))]
-        arena = _GradArena(params, needs) if any(needs) else None
-        grads = arena.views if arena is not None else [None] * len(params)
-        scratch = N.workspace(lib.srcgan_nlayerd_bwd_scratch_bytes(C.byref(cfg)), dy.device)
-        dx = torch.empty(cfg.B, cfg.in_ch, cfg.H, cfg.W, dtype=torch.float32, device=dy.device) if need_dx else None
+        lib, cfg = N.lib(), ctx.cfg
+        dy, params, arena, grads, scratch, dx = _backward_operands(ctx, dy, 4, lib.srcgan_nlayerd_bwd_scratch_bytes, "NLayerDiscriminator")
         opt = ctx.pstate.opts(lib.srcgan_nlayerd_wpack_bytes, cfg, params, ctx.layout, True, dy.device)
         N.check(lib.srcgan_nlayerd_backward_ex(C.byref(cfg), dy.data_ptr(), N.ptr_array(params), ctx.ws.data_ptr(),
-                                               scratch.data_ptr(), N.ptr_array(grads), dx.data_ptr() if need_dx else None,
+                                               scratch.data_ptr(), N.ptr_array(grads), dx.data_ptr() if dx is not None else None,
                                                C.byref(opt), N.stream_ptr(dy.device)), "srcgan_nlayerd_backward")
         ctx.pstate.done(True)
         ctx.ws = None
@@ -943,7 +832,7 @@ class _NLayerDFn(torch.autograd.Function):
         return (dx, None, None, None, *grads)
 
 
-class NLayerDiscriminator(nn.Module):
+class NLayerDiscriminator(_NativeRepr, nn.Module):
     """PatchGAN discriminator, drop-in for reference ``model.model.NLayerDiscriminator``
     (model/model.py:595-639): conv4x4 s2 + LeakyReLU | (n-1) x [conv4x4 s2, BatchNorm2d, LeakyReLU] |
     conv4x4 s1, BN, LeakyReLU | conv4x4 s1 -> 1 channel.  BatchNorm uses per-replica batch statistics
@@ -996,6 +885,3 @@ class NLayerDiscriminator(nn.Module):
         nbt = [m.num_batches_tracked for m in bns]
         cfg = (*self._cfg, N.dtype_id(self.compute_dtype), self.training, self._pack, self._norm)
         return _NLayerDFn.apply(input, cfg, running, nbt, *self.parameters())
-
-    def extra_repr(self):
-        return f"native gfx950, compute_dtype={self.compute_dtype}"

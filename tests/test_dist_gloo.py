@@ -82,7 +82,7 @@ def _worker(rank, world, port, q):
         gs2 = sd.GradSync(bucket_mb=0.00002, phases=3).once(net2)          # 5-float pieces: several collectives per arena
         gs2._active = True
         import srcgan_amd.model as smodel
-        assert "rddb" not in smodel._phase_hooks
+        assert smodel._phase_hook is None
         gs2.attach()
         try:
             sd.GradSync().attach()
@@ -108,6 +108,7 @@ def _worker(rank, world, port, q):
         assert gs2.stats["bytes"] == nbytes and gs2.stats["collectives"] > 1 and gs2.stats["calls"] == 1, gs2.stats
         gs2.sync([p for p in ps2 if False])                                # nothing to do
         gs2.detach()
+        assert smodel._phase_hook is None                                  # detach() leaves the slot empty
         # ... and the flatten fallback when the gradients are separate allocations
         gs3 = sd.GradSync(bucket_mb=0.0001)
         for i, p in enumerate(ps2):

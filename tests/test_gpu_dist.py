@@ -89,6 +89,60 @@ print("ok")
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), (out.stdout[-500:], out.stderr[-2000:])
 
 
+ATTACHED_NETS = ["RDDBNet(1, 1, 2, nf=16, nb=1, gc=8)", "NLayerDiscriminator(3, 16, 2)", "ESPCN(1, 1, 2)", "SRCNN(1, 1, 2, 16)",
+                 "EDSR(3, 3, 2, num_residuals=2)", "ResDeconv(1, 3)", "SRDenseNetA(1, 3, num_blocks=1, num_layers=2)",
+                 "SRDenseNetB(3, 1, num_blocks=1, num_layers=2)"]
+ATTACHED_SHAPES = [(1, 1, 8, 8), (2, 3, 32, 32), (2, 1, 8, 8), (2, 1, 8, 8), (1, 3, 18, 22), (1, 1, 32, 32), (1, 1, 8, 8), (1, 3, 8, 8)]
+
+
+def test_attached_grad_sync_exchanges_every_native_network():
+    """Every native network takes part in the attached gradient exchange (SRDenseNetA/B did not before the hook became one slot):
+    one forward + backward of an L1 loss, fp32, from the same seed plain and with ``GradSync(bucket_mb=0.05).attach()`` and no
+    ``once()``.  Attached, the network's one backward call counts as one exchange of exactly 4 bytes per parameter element that
+    received a gradient, and -- one rank's mean is the identity -- every gradient equals the plain run's bit for bit."""
+    code = r'''
+import json, sys, torch
+sys.path.insert(0, %r)
+import srcgan_amd
+from srcgan_amd import dist as sdist
+rank, local, world = sdist.init_from_env()
+import torch.distributed as dist
+assert dist.is_initialized() and dist.get_backend() == "nccl"
+def run(expr, shape, attach):
+    torch.manual_seed(0)
+    net = eval(expr, vars(srcgan_amd)).cuda()
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(*shape, generator=g).cuda().requires_grad_()
+    gs = sdist.GradSync(bucket_mb=0.05)
+    assert gs._active
+    if attach:
+        gs.attach()
+    try:
+        y = net(x)
+        torch.nn.functional.l1_loss(y, torch.rand(*y.shape, generator=g).cuda()).backward()
+        torch.cuda.synchronize()
+    finally:
+        gs.detach()
+    return [x.grad] + [p.grad for p in net.parameters()], dict(gs.stats)
+for expr, shape in zip(%r, %r):
+    plain, st0 = run(expr, shape, False)
+    got, st = run(expr, shape, True)
+    assert st0["calls"] == 0 and st0["bytes"] == 0, st0
+    same = all((a is None and b is None) or (a is not None and b is not None and torch.equal(a, b)) for a, b in zip(plain, got))
+    print(json.dumps({"net": expr, "calls": st["calls"], "bytes": st["bytes"], "grad_bytes": 4 * sum(g.numel() for g in got[1:] if g is not None),
+                      "tensors": sum(g is not None for g in got), "equal": same}), flush=True)
+dist.barrier(); dist.destroy_process_group()
+print("ok")
+''' % (ROOT, ATTACHED_NETS, ATTACHED_SHAPES)
+    out = subprocess.run([sys.executable, "-c", code], env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), (out.stdout[-500:], out.stderr[-2000:])
+    rows = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    print("\n".join(json.dumps(r) for r in rows))
+    assert [r["net"] for r in rows] == ATTACHED_NETS
+    bad = [r for r in rows if not (r["calls"] == 1 and r["bytes"] == r["grad_bytes"] > 0 and r["tensors"] > 1 and r["equal"])]
+    assert not bad, bad
+
+
 def test_bench_two_ranks_on_one_device_over_gloo():
     """bench.py's whole control flow with world_size 2 (torch.distributed.run, 127.0.0.1): broadcast, the generator reduce under
     the discriminator step, barriers, MAX of the timing, the instrumented extra step of --full on every rank, one JSON line from rank 0.
