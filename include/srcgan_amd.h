@@ -223,7 +223,23 @@ int srcgan_add_inplace_planes(void* y, int y_cs, int y_coff, long y_plane, const
  * (optional) f32 [C], += when accumulate (a GroupNorm module applied twice, edsr.py:41,47,49).
  * scratch: srcgan_gn_scratch_floats(B, C) floats.  C/epp must divide 256 (epp = 16 bytes of channels).
  * gamma and / or beta may be null: no affine part -- with G == C that is nn.InstanceNorm2d(C) (model/model.py:598-631 with
- * norm_layer = InstanceNorm2d, basicModel.py:24-25). */
+ * norm_layer = InstanceNorm2d, basicModel.py:24-25).
+ * Pinned by tests/test_gpu_groupnorm.py:
+ *   - every operand has its own channel stride (a multiple of epp, >= C); nothing outside [0, C) of a record is read or written.
+ *   - the statistics are those of the STORED x: |mean - mean64| <= 8 * 2^-24 (|mean64| + sd), |rstd - rstd64| <= 8 * 2^-24
+ *     (1 + |mean64| / sd) rstd64, sd = sqrt(var64 + eps), also with the mean 1000 standard deviations from 0; image b of a batch
+ *     has the bits of a call on that image alone, and a call repeated has the same bits.
+ *   - a constant group: mean is that number exactly, the variance exactly 0, rstd = rsqrtf(eps) (316.2278 for 1e-5), y = beta.
+ *   - y is ONE f32 expression cast once; with relu != 0 and slope == 0 a negative value gives -0 (v * 0), not +0.
+ *   - the mask of the backward is yact > 0 (a stored 0, of either sign, takes the slope); g = dy * slope is an f32 product (-0 for a
+ *     negative dy at slope 0).  dres = g cast once; with dres_accumulate, in a 16-bit type, g is FIRST rounded to the storage type
+ *     and then added to the old value and rounded again (two roundings; exact whenever g is representable).
+ *   - dx may be written over dy (dx == dy, same stride): a thread reads the elements it writes, and no others, before it writes
+ *     them; the result has the bits of the out-of-place call.  (Read from the code, not tested: dx must not alias x or yact,
+ *     dres must not alias dy or dx.)
+ *   - dgamma / dbeta are overwritten unless accumulate; each of dres, dgamma, dbeta may be null on its own.
+ *   - an error (C/epp not dividing 256, C > 1024, G not dividing C, a stride that is no multiple of epp, a bad dtype, a null
+ *     required pointer) names the entry point in srcgan_last_error() and writes nothing. */
 size_t srcgan_gn_scratch_floats(int B, int C);
 int srcgan_gn_forward(const void* x, int x_cs, const void* res, int res_cs, void* y, int y_cs, const float* gamma, const float* beta,
                       float* stats, int B, long hw, int C, int G, float eps, int relu, float slope, int dtype, float* scratch, void* stream);
@@ -258,8 +274,15 @@ int srcgan_psnr_from_mse(const float* mse, float* out, void* stream);
  * bilinear x(1/up) with align_corners=False == mean of the centre 2x2 of each up x up block. */
 int srcgan_rgb_to_gray(const float* rgb, float* gray, int B, int H, int W, void* stream);
 int srcgan_bilinear_down(const float* src, float* dst, int B, int C, int H, int W, int up, void* stream);
+/* nearest: the rule of F.interpolate(size=(OH, OW)), source index min(floor(dst * (float)in / out), in - 1) with the scale in f32.
+ * Equal to it bit for bit for any ratio (tests/test_gpu_resample.py: 2, 3, 4, their inverses, 7 -> 3, 5 -> 13, 1 -> 4); for the
+ * factors the callers pass (2, 4, 1/2, 1/4) F.interpolate(scale_factor=) gives the same picture. */
 int srcgan_nearest_resize(const float* src, float* dst, int B, int C, int H, int W, int OH, int OW, void* stream);
-/* bilinear x up (integer, align_corners=False): the second half of the blur of trainCasConst.py:89-92 */
+/* bilinear x up (integer up >= 1, align_corners=False): the second half of the blur of trainCasConst.py:89-92.  The source
+ * coordinate (2 o + 1 - up) / (2 up) is split in integers, each weight is one rounded quotient: equal to float64 F.interpolate cast
+ * to f32 on integer data for up = 1, 2, 4, 8, within 4 * 2^-24 * sum |w tap| of it for the tested factors 1, 2, 3, 4, 8
+ * (tests/test_gpu_resample.py; the constant is measured to hold there, not derived for every up).
+ * srcgan_bilinear_down is exact on integer data (weights 1/4). */
 int srcgan_bilinear_up(const float* src, float* dst, int B, int C, int H, int W, int up, void* stream);
 /* Gray-path preprocessing of the cycle step (train.py:251-260), NCHW f32, s = 2 or 4:
  *   gray_nearest_down: y[B,1,H/s,W/s], y[b,0,oy,ox] = gray(rgb[b,:,oy*s,ox*s])  == nearest x(1/s) of srcgan_rgb_to_gray (s | H, W)

@@ -1143,12 +1143,11 @@ extern "C" int srcgan_sum2x2_nhwc(const void* src, int s_cs, void* dst, int d_cs
 // sg_bilinear_sample, which the whole-scene tile gather evaluates on the fly and must reproduce bit for bit.
 __global__ __launch_bounds__(256) void bilinear_up_k(const float* __restrict__ src, float* __restrict__ dst, int H, int W, int up, long total) {
     const int OH = H * up, OW = W * up;
-    const float inv = sg_bilinear_inv(up);
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const int ox = (int)(e % OW); const long q = e / OW;
         const int oy = (int)(q % OH); const long bc = q / OH;
         const float* s = src + (size_t)bc * H * W;
-        dst[e] = sg_bilinear_sample([&](int y, int x) { return s[(size_t)y * W + x]; }, H, W, inv, oy, ox);
+        dst[e] = sg_bilinear_sample([&](int y, int x) { return s[(size_t)y * W + x]; }, sg_bilinear_axis(oy, H, up), sg_bilinear_axis(ox, W, up));
     }
 }
 extern "C" int srcgan_bilinear_up(const float* src, float* dst, int B, int C, int H, int W, int up, void* stream) {

@@ -22,22 +22,22 @@ __device__ __forceinline__ float sg_gray_u8(unsigned char r8, unsigned char g8, 
 }
 
 // One axis of F.interpolate(scale_factor=up, mode="bilinear", align_corners=False): output index o -> source coordinate
-// (o + 0.5) / up - 0.5 clamped at 0, its two neighbours (the upper one clamped at the border) and their weights.  inv = sg_bilinear_inv(up).
+// (o + 0.5) / up - 0.5 clamped at 0, its two neighbours (the upper one clamped at the border) and their weights.
+// The coordinate is (2 o + 1 - up) / (2 up): its integer part and remainder are taken in integers, so each weight is one correctly
+// rounded quotient, whatever the size of the coordinate.
 struct SgLerp { int i0, i1; float w0, w1; };
-__device__ __forceinline__ float sg_bilinear_inv(int up) { return 1.f / (float)up; }
-__device__ __forceinline__ SgLerp sg_bilinear_axis(int o, int n, float inv) {
-#pragma clang fp contract(off)
-    float s = __fmaf_rn(inv, (float)o + 0.5f, -0.5f);
-    s = s < 0.f ? 0.f : s;
-    const int i0 = min((int)s, n - 1);                      // (int)s <= n - 1 for every o < n * up; the clamp only documents it
-    const float l = s - (float)i0;
-    return SgLerp{i0, i0 + (i0 < n - 1 ? 1 : 0), 1.f - l, l};
+__device__ __forceinline__ SgLerp sg_bilinear_axis(int o, int n, int up) {
+    const int num = 2 * o + 1 - up, den = 2 * up;
+    int i0 = 0, r = 0;
+    if (num > 0) { i0 = num / den; r = num - i0 * den; }
+    i0 = min(i0, n - 1);                                   // num / den <= n - 1 for every o < n * up; the clamp only documents it
+    return SgLerp{i0, i0 + (i0 < n - 1 ? 1 : 0), (float)(den - r) / (float)den, (float)r / (float)den};
 }
+// The sample at the two axes' positions (a caller with several samples in one row or column computes that axis once).
 // tap(y, x) returns the source sample; it is called with 0 <= y < H, 0 <= x < W only
 template <typename Tap>
-__device__ __forceinline__ float sg_bilinear_sample(Tap tap, int H, int W, float inv, int oy, int ox) {
+__device__ __forceinline__ float sg_bilinear_sample(Tap tap, const SgLerp& y, const SgLerp& x) {
 #pragma clang fp contract(off)
-    const SgLerp y = sg_bilinear_axis(oy, H, inv), x = sg_bilinear_axis(ox, W, inv);
     const float top = __fmaf_rn(x.w1, tap(y.i0, x.i1), x.w0 * tap(y.i0, x.i0));
     const float bot = __fmaf_rn(x.w1, tap(y.i1, x.i1), x.w0 * tap(y.i1, x.i0));
     return __fmaf_rn(y.w0, top, y.w1 * bot);

@@ -54,7 +54,12 @@ __global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ sr
     const int y0 = a.yx[blockIdx.z][0], x0 = a.yx[blockIdx.z][1];
     const int OH = UP ? H * s : H, OW = UP ? W * s : W;
     const int oy = min(y0 + ty, OH - 1);
-    const float inv = UP ? sg_bilinear_inv(s) : 1.f;
+    SgLerp ly{}, lx[VEC]{};                                     // UP: the row's and the VEC columns' positions, once for all planes
+    if constexpr (UP) {
+        ly = sg_bilinear_axis(oy, H, s);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) lx[i] = sg_bilinear_axis(min(x0 + tx + i, OW - 1), W, s);
+    }
     const int Cd = KIND == 2 ? 1 : C;                           // planes written
     const int c_lo = KIND == 0 ? (int)blockIdx.y : 0, c_hi = KIND == 0 ? c_lo + 1 : Cd;
     const size_t plane = (size_t)th * tw;
@@ -71,7 +76,7 @@ __global__ __launch_bounds__(256) void tile_gather_k(const void* __restrict__ sr
 #pragma unroll
         for (int i = 0; i < VEC; ++i) {
             const int ox = min(x0 + tx + i, OW - 1);
-            if constexpr (UP) v[i] = sg_bilinear_sample([&](int y, int x) { return scene_at<KIND>(src, C, H, W, c, y, x); }, H, W, inv, oy, ox);
+            if constexpr (UP) v[i] = sg_bilinear_sample([&](int y, int x) { return scene_at<KIND>(src, C, H, W, c, y, x); }, ly, lx[i]);
             else v[i] = scene_at<KIND>(src, C, H, W, c, oy, ox);
         }
         if constexpr (VEC == 4) store4<float>(d + c * plane, v);
