@@ -490,6 +490,51 @@ int srcgan_srdense_backward(const srcgan_srdense_cfg* c, const float* dy_nchw, c
 size_t srcgan_srdense_infer_ws_bytes(const srcgan_srdense_cfg* c);
 int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
+/* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
+ * when strides and bases allow them, element by element otherwise).
+ *   srcgan_maxpool2_nhwc:     nn.MaxPool2d(2, 2), ceil_mode = False: [B,H,W,C] -> [B,H/2,W/2,C]; an odd last row / column is dropped.
+ *   srcgan_maxpool2_bwd_nhwc: dx = its gradient.  The argmax is recomputed from x (no index tensor): the first maximum of a window in
+ *                             the order (0,0), (0,1), (1,0), (1,1) takes dy (torch's strict >).  Channels [0,C) of EVERY pixel of dx are
+ *                             written exactly once (a dropped row / column gets zeros): no memset, no atomics.  relu_mask = 1: x is a
+ *                             post-ReLU activation and dx is the gradient w.r.t. its pre-activation (zero where the maximum is not > 0).
+ *   srcgan_feat_loss_fwd:     out_sum[0] = sum over npix pixels and channels [0,C) of |a - b| (kind 0) or (a - b)^2 (kind 1), accumulated
+ *                             in f32 in two stages of fixed order (deterministic).  scratch: srcgan_loss_scratch_floats() floats.
+ *   srcgan_feat_loss_bwd:     g = (accumulate ? g : 0) + scale * sign(a - b) (kind 0, sign(0) = 0) or scale * 2 (a - b) (kind 1). */
+int srcgan_maxpool2_nhwc(const void* src, int s_cs, void* dst, int d_cs, int B, int H, int W, int C, int dtype, void* stream);
+int srcgan_maxpool2_bwd_nhwc(const void* dy, int dy_cs, const void* x, int x_cs, void* dx, int dx_cs, int B, int H, int W, int C,
+                             int relu_mask, int dtype, void* stream);
+int srcgan_feat_loss_fwd(int kind, const void* a, int a_cs, const void* b, int b_cs, long npix, int C, int dtype,
+                         float* out_sum, float* scratch, void* stream);
+int srcgan_feat_loss_bwd(int kind, const void* a, int a_cs, const void* b, int b_cs, void* g, int g_cs, int accumulate, float scale,
+                         long npix, int C, int dtype, void* stream);
+
+/* Perceptual losses on a frozen VGG feature extractor (reference src/losses.py:344-393, 455-470), on the op-list executor.
+ *   kind 0: VGG16Loss -- torchvision vgg16.features[0:23] (ten 3x3 convolutions + ReLU, three max-pools); the loss is the mean over
+ *           the taps relu1_2, relu2_2, relu3_3, relu4_3 of the L1 mean between the two branches' features.
+ *   kind 1: PerceptionLoss -- vgg19.features[0:35]: sixteen convolutions, four max-pools, ending at conv5_4 WITHOUT its ReLU; one tap,
+ *           MSE.  H, W >= 16 (kind 0: >= 8).
+ * out_nchw / tgt_nchw: [B,3,H,W] f32 NCHW.  params: weight, bias of every convolution in order (f32, canonical layout); frozen: there
+ * are no parameter gradients.  forward keeps the output branch's activations in ws (the target branch runs on a slot-planned region
+ * that retains only its taps) and writes the loss to loss_out (device f32); backward writes d loss / d out * gout_dev[0] * gscale to
+ * dout_nchw.  Inside the backward gradients travel at unit scale (tap k contributes sign(a - b) * N_1 / N_k, resp. 2 (a - b)); the
+ * factor 1 / (ntaps * N_1) is applied in the final f32 store, so 16-bit gradients do not underflow at training sizes.
+ * infer: the same loss value (same launches, same bits) with both branches on slot-planned regions, for no_grad. */
+typedef struct srcgan_vggloss_cfg {
+    int kind;
+    int B, H, W;
+    int dtype;
+} srcgan_vggloss_cfg;
+int srcgan_vggloss_num_params(const srcgan_vggloss_cfg* c);
+size_t srcgan_vggloss_ws_bytes(const srcgan_vggloss_cfg* c);
+size_t srcgan_vggloss_bwd_scratch_bytes(const srcgan_vggloss_cfg* c);
+int srcgan_vggloss_forward(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
+                           float* loss_out, void* stream);
+int srcgan_vggloss_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws,
+                            void* scratch, float* dout_nchw, void* stream);
+size_t srcgan_vggloss_infer_ws_bytes(const srcgan_vggloss_cfg* c);
+int srcgan_vggloss_infer(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
+                         float* loss_out, void* stream);
+
 /* nn.PixelShuffle(r) on NHWC (espcn.py:44,50): src [B,H,W,C*r*r] -> dst [B,H*r,W*r,C]; inverse = 1: the adjoint, src [B,H*r,W*r,C]
  * -> dst [B,H,W,C*r*r].  srcgan_mask_inplace: g *= (act > 0 ? 1 : slope) over n elements (ReLU' / LeakyReLU' on an incoming gradient). */
 int srcgan_pixel_shuffle_nhwc(const void* src, int s_cs, void* dst, int d_cs, int B, int H, int W, int C, int r, int inverse,

@@ -103,6 +103,10 @@ class SrDenseCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "in_ch", "out_ch", "B", "H", "W", "dtype", "growth", "num_blocks", "num_layers", "up")]
 
 
+class VggLossCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kind", "B", "H", "W", "dtype")]
+
+
 class NLayerDCfg(C.Structure):
     _fields_ = [("in_ch", C.c_int), ("ndf", C.c_int), ("n_layers", C.c_int),
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("dtype", C.c_int), ("training", C.c_int), ("norm", C.c_int)]
@@ -177,6 +181,17 @@ SIGNATURES = {
     "srcgan_srdense_backward": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P, _P, _P]),
     "srcgan_srdense_infer_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
     "srcgan_srdense_infer": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
+    "srcgan_maxpool2_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "srcgan_maxpool2_bwd_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "srcgan_feat_loss_fwd": (_I, [_I, _P, _I, _P, _I, _L, _I, _I, _P, _P, _P]),
+    "srcgan_feat_loss_bwd": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _F, _L, _I, _I, _P]),
+    "srcgan_vggloss_num_params": (_I, [C.POINTER(VggLossCfg)]),
+    "srcgan_vggloss_ws_bytes": (_S, [C.POINTER(VggLossCfg)]),
+    "srcgan_vggloss_bwd_scratch_bytes": (_S, [C.POINTER(VggLossCfg)]),
+    "srcgan_vggloss_forward": (_I, [C.POINTER(VggLossCfg), _P, _P, _P, _P, _P, _P]),
+    "srcgan_vggloss_backward": (_I, [C.POINTER(VggLossCfg), _P, _F, _P, _P, _P, _P, _P]),
+    "srcgan_vggloss_infer_ws_bytes": (_S, [C.POINTER(VggLossCfg)]),
+    "srcgan_vggloss_infer": (_I, [C.POINTER(VggLossCfg), _P, _P, _P, _P, _P, _P]),
     "srcgan_pixel_shuffle_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_mask_inplace": (_I, [_P, _P, _F, _L, _I, _P]),
     "srcgan_metric_scratch_floats": (_I, [_I, _I, _I, _I]),

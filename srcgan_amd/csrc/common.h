@@ -137,4 +137,8 @@ void sg_pack_job_finish(SgPackJob& j, int dtype, long& blk_cursor);
 int sg_pack_multi_launch(const SgPackJob* jobs_dev, int njobs, long nblocks, void* wp_base, int dtype, hipStream_t st, const unsigned long long* guard = nullptr);
 // composed parity weights of ConvTranspose2d(64, 64, k2 s2, no bias) -> Conv2d(64, tar, 3x3 p1, no bias), written as four 2x2 packs of 8 rows
 int sg_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int tar, int dtype, hipStream_t st);
+// frozen VGG feature path (nets.hip -> vgg_loss.hip): out = sum_k sums[k] * weights[k] (host weights, n <= 4), and the final gradient
+// store: NHWC records of C <= 8 channels -> f32 NCHW, times gout[0] * gscale (gout on the device)
+int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, hipStream_t st);
+int sg_image_grad_store(const void* src, int cs, float* dst, int B, int C, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);
 int sg_fill_zero_guarded(void* p, size_t bytes, const unsigned long long* guard, hipStream_t st);     // guard == nullptr: plain hipMemsetAsync

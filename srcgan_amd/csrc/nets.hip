@@ -1261,6 +1261,7 @@ struct RdOp {
     int type;                 // 0 conv (+bias)(+ReLU), 1 GroupNorm(+res)(+ReLU), 2 ConvTranspose2d k2 s2, 3 PixelShuffle(r),
                               // 4 (inference plans only) ConvTranspose2d k2 s2 followed by a bias-free 3x3 conv, folded into four parity 2x2 convs
                               // 5 ConvTranspose2d k3 s2 p1 output_padding 1 + bias + ReLU (deconv_k3s2.hip)
+                              // 6 MaxPool2d(2, 2) (vgg_loss.hip)
     int in, out, res, relu;
     int icoff, iC, ocoff, oC; // type 0 on a dense buffer: reads channels [icoff, icoff + iC) of `in`, writes [ocoff, ocoff + oC) of `out` (iC / oC == 0: the whole tensor)
     int share;                // != 0: a module applied a second time -- op share - 1 owns the packs, this op's weight and bias gradients add to its
@@ -1287,11 +1288,13 @@ struct RdPlan {
     size_t wpack;             // inference plans: bytes of the packed-weight part
     std::vector<size_t> g;    // backward: gradient buffer offsets (scratch), same shapes as T
     size_t slab, gnscr, colscr, btmp, bwd_total;      // btmp: a bias gradient on its way to being added (second use of a shared module)
+    std::vector<int> taps;    // tensors whose last reader is a loss behind the walk (frozen feature extractors): the slot planner keeps them
 };
 
 struct RdBuilder {
     RdPlan& P; Bump b; int np = 0; int B;
     int inorm = 0;            // normalisation layers are InstanceNorm2d (no parameters) instead of GroupNorm(32, C)
+    int frozen = 0;           // no parameter takes a gradient and the ops form a chain: the backward scratch is two alternating gradient buffers
     RdBuilder(RdPlan& p, int B_) : P(p), B(B_) {}
     int tensor(int C, int cs, int H, int W, int act = 0) { P.T.push_back(RdT{C, cs, H, W, act, b.take((size_t)B * H * W * cs * P.esz)}); return (int)P.T.size() - 1; }
     int conv(int in, int cout, int k, int s, int pad, bool bias = false, bool relu = false) {
@@ -1342,6 +1345,14 @@ struct RdBuilder {
         o.out = tensor(ti.C / (r * r), ti.C / (r * r), ti.H * r, ti.W * r);
         P.ops.push_back(o); return o.out;
     }
+    int pool(int in) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 6; o.in = in; o.res = -1; o.k = 2; o.s = 2; o.w = -1; o.bias = -1;
+        o.out = tensor(ti.C, ti.cs, ti.H / 2, ti.W / 2);
+        P.ops.push_back(o); return o.out;
+    }
+    void tap(int t) { P.taps.push_back(t); }
     // BasicBlock (resdeconv.py:56-97).  state_dict order inside a block: conv1, bn1, conv2, bn2, downsample.{0,1}
     int block(int x, int planes, int stride) {
         const bool ds = stride != 1 || P.T[x].C != planes;
@@ -1393,6 +1404,15 @@ struct RdBuilder {
         // backward scratch
         Bump s;
         P.g.resize(P.T.size());
+        if (frozen) {       // op k maps tensor k to tensor k + 1, and a gradient is dead once its op has run: even and odd tensors share a buffer each
+            size_t mx = 0;
+            for (const RdT& t : P.T) mx = std::max(mx, (size_t)B * t.H * t.W * t.cs * P.esz);
+            const size_t g0 = s.take(mx), g1 = s.take(mx);
+            for (size_t i = 0; i < P.T.size(); ++i) P.g[i] = (i & 1) ? g1 : g0;
+            P.slab = P.gnscr = P.colscr = P.btmp = 0;
+            P.bwd_total = s.off + 256;
+            return;
+        }
         long maxpix = 1;
         for (size_t i = 0; i < P.T.size(); ++i) {
             P.g[i] = s.take((size_t)B * P.T[i].H * P.T[i].W * P.T[i].cs * P.esz);
@@ -1551,10 +1571,9 @@ static int sd_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
-static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, const char* tag, void* st) {
-    SG_REQUIRE(x_nchw && params && ws && y_nchw, "%s forward: null pointer", tag);
-    SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s forward: workspace must be 256-byte aligned", tag);
-    const int dt = P.dtype, B = P.B;
+// the forward in three parts (a frozen feature extractor packs once and walks twice, on two inputs)
+static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, const char* tag, void* st) {
+    const int dt = P.dtype;
     char* w8 = (char*)ws; char* wp = w8 + P.wpk;
     PackList packs(dt, wp);
     for (const RdOp& o : P.ops) {
@@ -1570,6 +1589,11 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
     SG_TRY(packs.run(key, params[0], st));
     for (const RdOp& o : P.ops)      // composed weights of a folded tail: made from both sources on every call, like the packs above
         if (o.type == 4) SG_TRY(sg_fold_tail_pack(params[o.w], params[o.w2], wp + o.wf[0], P.T[o.out].C, dt, (hipStream_t)st));
+    return 0;
+}
+static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, void* st) {
+    const int dt = P.dtype, B = P.B;
+    char* w8 = (char*)ws; char* wp = w8 + P.wpk;
     SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, P.in_ch, P.H, P.W, P.in_cs, dt, st));
     float* gnscr = (float*)(w8 + P.gnfwd);
     for (const RdOp& o : P.ops) {
@@ -1600,6 +1624,8 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
             cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0], params[o.bias]).out(out, ti.H, ti.W, to.C).pad(1, 1).scatter(2, 0, 0, to.H, to.W).lrelu();
             cv.d.slope = 0.f; cv.d.npar = 4; cv.d.wpar_stride = (long)(o.wf[1] - o.wf[0]);
             SG_TRY(cv.run(st));
+        } else if (o.type == 6) {
+            SG_TRY(srcgan_maxpool2_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, ti.C, dt, st));
         } else {
             // folded tail: output pixel (2i + a, 2j + b) = 2x2 window of the half-resolution input at (i + a - 1, j + b - 1) times the
             // composed weights of parity (a, b) -- the geometry of the 4x4 stride-2 input gradient, so its four-parity kernel serves.
@@ -1610,8 +1636,15 @@ static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* 
             SG_TRY(cv.run(st));
         }
     }
+    return 0;
+}
+static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, const char* tag, void* st) {
+    SG_REQUIRE(x_nchw && params && ws && y_nchw, "%s forward: null pointer", tag);
+    SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s forward: workspace must be 256-byte aligned", tag);
+    SG_TRY(rd_pack_fwd(P, params, ws, tag, st));
+    SG_TRY(rd_walk(P, x_nchw, params, ws, st));
     const RdT& last = P.T.back();
-    SG_TRY(srcgan_nhwc_to_nchw_f32(w8 + last.off, y_nchw, B, P.out_ch, last.H, last.W, last.cs, 0, dt, st));
+    SG_TRY(srcgan_nhwc_to_nchw_f32((char*)ws + last.off, y_nchw, P.B, P.out_ch, last.H, last.W, last.cs, 0, P.dtype, st));
     return 0;
 }
 
@@ -1641,6 +1674,7 @@ static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare =
     std::vector<int> last(nt, -1);
     for (int k = 0; k < nops; ++k) { last[P.ops[k].in] = k; if (P.ops[k].res >= 0) last[P.ops[k].res] = k; }
     last[nt - 1] = nops;                                       // the output conversion reads the last tensor
+    for (int t : P.taps) last[t] = nops;                       // a tap's last reader is the loss, behind the walk
     Bump b;
     std::map<size_t, std::vector<size_t>> pool;                // byte size -> free slots
     auto get = [&](int t) {
@@ -1715,9 +1749,14 @@ static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
     return n;
 }
 
+// A loss that sits behind the walk and reads the plan's taps (P.taps[k]) against a second branch's: the backward starts from it instead of
+// from dy_nchw.  Tap k adds scale[k] * d|a - b| (kind 0) or scale[k] * d(a - b)^2 (kind 1) to its tensor's gradient; the input gradient
+// leaves as f32 NCHW times gout[0] * gscale.
+struct RdTapLoss { int kind; const RdPlan* Pb; float scale[4]; const float* gout; float gscale; };
+
 static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, const float* const* params, void* ws, void* scratch, float* const* grads,
-                       const char* tag, void* st) {
-    SG_REQUIRE(dy_nchw && params && ws && scratch && grads, "%s backward: null pointer", tag);
+                       const char* tag, void* st, const RdTapLoss* tl = nullptr) {
+    SG_REQUIRE((dy_nchw || tl) && params && ws && scratch && grads, "%s backward: null pointer", tag);
     SG_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)scratch % 256) == 0, "%s backward: buffers must be 256-byte aligned", tag);
     const int dt = P.dtype, B = P.B;
     char* w8 = (char*)ws; char* s8 = (char*)scratch; char* wp = w8 + P.wpk;
@@ -1744,7 +1783,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
     }
     std::vector<char> written(P.T.size(), 0), seen_param(P.nparams + 2, 0);
     auto gt = [&](int id) { return tref(s8 + P.g[id], P.T[id].cs); };
-    {
+    if (!tl) {
         const RdT& last = P.T.back();
         const int id = (int)P.T.size() - 1;
         SG_TRY(srcgan_nchw_f32_to_nhwc(dy_nchw, s8 + P.g[id], B, P.out_ch, last.H, last.W, last.cs, dt, st));
@@ -1754,6 +1793,15 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
     for (int k = (int)P.ops.size() - 1; k >= 0; --k) {
         const RdOp& o = P.ops[k];
         const RdT ti = P.T[o.in], to = P.T[o.out];
+        auto tap_of = [&](int t) { if (tl) for (size_t i = 0; i < P.taps.size(); ++i) if (P.taps[i] == t) return (int)i; return -1; };
+        if (const int tk = tap_of(o.out); tk >= 0) {       // (a frozen chain: one op per tensor, so this runs once per tap)
+            const RdT tb = tl->Pb->T[o.out];
+            SG_TRY(srcgan_feat_loss_bwd(tl->kind, w8 + to.off, to.cs, w8 + tb.off, tb.cs, s8 + P.g[o.out], to.cs, written[o.out], tl->scale[tk],
+                                        (long)B * to.H * to.W, to.C, dt, st));
+            // the stored gradient of an activated tensor is the one w.r.t. its pre-activation (a pool behind a tap leaves the mask to this pass)
+            if (to.act) SG_TRY(srcgan_mask_inplace(s8 + P.g[o.out], w8 + to.off, 0.f, (long)B * to.H * to.W * to.cs, dt, st));
+            written[o.out] = 1;
+        }
         SG_REQUIRE(written[o.out], "%s backward: internal error (gradient of tensor %d missing)", tag, o.out);
         const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
         TRef xin = sl(rd_t(w8, ti), o.icoff), dy = sl(gt(o.out), o.ocoff);
@@ -1835,6 +1883,10 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
             SG_TRY(cv.run(st));
             written[o.in] = 1;
+        } else if (o.type == 6) {
+            SG_REQUIRE(!acc, "%s backward: internal error (pooled tensor with two consumers)", tag);
+            SG_TRY(srcgan_maxpool2_bwd_nhwc(dy.p, to.cs, xin.p, ti.cs, dx.p, ti.cs, B, ti.H, ti.W, ti.C, ti.act && tap_of(o.in) < 0, dt, st));
+            written[o.in] = 1;
         } else {
             SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (PixelShuffle input)", tag);
             SG_TRY(srcgan_pixel_shuffle_nhwc(dy.p, to.cs, dx.p, ti.cs, B, ti.H, ti.W, to.C, o.k, 1, dt, st));
@@ -1843,6 +1895,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
     }
     if (dx_nchw) {       // gradient w.r.t. the network input (an end-to-end cascade: trainCas.py:108 feeds one network's output to the next)
         SG_REQUIRE(written[0], "%s backward: internal error (no input gradient was produced)", tag);
+        if (tl) return sg_image_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B, P.in_ch, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
         SG_TRY(srcgan_nhwc_to_nchw_f32(s8 + P.g[0], dx_nchw, B, P.in_ch, P.H, P.W, P.in_cs, 0, dt, st));
     }
     return 0;
@@ -1936,4 +1989,139 @@ extern "C" int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_
     RdPlan P;
     SG_TRY(sd_infer_plan(c, P));
     return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind ? "srdenseB_infer" : "srdenseA_infer", st);
+}
+
+// ======================================================================================== frozen VGG feature losses
+// losses.VGG16Loss (reference src/losses.py:344-393) and losses.PerceptionLoss (:455-470): torchvision's VGG16 / VGG19 `features` prefix as an
+// op list of 3x3 convolutions (+ bias + ReLU) and max-pools, walked twice with one set of packs -- on the network's output, whose
+// activations stay for the backward, and on the target, on a slot-planned region that keeps only the taps -- and one feature-distance
+// reduction per tap.  Frozen: the backward launches input gradients only, on two alternating gradient buffers, at unit scale (see
+// include/srcgan_amd.h).
+namespace {
+struct VggPlan {
+    RdPlan P, Pt;             // output branch (every activation kept) / target branch (slot-planned, offsets inside the same workspace)
+    int kind, ntap;
+    size_t sums, lscr, total;
+    float wsum[4];            // loss = sum_k wsum[k] * sum|a_k - b_k|  (1 / (ntaps N_k))
+    float gscale[4], gfinal;  // tap k's gradient factor inside the backward (N_1 / N_k), and the one of the final store (1 / (ntaps N_1))
+};
+
+// move a slot-planned plan's activation part to `base` of a workspace whose packs are another plan's
+static void vgg_rebase(RdPlan& Q, size_t base, const RdPlan& packs) {
+    for (RdT& t : Q.T) t.off += base;
+    Q.xin += base; Q.gnfwd += base;
+    for (size_t k = 0; k < Q.ops.size(); ++k) memcpy(Q.ops[k].wf, packs.ops[k].wf, sizeof(Q.ops[k].wf));
+    Q.wpk = packs.wpk;
+}
+
+static int vgg_plan(const srcgan_vggloss_cfg* c, bool infer, VggPlan& V) {
+    SG_REQUIRE(c, "vggloss: null cfg");
+    RdPlan& P = V.P;
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "vggloss"));
+    SG_REQUIRE(c->kind == 0 || c->kind == 1, "vggloss: kind must be 0 (VGG16Loss) or 1 (PerceptionLoss)");
+    const int minhw = c->kind == 0 ? 8 : 16;
+    SG_REQUIRE(c->H >= minhw && c->W >= minhw, "vggloss: H and W must be at least %d (%d max-pools)", minhw, c->kind == 0 ? 3 : 4);
+    V.kind = c->kind;
+    RdBuilder nb(P, c->B);
+    nb.frozen = 1;
+    nb.input(3, c->H, c->W);
+    int t = 0;
+    if (c->kind == 0) {       // vgg16.features[0:23]; taps behind indices 3, 8, 15, 22 (losses.py:354-361, 381-393)
+        const int width[4] = {64, 128, 256, 512}, nconv[4] = {2, 2, 3, 3};
+        for (int s = 0; s < 4; ++s) {
+            if (s) t = nb.pool(t);
+            for (int k = 0; k < nconv[s]; ++k) t = nb.conv(t, width[s], 3, 1, 1, true, true);
+            nb.tap(t);
+        }
+    } else {                  // vgg19.features[0:35]: conv5_4 without its ReLU (losses.py:459-468)
+        const int width[5] = {64, 128, 256, 512, 512}, nconv[5] = {2, 2, 4, 4, 4};
+        for (int s = 0; s < 5; ++s) {
+            if (s) t = nb.pool(t);
+            for (int k = 0; k < nconv[s]; ++k) t = nb.conv(t, width[s], 3, 1, 1, true, !(s == 4 && k == 3));
+        }
+        nb.tap(t);
+    }
+    nb.finish(c->dtype);
+    V.ntap = (int)P.taps.size();
+    const RdT t1 = P.T[P.taps[0]];
+    const double n1 = (double)c->B * t1.C * t1.H * t1.W;
+    for (int k = 0; k < V.ntap; ++k) {
+        const RdT tk = P.T[P.taps[k]];
+        const double nk = (double)c->B * tk.C * tk.H * tk.W;
+        V.wsum[k] = (float)(1.0 / (V.ntap * nk));
+        V.gscale[k] = (float)(n1 / nk);
+    }
+    V.gfinal = (float)(1.0 / (V.ntap * n1));
+    const size_t packs = P.total - P.wpk;
+    V.Pt = P;
+    SG_TRY(rd_infer_replan(V.Pt, false, "vggloss"));
+    const size_t slot_bytes = V.Pt.act_bytes;
+    if (infer) {              // both branches on slot-planned regions, the packs laid out by the replan (forward packs only)
+        const size_t ipacks = V.Pt.total - V.Pt.wpk;
+        P = V.Pt;
+        Bump b;
+        b.take(slot_bytes);
+        const size_t tgt = b.take(slot_bytes);
+        V.sums = b.take(4 * sizeof(float));
+        V.lscr = b.take((size_t)srcgan_loss_scratch_floats() * sizeof(float));
+        P.wpk = b.off;
+        vgg_rebase(V.Pt, tgt, P);
+        V.total = align_up(b.off + ipacks, 256);
+        return 0;
+    }
+    Bump b;
+    b.take(P.act_bytes);
+    const size_t tgt = b.take(slot_bytes);
+    V.sums = b.take(4 * sizeof(float));
+    V.lscr = b.take((size_t)srcgan_loss_scratch_floats() * sizeof(float));
+    P.wpk = b.off;
+    vgg_rebase(V.Pt, tgt, P);
+    V.total = align_up(b.off + packs, 256);
+    return 0;
+}
+
+static int vgg_forward(const VggPlan& V, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws, float* loss_out,
+                       const char* tag, void* st) {
+    SG_REQUIRE(out_nchw && tgt_nchw && params && ws && loss_out, "%s: null pointer", tag);
+    SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", tag);
+    const RdPlan& P = V.P;
+    char* w8 = (char*)ws;
+    SG_TRY(rd_pack_fwd(P, params, ws, tag, st));
+    SG_TRY(rd_walk(P, out_nchw, params, ws, st));
+    SG_TRY(rd_walk(V.Pt, tgt_nchw, params, ws, st));
+    float* sums = (float*)(w8 + V.sums);
+    for (int k = 0; k < V.ntap; ++k) {
+        const RdT a = P.T[P.taps[k]], b = V.Pt.T[P.taps[k]];
+        SG_TRY(srcgan_feat_loss_fwd(V.kind, w8 + a.off, a.cs, w8 + b.off, b.cs, (long)P.B * a.H * a.W, a.C, P.dtype, sums + k, (float*)(w8 + V.lscr), st));
+    }
+    return sg_vgg_combine(sums, V.wsum, V.ntap, loss_out, (hipStream_t)st);
+}
+}  // namespace
+
+extern "C" int srcgan_vggloss_num_params(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return -1; return V.P.nparams; }
+extern "C" size_t srcgan_vggloss_ws_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return 0; return V.total; }
+extern "C" size_t srcgan_vggloss_infer_ws_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, true, V)) return 0; return V.total; }
+extern "C" size_t srcgan_vggloss_bwd_scratch_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return 0; return V.P.bwd_total; }
+extern "C" int srcgan_vggloss_forward(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
+                                      float* loss_out, void* st) {
+    VggPlan V;
+    SG_TRY(vgg_plan(c, false, V));
+    return vgg_forward(V, out_nchw, tgt_nchw, params, ws, loss_out, c->kind ? "vgg19loss" : "vgg16loss", st);
+}
+extern "C" int srcgan_vggloss_infer(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
+                                    float* loss_out, void* st) {
+    VggPlan V;
+    SG_TRY(vgg_plan(c, true, V));
+    return vgg_forward(V, out_nchw, tgt_nchw, params, ws, loss_out, c->kind ? "vgg19loss_infer" : "vgg16loss_infer", st);
+}
+extern "C" int srcgan_vggloss_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws,
+                                       void* scratch, float* dout_nchw, void* st) {
+    VggPlan V;
+    SG_TRY(vgg_plan(c, false, V));
+    SG_REQUIRE(gout_dev && dout_nchw, "vggloss backward: null pointer");
+    RdTapLoss tl;
+    tl.kind = V.kind; tl.Pb = &V.Pt; tl.gout = gout_dev; tl.gscale = gscale * V.gfinal;
+    for (int k = 0; k < 4; ++k) tl.scale[k] = k < V.ntap ? V.gscale[k] : 0.f;
+    std::vector<float*> nograds(V.P.nparams, nullptr);       // frozen: every parameter gradient is skipped
+    return rd_backward(V.P, nullptr, dout_nchw, params, ws, scratch, nograds.data(), c->kind ? "vgg19loss" : "vgg16loss", st, &tl);
 }

@@ -3,21 +3,28 @@
   L1Loss / MSELoss / PSNRLoss  <- reference src/losses.py:95-105,123-133,136-147
   GANLoss                      <- reference src/train.py:67-128 (only 'lsgan' is ever constructed, :186)
   DSSIMLoss                    <- reference src/losses.py:170-180 (on SSIM, :20-93)
+  VGG16Loss / PerceptionLoss   <- reference src/losses.py:344-393, 455-470 (frozen VGG16 / VGG19 features; weights come from the caller)
 
 Each forward is one native two-stage reduction (wavefront shuffles + fixed-order final sum,
 elementwise.hip) returning a 0-dim device tensor; backward is one fused elementwise kernel
 (sign(a-b)/N or 2(a-b)/N times the upstream gradient read from device memory -> no host sync).
 DSSIMLoss reuses the SSIM metric's range and tile kernels plus one fold for its forward; its backward is one fused
 stencil pass (metrics.hip, dssim_bwd_k) that recomputes the window statistics per output tile.
+The perceptual losses run a frozen VGG feature extractor on the op-list executor (nets.hip, srcgan_vggloss_*): one native forward
+over both branches and one native backward that carries input gradients only.
 """
 from __future__ import annotations
+
+import ctypes as C
+import os
+import warnings
 
 import torch
 import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss"]
+__all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss"]
 
 _K_L1, _K_MSE, _K_LABEL, _K_BCE, _K_SIGNED = 0, 1, 2, 3, 4       # srcgan_loss_fwd kinds; >= 2: scalar label instead of a target tensor
 
@@ -175,3 +182,166 @@ class DSSIMLoss(nn.Module):
         N.require_cuda(output, "DSSIMLoss output")
         N.require_cuda(target, "DSSIMLoss target")
         return _DSSIMFn.apply(output, target)
+
+
+# ------------------------------------------------------------------------------------------------ perceptual losses
+# torchvision's `features` layouts: 'M' = MaxPool2d(2, 2), a number = Conv2d(., n, 3, padding=1) followed by ReLU(inplace=True)
+_VGG16_FEATURES = (64, 64, "M", 128, 128, "M", 256, 256, 256, "M", 512, 512, 512)                                  # features[0:23]
+_VGG19_FEATURES = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512)     # features[0:36]
+_VGG16_SLICES = ((0, 4), (4, 9), (9, 16), (16, 23))       # losses.py:354-361
+
+
+def _vgg_layers(layout):
+    """[(features index, module)] of a torchvision VGG `features` layout."""
+    out, cin = [], 3
+    for v in layout:
+        if v == "M":
+            out.append((len(out), nn.MaxPool2d(kernel_size=2, stride=2)))
+        else:
+            out.append((len(out), nn.Conv2d(cin, v, kernel_size=3, padding=1)))
+            out.append((len(out), nn.ReLU(inplace=True)))
+            cin = v
+    return out
+
+
+def _load_vgg_weights(module, weights, rename):
+    """``weights``: a state dict under the module's own keys or torchvision's ``features.N.*`` keys (anything else in it, such as
+    the classifier, is ignored), or a local path to one saved with ``torch.save``."""
+    if isinstance(weights, (str, os.PathLike)):
+        weights = torch.load(os.fspath(weights), map_location="cpu")
+    if not hasattr(weights, "items"):
+        raise TypeError(f"{type(module).__name__}: weights must be a state dict or a local path to one, got {type(weights).__name__}")
+    own = module.state_dict()
+    picked = {}
+    for k, v in weights.items():
+        k = k if k in own else rename.get(k)
+        if k in own:
+            picked[k] = v
+    missing = [k for k in own if k not in picked]
+    if missing:
+        raise KeyError(f"{type(module).__name__}: weights lack {missing[:4]}{' ...' if len(missing) > 4 else ''}")
+    module.load_state_dict(picked)
+
+
+class _VggLossFn(torch.autograd.Function):
+    """One native forward over both branches and one native backward w.r.t. ``output``; the parameters are frozen."""
+
+    @staticmethod
+    def forward(ctx, output, target, kind, dtype, plist):
+        lib = N.lib()
+        o32, t32 = _as_f32(output, "perceptual loss output"), _as_f32(target, "perceptual loss target")
+        B, _, H, W = o32.shape
+        cfg = N.VggLossCfg(kind, B, H, W, dtype)
+        ws = N.workspace(lib.srcgan_vggloss_ws_bytes(C.byref(cfg)), o32.device)
+        out = torch.empty((), dtype=torch.float32, device=o32.device)
+        N.check(lib.srcgan_vggloss_forward(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), N.ptr_array(plist), ws.data_ptr(), out.data_ptr(),
+                                           N.stream_ptr(o32.device)), "srcgan_vggloss_forward")
+        ctx.cfg, ctx.ws, ctx.plist, ctx.in_dtype = cfg, ws, plist, output.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib, cfg = N.lib(), ctx.cfg
+        if ctx.ws is None:
+            raise RuntimeError("perceptual loss: backward called a second time (the workspace of the forward is released by the first)")
+        gout = gout.contiguous().float()
+        dev = ctx.ws.device
+        scratch = N.workspace(lib.srcgan_vggloss_bwd_scratch_bytes(C.byref(cfg)), dev)
+        dout = torch.empty((cfg.B, 3, cfg.H, cfg.W), dtype=torch.float32, device=dev)
+        N.check(lib.srcgan_vggloss_backward(C.byref(cfg), gout.data_ptr(), 1.0, N.ptr_array(ctx.plist), ctx.ws.data_ptr(), scratch.data_ptr(),
+                                            dout.data_ptr(), N.stream_ptr(dev)), "srcgan_vggloss_backward")
+        ctx.ws = None
+        return dout.to(ctx.in_dtype), None, None, None, None
+
+
+class _VggLossBase(nn.Module):
+    _kind = 0
+
+    def _init_weights(self, weights, rename):
+        for p in self.parameters():
+            p.requires_grad = False
+        if weights is None:
+            warnings.warn(f"{type(self).__name__}: no weights given -- the feature extractor keeps its seeded default initialisation. Nothing is "
+                          "downloaded here: pass weights= (a torchvision VGG state dict or a local path to one) for the pretrained loss.", stacklevel=3)
+        else:
+            _load_vgg_weights(self, weights, rename)
+
+    def forward(self, output, target):
+        name = type(self).__name__
+        if output.dim() != 4 or target.dim() != 4 or output.shape != target.shape:
+            raise ValueError(f"{name}: expected two [B,C,H,W] tensors of one shape, got {tuple(output.shape)} and {tuple(target.shape)}")
+        if output.shape[1] not in (1, 3):
+            raise ValueError(f"{name}: inputs must have 1 or 3 channels, got {output.shape[1]}")
+        if target.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(f"{name}: the target branch is frozen (it keeps no activations): detach the target")
+        N.require_cuda(output, f"{name} output")
+        N.require_cuda(target, f"{name} target")
+        if output.shape[1] == 1:       # losses.py:378-380: autograd sums the three gradients
+            output = torch.cat([output, output, output], dim=1)
+            target = torch.cat([target, target, target], dim=1)
+        plist = tuple(p.detach() for p in self.parameters())
+        for p in plist:
+            if p.device != output.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"{name}: parameters must be contiguous float32 tensors on {output.device} (move the loss with .to(device))")
+        if torch.is_grad_enabled() and output.requires_grad:
+            return _VggLossFn.apply(output, target, self._kind, self._dtype, plist)
+        lib = N.lib()
+        o32, t32 = _as_f32(output, f"{name} output"), _as_f32(target, f"{name} target")
+        B, _, H, W = o32.shape
+        cfg = N.VggLossCfg(self._kind, B, H, W, self._dtype)
+        ws = N.workspace(lib.srcgan_vggloss_infer_ws_bytes(C.byref(cfg)), o32.device)
+        out = torch.empty((), dtype=torch.float32, device=o32.device)
+        N.check(lib.srcgan_vggloss_infer(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), N.ptr_array(plist), ws.data_ptr(), out.data_ptr(),
+                                         N.stream_ptr(o32.device)), "srcgan_vggloss_infer")
+        return out
+
+
+class VGG16Loss(_VggLossBase):
+    """Mean over relu1_2, relu2_2, relu3_3, relu4_3 of the L1 distance between the VGG16 features of ``output`` and ``target``
+    (losses.py:344-393).  ``VGG16Loss(requires_grad=False, cuda=True, *, weights=None, dtype=None)``; the parameters are frozen
+    ``nn.Parameter``s under the reference's keys (``slice1.0.weight`` ... ``slice4.21.bias``), so a checkpoint of the reference loss
+    loads with ``load_state_dict``.  ``weights``: that state dict, torchvision's ``vgg16`` state dict (``features.N.*``), or a local
+    path to either; nothing is downloaded, and without weights the seeded default initialisation stays (with a warning).
+    ``forward(output, target)``: [B,1|3,H,W] CUDA tensors, H, W >= 8 -> 0-dim f32 device tensor; the gradient reaches ``output`` only.
+    Under ``no_grad`` (or when ``output`` needs no gradient) both branches run on slot-planned workspaces (same bits)."""
+    _kind = 0
+
+    def __init__(self, requires_grad=False, cuda=True, *, weights=None, dtype=None):
+        super().__init__()
+        if requires_grad:
+            raise NotImplementedError("VGG16Loss: the native feature extractor is frozen (no weight-gradient launches): requires_grad=True is not implemented")
+        self._dtype = N.dtype_id(dtype)
+        layers = _vgg_layers(_VGG16_FEATURES)
+        rename = {}
+        for k, (lo, hi) in enumerate(_VGG16_SLICES):
+            seq = nn.Sequential()
+            for idx, m in layers[lo:hi]:
+                seq.add_module(str(idx), m)
+                for leaf in ("weight", "bias"):
+                    rename[f"features.{idx}.{leaf}"] = f"slice{k + 1}.{idx}.{leaf}"
+            setattr(self, f"slice{k + 1}", seq)
+        self._init_weights(weights, rename)
+        if cuda and torch.cuda.is_available():
+            self.cuda()
+
+    def __repr__(self):
+        return "VGG16"
+
+
+class PerceptionLoss(_VggLossBase):
+    """MSE between the VGG19 ``features[:35]`` (conv5_4, before its ReLU) of ``input`` and ``target`` (losses.py:455-470).
+    ``PerceptionLoss(feature_layer=35, *, weights=None, dtype=None)``; frozen parameters under ``features.0.weight`` ...
+    ``features.34.bias`` (the reference's and torchvision's keys).  H, W >= 16.  Otherwise as ``VGG16Loss``; like the reference it is not
+    moved to a device by its constructor and keeps nn.Module's repr."""
+    _kind = 1
+
+    def __init__(self, feature_layer=35, *, weights=None, dtype=None):
+        super().__init__()
+        if feature_layer != 35:
+            raise NotImplementedError(f"PerceptionLoss: the native plan is vgg19.features[:35] (the reference's default); feature_layer={feature_layer} is not implemented")
+        self._dtype = N.dtype_id(dtype)
+        self.features = nn.Sequential()
+        for idx, m in _vgg_layers(_VGG19_FEATURES)[:35]:
+            self.features.add_module(str(idx), m)
+        self._init_weights(weights, {})
+
