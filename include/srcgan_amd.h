@@ -562,6 +562,29 @@ int srcgan_dssim_loss_fwd(const float* pred, const float* truth, int B, int C, i
 int srcgan_dssim_loss_bwd(const float* pred, const float* truth, int B, int C, int H, int W, const float* range,
                           const float* gout, float* dpred, float* dtruth, void* stream);
 
+/* Registration-tolerant pixel loss (losses.py:199-255, NearestSelector; with L1Loss at :522).  output / target: [B,C,H,W] f32 NCHW,
+ * contiguous.  n = 2 * shift; candidate k = i * n + j compares output[:, :, sd : sd + crop_h, sd : sd + crop_w] (sd = shift * stride)
+ * with target[:, :, i * stride : i * stride + crop_h, j * stride : j * stride + crop_w] (crop_h = H - 2 sd, crop_w = W - 2 sd in the
+ * loss; any crop that keeps every window inside the image is accepted).
+ *   srcgan_shift_search: diff[b][k] = sum over c, y, x of |target window - output crop| (f32 [B, n*n]); sel[b] = (k* / n, k* % n) of the
+ *                        FIRST minimum k* (int32 [B, 2]); loss (may be NULL) = sum_b diff[b][k*] / (B C crop_h crop_w), a device scalar.
+ *                        One pass over both tensors, no atomics, fixed summation order: two calls give the same bits.
+ *                        scratch: srcgan_shift_search_scratch_floats(...) floats (0 and an error string when the configuration is refused).
+ *                        Refused with an error string: shift > 4 (the n*n sums are kept in registers), a target window (tile + (n-1) *
+ *                        stride apron) that does not fit in LDS, an empty crop, a window that leaves the image.
+ *   srcgan_shift_gather: dst[b] = target[b, :, r*stride : r*stride + crop_h, c*stride : c*stride + crop_w] with (r, c) = sel[b] read on
+ *                        the device ([B,C,crop_h,crop_w] f32, a bit-exact copy).
+ *   srcgan_shift_l1_bwd: gradients of mean |output crop - selected target window|, full size [B,C,H,W] f32, overwritten: doutput =
+ *                        sign(o - t') * gout[0] * (1 / (float)N) inside the crop (N = B C crop_h crop_w, sign(0) = 0; the expression of
+ *                        srcgan_loss_bwd) and 0 on the border; dtarget (may be NULL) = -sign * g at each sample's window, 0 elsewhere. */
+size_t srcgan_shift_search_scratch_floats(int B, int C, int H, int W, int shift, int stride, int crop_h, int crop_w);
+int srcgan_shift_search(const float* output, const float* target, int B, int C, int H, int W, int shift, int stride, int crop_h,
+                        int crop_w, float* diff, int* sel, float* loss, float* scratch, void* stream);
+int srcgan_shift_gather(const float* target, const int* sel, int B, int C, int H, int W, int shift, int stride, int crop_h, int crop_w,
+                        float* dst, void* stream);
+int srcgan_shift_l1_bwd(const float* output, const float* target, const int* sel, int B, int C, int H, int W, int shift, int stride,
+                        int crop_h, int crop_w, const float* gout, float* doutput, float* dtarget, void* stream);
+
 /* Space-to-depth forms of an image-channel tensor for a 4x4 stride-2 pad-1 first layer (NLayerDiscriminator, model/model.py:612):
  * block (j,i) of the (H/2+1) x (W/2+1) grid = the 2x2 pixels (2j-1+dy, 2i-1+dx) as a 32-channel record [dy][dx][8], zero
  * outside the image / past C; the layer becomes a 2x2 stride-1 convolution with K = 4 x 32 and no padded K.

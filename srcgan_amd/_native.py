@@ -199,6 +199,10 @@ SIGNATURES = {
     "srcgan_metric_ssim": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "srcgan_dssim_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "srcgan_dssim_loss_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "srcgan_shift_search_scratch_floats": (_S, [_I, _I, _I, _I, _I, _I, _I, _I]),
+    "srcgan_shift_search": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "srcgan_shift_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "srcgan_shift_l1_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "srcgan_nchw_f32_to_s2d": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "srcgan_s2d_to_nchw_f32": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "srcgan_s2d_wgrad_unfold": (_I, [_P, _P, _I, _I, _I, _P]),

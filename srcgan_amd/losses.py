@@ -4,6 +4,7 @@
   GANLoss                      <- reference src/train.py:67-128 (only 'lsgan' is ever constructed, :186)
   DSSIMLoss                    <- reference src/losses.py:170-180 (on SSIM, :20-93)
   VGG16Loss / PerceptionLoss   <- reference src/losses.py:344-393, 455-470 (frozen VGG16 / VGG19 features; weights come from the caller)
+  NearestSelector              <- reference src/losses.py:199-255 (shift search + crops); NearestL1Loss = its use with L1Loss (:522), fused
 
 Each forward is one native two-stage reduction (wavefront shuffles + fixed-order final sum,
 elementwise.hip) returning a 0-dim device tensor; backward is one fused elementwise kernel
@@ -12,6 +13,8 @@ DSSIMLoss reuses the SSIM metric's range and tile kernels plus one fold for its 
 stencil pass (metrics.hip, dssim_bwd_k) that recomputes the window statistics per output tile.
 The perceptual losses run a frozen VGG feature extractor on the op-list executor (nets.hip, srcgan_vggloss_*): one native forward
 over both branches and one native backward that carries input gradients only.
+The shift search (shift_select.hip) reads both tensors once, accumulates every candidate offset in registers and leaves the selection on
+the device; NearestL1Loss takes its value from the search and never materialises a crop.
 """
 from __future__ import annotations
 
@@ -24,7 +27,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss"]
+__all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss", "NearestSelector", "NearestL1Loss"]
 
 _K_L1, _K_MSE, _K_LABEL, _K_BCE, _K_SIGNED = 0, 1, 2, 3, 4       # srcgan_loss_fwd kinds; >= 2: scalar label instead of a target tensor
 
@@ -182,6 +185,133 @@ class DSSIMLoss(nn.Module):
         N.require_cuda(output, "DSSIMLoss output")
         N.require_cuda(target, "DSSIMLoss target")
         return _DSSIMFn.apply(output, target)
+
+
+# ------------------------------------------------------------------------------------------------ shift-tolerant pixel loss
+def _shift_check(name, output, target, shift, stride, crop=None):
+    """Shape checks of the shift search, before any launch -> (B, C, H, W, crop_h, crop_w)."""
+    if not (isinstance(shift, int) and isinstance(stride, int) and shift >= 1 and stride >= 1):
+        raise ValueError(f"{name}: shift and stride must be integers >= 1, got shift={shift!r} stride={stride!r}")
+    if output.dim() != 4 or target.dim() != 4 or output.shape != target.shape:
+        raise ValueError(f"{name}: expected two [B,C,H,W] tensors of one shape, got {tuple(output.shape)} and {tuple(target.shape)}")
+    B, Cc, H, W = (int(v) for v in output.shape)
+    ch, cw = (H - 2 * shift * stride, W - 2 * shift * stride) if crop is None else (int(crop[0]), int(crop[1]))
+    if ch < 1 or cw < 1 or B < 1 or Cc < 1:
+        raise ValueError(f"{name}: empty crop {ch} x {cw} of a {tuple(output.shape)} tensor (shift={shift}, stride={stride})")
+    if (2 * shift - 1) * stride + ch > H or (2 * shift - 1) * stride + cw > W:
+        raise ValueError(f"{name}: the shifted {ch} x {cw} crops leave the {H} x {W} image (shift={shift}, stride={stride})")
+    N.require_cuda(output, f"{name} output")
+    N.require_cuda(target, f"{name} target")
+    return B, Cc, H, W, ch, cw
+
+
+def _shift_search(o32, t32, dims, shift, stride, want_loss):
+    """srcgan_shift_search on contiguous f32 tensors -> (diff [B,n*n] f32, sel [B,2] int32, loss or None), all on the device."""
+    lib = N.lib()
+    B, Cc, H, W, ch, cw = dims
+    dev = o32.device
+    nfl = lib.srcgan_shift_search_scratch_floats(B, Cc, H, W, shift, stride, ch, cw)
+    if nfl == 0:
+        N.check(1, "srcgan_shift_search")
+    scratch = torch.empty(nfl, dtype=torch.float32, device=dev)
+    diff = torch.empty((B, 4 * shift * shift), dtype=torch.float32, device=dev)
+    sel = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+    N.check(lib.srcgan_shift_search(o32.data_ptr(), t32.data_ptr(), B, Cc, H, W, shift, stride, ch, cw, diff.data_ptr(), sel.data_ptr(),
+                                    None if loss is None else loss.data_ptr(), scratch.data_ptr(), N.stream_ptr(dev)), "srcgan_shift_search")
+    return diff, sel, loss
+
+
+class NearestSelector(object):
+    """Shift search of the reference (losses.py:199-255), ``NearestSelector(shift=2, stride=1, criter='l1')``: per sample, the centre
+    crop of ``output`` is compared with ``target`` shifted by each of ``(2*shift)**2`` offsets ``(i*stride, j*stride)`` and the offset of
+    the smallest L1 sum is kept.  ``crop(output, target)`` -> ``(output_, target_)``: ``output_`` is the autograd slice view
+    ``output[:, :, sd:sd+ch, sd:sd+cw]`` (sd = shift*stride, ch = H - 2 sd, cw = W - 2 sd), ``target_`` the f32 copy of each sample's best
+    window, detached like the reference's search.  ``shift_diff`` returns the ``[B, (2*shift)**2]`` f32 sums.  [B,C,H,W] CUDA tensors
+    (other float dtypes compute in f32); shift <= 4.
+
+    Deviations from the reference, all deliberate:
+      * ``unravel_index`` uses integer (floor) division.  The reference writes ``index / cols``, which is true division on current
+        torch, so its ``crop`` raises ``TypeError: only integer tensors of a single element can be converted to an index``.
+      * the target window's column extent is ``cw``; the reference writes ``crop_row`` there (losses.py:254), equal for square images and
+        a shape error otherwise.
+      * the selection is never read on the host: the search, the selection and the copy of the window are device work
+        (shift_select.hip), so ``crop`` does not synchronise."""
+
+    def __init__(self, shift=2, stride=1, criter='l1'):
+        self.shift = shift
+        self.stride = stride
+        self.criter = criter
+
+    def __repr__(self):
+        return "NS"
+
+    @staticmethod
+    def unravel_index(tensor, cols):
+        """[nb, rows*cols] -> [nb, 2] int64 (row, column) of each row's first minimum."""
+        index = torch.argmin(tensor, dim=1).view(-1, 1)
+        return torch.cat([index // cols, index % cols], dim=1)
+
+    def shift_diff(self, output, target, crop_row, crop_col):
+        dims = _shift_check("NearestSelector", output, target, self.shift, self.stride, (crop_row, crop_col))
+        return _shift_search(_as_f32(output, "NearestSelector output"), _as_f32(target, "NearestSelector target"), dims, self.shift,
+                             self.stride, False)[0]
+
+    def crop(self, output, target):
+        dims = _shift_check("NearestSelector", output, target, self.shift, self.stride)
+        B, Cc, H, W, ch, cw = dims
+        lib = N.lib()
+        t32 = _as_f32(target, "NearestSelector target")
+        _, sel, _ = _shift_search(_as_f32(output, "NearestSelector output"), t32, dims, self.shift, self.stride, False)
+        target_ = torch.empty((B, Cc, ch, cw), dtype=torch.float32, device=t32.device)
+        N.check(lib.srcgan_shift_gather(t32.data_ptr(), sel.data_ptr(), B, Cc, H, W, self.shift, self.stride, ch, cw, target_.data_ptr(),
+                                        N.stream_ptr(t32.device)), "srcgan_shift_gather")
+        sd = self.shift * self.stride
+        return output[:, :, sd:sd + ch, sd:sd + cw], target_
+
+
+class _NearestL1Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target, shift, stride, dims):
+        o32, t32 = _as_f32(output, "NearestL1Loss output"), _as_f32(target, "NearestL1Loss target")
+        _, sel, loss = _shift_search(o32, t32, dims, shift, stride, True)
+        ctx.cfg = (shift, stride, dims)
+        ctx.dtypes = (output.dtype, target.dtype)
+        ctx.save_for_backward(o32, t32, sel)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = N.lib()
+        o32, t32, sel = ctx.saved_tensors
+        shift, stride, (B, Cc, H, W, ch, cw) = ctx.cfg
+        gout = gout.contiguous().float()
+        do = torch.empty_like(o32)                       # the kernel always produces the output's gradient
+        dt = torch.empty_like(t32) if ctx.needs_input_grad[1] else None
+        N.check(lib.srcgan_shift_l1_bwd(o32.data_ptr(), t32.data_ptr(), sel.data_ptr(), B, Cc, H, W, shift, stride, ch, cw, gout.data_ptr(),
+                                        do.data_ptr(), None if dt is None else dt.data_ptr(), N.stream_ptr(o32.device)), "srcgan_shift_l1_bwd")
+        do = do.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
+        return do, None if dt is None else dt.to(ctx.dtypes[1]), None, None, None
+
+
+class NearestL1Loss(nn.Module):
+    """``L1Loss()(*NearestSelector(shift, stride).crop(output, target))`` (losses.py:522) in one autograd Function: the forward is the
+    shift search itself (the loss is the sum of the per-sample minima over B*C*ch*cw), the backward one kernel that writes the full-size
+    gradients; no crop is materialised.  As in ``NearestSelector.crop`` the selection carries no gradient; the gradient reaches the
+    target (at each sample's selected window) only when the target requires one.  Returns a 0-dim f32 device tensor; forward and
+    backward never synchronise with the host."""
+
+    def __init__(self, shift=2, stride=1):
+        super().__init__()
+        self.shift = shift
+        self.stride = stride
+
+    def __repr__(self):
+        return "NSL1"
+
+    def forward(self, output, target):
+        dims = _shift_check("NearestL1Loss", output, target, self.shift, self.stride)
+        return _NearestL1Fn.apply(output, target, self.shift, self.stride, dims)
 
 
 # ------------------------------------------------------------------------------------------------ perceptual losses
