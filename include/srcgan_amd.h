@@ -646,6 +646,29 @@ int srcgan_tile_gather_ex(const void* src, int src_kind, int C, int H, int W, in
 int srcgan_tile_scatter_u8(const float* tiles_a, int Ca, const float* tiles_b, int Cb, unsigned char* dst_u8hwc, int H, int W, int up,
                            int T, int th, int tw, const int* rects, int mode, void* stream);
 
+/* ---- geometric self-ensemble: the D4 views of a tile and their fold (infer.py upscale_scene / cascade_scene, ensemble=) ----
+ * op = 0..7 numbers the dihedral group of the square: t = op & 1 (transpose), fy = (op >> 1) & 1 (mirror the view's rows), fx =
+ * (op >> 2) & 1 (mirror its columns).  The view of a window win[th][tw] is [Hv][Wv] = [tw][th] if t, else [th][tw], and
+ *   view[y][x] = win[a][b],  y' = fy ? Hv - 1 - y : y,  x' = fx ? Wv - 1 - x : x,  (a, b) = t ? (x', y') : (y', x').
+ * op 0 identity, 2 np.flipud, 4 np.fliplr, 6 rot180, 1 transpose, 3 np.rot90(k=1), 5 np.rot90(k=3), 7 anti-transpose.
+ * srcgan_tile_gather_d4: dst[t][c] = the `op` view of exactly the window srcgan_tile_gather_ex returns -- the same kinds, the same
+ *   conversion, up-sampling and clamping, every sample evaluated by the same device functions, so the bits are those of transforming
+ *   srcgan_tile_gather_ex's output and op = 0 IS srcgan_tile_gather_ex.  th, tw are the window's extents whatever op is.  A mirrored
+ *   row is read forwards as the segment it mirrors and reversed in registers; a transposition stages 32 x 32 blocks through LDS
+ *   (pitch 33 dwords, conflict-free on both sides), so scene reads and tile writes both run along W.  16-byte stores where th, tw
+ *   and dst allow, scalar otherwise (same bits).
+ * srcgan_d4_accumulate: the same mapping read in the other direction.  acc is [planes][ah][aw] in identity orientation, view is
+ *   [planes][Hv][Wv], (Hv, Wv) = op & 1 ? (aw, ah) : (ah, aw):
+ *     acc[a][b] = ((first ? 0 : acc[a][b]) + view[y][x]) * scale      in f32: one addition, one multiplication, never contracted;
+ *   `first` != 0 does not read acc.  An ensemble of V views calls it V times in op order, first = 1 on the first and scale = 1 / V
+ *   on the last (1 elsewhere; V is a power of two, so the scale is exact).  view must not overlap acc.  16-byte accesses where ah,
+ *   aw and both pointers allow, scalar otherwise (same bits); the same LDS transposition for op & 1.
+ * Both validate before launching (null pointers, op outside 0..7, C / kind combinations, extents over 16384 per side, origins
+ * outside the grid, a non-finite scale, aliasing) and write nothing on error. */
+int srcgan_tile_gather_d4(const void* src, int src_kind, int C, int H, int W, int s, float* dst, int T, int th, int tw,
+                          const int* origins_yx, int op, void* stream);
+int srcgan_d4_accumulate(const float* view, float* acc, long planes, int ah, int aw, int op, int first, float scale, void* stream);
+
 /* ---- whole-scene scoring (csrc/scene_score.hip, metrics.py score_scene) ----
  * MSE, PSNR, AE, SSIM and CS of metrics.py:10-144 for ONE image pair of any size, in one pass and without scene-sized intermediates.
  *   pred / truth: kind 0 = f32 planes [C][H][W] (taken as is), kind 1 = u8 [H][W][C] (v / 255 as srcgan_tile_gather kind 1; any byte

@@ -2,6 +2,7 @@
 process, and record time and peak allocation of both in profiles/cascade_scene.txt.
 
   python scripts/bench_cascade_scene.py [--hw 1024] [--up 4] [--tile 512] [--batch 1] [--samples 3] [--out profiles/cascade_scene.txt]
+  python scripts/bench_cascade_scene.py --ensemble 8 [...] [--ensemble-out profiles/scene_ensemble.txt]
 
 Two configurations, each timed both ways (interleaved round-robin, device events, the median of --samples runs):
 
@@ -13,7 +14,10 @@ Two configurations, each timed both ways (interleaved round-robin, device events
             -> torch.cat -> data.lab2img: five scene-sized f32 tensors on the way
 
 The peak is torch.cuda.max_memory_allocated above the allocation at the start of the call (the input scene excluded, the result
-included).  There is no pass mark; the numbers are written down."""
+included).  There is no pass mark; the numbers are written down.
+
+With --ensemble N the fused call of each configuration is timed with ensemble=N against N x its ensemble=1 time instead
+(bench_scene.py's ``ensemble_ab``: alternating rounds, medians, the peak of both) and the lines are APPENDED to --ensemble-out."""
 import argparse
 import json
 import os
@@ -22,6 +26,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
@@ -32,6 +37,8 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--samples", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "cascade_scene.txt"))
+    ap.add_argument("--ensemble", type=int, default=1, choices=[1, 2, 4, 8])
+    ap.add_argument("--ensemble-out", default=os.path.join("profiles", "scene_ensemble.txt"))
     a = ap.parse_args()
 
     from srcgan_amd import SRCNN, SRDN, ResDeconv, cascade_scene, data, ops, upscale_scene
@@ -52,14 +59,25 @@ def main():
     sr, col = SRDN(1, 1, up).cuda().eval(), ResDeconv(1, 2).cuda().eval()
     kw = dict(tile=a.tile, halo=32, multiple=16, batch=a.batch, blend="feather")
     configs.append(("feather/lab SRDN(1,1,%d) -> ResDeconv(1,2)" % up,
-                    lambda sr=sr, col=col, kw=kw: cascade_scene(sr, col, scene, up=up, const=True, space="lab", out="u8", **kw),
+                    lambda sr=sr, col=col, kw=kw, e=1: cascade_scene(sr, col, scene, up=up, const=True, space="lab", out="u8", ensemble=e, **kw),
                     lambda sr=sr, col=col, kw=kw: composed(sr, col, **kw)))
     sr, col = SRCNN(1, 1, up).cuda().eval(), SRCNN(1, 2, up).cuda().eval()
     kw = dict(tile=a.tile, batch=a.batch, blend="crop")
     # the composition runs the networks in two passes, each with its own exact halo (6); the fused chain needs their sum (12)
     configs.append(("crop/lab SRCNN(1,1,%d) -> SRCNN(1,2,%d)" % (up, up),
-                    lambda sr=sr, col=col, kw=kw: cascade_scene(sr, col, scene, up=up, const=True, space="lab", out="u8", halo=None, **kw),
+                    lambda sr=sr, col=col, kw=kw, e=1: cascade_scene(sr, col, scene, up=up, const=True, space="lab", out="u8", halo=None, ensemble=e,
+                                                                     **kw),
                     lambda sr=sr, col=col, kw=kw: composed(sr, col, halo=None, **kw)))
+
+    if a.ensemble > 1:
+        from bench_scene import append_lines, ensemble_ab
+        lines = []
+        for name, fused, _ in configs:
+            r = ensemble_ab(lambda e: fused(e=e), a.ensemble, a.samples)
+            lines.append(json.dumps({"cfg": name, "run": "cascade_scene", "scene": f"{a.hw}x{a.hw} u8 RGB, up {up}, tile {a.tile}, batch {a.batch}", **r}))
+            print(lines[-1], flush=True)
+        append_lines(a.ensemble_out, lines)
+        return
 
     lines = []
     for name, fused, comp in configs:

@@ -1,6 +1,7 @@
 """Measure whole-scene inference (srcgan_amd.infer): RDDBNet(3,3,4,nb=23), bf16, on a 2048x2048 scene -> 8192x8192.
 
   python scripts/bench_scene.py [--scene 2048] [--big 4096] [--nb 23] [--dtype bf16] [--reps 3] [--out profiles/scene_infer.txt]
+  python scripts/bench_scene.py --ensemble 8 [--scene 2048] [--nb 23] [--dtype bf16] [--reps 3] [--ensemble-out profiles/scene_ensemble.txt]
 
 Three runs on the same scene, each timed with device events (median of --reps) with its peak allocation above what was resident
 before the call (torch.cuda.max_memory_allocated):
@@ -10,7 +11,11 @@ before the call (torch.cuda.max_memory_allocated):
 then a --big x --big scene (which the whole-image path cannot hold) in feather mode, and the yardstick of the gather / scatter
 kernels: the same copies done with torch slicing in this process, side by side (and the cascade's fused gather, which has no torch
 twin).  A measurement tool only: no test runs it and no
-gate is set on its numbers.  One JSON line per measurement, echoed to --out."""
+gate is set on its numbers.  One JSON line per measurement, echoed to --out.
+
+With --ensemble N only the geometric self-ensemble is measured: upscale_scene(tile=512, halo=32, blend="feather", ensemble=N) against
+N x the ensemble=1 time of the same call (`ensemble_ab`: alternating rounds, device events, medians, the peak of both); its line is
+APPENDED to --ensemble-out, the file scripts/bench_cascade_scene.py --ensemble appends to as well."""
 import argparse
 import json
 import os
@@ -39,8 +44,44 @@ def timed(fn, reps):
     return sorted(ms)[len(ms) // 2], torch.cuda.max_memory_allocated() - base, y
 
 
+def ensemble_ab(call, n, reps):
+    """``call(ensemble)`` runs one scene.  Times ensemble=n and ensemble=1 in alternating rounds (device events, median of ``reps``)
+    and takes each one's peak allocation above what was resident before the call -> the fields of one result line; ``ratio`` is the
+    ensemble=n time over n x the ensemble=1 time: what views, folds and the accumulators cost beyond running the network n times."""
+    peak, ms = {}, {1: [], n: []}
+    for e in (1, n):                                  # warm up (allocator, weight pack, workspaces of every tile shape), then the peak
+        call(e)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        y = call(e)
+        torch.cuda.synchronize()
+        peak[e] = torch.cuda.max_memory_allocated() - base
+        del y
+    for _ in range(reps):
+        for e in (1, n):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            call(e)
+            e1.record()
+            torch.cuda.synchronize()
+            ms[e].append(e0.elapsed_time(e1))
+    med = {e: sorted(v)[len(v) // 2] for e, v in ms.items()}
+    return {"ensemble": n, "ms_1": round(med[1], 2), f"ms_{n}": round(med[n], 2), "ratio_to_n_times_1": round(med[n] / (n * med[1]), 4),
+            "peak_mib_1": round(peak[1] / 2 ** 20, 1), f"peak_mib_{n}": round(peak[n] / 2 ** 20, 1), "rounds": reps}
+
+
+def append_lines(path, lines):
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "a") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ensemble", type=int, default=1, choices=[1, 2, 4, 8])
+    ap.add_argument("--ensemble-out", default=os.path.join("profiles", "scene_ensemble.txt"))
     ap.add_argument("--scene", type=int, default=2048)
     ap.add_argument("--big", type=int, default=4096)
     ap.add_argument("--nb", type=int, default=23)
@@ -62,6 +103,11 @@ def main():
 
     S = a.scene
     x = torch.rand(1, 3, S, S, device="cuda")
+    if a.ensemble > 1:
+        r = ensemble_ab(lambda e: infer.upscale_scene(net, x, up=up, tile=512, halo=32, blend="feather", ensemble=e), a.ensemble, a.reps)
+        emit(run="upscale_scene feather", scene=S, tile=512, halo=32, **r)
+        append_lines(a.ensemble_out, lines)
+        return
 
     def whole():
         with torch.no_grad():

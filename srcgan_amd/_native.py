@@ -213,6 +213,8 @@ SIGNATURES = {
     "srcgan_planes_to_u8hwc": (_I, [_P, _P, _I, _L, _P]),
     "srcgan_tile_gather_ex": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_int), _P]),
     "srcgan_tile_scatter_u8": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int), _I, _P]),
+    "srcgan_tile_gather_d4": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, C.POINTER(C.c_int), _I, _P]),
+    "srcgan_d4_accumulate": (_I, [_P, _P, _L, _I, _I, _I, _I, _F, _P]),
     "srcgan_scene_score_tile": (_I, []),
     "srcgan_scene_score_ws_bytes": (_S, [_L, _L, _I]),
     "srcgan_scene_score": (_I, [_P, _I, _P, _I, _L, _L, _I, _P, _P, _P]),

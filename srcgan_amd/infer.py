@@ -13,6 +13,10 @@ plain ``srcgan_tile_gather`` is its ``s = 1`` case with the kind taken from the 
 first network next to the ab tile of the second, and in crop mode the 8-bit conversion happens inside the write-back
 (``srcgan_tile_scatter_u8``) -- no f32 scene is made on the way.
 
+``ensemble=`` on both drivers is the geometric self-ensemble: every tile batch runs under 2, 4 or 8 flips / rotations made inside the
+gather (``srcgan_tile_gather_d4``), and the outputs are folded back and averaged in f32 (``srcgan_d4_accumulate``) before the
+write-back -- the plan, the sinks and the memory rule (nothing scene-sized beyond the result) stay as they are.
+
 Two modes:
   exact    ``halo=None``: the halo is the receptive radius of the chain (``receptive_halo``), tiles are cropped to their cores, and
            the result is the whole-image forward's (networks without normalisation layers only).
@@ -232,16 +236,21 @@ def _int_array(values):
 _KINDS = {"f32": 0, "u8": 1, "u8rgb2gray": 2}
 
 
-def _gather(who: str, scene: torch.Tensor, lay, kind: str, s: int, origins, th: int, tw: int) -> torch.Tensor:
-    """The one native gather call; ``lay`` = ``N.scene_layout(scene)``, already checked against ``kind`` by the caller."""
+def _gather(who: str, scene: torch.Tensor, lay, kind: str, s: int, origins, th: int, tw: int, op: Optional[int] = None) -> torch.Tensor:
+    """The one native gather call; ``lay`` = ``N.scene_layout(scene)``, already checked against ``kind`` by the caller.  ``op`` given:
+    ``srcgan_tile_gather_d4``, whose tiles are ``tw`` x ``th`` for a transposing ``op``."""
     _, sc, Cc, H, W = lay
     if not sc.is_contiguous():
         raise ValueError(f"{who}: the scene must be contiguous")
     T = len(origins)
-    out = torch.empty(T, 1 if kind == "u8rgb2gray" else Cc, th, tw, dtype=torch.float32, device=scene.device)
+    vh, vw = (tw, th) if op is not None and op & 1 else (th, tw)
+    out = torch.empty(T, 1 if kind == "u8rgb2gray" else Cc, vh, vw, dtype=torch.float32, device=scene.device)
     flat = _int_array([int(v) for yx in origins for v in yx])
-    N.check(N.lib().srcgan_tile_gather_ex(sc.data_ptr(), _KINDS[kind], Cc, H, W, int(s), out.data_ptr(), T, th, tw, flat,
-                                          N.stream_ptr(scene.device)), who)
+    args = (sc.data_ptr(), _KINDS[kind], Cc, H, W, int(s), out.data_ptr(), T, th, tw, flat)
+    if op is None:
+        N.check(N.lib().srcgan_tile_gather_ex(*args, N.stream_ptr(scene.device)), who)
+    else:
+        N.check(N.lib().srcgan_tile_gather_d4(*args, int(op), N.stream_ptr(scene.device)), who)
     return out
 
 
@@ -260,13 +269,42 @@ def tile_gather_ex(scene: torch.Tensor, kind: str, s: int, origins, th: int, tw:
     [H,W,3] -> one gray plane as ``data.arr2gray``) and up-sampled ``s`` times bilinearly (as ``ops.bilinear_up``), evaluated on the
     fly; origins are on the up-sampled grid.  Bit-identical to ``tile_gather`` of the materialised scene."""
     N.require_cuda(scene, "tile_gather_ex")
+    return _gather("tile_gather_ex", scene, _kind_layout("tile_gather_ex", scene, kind), kind, s, origins, th, tw)
+
+
+def _kind_layout(who: str, scene: torch.Tensor, kind: str):
+    """``N.scene_layout(scene)``, checked against an explicit ``kind``."""
     if kind not in _KINDS:
-        raise ValueError(f"tile_gather_ex: kind must be one of {sorted(_KINDS)}, got {kind!r}")
+        raise ValueError(f"{who}: kind must be one of {sorted(_KINDS)}, got {kind!r}")
     lay = N.scene_layout(scene)
     if lay is None or lay[0] != ("f32" if kind == "f32" else "u8"):
-        raise TypeError(f"tile_gather_ex: kind {kind!r} takes " + ("float32 [C,H,W] / [1,C,H,W]" if kind == "f32" else "uint8 [H,W] / [H,W,C]")
+        raise TypeError(f"{who}: kind {kind!r} takes " + ("float32 [C,H,W] / [1,C,H,W]" if kind == "f32" else "uint8 [H,W] / [H,W,C]")
                         + f", got {scene.dtype} {tuple(scene.shape)}")
-    return _gather("tile_gather_ex", scene, lay, kind, s, origins, th, tw)
+    return lay
+
+
+def tile_gather_d4(scene: torch.Tensor, kind: str, s: int, origins, th: int, tw: int, op: int) -> torch.Tensor:
+    """``srcgan_tile_gather_d4``: the ``op`` view (``ENSEMBLE_OPS``: bit 0 transposes, bit 1 mirrors rows, bit 2 mirrors columns) of
+    every ``th`` x ``tw`` window ``tile_gather_ex`` returns -> f32 [T,C,th,tw], or [T,C,tw,th] for a transposing ``op``.  Bit-identical
+    to transforming ``tile_gather_ex``'s output; ``op = 0`` is ``tile_gather_ex``."""
+    N.require_cuda(scene, "tile_gather_d4")
+    return _gather("tile_gather_d4", scene, _kind_layout("tile_gather_d4", scene, kind), kind, s, origins, th, tw, op)
+
+
+def d4_accumulate(view: torch.Tensor, acc: torch.Tensor, op: int, first: bool, scale: float) -> None:
+    """``srcgan_d4_accumulate``: fold ``view``, f32 [T,C,Hv,Wv] in the orientation of ``op``, back to the identity orientation into
+    ``acc``, f32 [T,C,ah,aw] ((Hv, Wv) = (aw, ah) for a transposing ``op``): ``acc = ((0 if first else acc) + folded view) * scale`` in
+    f32, one addition and one multiplication.  ``first`` does not read ``acc``."""
+    N.require_cuda(view, "d4_accumulate")
+    N.require_cuda(acc, "d4_accumulate")
+    for t in (view, acc):
+        if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+            raise TypeError("d4_accumulate: view and accumulator must be contiguous float32 [T,C,H,W]")
+    T, Cc, ah, aw = acc.shape
+    if tuple(view.shape) != (T, Cc, *((aw, ah) if int(op) & 1 else (ah, aw))):
+        raise ValueError(f"d4_accumulate: a view {tuple(view.shape)} under op = {op} does not fold into {tuple(acc.shape)}")
+    N.check(N.lib().srcgan_d4_accumulate(view.data_ptr(), acc.data_ptr(), T * Cc, ah, aw, int(op), int(bool(first)), float(scale),
+                                         N.stream_ptr(acc.device)), "srcgan_d4_accumulate")
 
 
 def tile_scatter(tiles: torch.Tensor, dst: torch.Tensor, up: int, rects, feather: bool) -> None:
@@ -327,7 +365,14 @@ def tile_scatter_u8(tiles_a: torch.Tensor, tiles_b: Optional[torch.Tensor], dst:
 
 
 # ------------------------------------------------------------------------------------------------ the drivers
-def _check_options(who: str, up: int, batch: int, blend: str, out: str, halo: Optional[int]) -> None:
+# The views of the geometric self-ensemble: elements of the dihedral group D4 numbered op = 0..7, bit 0 transposes, bit 1 mirrors the
+# view's rows, bit 2 its columns (include/srcgan_amd.h states the index mapping).  ensemble=4 is the flips only: no tile changes shape.
+ENSEMBLE_OPS = {1: (0,), 2: (0, 4), 4: (0, 2, 4, 6), 8: tuple(range(8))}
+
+
+def _check_options(who: str, up: int, batch: int, blend: str, out: str, halo: Optional[int], ensemble: int = 1) -> None:
+    if ensemble not in ENSEMBLE_OPS or isinstance(ensemble, bool):
+        raise ValueError(f"{who}: ensemble must be 1, 2, 4 or 8, got {ensemble!r}")
     if blend not in ("crop", "feather"):
         raise ValueError(f"{who}: blend must be 'crop' or 'feather', got {blend!r}")
     if out not in ("f32", "u8"):
@@ -349,30 +394,62 @@ def _scene_plan(who: str, nets, H: int, W: int, tile: int, halo: Optional[int], 
     return plan
 
 
-def _run_tiles(nets, plan: TilePlan, batch: int, feather: bool, gather, forward, sink, hr, u8: bool = False) -> torch.Tensor:
-    """The tile loop of both drivers, class by class in batches of ``batch``: ``gather(origins, th, tw)`` -> the input batch;
-    ``forward(x, th, tw)`` -> the tensors to write back (shape-checked by the caller); ``sink(tensors, result, rects)`` writes them.
+def _view_gather(scene: torch.Tensor, kind: str, s: int):
+    """``gather(origins, th, tw, op)`` of the drivers: the plain gather for ``op=None``, the view ``op`` otherwise."""
+    def gather(origins, th, tw, op):
+        if op is None:
+            return tile_gather_ex(scene, kind, s, origins, th, tw)
+        return tile_gather_d4(scene, kind, s, origins, th, tw, op)
+    return gather
+
+
+def _run_views(ops, origins, th: int, tw: int, gather, forward) -> List[torch.Tensor]:
+    """One tile batch under the self-ensemble: for each op in turn (ascending, the identity first) gather the batch under that view,
+    run the chain on it (a transposing view is a ``tw`` x ``th`` batch) and fold what it returns back into one f32 accumulator per
+    tensor -- ``acc = v0; acc = acc + v1; ...``, the last addition scaled by ``1 / V``.  One view's tensors are alive at a time."""
+    accs = None
+    for k, op in enumerate(ops):
+        x = gather(origins, th, tw, op)
+        views = [t.contiguous().float() for t in forward(x, *((tw, th) if op & 1 else (th, tw)))]
+        if accs is None:
+            accs = [torch.empty_like(v) for v in views]         # op 0 comes first: its tensors have the identity's shape
+        for v, acc in zip(views, accs):
+            d4_accumulate(v, acc, op, k == 0, 1.0 / len(ops) if k == len(ops) - 1 else 1.0)
+        del x, views
+    return accs
+
+
+def _run_tiles(nets, plan: TilePlan, batch: int, feather: bool, gather, forward, sink, hr, u8: bool = False, ensemble: int = 1) -> torch.Tensor:
+    """The tile loop of both drivers, class by class in batches of ``batch``: ``gather(origins, th, tw, op)`` -> the input batch
+    (``op=None``: the plain gather); ``forward(x, th, tw)`` -> the tensors to write back (shape-checked by the caller);
+    ``sink(tensors, result, rects)`` writes them.  ``ensemble > 1``: the tensors are the averages over the views (``_run_views``).
     The result is made when the first batch is there: f32 [1, planes of all written tensors, *hr], or u8 [*hr, 3] with ``u8``; zeroed
     for a feathered blend, which adds into it.  Under ``no_grad`` with ``nets`` in ``eval()``."""
     result = None
+    ops = ENSEMBLE_OPS[ensemble]
     with torch.no_grad():
         for net in nets:
             net.eval()
         for (th, tw), idx in plan.classes.items():
             for b0 in range(0, len(idx), batch):
                 ids = idx[b0:b0 + batch]
-                x = gather([(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids], th, tw)
-                tensors = [t.contiguous().float() for t in forward(x, th, tw)]
+                origins = [(plan.tiles[i].y0, plan.tiles[i].x0) for i in ids]
+                if ensemble == 1:
+                    x = gather(origins, th, tw, None)
+                    tensors = [t.contiguous().float() for t in forward(x, th, tw)]
+                    del x
+                else:
+                    tensors = _run_views(ops, origins, th, tw, gather, forward)
                 if result is None:
                     shape = (*hr, 3) if u8 else (1, sum(t.shape[1] for t in tensors), *hr)
-                    result = (torch.zeros if feather else torch.empty)(shape, dtype=torch.uint8 if u8 else torch.float32, device=x.device)
+                    result = (torch.zeros if feather else torch.empty)(shape, dtype=torch.uint8 if u8 else torch.float32, device=tensors[0].device)
                 sink(tensors, result, plan.rects(ids, feather))
-                del x, tensors                          # nothing of this batch is held while the next one runs
+                del tensors                             # nothing of this batch is held while the next one runs
     return result
 
 
 def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: Optional[int] = None, batch: int = 1,
-                  blend: str = "crop", out: str = "f32", multiple: int = 1) -> torch.Tensor:
+                  blend: str = "crop", out: str = "f32", multiple: int = 1, ensemble: int = 1) -> torch.Tensor:
     """Run ``nets`` (a module, or a sequence applied in order, e.g. ``[sr, colouriser]``) over a whole scene, tile by tile.
 
     ``scene``: a device tensor, u8 [H,W,C] (C = 1 or 3; mapped v / 255 like ``data.arr2rgb``) or f32 [1,C,H,W].  ``up``: output pixels
@@ -381,14 +458,19 @@ def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: 
     and then equals the whole-image forward.  ``blend``: "crop" (each tile writes its core) or "feather" (neighbours are cross-faded
     over linear ramps, accumulated in f32 in tile order: bitwise reproducible).  ``multiple``: round tile extents up to a multiple (16
     / up of the first stage for a ResDeconv behind it).  ``out``: "f32" -> [1,C',H*up,W*up], "u8" -> u8 [H*up,W*up,C']
-    (``planes_to_u8hwc``).
+    (``planes_to_u8hwc``).  ``ensemble``: 1, 2, 4 or 8 -- the geometric self-ensemble (the "+" variants of EDSR / RCAN): every tile
+    batch runs under the views ``ENSEMBLE_OPS[ensemble]`` (2: identity and the mirror image; 4: the four flips, tile shapes unchanged;
+    8: all of D4), each output is folded back and the outputs are averaged in f32, in op order, BEFORE the write-back -- so before
+    the blend and before any 8-bit conversion.  Views are made per tile inside the gather (``tile_gather_d4``) on the unchanged plan;
+    in exact mode the result is the mean over ``g`` of ``g^-1(whole-image forward of g(scene))``.  1 is the path without it.
 
     Runs under ``no_grad`` with the modules in ``eval()``.  Extra memory: one tile batch's inference workspace and its input / output
-    tensors, next to the input and output scenes -- independent of the scene size."""
+    tensors (with ``ensemble > 1`` one f32 accumulator per written tensor more), next to the input and output scenes -- independent
+    of the scene size."""
     nets = list(nets) if isinstance(nets, (list, tuple)) else [nets]
     if not nets or not all(isinstance(n, nn.Module) for n in nets):
         raise TypeError("upscale_scene: nets must be a module or a sequence of modules")
-    _check_options("upscale_scene", up, batch, blend, out, halo)
+    _check_options("upscale_scene", up, batch, blend, out, halo, ensemble)
     lay = N.scene_layout(scene)
     if lay is None or (lay[0] == "f32" and scene.dim() != 4):
         raise ValueError(f"upscale_scene: the scene must be u8 [H,W,C] or f32 [1,C,H,W], got {scene.dtype} {tuple(scene.shape)}")
@@ -406,8 +488,8 @@ def upscale_scene(nets, scene: torch.Tensor, *, up: int, tile: int = 512, halo: 
             raise ValueError(f"upscale_scene: the chain maps a {th}x{tw} tile to {tuple(x.shape)}, not to {th * up}x{tw * up} (up = {up})")
         return [x]
 
-    result = _run_tiles(nets, plan, batch, feather, lambda org, th, tw: tile_gather_ex(scene, kind, 1, org, th, tw), forward,
-                        lambda ts, res, rects: tile_scatter(ts[0], res, up, rects, feather), (H * up, W * up))
+    result = _run_tiles(nets, plan, batch, feather, _view_gather(scene, kind, 1), forward,
+                        lambda ts, res, rects: tile_scatter(ts[0], res, up, rects, feather), (H * up, W * up), ensemble=ensemble)
     return planes_to_u8hwc(result) if out == "u8" else result
 
 
@@ -425,7 +507,8 @@ def _cascade_plan(netG_A2C, netG_C2B, H: int, W: int, *, up: int, const: bool, t
 
 
 def cascade_scene(netG_A2C, netG_C2B, scene: torch.Tensor, *, up: int, space: str = "rgb", const: bool = False, tile: int = 512,
-                  halo: Optional[int] = None, batch: int = 1, blend: str = "crop", out: str = "u8", multiple: int = 1) -> torch.Tensor:
+                  halo: Optional[int] = None, batch: int = 1, blend: str = "crop", out: str = "u8", multiple: int = 1,
+                  ensemble: int = 1) -> torch.Tensor:
     """The reference's cascade over a whole LR scene: gray -> ``netG_A2C`` (super-resolution) -> ``netG_C2B`` (colourisation) -> picture.
 
         testCas.py          cascade_scene(sr, col, scene, up=up)
@@ -442,15 +525,17 @@ def cascade_scene(netG_A2C, netG_C2B, scene: torch.Tensor, *, up: int, space: st
     image is normalised LAB, cat(L tile of ``netG_A2C``, ab tile), converted as ``data.lab2img`` for ``out="u8"``.  ``out``: "u8" ->
     u8 [H*up,W*up,3] RGB; "f32" -> f32 [1,3,H*up,W*up], RGB planes or normalised LAB planes.  ``tile, halo, batch, blend, multiple``:
     as in ``upscale_scene`` (``halo=None``: exact mode over both networks' receptive radii, crop only, no normalisation layers).
+    ``ensemble``: as in ``upscale_scene``; the whole cascade runs per view, and in LAB mode both the L tile and the ab tile are folded
+    and averaged in f32 before the non-linear ``lab2img``.
 
     Memory: with ``blend="crop", out="u8"`` nothing scene-sized is allocated but the u8 result (the conversion is fused into the
     write-back); ``blend="feather"`` accumulates in ONE f32 [3,H*up,W*up] buffer (L into plane 0, ab into planes 1-2) converted once at
-    the end; ``out="f32"`` allocates the f32 result.  Everything else follows the tile batch."""
+    the end; ``out="f32"`` allocates the f32 result.  Everything else follows the tile batch, the accumulators of ``ensemble > 1`` included."""
     if not isinstance(netG_A2C, nn.Module) or not isinstance(netG_C2B, nn.Module):
         raise TypeError("cascade_scene: netG_A2C and netG_C2B must be modules")
     if space not in ("rgb", "lab"):
         raise ValueError(f"cascade_scene: space must be 'rgb' or 'lab', got {space!r}")
-    _check_options("cascade_scene", up, batch, blend, out, halo)
+    _check_options("cascade_scene", up, batch, blend, out, halo, ensemble)
     lay = N.scene_layout(scene)
     if lay is None or not (lay[2] in (1, 3) if lay[0] == "u8" else scene.dim() == 4 and lay[2] == 1):
         raise ValueError(f"cascade_scene: the scene must be u8 [H,W], [H,W,1], [H,W,3] or f32 [1,1,H,W], got {scene.dtype} {tuple(scene.shape)}")
@@ -489,8 +574,8 @@ def cascade_scene(netG_A2C, netG_C2B, scene: torch.Tensor, *, up: int, space: st
         def sink(ts, res, rects):
             tile_scatter(ts[0], res, cu, rects, feather)
 
-    result = _run_tiles([netG_A2C, netG_C2B], plan, batch, feather, lambda org, th, tw: tile_gather_ex(scene, kind, s, org, th, tw), forward,
-                        sink, (H * up, W * up), u8=fused)
+    result = _run_tiles([netG_A2C, netG_C2B], plan, batch, feather, _view_gather(scene, kind, s), forward, sink, (H * up, W * up), u8=fused,
+                        ensemble=ensemble)
     if fused or out == "f32":
         return result
     if lab:
