@@ -535,6 +535,20 @@ size_t srcgan_vggloss_infer_ws_bytes(const srcgan_vggloss_cfg* c);
 int srcgan_vggloss_infer(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
                          float* loss_out, void* stream);
 
+/* The same losses on frames of 5-D tensors (losses.VGG16Loss3D, reference src/losses.py:396-453).  out5d / tgt5d / dout5d: contiguous f32
+ * [Bt, C_in, F, H, W] with C_in = 1 or 3.  A call covers the k frames [f0, f0 + k) as c->B = Bt * k images (image j * Bt + b = frame
+ * f0 + j of sample b): the input pack reads the frames in place, and the input-gradient store writes them in place -- every element of
+ * those k frames of dout5d exactly once, other frames untouched.  C_in = 1: the plane is replicated to the three VGG channels inside the
+ * pack and the three channel gradients are summed into the one plane (what autograd does for the reference's torch.cat).  The loss
+ * written is the mean over the k frames of the per-frame loss; everything else (params, ws, scratch, gout_dev, gscale, sizes by the
+ * functions above for the same cfg) is as in the 4-D entry points. */
+int srcgan_vggloss_forward_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
+                                  const float* const* params, void* ws, float* loss_out, void* stream);
+int srcgan_vggloss_backward_frames(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, int C_in, int F, int f0, int k,
+                                   const float* const* params, void* ws, void* scratch, float* dout5d, void* stream);
+int srcgan_vggloss_infer_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
+                                const float* const* params, void* ws, float* loss_out, void* stream);
+
 /* nn.PixelShuffle(r) on NHWC (espcn.py:44,50): src [B,H,W,C*r*r] -> dst [B,H*r,W*r,C]; inverse = 1: the adjoint, src [B,H*r,W*r,C]
  * -> dst [B,H,W,C*r*r].  srcgan_mask_inplace: g *= (act > 0 ? 1 : slope) over n elements (ReLU' / LeakyReLU' on an incoming gradient). */
 int srcgan_pixel_shuffle_nhwc(const void* src, int s_cs, void* dst, int d_cs, int B, int H, int W, int C, int r, int inverse,
@@ -561,6 +575,22 @@ int srcgan_dssim_loss_fwd(const float* pred, const float* truth, int B, int C, i
                           float* scratch, void* stream);
 int srcgan_dssim_loss_bwd(const float* pred, const float* truth, int B, int C, int H, int W, const float* range,
                           const float* gout, float* dpred, float* dtruth, void* stream);
+
+/* Multi-frame DSSIM loss (losses.py:183-196, DSSIMLoss3D): the mean over frames f of the DSSIM loss of frame f, each frame with the
+ * dynamic range of its own prediction (min / max over all B*C planes of that frame), as the reference's loop over frames has it.
+ * pred / truth / dpred / dtruth: contiguous f32 [B,C,F,H,W]; plane (b, c) of frame f starts at element ((b*C + c)*F + f)*H*W (64-bit
+ * offsets); H, W >= 11; B*C and F at most 65535.
+ *   srcgan_dssim3d_loss_fwd: out[0] = the loss; range[f][0..1] = min / max of frame f of pred (device, 2 F floats), which backward reads;
+ *                            scratch: srcgan_dssim3d_scratch_floats(B, C, F, H, W) floats (0 for a refused shape).  One range launch,
+ *                            one tile launch and one f64 fold cover all frames; no per-frame copy, no host synchronisation.
+ *   srcgan_dssim3d_loss_bwd: as srcgan_dssim_loss_bwd, on the 5-D layout; the upstream scalar enters as gout[0] * (1.0f / F).
+ * The device code is that of the 4-D loss (which is its F = 1 instance), so with F = 1 both give the same bits, and the gradient of
+ * frame f has the bits of the 4-D backward of that frame at upstream gout[0] * (1.0f / F). */
+long srcgan_dssim3d_scratch_floats(int B, int C, int F, int H, int W);
+int srcgan_dssim3d_loss_fwd(const float* pred, const float* truth, int B, int C, int F, int H, int W, float* out, float* range,
+                            float* scratch, void* stream);
+int srcgan_dssim3d_loss_bwd(const float* pred, const float* truth, int B, int C, int F, int H, int W, const float* range,
+                            const float* gout, float* dpred, float* dtruth, void* stream);
 
 /* Registration-tolerant pixel loss (losses.py:199-255, NearestSelector; with L1Loss at :522).  output / target: [B,C,H,W] f32 NCHW,
  * contiguous.  n = 2 * shift; candidate k = i * n + j compares output[:, :, sd : sd + crop_h, sd : sd + crop_w] (sd = shift * stride)

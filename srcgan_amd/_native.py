@@ -192,6 +192,9 @@ SIGNATURES = {
     "srcgan_vggloss_backward": (_I, [C.POINTER(VggLossCfg), _P, _F, _P, _P, _P, _P, _P]),
     "srcgan_vggloss_infer_ws_bytes": (_S, [C.POINTER(VggLossCfg)]),
     "srcgan_vggloss_infer": (_I, [C.POINTER(VggLossCfg), _P, _P, _P, _P, _P, _P]),
+    "srcgan_vggloss_forward_frames": (_I, [C.POINTER(VggLossCfg), _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "srcgan_vggloss_backward_frames": (_I, [C.POINTER(VggLossCfg), _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "srcgan_vggloss_infer_frames": (_I, [C.POINTER(VggLossCfg), _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "srcgan_pixel_shuffle_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_mask_inplace": (_I, [_P, _P, _F, _L, _I, _P]),
     "srcgan_metric_scratch_floats": (_I, [_I, _I, _I, _I]),
@@ -199,6 +202,9 @@ SIGNATURES = {
     "srcgan_metric_ssim": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "srcgan_dssim_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "srcgan_dssim_loss_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "srcgan_dssim3d_scratch_floats": (_L, [_I, _I, _I, _I, _I]),
+    "srcgan_dssim3d_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "srcgan_dssim3d_loss_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "srcgan_shift_search_scratch_floats": (_S, [_I, _I, _I, _I, _I, _I, _I, _I]),
     "srcgan_shift_search": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "srcgan_shift_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),

@@ -141,4 +141,10 @@ int sg_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int 
 // store: NHWC records of C <= 8 channels -> f32 NCHW, times gout[0] * gscale (gout on the device)
 int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, hipStream_t st);
 int sg_image_grad_store(const void* src, int cs, float* dst, int B, int C, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);
+// the same path on frames of 5-D tensors (losses.VGG16Loss3D): frames [f0, f0 + k) of a contiguous f32 [Bt, Cin, F, H, W] tensor (Cin = 1 or
+// 3) <-> the 8-channel NHWC records of Bt * k images (image j * Bt + b = frame f0 + j of sample b).  The pack replicates a gray plane to
+// the three channels and zeroes channels 3..7; the store sums the three channel gradients into a gray plane.
+struct SgFrames { int Cin, F, f0, k; };
+int sg_frames_pack(const float* src5d, void* dst, int cs, int Bt, SgFrames fr, int H, int W, int dtype, hipStream_t st);
+int sg_frames_grad_store(const void* src, int cs, float* dst5d, int Bt, SgFrames fr, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);
 int sg_fill_zero_guarded(void* p, size_t bytes, const unsigned long long* guard, hipStream_t st);     // guard == nullptr: plain hipMemsetAsync

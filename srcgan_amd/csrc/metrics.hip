@@ -59,29 +59,55 @@ __global__ __launch_bounds__(256) void minmax_partial_k(const float* __restrict_
 }
 __global__ void minmax_fold_k(const float* __restrict__ partial, int nblk, float* __restrict__ out) {
     if (threadIdx.x) return;
+    partial += (size_t)blockIdx.y * nblk * 2; out += 2 * blockIdx.y;       // one (min, max) pair per blockIdx.y; the flat callers launch y = 1
     float lo = partial[0], hi = partial[1];
     for (int k = 1; k < nblk; ++k) { lo = fminf(lo, partial[2 * k]); hi = fmaxf(hi, partial[2 * k + 1]); }
     out[0] = lo; out[1] = hi;
+}
+
+// per-frame min / max of a [BC, F, HW] tensor over all BC planes of frame f = blockIdx.y (DSSIMLoss3D picks one range per frame, like
+// the reference's loop over frames): partial[(f*gridDim.x + blk)*2 + {min, max}], folded by minmax_fold_k on a (1, F) grid
+__global__ __launch_bounds__(256) void minmax_frames_partial_k(const float* __restrict__ x, int BC, int F, long hw, float* __restrict__ partial) {
+    __shared__ float rmin[4], rmax[4];
+    float lo = 3.4e38f, hi = -3.4e38f;
+    for (int bc = 0; bc < BC; ++bc) {
+        const float* xp = x + ((size_t)bc * F + blockIdx.y) * hw;
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < hw; i += (long)gridDim.x * 256) { const float v = xp[i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_down(lo, o, 64)); hi = fmaxf(hi, __shfl_down(hi, o, 64)); }
+    if ((threadIdx.x & 63) == 0) { rmin[threadIdx.x >> 6] = lo; rmax[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        lo = rmin[0]; hi = rmax[0];
+        for (int w = 1; w < 4; ++w) { lo = fminf(lo, rmin[w]); hi = fmaxf(hi, rmax[w]); }
+        float* o = partial + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+        o[0] = lo; o[1] = hi;
+    }
 }
 
 // SSIM (metrics.py:72-144): 11x11 gaussian (sigma 1.5) depth-wise "valid" windows of x, y, x^2, y^2, xy; one workgroup per
 // 16x16 tile of the (H-10)x(W-10) map of one (image, channel): 26x26 patches in LDS, separable passes, map value + contrast term
 // summed per tile: partial[((b*C + c)*ntiles + tile)*2 + {ssim, cs}].  The dynamic range L is read from device memory
 // (written by the range kernel) so the whole metric is stream-ordered without a host round trip.
-__global__ __launch_bounds__(256) void ssim_tile_k(const float* __restrict__ p, const float* __restrict__ t, int H, int W, int tiles_x, int ntiles,
+// Frames: blockIdx.z = f of a [B,C,F,H,W] tensor; plane (bc, f) starts at element (bc*F + f)*H*W (64-bit), its partials sit at
+// ((bc*F + f)*ntiles + tile)*2 and its dynamic range is range[2f .. 2f+1].  The 4-D callers are the F = 1 instance (same addresses).
+__global__ __launch_bounds__(256) void ssim_tile_k(const float* __restrict__ p, const float* __restrict__ t, int F, int H, int W, int tiles_x, int ntiles,
                                                   const float* __restrict__ range, float* __restrict__ partial) {
     __shared__ float sp[26][27], st[26][27];
     __shared__ float hz[5][26][16];
     __shared__ float red[4];
     __shared__ float gw[11];
     const int bc = blockIdx.y, tile = blockIdx.x, ty = tile / tiles_x, tx = tile % tiles_x;
+    const size_t plane = (size_t)bc * F + blockIdx.z;
+    range += 2 * blockIdx.z;
     const int oy0 = ty * 16, ox0 = tx * 16, OH = H - 10, OW = W - 10;
     if (threadIdx.x < 11) {
         float s = 0.f;
         for (int i = 0; i < 11; ++i) s += expf(-(float)((i - 5) * (i - 5)) / 4.5f);
         gw[threadIdx.x] = expf(-(float)((threadIdx.x - 5) * (threadIdx.x - 5)) / 4.5f) / s;
     }
-    const float* pb = p + (size_t)bc * H * W; const float* tb = t + (size_t)bc * H * W;
+    const float* pb = p + plane * H * W; const float* tb = t + plane * H * W;
     for (int i = threadIdx.x; i < 26 * 26; i += 256) {
         const int y = i / 26, x = i % 26, gy = oy0 + y, gx = ox0 + x;
         const bool ok = gy < H && gx < W;
@@ -114,7 +140,7 @@ __global__ __launch_bounds__(256) void ssim_tile_k(const float* __restrict__ p, 
     }
     const float s0 = block_sum(ssim, red);
     const float s1 = block_sum(cs, red);
-    if (threadIdx.x == 0) { float* o = partial + ((size_t)bc * ntiles + tile) * 2; o[0] = s0; o[1] = s1; }
+    if (threadIdx.x == 0) { float* o = partial + (plane * ntiles + tile) * 2; o[0] = s0; o[1] = s1; }
 }
 
 // DSSIM loss forward fold: out = (1 - mean of the ssim_tile_k map sums) / 2 over all npart tiles of all (image, channel) slices.
@@ -155,10 +181,12 @@ __global__ __launch_bounds__(256) void dssim_fold_k(const double* __restrict__ d
 // range) -> separable transposed blur back onto the tile.  No intermediate map leaves LDS; each output is written by one thread.
 // Every pass is register-blocked along its stencil axis (a thread slides the 11 taps over a run of 7, 7, 8 or 4 outputs), so each
 // LDS value is read once per run instead of once per tap.
+// Frames: blockIdx.z = f of a [B,C,F,H,W] tensor, addressed like ssim_tile_k; the upstream scalar enters as gout[0] * invF (the mean
+// over frames).  The 4-D loss is the F = 1, invF = 1 instance: the same addresses and, the product by 1 being exact, the same bits.
 constexpr int DS_T = 32, DS_P = DS_T + 20, DS_Q = DS_T + 10, DS_QS = DS_Q + 1;
 template <bool DY>
-__global__ __launch_bounds__(256) void dssim_bwd_k(const float* __restrict__ p, const float* __restrict__ t, int H, int W, int tiles_x,
-                                                  const float* __restrict__ range, const float* __restrict__ gout, float inv2n,
+__global__ __launch_bounds__(256) void dssim_bwd_k(const float* __restrict__ p, const float* __restrict__ t, int F, int H, int W, int tiles_x,
+                                                  const float* __restrict__ range, const float* __restrict__ gout, float invF, float inv2n,
                                                   float* __restrict__ dp, float* __restrict__ dt) {
     constexpr int NM = DY ? 4 : 3;                            // maps: b, c, a_x [, a_y]
     constexpr int RH = 7, RV = 7, RT = 8, RO = 4;             // run lengths of the four passes
@@ -178,7 +206,8 @@ __global__ __launch_bounds__(256) void dssim_bwd_k(const float* __restrict__ p, 
         for (int i = 0; i < 11; ++i) s += expf(-(float)((i - 5) * (i - 5)) / 4.5f);
         gws[tid] = expf(-(float)((tid - 5) * (tid - 5)) / 4.5f) / s;
     }
-    const size_t base = (size_t)bc * H * W;
+    const size_t base = ((size_t)bc * F + blockIdx.z) * H * W;
+    range += 2 * blockIdx.z;
     const float* pb = p + base; const float* tb = t + base;
     for (int i = tid; i < DS_P * DS_P; i += 256) {
         const int y = i / DS_P, x = i % DS_P, gy = oy0 - 10 + y, gx = ox0 - 10 + x;
@@ -300,7 +329,8 @@ __global__ __launch_bounds__(256) void dssim_bwd_k(const float* __restrict__ p, 
             acc[o][q] = a;
         }
     }
-    const float sc = -gout[0] * inv2n;
+    const float g = gout[0] * invF;
+    const float sc = -g * inv2n;
     const int gx = ox0 + lx;
 #pragma unroll
     for (int o = 0; o < RO; ++o) {
@@ -343,7 +373,7 @@ extern "C" int srcgan_metric_ssim(const float* pred, const float* truth, int B, 
     const long n = (long)B * C * H * W;
     hipLaunchKernelGGL(minmax_partial_k, dim3(256), dim3(256), 0, st, pred, n, mm);
     hipLaunchKernelGGL(minmax_fold_k, dim3(1), dim3(64), 0, st, (const float*)mm, 256, range);
-    hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, H, W, tiles_x, ntiles, (const float*)range, scratch);
+    hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, ntiles, (const float*)range, scratch);
     hipLaunchKernelGGL(fold_k, dim3(B), dim3(64), 0, st, (const float*)scratch, C * ntiles, 2, 1.f / ((float)C * OH * OW), out);
     SG_LAUNCH_CHECK();
     return 0;
@@ -364,7 +394,7 @@ extern "C" int srcgan_dssim_loss_fwd(const float* pred, const float* truth, int 
     const long n = (long)B * C * H * W;
     hipLaunchKernelGGL(minmax_partial_k, dim3(256), dim3(256), 0, st, pred, n, mm);
     hipLaunchKernelGGL(minmax_fold_k, dim3(1), dim3(64), 0, st, (const float*)mm, 256, range);
-    hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, H, W, tiles_x, ntiles, (const float*)range, scratch);
+    hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, ntiles, (const float*)range, scratch);
     double* dpart = (double*)mm;            // the min / max partials are consumed by minmax_fold_k before this point
     hipLaunchKernelGGL(dssim_fold_partial_k, dim3(DS_FOLD), dim3(256), 0, st, (const float*)scratch, (long)B * C * ntiles, dpart);
     hipLaunchKernelGGL(dssim_fold_k, dim3(1), dim3(DS_FOLD), 0, st, (const double*)dpart, (double)B * C * OH * OW, out);
@@ -382,9 +412,65 @@ extern "C" int srcgan_dssim_loss_bwd(const float* pred, const float* truth, int 
     const int tiles_x = cdiv(W, DS_T), ntiles = tiles_x * cdiv(H, DS_T);
     const float inv2n = (float)(0.5 / ((double)B * C * (H - 10) * (W - 10)));
     if (dtruth)
-        hipLaunchKernelGGL(dssim_bwd_k<true>, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, H, W, tiles_x, range, gout, inv2n, dpred, dtruth);
+        hipLaunchKernelGGL(dssim_bwd_k<true>, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, range, gout, 1.f, inv2n, dpred, dtruth);
     else
-        hipLaunchKernelGGL(dssim_bwd_k<false>, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, H, W, tiles_x, range, gout, inv2n, dpred, dtruth);
+        hipLaunchKernelGGL(dssim_bwd_k<false>, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, range, gout, 1.f, inv2n, dpred, dtruth);
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- multi-frame DSSIM (losses.DSSIMLoss3D, reference src/losses.py:183-196): contiguous f32 [B,C,F,H,W]; the loss is the mean over
+// frames of the per-frame DSSIM, each frame with the dynamic range of its own prediction.  One range launch, one tile launch and one
+// fold cover all frames; nothing is copied per frame.
+static inline int ds3_blocks(long hw) { const long b = cdivl(hw, 256); return (int)(b > 256 ? 256 : b); }       // range blocks per frame
+
+extern "C" long srcgan_dssim3d_scratch_floats(int B, int C, int F, int H, int W) {
+    if (B <= 0 || C <= 0 || F <= 0 || H < 11 || W < 11) return 0;
+    const long tiles = (long)cdiv(H - 10, 16) * cdiv(W - 10, 16);
+    const long mm = (long)F * 256 * 2;          // per-frame range partials; the DS_FOLD f64 partials of the fold alias them
+    return (long)B * C * F * tiles * 2 + (mm > 2 * DS_FOLD ? mm : 2 * DS_FOLD) + 16;
+}
+
+static int ds3_check(const char* who, int B, int C, int F, int H, int W) {
+    SG_REQUIRE(B > 0 && C > 0 && F > 0, "%s: bad arguments", who);
+    SG_REQUIRE(H >= 11 && W >= 11, "%s: images must be at least 11x11 (valid 11x11 windows)", who);
+    SG_REQUIRE((long)B * C <= 65535 && F <= 65535, "%s: B*C and F must be at most 65535", who);
+    return 0;
+}
+
+// out[0] = mean over f of (1 - SSIM_f) / 2; range[f][0..1] = min / max of frame f of the prediction (kept for the backward).  Every
+// frame has the same number of window positions, so the mean over frames is one fold over all B*C*F plane sums.
+extern "C" int srcgan_dssim3d_loss_fwd(const float* pred, const float* truth, int B, int C, int F, int H, int W, float* out, float* range,
+                                       float* scratch, void* stream) {
+    SG_REQUIRE(pred && truth && out && range && scratch, "srcgan_dssim3d_loss_fwd: null pointer");
+    SG_TRY(ds3_check("srcgan_dssim3d_loss_fwd", B, C, F, H, W));
+    hipStream_t st = (hipStream_t)stream;
+    const int OH = H - 10, OW = W - 10, tiles_x = cdiv(OW, 16), ntiles = tiles_x * cdiv(OH, 16);
+    const long npart = (long)B * C * F * ntiles, hw = (long)H * W;
+    float* mm = scratch + (size_t)npart * 2;
+    const int nblk = ds3_blocks(hw);
+    hipLaunchKernelGGL(minmax_frames_partial_k, dim3(nblk, F), dim3(256), 0, st, pred, B * C, F, hw, mm);
+    hipLaunchKernelGGL(minmax_fold_k, dim3(1, F), dim3(64), 0, st, (const float*)mm, nblk, range);
+    hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C, F), dim3(256), 0, st, pred, truth, F, H, W, tiles_x, ntiles, (const float*)range, scratch);
+    double* dpart = (double*)mm;            // the range partials are consumed by minmax_fold_k before this point
+    hipLaunchKernelGGL(dssim_fold_partial_k, dim3(DS_FOLD), dim3(256), 0, st, (const float*)scratch, npart, dpart);
+    hipLaunchKernelGGL(dssim_fold_k, dim3(1), dim3(DS_FOLD), 0, st, (const double*)dpart, (double)B * C * F * OH * OW, out);
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
+// dpred = gout[0] * d loss / d pred on the [B,C,F,H,W] layout; dtruth (may be null) likewise; range = what the forward wrote
+extern "C" int srcgan_dssim3d_loss_bwd(const float* pred, const float* truth, int B, int C, int F, int H, int W, const float* range,
+                                       const float* gout, float* dpred, float* dtruth, void* stream) {
+    SG_REQUIRE(pred && truth && range && gout && dpred, "srcgan_dssim3d_loss_bwd: null pointer");
+    SG_TRY(ds3_check("srcgan_dssim3d_loss_bwd", B, C, F, H, W));
+    hipStream_t st = (hipStream_t)stream;
+    const int tiles_x = cdiv(W, DS_T), ntiles = tiles_x * cdiv(H, DS_T);
+    const float invF = 1.0f / (float)F, inv2n = (float)(0.5 / ((double)B * C * (H - 10) * (W - 10)));
+    if (dtruth)
+        hipLaunchKernelGGL(dssim_bwd_k<true>, dim3(ntiles, B * C, F), dim3(256), 0, st, pred, truth, F, H, W, tiles_x, range, gout, invF, inv2n, dpred, dtruth);
+    else
+        hipLaunchKernelGGL(dssim_bwd_k<false>, dim3(ntiles, B * C, F), dim3(256), 0, st, pred, truth, F, H, W, tiles_x, range, gout, invF, inv2n, dpred, dtruth);
     SG_LAUNCH_CHECK();
     return 0;
 }

@@ -1591,10 +1591,12 @@ static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, co
         if (o.type == 4) SG_TRY(sg_fold_tail_pack(params[o.w], params[o.w2], wp + o.wf[0], P.T[o.out].C, dt, (hipStream_t)st));
     return 0;
 }
-static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, void* st) {
+// fr != nullptr: x_nchw is a 5-D tensor whose frames [f0, f0 + k) are the B images (common.h, SgFrames)
+static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, void* st, const SgFrames* fr = nullptr) {
     const int dt = P.dtype, B = P.B;
     char* w8 = (char*)ws; char* wp = w8 + P.wpk;
-    SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, P.in_ch, P.H, P.W, P.in_cs, dt, st));
+    if (fr) SG_TRY(sg_frames_pack(x_nchw, w8 + P.xin, P.in_cs, B / fr->k, *fr, P.H, P.W, dt, (hipStream_t)st));
+    else SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, P.in_ch, P.H, P.W, P.in_cs, dt, st));
     float* gnscr = (float*)(w8 + P.gnfwd);
     for (const RdOp& o : P.ops) {
         const RdT ti = P.T[o.in], to = P.T[o.out];
@@ -1752,7 +1754,7 @@ static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
 // A loss that sits behind the walk and reads the plan's taps (P.taps[k]) against a second branch's: the backward starts from it instead of
 // from dy_nchw.  Tap k adds scale[k] * d|a - b| (kind 0) or scale[k] * d(a - b)^2 (kind 1) to its tensor's gradient; the input gradient
 // leaves as f32 NCHW times gout[0] * gscale.
-struct RdTapLoss { int kind; const RdPlan* Pb; float scale[4]; const float* gout; float gscale; };
+struct RdTapLoss { int kind; const RdPlan* Pb; float scale[4]; const float* gout; float gscale; const SgFrames* fr = nullptr; };      // fr: dx_nchw is a 5-D tensor (rd_walk)
 
 static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, const float* const* params, void* ws, void* scratch, float* const* grads,
                        const char* tag, void* st, const RdTapLoss* tl = nullptr) {
@@ -1895,6 +1897,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
     }
     if (dx_nchw) {       // gradient w.r.t. the network input (an end-to-end cascade: trainCas.py:108 feeds one network's output to the next)
         SG_REQUIRE(written[0], "%s backward: internal error (no input gradient was produced)", tag);
+        if (tl && tl->fr) return sg_frames_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B / tl->fr->k, *tl->fr, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
         if (tl) return sg_image_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B, P.in_ch, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
         SG_TRY(srcgan_nhwc_to_nchw_f32(s8 + P.g[0], dx_nchw, B, P.in_ch, P.H, P.W, P.in_cs, 0, dt, st));
     }
@@ -2081,20 +2084,42 @@ static int vgg_plan(const srcgan_vggloss_cfg* c, bool infer, VggPlan& V) {
 }
 
 static int vgg_forward(const VggPlan& V, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws, float* loss_out,
-                       const char* tag, void* st) {
+                       const char* tag, void* st, const SgFrames* fr = nullptr) {
     SG_REQUIRE(out_nchw && tgt_nchw && params && ws && loss_out, "%s: null pointer", tag);
     SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", tag);
     const RdPlan& P = V.P;
     char* w8 = (char*)ws;
     SG_TRY(rd_pack_fwd(P, params, ws, tag, st));
-    SG_TRY(rd_walk(P, out_nchw, params, ws, st));
-    SG_TRY(rd_walk(V.Pt, tgt_nchw, params, ws, st));
+    SG_TRY(rd_walk(P, out_nchw, params, ws, st, fr));
+    SG_TRY(rd_walk(V.Pt, tgt_nchw, params, ws, st, fr));
     float* sums = (float*)(w8 + V.sums);
     for (int k = 0; k < V.ntap; ++k) {
         const RdT a = P.T[P.taps[k]], b = V.Pt.T[P.taps[k]];
         SG_TRY(srcgan_feat_loss_fwd(V.kind, w8 + a.off, a.cs, w8 + b.off, b.cs, (long)P.B * a.H * a.W, a.C, P.dtype, sums + k, (float*)(w8 + V.lscr), st));
     }
     return sg_vgg_combine(sums, V.wsum, V.ntap, loss_out, (hipStream_t)st);
+}
+
+static int vgg_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws, void* scratch,
+                        float* dout, void* st, const SgFrames* fr = nullptr) {
+    VggPlan V;
+    SG_TRY(vgg_plan(c, false, V));
+    SG_REQUIRE(gout_dev && dout, "vggloss backward: null pointer");
+    RdTapLoss tl;
+    tl.kind = V.kind; tl.Pb = &V.Pt; tl.gout = gout_dev; tl.gscale = gscale * V.gfinal; tl.fr = fr;
+    for (int k = 0; k < 4; ++k) tl.scale[k] = k < V.ntap ? V.gscale[k] : 0.f;
+    std::vector<float*> nograds(V.P.nparams, nullptr);       // frozen: every parameter gradient is skipped
+    return rd_backward(V.P, nullptr, dout, params, ws, scratch, nograds.data(), c->kind ? "vgg19loss" : "vgg16loss", st, &tl);
+}
+
+// the frames [f0, f0 + k) of a [Bt, C_in, F, H, W] tensor as the c->B = Bt * k images of a call
+static int vgg_frames(const srcgan_vggloss_cfg* c, int C_in, int F, int f0, int k, SgFrames& fr) {
+    SG_REQUIRE(c, "vggloss frames: null cfg");
+    SG_REQUIRE(C_in == 1 || C_in == 3, "vggloss frames: C_in must be 1 or 3, got %d", C_in);
+    SG_REQUIRE(F > 0 && k > 0 && f0 >= 0 && f0 <= F - k, "vggloss frames: frames [%d, %d + %d) leave the %d frames of the tensor", f0, f0, k, F);
+    SG_REQUIRE(c->B > 0 && c->B % k == 0, "vggloss frames: cfg.B = %d is not a multiple of the %d frames of the call", c->B, k);
+    fr.Cin = C_in; fr.F = F; fr.f0 = f0; fr.k = k;
+    return 0;
 }
 }  // namespace
 
@@ -2116,12 +2141,26 @@ extern "C" int srcgan_vggloss_infer(const srcgan_vggloss_cfg* c, const float* ou
 }
 extern "C" int srcgan_vggloss_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws,
                                        void* scratch, float* dout_nchw, void* st) {
-    VggPlan V;
+    return vgg_backward(c, gout_dev, gscale, params, ws, scratch, dout_nchw, st);
+}
+
+extern "C" int srcgan_vggloss_forward_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
+                                             const float* const* params, void* ws, float* loss_out, void* st) {
+    SgFrames fr; VggPlan V;
+    SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
     SG_TRY(vgg_plan(c, false, V));
-    SG_REQUIRE(gout_dev && dout_nchw, "vggloss backward: null pointer");
-    RdTapLoss tl;
-    tl.kind = V.kind; tl.Pb = &V.Pt; tl.gout = gout_dev; tl.gscale = gscale * V.gfinal;
-    for (int k = 0; k < 4; ++k) tl.scale[k] = k < V.ntap ? V.gscale[k] : 0.f;
-    std::vector<float*> nograds(V.P.nparams, nullptr);       // frozen: every parameter gradient is skipped
-    return rd_backward(V.P, nullptr, dout_nchw, params, ws, scratch, nograds.data(), c->kind ? "vgg19loss" : "vgg16loss", st, &tl);
+    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss" : "vgg16loss", st, &fr);
+}
+extern "C" int srcgan_vggloss_infer_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
+                                           const float* const* params, void* ws, float* loss_out, void* st) {
+    SgFrames fr; VggPlan V;
+    SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
+    SG_TRY(vgg_plan(c, true, V));
+    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss_infer" : "vgg16loss_infer", st, &fr);
+}
+extern "C" int srcgan_vggloss_backward_frames(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, int C_in, int F, int f0, int k,
+                                              const float* const* params, void* ws, void* scratch, float* dout5d, void* st) {
+    SgFrames fr;
+    SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
+    return vgg_backward(c, gout_dev, gscale, params, ws, scratch, dout5d, st, &fr);
 }

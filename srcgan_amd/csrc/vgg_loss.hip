@@ -194,10 +194,74 @@ __global__ __launch_bounds__(256) void image_grad_store_k(const T* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------------------------ frames of a 5-D tensor as images
+// Frames [f0, f0 + k) of a contiguous f32 [Bt, Cin, F, H, W] tensor <-> the 8-channel NHWC records of Bt * k images (image n = j * Bt + b
+// is frame f0 + j of sample b).  Plane (b, c) of frame f starts at element ((b * Cin + c) * F + f) * HW, in 64 bits.  Both passes are
+// HBM-bound: a thread owns V consecutive pixels of one image -- one 16-byte load / store per channel plane when V = 4 (HW % 4 == 0, so
+// every plane base keeps the tensor's 16-byte alignment), one element at a time when V = 1 -- and moves whole records in 16-byte pieces.
+template <typename T, int V>
+__global__ __launch_bounds__(256) void frames_pack_k(const float* __restrict__ src, T* __restrict__ dst, int Bt, int Cin, int F, int f0,
+                                                     long HW, long total) {
+    constexpr int PW = pk_width<T>();
+    const long npv = HW / V;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const long n = e / npv, p = (e % npv) * V;
+        const long b = n % Bt, j = n / Bt;
+        Pk<float, V> x[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (c < Cin) x[c] = *(const Pk<float, V>*)(src + (((size_t)b * Cin + c) * F + f0 + j) * HW + p);
+        if (Cin == 1) { x[1] = x[0]; x[2] = x[0]; }       // losses.py:378-380, the reference's torch.cat of three copies
+        T* d = dst + ((size_t)n * HW + p) * 8;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            Pk<T, PW> r[8 / PW];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) r[q / PW].v[q % PW] = from_f<T>(q < 3 ? x[q].v[i] : 0.f);
+#pragma unroll
+            for (int h = 0; h < 8 / PW; ++h) *(Pk<T, PW>*)(d + i * 8 + h * PW) = r[h];
+        }
+    }
+}
+
+// the input gradient back onto those frames, times gout[0] * gscale; every element of the k frames is written once
+template <typename T, int V>
+__global__ __launch_bounds__(256) void frames_grad_store_k(const T* __restrict__ src, float* __restrict__ dst, int Bt, int Cin, int F, int f0,
+                                                           long HW, long total, const float* __restrict__ gout, float gscale) {
+    constexpr int PW = pk_width<T>();      // >= 4: the first piece of a record holds the three channels
+    const float f = gout[0] * gscale;
+    const long npv = HW / V;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const long n = e / npv, p = (e % npv) * V;
+        const long b = n % Bt, j = n / Bt;
+        const T* s = src + ((size_t)n * HW + p) * 8;
+        Pk<float, V> g[3];
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+            const Pk<T, PW> r = *(const Pk<T, PW>*)(s + i * 8);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[c].v[i] = to_f(r.v[c]) * f;
+        }
+        if (Cin == 1) {
+#pragma unroll
+            for (int i = 0; i < V; ++i) g[0].v[i] = (g[0].v[i] + g[1].v[i]) + g[2].v[i];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (c < Cin) *(Pk<float, V>*)(dst + (((size_t)b * Cin + c) * F + f0 + j) * HW + p) = g[c];
+    }
+}
+
 #define VL_DISPATCH(dtype, vec, ...) \
     if ((dtype) == SRCGAN_F32) { using T = float; if (vec) { constexpr int V = 4; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } } \
     else if ((dtype) == SRCGAN_BF16) { using T = __bf16; if (vec) { constexpr int V = 8; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } } \
     else if ((dtype) == SRCGAN_F16) { using T = _Float16; if (vec) { constexpr int V = 8; __VA_ARGS__; } else { constexpr int V = 1; __VA_ARGS__; } } \
+    else SG_FAIL("bad dtype %d", (int)(dtype));
+
+#define DISPATCH_T(dtype, ...) \
+    if ((dtype) == SRCGAN_F32) { using T = float; __VA_ARGS__; } \
+    else if ((dtype) == SRCGAN_BF16) { using T = __bf16; __VA_ARGS__; } \
+    else if ((dtype) == SRCGAN_F16) { using T = _Float16; __VA_ARGS__; } \
     else SG_FAIL("bad dtype %d", (int)(dtype));
 
 static inline int vl_width(int dtype) { return dtype == SRCGAN_F32 ? 4 : 8; }
@@ -284,6 +348,38 @@ int sg_image_grad_store(const void* src, int cs, float* dst, int B, int C, int H
     else if (dtype == SRCGAN_BF16) hipLaunchKernelGGL(image_grad_store_k<__bf16>, dim3(vl_blocks(total)), dim3(256), 0, st, (const __bf16*)src, cs, C, HW, total, gout, gscale, dst);
     else if (dtype == SRCGAN_F16) hipLaunchKernelGGL(image_grad_store_k<_Float16>, dim3(vl_blocks(total)), dim3(256), 0, st, (const _Float16*)src, cs, C, HW, total, gout, gscale, dst);
     else SG_FAIL("sg_image_grad_store: bad dtype %d", dtype);
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
+static int frames_check(const char* who, const void* a, const void* b, int cs, int Bt, SgFrames fr, int H, int W) {
+    SG_REQUIRE(a && b && Bt > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+    SG_REQUIRE(cs == 8, "%s: records of 8 channels expected, got %d", who, cs);
+    SG_REQUIRE(fr.Cin == 1 || fr.Cin == 3, "%s: frames must have 1 or 3 channels, got %d", who, fr.Cin);
+    SG_REQUIRE(fr.F > 0 && fr.k > 0 && fr.f0 >= 0 && fr.f0 <= fr.F - fr.k, "%s: frames [%d, %d + %d) leave the %d frames of the tensor", who, fr.f0, fr.f0, fr.k, fr.F);
+    SG_REQUIRE(al16(b), "%s: the record buffer must be 16-byte aligned", who);
+    return 0;
+}
+
+int sg_frames_pack(const float* src5d, void* dst, int cs, int Bt, SgFrames fr, int H, int W, int dtype, hipStream_t st) {
+    SG_TRY(frames_check("sg_frames_pack", src5d, dst, cs, Bt, fr, H, W));
+    const long HW = (long)H * W;
+    const bool vec = HW % 4 == 0 && al16(src5d);
+    const long total = (long)Bt * fr.k * (vec ? HW / 4 : HW);
+    if (vec) { constexpr int V = 4; DISPATCH_T(dtype, hipLaunchKernelGGL((frames_pack_k<T, V>), dim3(vl_blocks(total)), dim3(256), 0, st, src5d, (T*)dst, Bt, fr.Cin, fr.F, fr.f0, HW, total)); }
+    else { constexpr int V = 1; DISPATCH_T(dtype, hipLaunchKernelGGL((frames_pack_k<T, V>), dim3(vl_blocks(total)), dim3(256), 0, st, src5d, (T*)dst, Bt, fr.Cin, fr.F, fr.f0, HW, total)); }
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
+int sg_frames_grad_store(const void* src, int cs, float* dst5d, int Bt, SgFrames fr, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st) {
+    SG_TRY(frames_check("sg_frames_grad_store", dst5d, src, cs, Bt, fr, H, W));
+    SG_REQUIRE(gout, "sg_frames_grad_store: null upstream gradient");
+    const long HW = (long)H * W;
+    const bool vec = HW % 4 == 0 && al16(dst5d);
+    const long total = (long)Bt * fr.k * (vec ? HW / 4 : HW);
+    if (vec) { constexpr int V = 4; DISPATCH_T(dtype, hipLaunchKernelGGL((frames_grad_store_k<T, V>), dim3(vl_blocks(total)), dim3(256), 0, st, (const T*)src, dst5d, Bt, fr.Cin, fr.F, fr.f0, HW, total, gout, gscale)); }
+    else { constexpr int V = 1; DISPATCH_T(dtype, hipLaunchKernelGGL((frames_grad_store_k<T, V>), dim3(vl_blocks(total)), dim3(256), 0, st, (const T*)src, dst5d, Bt, fr.Cin, fr.F, fr.f0, HW, total, gout, gscale)); }
     SG_LAUNCH_CHECK();
     return 0;
 }

@@ -5,6 +5,7 @@
   DSSIMLoss                    <- reference src/losses.py:170-180 (on SSIM, :20-93)
   VGG16Loss / PerceptionLoss   <- reference src/losses.py:344-393, 455-470 (frozen VGG16 / VGG19 features; weights come from the caller)
   NearestSelector              <- reference src/losses.py:199-255 (shift search + crops); NearestL1Loss = its use with L1Loss (:522), fused
+  L1Loss3D / DSSIMLoss3D / VGG16Loss3D <- reference src/losses.py:107-120, 183-196, 396-453 (means over the frames of [nb,ch,frame,row,col])
 
 Each forward is one native two-stage reduction (wavefront shuffles + fixed-order final sum,
 elementwise.hip) returning a 0-dim device tensor; backward is one fused elementwise kernel
@@ -15,6 +16,8 @@ The perceptual losses run a frozen VGG feature extractor on the op-list executor
 over both branches and one native backward that carries input gradients only.
 The shift search (shift_select.hip) reads both tensors once, accumulates every candidate offset in registers and leaves the selection on
 the device; NearestL1Loss takes its value from the search and never materialises a crop.
+The multi-frame losses read and write the 5-D layout in place: DSSIMLoss3D runs the 2-D kernels with a frame dimension in the grid and one
+dynamic range per frame, VGG16Loss3D packs chunks of frames as images straight from the 5-D tensor and runs each chunk's backward at once.
 """
 from __future__ import annotations
 
@@ -27,7 +30,8 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss", "NearestSelector", "NearestL1Loss"]
+__all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss", "NearestSelector", "NearestL1Loss",
+           "L1Loss3D", "DSSIMLoss3D", "VGG16Loss3D"]
 
 _K_L1, _K_MSE, _K_LABEL, _K_BCE, _K_SIGNED = 0, 1, 2, 3, 4       # srcgan_loss_fwd kinds; >= 2: scalar label instead of a target tensor
 
@@ -103,6 +107,47 @@ class _DSSIMFn(torch.autograd.Function):
                 "srcgan_dssim_loss_bwd")
         dp = dp.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
         return dp, None if dt is None else dt.to(ctx.dtypes[1])
+
+
+class _DSSIM3DFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target):
+        lib = N.lib()
+        p32, t32 = _as_f32(output, "DSSIMLoss3D output"), _as_f32(target, "DSSIMLoss3D target")
+        B, Cc, Fr, H, W = p32.shape
+        dev = p32.device
+        nfl = lib.srcgan_dssim3d_scratch_floats(B, Cc, Fr, H, W)
+        if nfl <= 0:
+            raise RuntimeError(f"srcgan_amd: srcgan_dssim3d_scratch_floats refused the shape {tuple(p32.shape)}")
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        rng = torch.empty((Fr, 2), dtype=torch.float32, device=dev)
+        scratch = torch.empty(nfl, dtype=torch.float32, device=dev)
+        N.check(lib.srcgan_dssim3d_loss_fwd(p32.data_ptr(), t32.data_ptr(), B, Cc, Fr, H, W, out.data_ptr(), rng.data_ptr(),
+                                            scratch.data_ptr(), N.stream_ptr(dev)), "srcgan_dssim3d_loss_fwd")
+        ctx.dtypes = (output.dtype, target.dtype)
+        ctx.save_for_backward(p32, t32, rng)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = N.lib()
+        p32, t32, rng = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        B, Cc, Fr, H, W = p32.shape
+        dp = torch.empty_like(p32)                       # the kernel always produces the output's gradient
+        dt = torch.empty_like(t32) if ctx.needs_input_grad[1] else None
+        N.check(lib.srcgan_dssim3d_loss_bwd(p32.data_ptr(), t32.data_ptr(), B, Cc, Fr, H, W, rng.data_ptr(), gout.data_ptr(),
+                                            dp.data_ptr(), None if dt is None else dt.data_ptr(), N.stream_ptr(p32.device)),
+                "srcgan_dssim3d_loss_bwd")
+        dp = dp.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
+        return dp, None if dt is None else dt.to(ctx.dtypes[1])
+
+
+def _check_5d(name, output, target):
+    if output.dim() != 5 or target.dim() != 5 or output.shape != target.shape:
+        raise ValueError(f"{name}: expected two [nb,ch,frame,row,col] tensors of one shape, got {tuple(output.shape)} and {tuple(target.shape)}")
+    if output.numel() == 0:
+        raise ValueError(f"{name}: empty input {tuple(output.shape)}")
 
 
 class L1Loss(nn.Module):
@@ -185,6 +230,42 @@ class DSSIMLoss(nn.Module):
         N.require_cuda(output, "DSSIMLoss output")
         N.require_cuda(target, "DSSIMLoss target")
         return _DSSIMFn.apply(output, target)
+
+
+class L1Loss3D(nn.Module):
+    """Mean over the frames of ``[nb,ch,frame,row,col]`` inputs of the per-frame L1 mean (losses.py:107-120).  Every frame has the same
+    element count, so the mean of the per-frame means is the mean over the whole tensor: this is ``L1Loss``'s reduction and backward
+    kernel (``srcgan_loss_fwd`` / ``_bwd``, kind L1) on the flat 5-D tensor -- no frame loop, no slice copies, no new kernel."""
+
+    def __repr__(self):
+        return "L13D"
+
+    def forward(self, output, target):
+        _check_5d("L1Loss3D", output, target)
+        N.require_cuda(output, "L1Loss3D output")
+        N.require_cuda(target, "L1Loss3D target")
+        return _MeanLossFn.apply(_K_L1, 0.0, output, target)
+
+
+class DSSIMLoss3D(nn.Module):
+    """Mean over the frames f of ``DSSIMLoss(output[:, :, f], target[:, :, f])`` (losses.py:183-196) in one autograd Function.  Like the
+    reference's loop, every frame takes the dynamic range of its own prediction (min / max over that frame of the whole batch), so a
+    stack that mixes 0..1, 0..255 and -1..1 frames is not the 2-D loss of the frames folded into the batch.  Inputs are
+    [nb,ch,frame,row,col] CUDA tensors with row, col >= 11 (other float dtypes compute in f32); the kernels address the 5-D layout
+    directly (one range launch, one SSIM launch and one fused backward pass for all frames, no per-frame copy).  The gradient reaches
+    the target only when it requires one.  Returns a 0-dim f32 device tensor; forward and backward never synchronise with the host.
+    The gradient of frame f has the bits of ``DSSIMLoss`` on that frame at upstream ``gout * (1 / frame)``."""
+
+    def __repr__(self):
+        return "DSSIM3D"
+
+    def forward(self, output, target):
+        _check_5d("DSSIMLoss3D", output, target)
+        if output.shape[3] < 11 or output.shape[4] < 11:
+            raise ValueError(f"DSSIMLoss3D: frames must be at least 11x11 (valid 11x11 windows), got {tuple(output.shape)}")
+        N.require_cuda(output, "DSSIMLoss3D output")
+        N.require_cuda(target, "DSSIMLoss3D target")
+        return _DSSIM3DFn.apply(output, target)
 
 
 # ------------------------------------------------------------------------------------------------ shift-tolerant pixel loss
@@ -439,7 +520,7 @@ class VGG16Loss(_VggLossBase):
     def __init__(self, requires_grad=False, cuda=True, *, weights=None, dtype=None):
         super().__init__()
         if requires_grad:
-            raise NotImplementedError("VGG16Loss: the native feature extractor is frozen (no weight-gradient launches): requires_grad=True is not implemented")
+            raise NotImplementedError(f"{type(self).__name__}: the native feature extractor is frozen (no weight-gradient launches): requires_grad=True is not implemented")
         self._dtype = N.dtype_id(dtype)
         layers = _vgg_layers(_VGG16_FEATURES)
         rename = {}
@@ -456,6 +537,94 @@ class VGG16Loss(_VggLossBase):
 
     def __repr__(self):
         return "VGG16"
+
+
+class _VggFramesFn(torch.autograd.Function):
+    """Carries the gradient that ``VGG16Loss3D.forward`` has already computed chunk by chunk: backward only scales it."""
+
+    @staticmethod
+    def forward(ctx, output, loss, grad):
+        ctx.grad = grad
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        if ctx.grad is None:
+            raise RuntimeError("perceptual loss: backward called a second time (the stored gradient is released by the first)")
+        grad, ctx.grad = ctx.grad, None
+        return (grad.float() * gout.float()).to(grad.dtype), None, None
+
+
+class VGG16Loss3D(VGG16Loss):
+    """Mean over the frames f of ``VGG16Loss(output[:, :, f], target[:, :, f])`` (losses.py:396-453).
+    ``VGG16Loss3D(requires_grad=False, cuda=True, *, weights=None, dtype=None, frames_per_pass=None)``: parameters, keys and weight
+    loading are ``VGG16Loss``'s.  ``forward(output, target)``: [nb,1|3,frame,row,col] CUDA tensors, row, col >= 8 -> 0-dim f32 device
+    tensor; the target branch is frozen.  Every per-frame mean has the same count, so the value is the four-tap loss of the frames taken
+    as a batch: frames run in chunks of ``frames_per_pass`` (``None``: all in one pass) as nb * chunk images that the native pack reads
+    straight from the 5-D tensor (a gray plane is replicated to three channels inside the pack, its three gradients summed in the
+    unpack), and the loss is the fixed-order sum of the chunks' shares.
+
+    When ``output`` requires grad, each chunk's native backward runs right after its forward (unit upstream scalar, the chunk's share
+    as scale) into that chunk's frames of one 5-D gradient buffer, and the chunk's workspace is released before the next chunk: peak
+    memory follows one chunk, not the frame count.  ``backward()`` then only multiplies the stored gradient by the upstream scalar; a
+    second ``backward()`` raises, like ``VGG16Loss``.  Under ``no_grad`` (or when ``output`` needs no gradient) the slot-planned
+    inference path runs per chunk."""
+
+    def __init__(self, requires_grad=False, cuda=True, *, weights=None, dtype=None, frames_per_pass=None):
+        if frames_per_pass is not None and not (isinstance(frames_per_pass, int) and frames_per_pass >= 1):
+            raise ValueError(f"VGG16Loss3D: frames_per_pass must be None or an integer >= 1, got {frames_per_pass!r}")
+        super().__init__(requires_grad, cuda, weights=weights, dtype=dtype)
+        self.frames_per_pass = frames_per_pass
+
+    def __repr__(self):
+        return "VGG163D"
+
+    def forward(self, output, target):
+        name = "VGG16Loss3D"
+        _check_5d(name, output, target)
+        Bt, Cin, Fr, H, W = (int(v) for v in output.shape)
+        if Cin not in (1, 3):
+            raise ValueError(f"{name}: inputs must have 1 or 3 channels, got {Cin}")
+        if H < 8 or W < 8:
+            raise ValueError(f"{name}: frames must be at least 8x8 (three max-pools), got {tuple(output.shape)}")
+        if target.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError(f"{name}: the target branch is frozen (it keeps no activations): detach the target")
+        N.require_cuda(output, f"{name} output")
+        N.require_cuda(target, f"{name} target")
+        plist = tuple(p.detach() for p in self.parameters())
+        for p in plist:
+            if p.device != output.device or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError(f"{name}: parameters must be contiguous float32 tensors on {output.device} (move the loss with .to(device))")
+        lib, dev = N.lib(), output.device
+        o32, t32 = _as_f32(output, f"{name} output"), _as_f32(target, f"{name} target")
+        need_grad = torch.is_grad_enabled() and output.requires_grad
+        params, st = N.ptr_array(plist), N.stream_ptr(dev)
+        step = Fr if self.frames_per_pass is None else min(self.frames_per_pass, Fr)
+        grad = torch.empty_like(o32) if need_grad else None
+        one = torch.ones((), dtype=torch.float32, device=dev) if need_grad else None
+        part = torch.empty((), dtype=torch.float32, device=dev)
+        total = torch.zeros((), dtype=torch.float32, device=dev)
+        for f0 in range(0, Fr, step):
+            k = min(step, Fr - f0)
+            share = k / Fr
+            cfg = N.VggLossCfg(self._kind, Bt * k, H, W, self._dtype)
+            if need_grad:
+                ws = N.workspace(lib.srcgan_vggloss_ws_bytes(C.byref(cfg)), dev)
+                N.check(lib.srcgan_vggloss_forward_frames(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), Cin, Fr, f0, k, params, ws.data_ptr(),
+                                                          part.data_ptr(), st), "srcgan_vggloss_forward_frames")
+                scratch = N.workspace(lib.srcgan_vggloss_bwd_scratch_bytes(C.byref(cfg)), dev)
+                N.check(lib.srcgan_vggloss_backward_frames(C.byref(cfg), one.data_ptr(), share, Cin, Fr, f0, k, params, ws.data_ptr(),
+                                                           scratch.data_ptr(), grad.data_ptr(), st), "srcgan_vggloss_backward_frames")
+                del ws, scratch               # the next chunk's workspace reuses this memory
+            else:
+                ws = N.workspace(lib.srcgan_vggloss_infer_ws_bytes(C.byref(cfg)), dev)
+                N.check(lib.srcgan_vggloss_infer_frames(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), Cin, Fr, f0, k, params, ws.data_ptr(),
+                                                        part.data_ptr(), st), "srcgan_vggloss_infer_frames")
+                del ws
+            total = total + part * share      # stream-ordered: `part` is rewritten by the next chunk only after this read
+        if not need_grad:
+            return total
+        return _VggFramesFn.apply(output, total, grad.to(output.dtype))
 
 
 class PerceptionLoss(_VggLossBase):
