@@ -513,11 +513,17 @@ int srcgan_feat_loss_bwd(int kind, const void* a, int a_cs, const void* b, int b
  *           the taps relu1_2, relu2_2, relu3_3, relu4_3 of the L1 mean between the two branches' features.
  *   kind 1: PerceptionLoss -- vgg19.features[0:35]: sixteen convolutions, four max-pools, ending at conv5_4 WITHOUT its ReLU; one tap,
  *           MSE.  H, W >= 16 (kind 0: >= 8).
- * out_nchw / tgt_nchw: [B,3,H,W] f32 NCHW.  params: weight, bias of every convolution in order (f32, canonical layout); frozen: there
- * are no parameter gradients.  forward keeps the output branch's activations in ws (the target branch runs on a slot-planned region
- * that retains only its taps) and writes the loss to loss_out (device f32); backward writes d loss / d out * gout_dev[0] * gscale to
- * dout_nchw.  Inside the backward gradients travel at unit scale (tap k contributes sign(a - b) * N_1 / N_k, resp. 2 (a - b)); the
- * factor 1 / (ntaps * N_1) is applied in the final f32 store, so 16-bit gradients do not underflow at training sizes.
+ * The images of a call are frames of 5-D tensors (losses.VGG16Loss3D, reference src/losses.py:396-453; a [B, C_in, H, W] tensor is
+ * F = 1, f0 = 0, k = 1 with c->B = B).  out5d / tgt5d / dout5d: contiguous f32 [Bt, C_in, F, H, W] with C_in = 1 or 3.  A call covers
+ * the k frames [f0, f0 + k) as c->B = Bt * k images (image j * Bt + b = frame f0 + j of sample b): the input pack reads the frames in
+ * place, and the input-gradient store writes them in place -- every element of those k frames of dout5d exactly once, other frames
+ * untouched.  C_in = 1: the plane is replicated to the three VGG channels inside the pack and the three channel gradients are summed
+ * into the one plane (what autograd does for the reference's torch.cat).
+ * params: weight, bias of every convolution in order (f32, canonical layout); frozen: there are no parameter gradients.  forward keeps
+ * the output branch's activations in ws (the target branch runs on a slot-planned region that retains only its taps) and writes the
+ * loss, the mean over the k frames of the per-frame loss, to loss_out (device f32); backward writes d loss / d out * gout_dev[0] *
+ * gscale to dout5d.  Inside the backward gradients travel at unit scale (tap k contributes sign(a - b) * N_1 / N_k, resp. 2 (a - b));
+ * the factor 1 / (ntaps * N_1) is applied in the final f32 store, so 16-bit gradients do not underflow at training sizes.
  * infer: the same loss value (same launches, same bits) with both branches on slot-planned regions, for no_grad. */
 typedef struct srcgan_vggloss_cfg {
     int kind;
@@ -527,21 +533,7 @@ typedef struct srcgan_vggloss_cfg {
 int srcgan_vggloss_num_params(const srcgan_vggloss_cfg* c);
 size_t srcgan_vggloss_ws_bytes(const srcgan_vggloss_cfg* c);
 size_t srcgan_vggloss_bwd_scratch_bytes(const srcgan_vggloss_cfg* c);
-int srcgan_vggloss_forward(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
-                           float* loss_out, void* stream);
-int srcgan_vggloss_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws,
-                            void* scratch, float* dout_nchw, void* stream);
 size_t srcgan_vggloss_infer_ws_bytes(const srcgan_vggloss_cfg* c);
-int srcgan_vggloss_infer(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
-                         float* loss_out, void* stream);
-
-/* The same losses on frames of 5-D tensors (losses.VGG16Loss3D, reference src/losses.py:396-453).  out5d / tgt5d / dout5d: contiguous f32
- * [Bt, C_in, F, H, W] with C_in = 1 or 3.  A call covers the k frames [f0, f0 + k) as c->B = Bt * k images (image j * Bt + b = frame
- * f0 + j of sample b): the input pack reads the frames in place, and the input-gradient store writes them in place -- every element of
- * those k frames of dout5d exactly once, other frames untouched.  C_in = 1: the plane is replicated to the three VGG channels inside the
- * pack and the three channel gradients are summed into the one plane (what autograd does for the reference's torch.cat).  The loss
- * written is the mean over the k frames of the per-frame loss; everything else (params, ws, scratch, gout_dev, gscale, sizes by the
- * functions above for the same cfg) is as in the 4-D entry points. */
 int srcgan_vggloss_forward_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
                                   const float* const* params, void* ws, float* loss_out, void* stream);
 int srcgan_vggloss_backward_frames(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, int C_in, int F, int f0, int k,
@@ -564,28 +556,20 @@ int srcgan_metric_scratch_floats(int B, int C, int H, int W);
 int srcgan_metric_ae(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* scratch, void* stream);
 int srcgan_metric_ssim(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* scratch, void* stream);
 
-/* DSSIM training loss (losses.py:170-180): (1 - SSIM(pred, truth)) / 2 with the metric's SSIM (11x11 gaussian sigma 1.5 "valid"
- * depth-wise windows, dynamic range L from the prediction's min / max).  pred / truth: [B,C,H,W] f32 NCHW, contiguous; H, W >= 11.
- *   srcgan_dssim_loss_fwd: out[0] = the loss (a device scalar); range[0..1] = min / max of pred, which backward reads (device, 2 floats);
- *                          scratch: srcgan_metric_scratch_floats(B, C, H, W) floats.
- *   srcgan_dssim_loss_bwd: dpred = gout[0] * dloss/dpred, dtruth = gout[0] * dloss/dtruth ([B,C,H,W] f32, overwritten); gout is a device
- *                          scalar, range the buffer the forward wrote for the same inputs.  dtruth may be NULL (no target gradient).
- *                          One fused pass per 32x32 output tile; deterministic (every element written once, no atomics). */
-int srcgan_dssim_loss_fwd(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* range,
-                          float* scratch, void* stream);
-int srcgan_dssim_loss_bwd(const float* pred, const float* truth, int B, int C, int H, int W, const float* range,
-                          const float* gout, float* dpred, float* dtruth, void* stream);
-
-/* Multi-frame DSSIM loss (losses.py:183-196, DSSIMLoss3D): the mean over frames f of the DSSIM loss of frame f, each frame with the
- * dynamic range of its own prediction (min / max over all B*C planes of that frame), as the reference's loop over frames has it.
- * pred / truth / dpred / dtruth: contiguous f32 [B,C,F,H,W]; plane (b, c) of frame f starts at element ((b*C + c)*F + f)*H*W (64-bit
- * offsets); H, W >= 11; B*C and F at most 65535.
- *   srcgan_dssim3d_loss_fwd: out[0] = the loss; range[f][0..1] = min / max of frame f of pred (device, 2 F floats), which backward reads;
- *                            scratch: srcgan_dssim3d_scratch_floats(B, C, F, H, W) floats (0 for a refused shape).  One range launch,
- *                            one tile launch and one f64 fold cover all frames; no per-frame copy, no host synchronisation.
- *   srcgan_dssim3d_loss_bwd: as srcgan_dssim_loss_bwd, on the 5-D layout; the upstream scalar enters as gout[0] * (1.0f / F).
- * The device code is that of the 4-D loss (which is its F = 1 instance), so with F = 1 both give the same bits, and the gradient of
- * frame f has the bits of the 4-D backward of that frame at upstream gout[0] * (1.0f / F). */
+/* DSSIM training loss (losses.py:170-196, DSSIMLoss and DSSIMLoss3D): the mean over frames f of (1 - SSIM(pred_f, truth_f)) / 2 with the
+ * metric's SSIM (11x11 gaussian sigma 1.5 "valid" depth-wise windows), each frame with the dynamic range of its own prediction (min /
+ * max over all B*C planes of that frame), as the reference's loop over frames has it.  pred / truth / dpred / dtruth: contiguous f32
+ * [B,C,F,H,W], a [B,C,H,W] tensor being F = 1; plane (b, c) of frame f starts at element ((b*C + c)*F + f)*H*W (64-bit offsets);
+ * H, W >= 11; B*C and F at most 65535.
+ *   srcgan_dssim3d_loss_fwd: out[0] = the loss (a device scalar); range[f][0..1] = min / max of frame f of pred (device, 2 F floats),
+ *                            which backward reads; scratch: srcgan_dssim3d_scratch_floats(B, C, F, H, W) floats (0 for a refused
+ *                            shape).  One range launch, one tile launch and one f64 fold cover all frames; no per-frame copy, no host
+ *                            synchronisation.
+ *   srcgan_dssim3d_loss_bwd: dpred = gout[0] * dloss/dpred, dtruth = gout[0] * dloss/dtruth (overwritten); gout is a device scalar,
+ *                            which enters as gout[0] * (1.0f / F), range the buffer the forward wrote for the same inputs.  dtruth may
+ *                            be NULL (no target gradient).  One fused pass per 32x32 output tile; deterministic (every element
+ *                            written once, no atomics).
+ * The gradient of frame f has the bits of a one-frame backward of that frame at upstream gout[0] * (1.0f / F). */
 long srcgan_dssim3d_scratch_floats(int B, int C, int F, int H, int W);
 int srcgan_dssim3d_loss_fwd(const float* pred, const float* truth, int B, int C, int F, int H, int W, float* out, float* range,
                             float* scratch, void* stream);

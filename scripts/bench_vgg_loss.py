@@ -3,7 +3,7 @@ record time and peak allocation of both in profiles/vgg_loss.txt.
 
   python scripts/bench_vgg_loss.py [--sizes 1024 256] [--batch 16] [--dtypes bf16 fp32] [--kinds 0 1] [--samples 7] [--out profiles/vgg_loss.txt]
 
-  native    the module's forward (one srcgan_vggloss_forward) and loss.backward() (one srcgan_vggloss_backward)
+  native    the module's forward (one srcgan_vggloss_forward_frames) and loss.backward() (one srcgan_vggloss_backward_frames)
   composed  F.conv2d / F.relu / F.max_pool2d on NCHW tensors of the same dtype (torch.autocast for bf16), the target branch under
             no_grad, F.l1_loss / F.mse_loss on the taps, loss.backward() through autograd -- the same weights
 

@@ -60,16 +60,17 @@ def main():
     st = N.stream_ptr(x.device)
     out = torch.empty((), device="cuda")
     rng = torch.empty(2, device="cuda")
-    scr = torch.empty(lib.srcgan_metric_scratch_floats(B, C, H, W), device="cuda")
+    scr = torch.empty(lib.srcgan_dssim3d_scratch_floats(B, C, 1, H, W), device="cuda")
     gout = torch.ones((), device="cuda")
     dx, dt = torch.empty_like(x), torch.empty_like(t)
 
-    fwd = lambda: N.check(lib.srcgan_dssim_loss_fwd(x.data_ptr(), t.data_ptr(), B, C, H, W, out.data_ptr(), rng.data_ptr(),
-                                                    scr.data_ptr(), st), "fwd")
-    bwd1 = lambda: N.check(lib.srcgan_dssim_loss_bwd(x.data_ptr(), t.data_ptr(), B, C, H, W, rng.data_ptr(), gout.data_ptr(),
-                                                     dx.data_ptr(), None, st), "bwd")
-    bwd2 = lambda: N.check(lib.srcgan_dssim_loss_bwd(x.data_ptr(), t.data_ptr(), B, C, H, W, rng.data_ptr(), gout.data_ptr(),
-                                                     dx.data_ptr(), dt.data_ptr(), st), "bwd")
+    # a [B,C,H,W] tensor is the F = 1 instance of the loss's [B,C,F,H,W] entry points
+    fwd = lambda: N.check(lib.srcgan_dssim3d_loss_fwd(x.data_ptr(), t.data_ptr(), B, C, 1, H, W, out.data_ptr(), rng.data_ptr(),
+                                                      scr.data_ptr(), st), "fwd")
+    bwd1 = lambda: N.check(lib.srcgan_dssim3d_loss_bwd(x.data_ptr(), t.data_ptr(), B, C, 1, H, W, rng.data_ptr(), gout.data_ptr(),
+                                                       dx.data_ptr(), None, st), "bwd")
+    bwd2 = lambda: N.check(lib.srcgan_dssim3d_loss_bwd(x.data_ptr(), t.data_ptr(), B, C, 1, H, W, rng.data_ptr(), gout.data_ptr(),
+                                                       dx.data_ptr(), dt.data_ptr(), st), "bwd")
     xg = x.clone().requires_grad_(True)
 
     def native_autograd():

@@ -188,10 +188,7 @@ SIGNATURES = {
     "srcgan_vggloss_num_params": (_I, [C.POINTER(VggLossCfg)]),
     "srcgan_vggloss_ws_bytes": (_S, [C.POINTER(VggLossCfg)]),
     "srcgan_vggloss_bwd_scratch_bytes": (_S, [C.POINTER(VggLossCfg)]),
-    "srcgan_vggloss_forward": (_I, [C.POINTER(VggLossCfg), _P, _P, _P, _P, _P, _P]),
-    "srcgan_vggloss_backward": (_I, [C.POINTER(VggLossCfg), _P, _F, _P, _P, _P, _P, _P]),
     "srcgan_vggloss_infer_ws_bytes": (_S, [C.POINTER(VggLossCfg)]),
-    "srcgan_vggloss_infer": (_I, [C.POINTER(VggLossCfg), _P, _P, _P, _P, _P, _P]),
     "srcgan_vggloss_forward_frames": (_I, [C.POINTER(VggLossCfg), _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "srcgan_vggloss_backward_frames": (_I, [C.POINTER(VggLossCfg), _P, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "srcgan_vggloss_infer_frames": (_I, [C.POINTER(VggLossCfg), _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
@@ -200,8 +197,6 @@ SIGNATURES = {
     "srcgan_metric_scratch_floats": (_I, [_I, _I, _I, _I]),
     "srcgan_metric_ae": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "srcgan_metric_ssim": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "srcgan_dssim_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "srcgan_dssim_loss_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
     "srcgan_dssim3d_scratch_floats": (_L, [_I, _I, _I, _I, _I]),
     "srcgan_dssim3d_loss_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "srcgan_dssim3d_loss_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

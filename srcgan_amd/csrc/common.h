@@ -137,13 +137,15 @@ void sg_pack_job_finish(SgPackJob& j, int dtype, long& blk_cursor);
 int sg_pack_multi_launch(const SgPackJob* jobs_dev, int njobs, long nblocks, void* wp_base, int dtype, hipStream_t st, const unsigned long long* guard = nullptr);
 // composed parity weights of ConvTranspose2d(64, 64, k2 s2, no bias) -> Conv2d(64, tar, 3x3 p1, no bias), written as four 2x2 packs of 8 rows
 int sg_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int tar, int dtype, hipStream_t st);
-// frozen VGG feature path (nets.hip -> vgg_loss.hip): out = sum_k sums[k] * weights[k] (host weights, n <= 4), and the final gradient
-// store: NHWC records of C <= 8 channels -> f32 NCHW, times gout[0] * gscale (gout on the device)
+// value range (metrics.hip; also scene_score.hip): range[2f .. 2f+1] = min / max of frame f of a contiguous f32 [planes, frames, n] tensor
+// over all its planes, left on the device by two launches.  nblk = the caller's partial blocks per frame; partial = frames * nblk * 2 floats
+void sg_minmax_frames(const float* x, int planes, int frames, long n, int nblk, float* partial, float* range, hipStream_t st);
+// frozen VGG feature path (nets.hip -> vgg_loss.hip): out = sum_k sums[k] * weights[k] (host weights, n <= 4)
 int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, hipStream_t st);
-int sg_image_grad_store(const void* src, int cs, float* dst, int B, int C, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);
-// the same path on frames of 5-D tensors (losses.VGG16Loss3D): frames [f0, f0 + k) of a contiguous f32 [Bt, Cin, F, H, W] tensor (Cin = 1 or
-// 3) <-> the 8-channel NHWC records of Bt * k images (image j * Bt + b = frame f0 + j of sample b).  The pack replicates a gray plane to
-// the three channels and zeroes channels 3..7; the store sums the three channel gradients into a gray plane.
+// its images are frames of 5-D tensors: frames [f0, f0 + k) of a contiguous f32 [Bt, Cin, F, H, W] tensor (Cin = 1 or 3; a [Bt, Cin, H, W]
+// tensor is F = 1, f0 = 0, k = 1) <-> the 8-channel NHWC records of Bt * k images (image j * Bt + b = frame f0 + j of sample b).  The pack
+// replicates a gray plane to the three channels and zeroes channels 3..7; the store multiplies by gout[0] * gscale (gout on the device)
+// and sums the three channel gradients into a gray plane.
 struct SgFrames { int Cin, F, f0, k; };
 int sg_frames_pack(const float* src5d, void* dst, int cs, int Bt, SgFrames fr, int H, int W, int dtype, hipStream_t st);
 int sg_frames_grad_store(const void* src, int cs, float* dst5d, int Bt, SgFrames fr, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);

@@ -42,31 +42,9 @@ __global__ void fold_k(const float* __restrict__ partial, int nblk, int nout, fl
     out[b * nout + j] = s * scale;
 }
 
-// min / max of a flat array (SSIM picks its dynamic range from them, metrics.py:100-107)
-__global__ __launch_bounds__(256) void minmax_partial_k(const float* __restrict__ x, long n, float* __restrict__ partial) {
-    __shared__ float rmin[4], rmax[4];
-    float lo = 3.4e38f, hi = -3.4e38f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) { const float v = x[i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_down(lo, o, 64)); hi = fmaxf(hi, __shfl_down(hi, o, 64)); }
-    if ((threadIdx.x & 63) == 0) { rmin[threadIdx.x >> 6] = lo; rmax[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        lo = rmin[0]; hi = rmax[0];
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, rmin[w]); hi = fmaxf(hi, rmax[w]); }
-        partial[blockIdx.x * 2] = lo; partial[blockIdx.x * 2 + 1] = hi;
-    }
-}
-__global__ void minmax_fold_k(const float* __restrict__ partial, int nblk, float* __restrict__ out) {
-    if (threadIdx.x) return;
-    partial += (size_t)blockIdx.y * nblk * 2; out += 2 * blockIdx.y;       // one (min, max) pair per blockIdx.y; the flat callers launch y = 1
-    float lo = partial[0], hi = partial[1];
-    for (int k = 1; k < nblk; ++k) { lo = fminf(lo, partial[2 * k]); hi = fmaxf(hi, partial[2 * k + 1]); }
-    out[0] = lo; out[1] = hi;
-}
-
-// per-frame min / max of a [BC, F, HW] tensor over all BC planes of frame f = blockIdx.y (DSSIMLoss3D picks one range per frame, like
-// the reference's loop over frames): partial[(f*gridDim.x + blk)*2 + {min, max}], folded by minmax_fold_k on a (1, F) grid
+// per-frame min / max of a [BC, F, HW] tensor over all BC planes of frame f = blockIdx.y (SSIM picks its dynamic range from them,
+// metrics.py:100-107; DSSIMLoss3D picks one range per frame, like the reference's loop over frames):
+// partial[(f*gridDim.x + blk)*2 + {min, max}], folded by minmax_fold_k on a (1, F) grid
 __global__ __launch_bounds__(256) void minmax_frames_partial_k(const float* __restrict__ x, int BC, int F, long hw, float* __restrict__ partial) {
     __shared__ float rmin[4], rmax[4];
     float lo = 3.4e38f, hi = -3.4e38f;
@@ -85,13 +63,27 @@ __global__ __launch_bounds__(256) void minmax_frames_partial_k(const float* __re
         o[0] = lo; o[1] = hi;
     }
 }
+__global__ __launch_bounds__(256) void minmax_fold_k(const float* __restrict__ partial, int nblk, float* __restrict__ out) {
+    __shared__ float rmin[4], rmax[4];
+    partial += (size_t)blockIdx.y * nblk * 2; out += 2 * blockIdx.y;       // one (min, max) pair per frame
+    float lo = 3.4e38f, hi = -3.4e38f;
+    for (int k = threadIdx.x; k < nblk; k += 256) { lo = fminf(lo, partial[2 * k]); hi = fmaxf(hi, partial[2 * k + 1]); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_down(lo, o, 64)); hi = fmaxf(hi, __shfl_down(hi, o, 64)); }
+    if ((threadIdx.x & 63) == 0) { rmin[threadIdx.x >> 6] = lo; rmax[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) { lo = fminf(lo, rmin[w]); hi = fmaxf(hi, rmax[w]); }
+        out[0] = lo; out[1] = hi;
+    }
+}
 
 // SSIM (metrics.py:72-144): 11x11 gaussian (sigma 1.5) depth-wise "valid" windows of x, y, x^2, y^2, xy; one workgroup per
 // 16x16 tile of the (H-10)x(W-10) map of one (image, channel): 26x26 patches in LDS, separable passes, map value + contrast term
 // summed per tile: partial[((b*C + c)*ntiles + tile)*2 + {ssim, cs}].  The dynamic range L is read from device memory
 // (written by the range kernel) so the whole metric is stream-ordered without a host round trip.
 // Frames: blockIdx.z = f of a [B,C,F,H,W] tensor; plane (bc, f) starts at element (bc*F + f)*H*W (64-bit), its partials sit at
-// ((bc*F + f)*ntiles + tile)*2 and its dynamic range is range[2f .. 2f+1].  The 4-D callers are the F = 1 instance (same addresses).
+// ((bc*F + f)*ntiles + tile)*2 and its dynamic range is range[2f .. 2f+1].  A 4-D tensor is the F = 1 instance (same addresses).
 __global__ __launch_bounds__(256) void ssim_tile_k(const float* __restrict__ p, const float* __restrict__ t, int F, int H, int W, int tiles_x, int ntiles,
                                                   const float* __restrict__ range, float* __restrict__ partial) {
     __shared__ float sp[26][27], st[26][27];
@@ -342,7 +334,13 @@ __global__ __launch_bounds__(256) void dssim_bwd_k(const float* __restrict__ p, 
         }
     }
 }
+static inline int ds3_blocks(long n) { const long b = cdivl(n, 256); return (int)(b > 256 ? 256 : b); }       // range blocks per frame
 }  // namespace
+
+void sg_minmax_frames(const float* x, int planes, int frames, long n, int nblk, float* partial, float* range, hipStream_t st) {
+    hipLaunchKernelGGL(minmax_frames_partial_k, dim3(nblk, frames), dim3(256), 0, st, x, planes, frames, n, partial);
+    hipLaunchKernelGGL(minmax_fold_k, dim3(1, frames), dim3(256), 0, st, (const float*)partial, nblk, range);
+}
 
 extern "C" int srcgan_metric_scratch_floats(int B, int C, int H, int W) {
     const long tiles = (long)cdiv(H > 10 ? H - 10 : 1, 16) * cdiv(W > 10 ? W - 10 : 1, 16);
@@ -371,58 +369,16 @@ extern "C" int srcgan_metric_ssim(const float* pred, const float* truth, int B, 
     float* range = scratch + (size_t)B * C * ntiles * 2;
     float* mm = range + 8;
     const long n = (long)B * C * H * W;
-    hipLaunchKernelGGL(minmax_partial_k, dim3(256), dim3(256), 0, st, pred, n, mm);
-    hipLaunchKernelGGL(minmax_fold_k, dim3(1), dim3(64), 0, st, (const float*)mm, 256, range);
+    sg_minmax_frames(pred, 1, 1, n, ds3_blocks(n), mm, range, st);        // one frame: the tensor is one contiguous run
     hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, ntiles, (const float*)range, scratch);
     hipLaunchKernelGGL(fold_k, dim3(B), dim3(64), 0, st, (const float*)scratch, C * ntiles, 2, 1.f / ((float)C * OH * OW), out);
     SG_LAUNCH_CHECK();
     return 0;
 }
 
-
-// DSSIM loss (losses.py:170-180): out[0] = (1 - mean SSIM over all B*C*(H-10)*(W-10) positions) / 2; range[0..1] = min / max of the
-// prediction (kept for srcgan_dssim_loss_bwd).  The per-image metric means share one position count, so the loss is the metric's
-// tile sums folded once more.
-extern "C" int srcgan_dssim_loss_fwd(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* range,
-                                     float* scratch, void* stream) {
-    SG_REQUIRE(pred && truth && out && range && scratch && B > 0 && C > 0, "srcgan_dssim_loss_fwd: bad arguments");
-    SG_REQUIRE(H >= 11 && W >= 11, "srcgan_dssim_loss_fwd: images must be at least 11x11 (valid 11x11 windows)");
-    SG_REQUIRE((long)B * C <= 65535, "srcgan_dssim_loss_fwd: B*C must be at most 65535");
-    hipStream_t st = (hipStream_t)stream;
-    const int OH = H - 10, OW = W - 10, tiles_x = cdiv(OW, 16), ntiles = tiles_x * cdiv(OH, 16);
-    float* mm = scratch + (size_t)B * C * ntiles * 2;
-    const long n = (long)B * C * H * W;
-    hipLaunchKernelGGL(minmax_partial_k, dim3(256), dim3(256), 0, st, pred, n, mm);
-    hipLaunchKernelGGL(minmax_fold_k, dim3(1), dim3(64), 0, st, (const float*)mm, 256, range);
-    hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, ntiles, (const float*)range, scratch);
-    double* dpart = (double*)mm;            // the min / max partials are consumed by minmax_fold_k before this point
-    hipLaunchKernelGGL(dssim_fold_partial_k, dim3(DS_FOLD), dim3(256), 0, st, (const float*)scratch, (long)B * C * ntiles, dpart);
-    hipLaunchKernelGGL(dssim_fold_k, dim3(1), dim3(DS_FOLD), 0, st, (const double*)dpart, (double)B * C * OH * OW, out);
-    SG_LAUNCH_CHECK();
-    return 0;
-}
-
-// dpred = gout[0] * d loss / d pred; dtruth (may be null) likewise; range = what srcgan_dssim_loss_fwd wrote for these inputs
-extern "C" int srcgan_dssim_loss_bwd(const float* pred, const float* truth, int B, int C, int H, int W, const float* range,
-                                     const float* gout, float* dpred, float* dtruth, void* stream) {
-    SG_REQUIRE(pred && truth && range && gout && dpred && B > 0 && C > 0, "srcgan_dssim_loss_bwd: bad arguments");
-    SG_REQUIRE(H >= 11 && W >= 11, "srcgan_dssim_loss_bwd: images must be at least 11x11 (valid 11x11 windows)");
-    SG_REQUIRE((long)B * C <= 65535, "srcgan_dssim_loss_bwd: B*C must be at most 65535");
-    hipStream_t st = (hipStream_t)stream;
-    const int tiles_x = cdiv(W, DS_T), ntiles = tiles_x * cdiv(H, DS_T);
-    const float inv2n = (float)(0.5 / ((double)B * C * (H - 10) * (W - 10)));
-    if (dtruth)
-        hipLaunchKernelGGL(dssim_bwd_k<true>, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, range, gout, 1.f, inv2n, dpred, dtruth);
-    else
-        hipLaunchKernelGGL(dssim_bwd_k<false>, dim3(ntiles, B * C), dim3(256), 0, st, pred, truth, 1, H, W, tiles_x, range, gout, 1.f, inv2n, dpred, dtruth);
-    SG_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- multi-frame DSSIM (losses.DSSIMLoss3D, reference src/losses.py:183-196): contiguous f32 [B,C,F,H,W]; the loss is the mean over
-// frames of the per-frame DSSIM, each frame with the dynamic range of its own prediction.  One range launch, one tile launch and one
-// fold cover all frames; nothing is copied per frame.
-static inline int ds3_blocks(long hw) { const long b = cdivl(hw, 256); return (int)(b > 256 ? 256 : b); }       // range blocks per frame
+// ---- DSSIM loss (losses.DSSIMLoss and DSSIMLoss3D, reference src/losses.py:170-196): contiguous f32 [B,C,F,H,W], a [B,C,H,W] tensor
+// being F = 1; the loss is the mean over frames of the per-frame DSSIM, each frame with the dynamic range of its own prediction.  One
+// range launch, one tile launch and one fold cover all frames; nothing is copied per frame.
 
 extern "C" long srcgan_dssim3d_scratch_floats(int B, int C, int F, int H, int W) {
     if (B <= 0 || C <= 0 || F <= 0 || H < 11 || W < 11) return 0;
@@ -448,11 +404,11 @@ extern "C" int srcgan_dssim3d_loss_fwd(const float* pred, const float* truth, in
     const int OH = H - 10, OW = W - 10, tiles_x = cdiv(OW, 16), ntiles = tiles_x * cdiv(OH, 16);
     const long npart = (long)B * C * F * ntiles, hw = (long)H * W;
     float* mm = scratch + (size_t)npart * 2;
-    const int nblk = ds3_blocks(hw);
-    hipLaunchKernelGGL(minmax_frames_partial_k, dim3(nblk, F), dim3(256), 0, st, pred, B * C, F, hw, mm);
-    hipLaunchKernelGGL(minmax_fold_k, dim3(1, F), dim3(64), 0, st, (const float*)mm, nblk, range);
+    const int planes = F == 1 ? 1 : B * C;          // one frame: the tensor is one contiguous run, so no block idles on a small image
+    const long n = F == 1 ? (long)B * C * hw : hw;
+    sg_minmax_frames(pred, planes, F, n, ds3_blocks(n), mm, range, st);
     hipLaunchKernelGGL(ssim_tile_k, dim3(ntiles, B * C, F), dim3(256), 0, st, pred, truth, F, H, W, tiles_x, ntiles, (const float*)range, scratch);
-    double* dpart = (double*)mm;            // the range partials are consumed by minmax_fold_k before this point
+    double* dpart = (double*)mm;            // the range partials are consumed by sg_minmax_frames before this point
     hipLaunchKernelGGL(dssim_fold_partial_k, dim3(DS_FOLD), dim3(256), 0, st, (const float*)scratch, npart, dpart);
     hipLaunchKernelGGL(dssim_fold_k, dim3(1), dim3(DS_FOLD), 0, st, (const double*)dpart, (double)B * C * F * OH * OW, out);
     SG_LAUNCH_CHECK();

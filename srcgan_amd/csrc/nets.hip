@@ -1753,8 +1753,8 @@ static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
 
 // A loss that sits behind the walk and reads the plan's taps (P.taps[k]) against a second branch's: the backward starts from it instead of
 // from dy_nchw.  Tap k adds scale[k] * d|a - b| (kind 0) or scale[k] * d(a - b)^2 (kind 1) to its tensor's gradient; the input gradient
-// leaves as f32 NCHW times gout[0] * gscale.
-struct RdTapLoss { int kind; const RdPlan* Pb; float scale[4]; const float* gout; float gscale; const SgFrames* fr = nullptr; };      // fr: dx_nchw is a 5-D tensor (rd_walk)
+// leaves times gout[0] * gscale on the frames fr of the 5-D tensor dx_nchw (rd_walk).
+struct RdTapLoss { int kind; const RdPlan* Pb; float scale[4]; const float* gout; float gscale; SgFrames fr; };
 
 static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, const float* const* params, void* ws, void* scratch, float* const* grads,
                        const char* tag, void* st, const RdTapLoss* tl = nullptr) {
@@ -1897,8 +1897,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
     }
     if (dx_nchw) {       // gradient w.r.t. the network input (an end-to-end cascade: trainCas.py:108 feeds one network's output to the next)
         SG_REQUIRE(written[0], "%s backward: internal error (no input gradient was produced)", tag);
-        if (tl && tl->fr) return sg_frames_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B / tl->fr->k, *tl->fr, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
-        if (tl) return sg_image_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B, P.in_ch, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
+        if (tl) return sg_frames_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B / tl->fr.k, tl->fr, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
         SG_TRY(srcgan_nhwc_to_nchw_f32(s8 + P.g[0], dx_nchw, B, P.in_ch, P.H, P.W, P.in_cs, 0, dt, st));
     }
     return 0;
@@ -2083,15 +2082,15 @@ static int vgg_plan(const srcgan_vggloss_cfg* c, bool infer, VggPlan& V) {
     return 0;
 }
 
-static int vgg_forward(const VggPlan& V, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws, float* loss_out,
-                       const char* tag, void* st, const SgFrames* fr = nullptr) {
-    SG_REQUIRE(out_nchw && tgt_nchw && params && ws && loss_out, "%s: null pointer", tag);
+static int vgg_forward(const VggPlan& V, const float* out5d, const float* tgt5d, const float* const* params, void* ws, float* loss_out,
+                       const char* tag, void* st, const SgFrames& fr) {
+    SG_REQUIRE(out5d && tgt5d && params && ws && loss_out, "%s: null pointer", tag);
     SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", tag);
     const RdPlan& P = V.P;
     char* w8 = (char*)ws;
     SG_TRY(rd_pack_fwd(P, params, ws, tag, st));
-    SG_TRY(rd_walk(P, out_nchw, params, ws, st, fr));
-    SG_TRY(rd_walk(V.Pt, tgt_nchw, params, ws, st, fr));
+    SG_TRY(rd_walk(P, out5d, params, ws, st, &fr));
+    SG_TRY(rd_walk(V.Pt, tgt5d, params, ws, st, &fr));
     float* sums = (float*)(w8 + V.sums);
     for (int k = 0; k < V.ntap; ++k) {
         const RdT a = P.T[P.taps[k]], b = V.Pt.T[P.taps[k]];
@@ -2101,7 +2100,7 @@ static int vgg_forward(const VggPlan& V, const float* out_nchw, const float* tgt
 }
 
 static int vgg_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws, void* scratch,
-                        float* dout, void* st, const SgFrames* fr = nullptr) {
+                        float* dout, void* st, const SgFrames& fr) {
     VggPlan V;
     SG_TRY(vgg_plan(c, false, V));
     SG_REQUIRE(gout_dev && dout, "vggloss backward: null pointer");
@@ -2127,40 +2126,23 @@ extern "C" int srcgan_vggloss_num_params(const srcgan_vggloss_cfg* c) { VggPlan 
 extern "C" size_t srcgan_vggloss_ws_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return 0; return V.total; }
 extern "C" size_t srcgan_vggloss_infer_ws_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, true, V)) return 0; return V.total; }
 extern "C" size_t srcgan_vggloss_bwd_scratch_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return 0; return V.P.bwd_total; }
-extern "C" int srcgan_vggloss_forward(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
-                                      float* loss_out, void* st) {
-    VggPlan V;
-    SG_TRY(vgg_plan(c, false, V));
-    return vgg_forward(V, out_nchw, tgt_nchw, params, ws, loss_out, c->kind ? "vgg19loss" : "vgg16loss", st);
-}
-extern "C" int srcgan_vggloss_infer(const srcgan_vggloss_cfg* c, const float* out_nchw, const float* tgt_nchw, const float* const* params, void* ws,
-                                    float* loss_out, void* st) {
-    VggPlan V;
-    SG_TRY(vgg_plan(c, true, V));
-    return vgg_forward(V, out_nchw, tgt_nchw, params, ws, loss_out, c->kind ? "vgg19loss_infer" : "vgg16loss_infer", st);
-}
-extern "C" int srcgan_vggloss_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws,
-                                       void* scratch, float* dout_nchw, void* st) {
-    return vgg_backward(c, gout_dev, gscale, params, ws, scratch, dout_nchw, st);
-}
-
 extern "C" int srcgan_vggloss_forward_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
                                              const float* const* params, void* ws, float* loss_out, void* st) {
     SgFrames fr; VggPlan V;
     SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
     SG_TRY(vgg_plan(c, false, V));
-    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss" : "vgg16loss", st, &fr);
+    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss" : "vgg16loss", st, fr);
 }
 extern "C" int srcgan_vggloss_infer_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
                                            const float* const* params, void* ws, float* loss_out, void* st) {
     SgFrames fr; VggPlan V;
     SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
     SG_TRY(vgg_plan(c, true, V));
-    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss_infer" : "vgg16loss_infer", st, &fr);
+    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss_infer" : "vgg16loss_infer", st, fr);
 }
 extern "C" int srcgan_vggloss_backward_frames(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, int C_in, int F, int f0, int k,
                                               const float* const* params, void* ws, void* scratch, float* dout5d, void* st) {
     SgFrames fr;
     SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
-    return vgg_backward(c, gout_dev, gscale, params, ws, scratch, dout5d, st, &fr);
+    return vgg_backward(c, gout_dev, gscale, params, ws, scratch, dout5d, st, fr);
 }

@@ -190,34 +190,6 @@ __global__ __launch_bounds__(256) void scene_score_k(const void* __restrict__ pr
     }
 }
 
-// min / max of n floats -> partial[block][{min, max}]
-__global__ __launch_bounds__(256) void ss_minmax_partial_k(const float* __restrict__ x, long n, float* __restrict__ partial) {
-    __shared__ float rmin[4], rmax[4];
-    float lo = 3.4e38f, hi = -3.4e38f;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) { const float v = x[i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_down(lo, o, 64)); hi = fmaxf(hi, __shfl_down(hi, o, 64)); }
-    if ((threadIdx.x & 63) == 0) { rmin[threadIdx.x >> 6] = lo; rmax[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, rmin[w]); hi = fmaxf(hi, rmax[w]); }
-        partial[blockIdx.x * 2] = lo; partial[blockIdx.x * 2 + 1] = hi;
-    }
-}
-__global__ __launch_bounds__(256) void ss_minmax_fold_k(const float* __restrict__ partial, int nblk, float* __restrict__ out) {
-    __shared__ float rmin[4], rmax[4];
-    float lo = 3.4e38f, hi = -3.4e38f;
-    for (int k = threadIdx.x; k < nblk; k += 256) { lo = fminf(lo, partial[2 * k]); hi = fmaxf(hi, partial[2 * k + 1]); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_down(lo, o, 64)); hi = fmaxf(hi, __shfl_down(hi, o, 64)); }
-    if ((threadIdx.x & 63) == 0) { rmin[threadIdx.x >> 6] = lo; rmax[threadIdx.x >> 6] = hi; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) { lo = fminf(lo, rmin[w]); hi = fmaxf(hi, rmax[w]); }
-        out[0] = lo; out[1] = hi;
-    }
-}
-
 // Sum of v over the threads with the same threadIdx.x & 3, fixed order; valid in threads 0..3 (for their own residue).  red: 16 doubles
 __device__ __forceinline__ double ss_sum_mod4(double v, double* red) {
 #pragma unroll
@@ -302,17 +274,14 @@ extern "C" int srcgan_scene_score(const void* pred, int pred_kind, const void* t
     char* ws = (char*)workspace;
     float* range = (float*)ws;
     float* mm = (float*)(ws + p.off_a);
-    double* dpart = (double*)(ws + p.off_a);        // the min / max partials are consumed by ss_minmax_fold_k before the fold writes here
+    double* dpart = (double*)(ws + p.off_a);        // the min / max partials are consumed by sg_minmax_frames before the fold writes here
     float* partial = (float*)(ws + p.off_part);
     // the reference's window: exp in double, stored as float, normalised in float (metrics.py:81-83)
     SsWin win;
     float gs = 0.f;
     for (int i = 0; i < 11; ++i) { win.w[i] = (float)exp(-(double)((i - 5) * (i - 5)) / 4.5); gs += win.w[i]; }
     for (int i = 0; i < 11; ++i) win.w[i] /= gs;
-    if (pred_kind == 0) {
-        hipLaunchKernelGGL(ss_minmax_partial_k, dim3(p.mmblk), dim3(256), 0, st, (const float*)pred, H * W * C, mm);
-        hipLaunchKernelGGL(ss_minmax_fold_k, dim3(1), dim3(256), 0, st, (const float*)mm, p.mmblk, range);
-    }
+    if (pred_kind == 0) sg_minmax_frames((const float*)pred, 1, 1, H * W * C, p.mmblk, mm, range, st);
     const dim3 grid((unsigned)p.ntiles);
     if (C == 1) ss_launch<1>(pred_kind, truth_kind, grid, st, pred, truth, H, W, (int)p.tiles_x, (int)p.tiles_y, win, range, partial);
     else        ss_launch<3>(pred_kind, truth_kind, grid, st, pred, truth, H, W, (int)p.tiles_x, (int)p.tiles_y, win, range, partial);

@@ -182,18 +182,6 @@ __global__ void vgg_combine_k(const float* __restrict__ sums, VlWeights w, int n
     *out = s;
 }
 
-// image-like NHWC records (C <= 8 channels at stride cs) -> f32 NCHW, times gout[0] * gscale read on the device
-template <typename T>
-__global__ __launch_bounds__(256) void image_grad_store_k(const T* __restrict__ src, int cs, int C, long HW, long total,
-                                                          const float* __restrict__ gout, float gscale, float* __restrict__ dst) {
-    const float f = gout[0] * gscale;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-        const long b = e / HW, p = e % HW;
-        const T* s = src + (size_t)e * cs;
-        for (int c = 0; c < C; ++c) dst[((size_t)b * C + c) * HW + p] = to_f(s[c]) * f;
-    }
-}
-
 // ------------------------------------------------------------------------------------------ frames of a 5-D tensor as images
 // Frames [f0, f0 + k) of a contiguous f32 [Bt, Cin, F, H, W] tensor <-> the 8-channel NHWC records of Bt * k images (image n = j * Bt + b
 // is frame f0 + j of sample b).  Plane (b, c) of frame f starts at element ((b * Cin + c) * F + f) * HW, in 64 bits.  Both passes are
@@ -337,17 +325,6 @@ int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, h
     VlWeights w = {{0.f, 0.f, 0.f, 0.f}};
     for (int k = 0; k < n; ++k) w.w[k] = weights[k];
     hipLaunchKernelGGL(vgg_combine_k, dim3(1), dim3(1), 0, st, sums, w, n, out);
-    SG_LAUNCH_CHECK();
-    return 0;
-}
-
-int sg_image_grad_store(const void* src, int cs, float* dst, int B, int C, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st) {
-    SG_REQUIRE(src && dst && gout && B > 0 && C > 0 && C <= cs && H > 0 && W > 0, "sg_image_grad_store: bad arguments");
-    const long HW = (long)H * W, total = (long)B * HW;
-    if (dtype == SRCGAN_F32) hipLaunchKernelGGL(image_grad_store_k<float>, dim3(vl_blocks(total)), dim3(256), 0, st, (const float*)src, cs, C, HW, total, gout, gscale, dst);
-    else if (dtype == SRCGAN_BF16) hipLaunchKernelGGL(image_grad_store_k<__bf16>, dim3(vl_blocks(total)), dim3(256), 0, st, (const __bf16*)src, cs, C, HW, total, gout, gscale, dst);
-    else if (dtype == SRCGAN_F16) hipLaunchKernelGGL(image_grad_store_k<_Float16>, dim3(vl_blocks(total)), dim3(256), 0, st, (const _Float16*)src, cs, C, HW, total, gout, gscale, dst);
-    else SG_FAIL("sg_image_grad_store: bad dtype %d", dtype);
     SG_LAUNCH_CHECK();
     return 0;
 }

@@ -16,8 +16,9 @@ The perceptual losses run a frozen VGG feature extractor on the op-list executor
 over both branches and one native backward that carries input gradients only.
 The shift search (shift_select.hip) reads both tensors once, accumulates every candidate offset in registers and leaves the selection on
 the device; NearestL1Loss takes its value from the search and never materialises a crop.
-The multi-frame losses read and write the 5-D layout in place: DSSIMLoss3D runs the 2-D kernels with a frame dimension in the grid and one
+The multi-frame losses read and write the 5-D layout in place: DSSIMLoss3D runs the SSIM kernels with a frame dimension in the grid and one
 dynamic range per frame, VGG16Loss3D packs chunks of frames as images straight from the 5-D tensor and runs each chunk's backward at once.
+Their native entry points (srcgan_dssim3d_*, srcgan_vggloss_*_frames) also serve the 4-D classes, for which a tensor is one frame.
 """
 from __future__ import annotations
 
@@ -79,42 +80,14 @@ class _MeanLossFn(torch.autograd.Function):
 
 
 class _DSSIMFn(torch.autograd.Function):
+    """DSSIM of [B,C,H,W] (one frame) or [B,C,F,H,W] tensors; the gradients come back in the input's own shape."""
+
     @staticmethod
     def forward(ctx, output, target):
         lib = N.lib()
-        p32, t32 = _as_f32(output, "DSSIMLoss output"), _as_f32(target, "DSSIMLoss target")
-        B, Cc, H, W = p32.shape
-        dev = p32.device
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        rng = torch.empty(2, dtype=torch.float32, device=dev)
-        scratch = torch.empty(lib.srcgan_metric_scratch_floats(B, Cc, H, W), dtype=torch.float32, device=dev)
-        N.check(lib.srcgan_dssim_loss_fwd(p32.data_ptr(), t32.data_ptr(), B, Cc, H, W, out.data_ptr(), rng.data_ptr(),
-                                          scratch.data_ptr(), N.stream_ptr(dev)), "srcgan_dssim_loss_fwd")
-        ctx.dtypes = (output.dtype, target.dtype)
-        ctx.save_for_backward(p32, t32, rng)
-        return out
-
-    @staticmethod
-    def backward(ctx, gout):
-        lib = N.lib()
-        p32, t32, rng = ctx.saved_tensors
-        gout = gout.contiguous().float()
-        B, Cc, H, W = p32.shape
-        dp = torch.empty_like(p32)                       # the kernel always produces the output's gradient
-        dt = torch.empty_like(t32) if ctx.needs_input_grad[1] else None
-        N.check(lib.srcgan_dssim_loss_bwd(p32.data_ptr(), t32.data_ptr(), B, Cc, H, W, rng.data_ptr(), gout.data_ptr(),
-                                          dp.data_ptr(), None if dt is None else dt.data_ptr(), N.stream_ptr(p32.device)),
-                "srcgan_dssim_loss_bwd")
-        dp = dp.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
-        return dp, None if dt is None else dt.to(ctx.dtypes[1])
-
-
-class _DSSIM3DFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, output, target):
-        lib = N.lib()
-        p32, t32 = _as_f32(output, "DSSIMLoss3D output"), _as_f32(target, "DSSIMLoss3D target")
-        B, Cc, Fr, H, W = p32.shape
+        p32, t32 = _as_f32(output, "DSSIM loss output"), _as_f32(target, "DSSIM loss target")
+        B, Cc, H, W = p32.shape[0], p32.shape[1], p32.shape[-2], p32.shape[-1]
+        Fr = p32.shape[2] if p32.dim() == 5 else 1
         dev = p32.device
         nfl = lib.srcgan_dssim3d_scratch_floats(B, Cc, Fr, H, W)
         if nfl <= 0:
@@ -124,6 +97,7 @@ class _DSSIM3DFn(torch.autograd.Function):
         scratch = torch.empty(nfl, dtype=torch.float32, device=dev)
         N.check(lib.srcgan_dssim3d_loss_fwd(p32.data_ptr(), t32.data_ptr(), B, Cc, Fr, H, W, out.data_ptr(), rng.data_ptr(),
                                             scratch.data_ptr(), N.stream_ptr(dev)), "srcgan_dssim3d_loss_fwd")
+        ctx.dims = (B, Cc, Fr, H, W)
         ctx.dtypes = (output.dtype, target.dtype)
         ctx.save_for_backward(p32, t32, rng)
         return out
@@ -133,10 +107,9 @@ class _DSSIM3DFn(torch.autograd.Function):
         lib = N.lib()
         p32, t32, rng = ctx.saved_tensors
         gout = gout.contiguous().float()
-        B, Cc, Fr, H, W = p32.shape
         dp = torch.empty_like(p32)                       # the kernel always produces the output's gradient
         dt = torch.empty_like(t32) if ctx.needs_input_grad[1] else None
-        N.check(lib.srcgan_dssim3d_loss_bwd(p32.data_ptr(), t32.data_ptr(), B, Cc, Fr, H, W, rng.data_ptr(), gout.data_ptr(),
+        N.check(lib.srcgan_dssim3d_loss_bwd(p32.data_ptr(), t32.data_ptr(), *ctx.dims, rng.data_ptr(), gout.data_ptr(),
                                             dp.data_ptr(), None if dt is None else dt.data_ptr(), N.stream_ptr(p32.device)),
                 "srcgan_dssim3d_loss_bwd")
         dp = dp.to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
@@ -265,7 +238,7 @@ class DSSIMLoss3D(nn.Module):
             raise ValueError(f"DSSIMLoss3D: frames must be at least 11x11 (valid 11x11 windows), got {tuple(output.shape)}")
         N.require_cuda(output, "DSSIMLoss3D output")
         N.require_cuda(target, "DSSIMLoss3D target")
-        return _DSSIM3DFn.apply(output, target)
+        return _DSSIMFn.apply(output, target)
 
 
 # ------------------------------------------------------------------------------------------------ shift-tolerant pixel loss
@@ -434,6 +407,15 @@ def _load_vgg_weights(module, weights, rename):
     module.load_state_dict(picked)
 
 
+def _vgg_infer(kind, dtype, o32, t32, nb, Fr, f0, k, params, out):
+    """The no-grad loss of frames [f0, f0 + k) of two f32 [nb, C, Fr, H, W] tensors (a [nb, C, H, W] tensor is Fr = 1) -> ``out``."""
+    lib = N.lib()
+    cfg = N.VggLossCfg(kind, nb * k, o32.shape[-2], o32.shape[-1], dtype)
+    ws = N.workspace(lib.srcgan_vggloss_infer_ws_bytes(C.byref(cfg)), o32.device)
+    N.check(lib.srcgan_vggloss_infer_frames(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), o32.shape[1], Fr, f0, k, params, ws.data_ptr(),
+                                            out.data_ptr(), N.stream_ptr(o32.device)), "srcgan_vggloss_infer_frames")
+
+
 class _VggLossFn(torch.autograd.Function):
     """One native forward over both branches and one native backward w.r.t. ``output``; the parameters are frozen."""
 
@@ -445,8 +427,8 @@ class _VggLossFn(torch.autograd.Function):
         cfg = N.VggLossCfg(kind, B, H, W, dtype)
         ws = N.workspace(lib.srcgan_vggloss_ws_bytes(C.byref(cfg)), o32.device)
         out = torch.empty((), dtype=torch.float32, device=o32.device)
-        N.check(lib.srcgan_vggloss_forward(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), N.ptr_array(plist), ws.data_ptr(), out.data_ptr(),
-                                           N.stream_ptr(o32.device)), "srcgan_vggloss_forward")
+        N.check(lib.srcgan_vggloss_forward_frames(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), 3, 1, 0, 1, N.ptr_array(plist), ws.data_ptr(),
+                                                  out.data_ptr(), N.stream_ptr(o32.device)), "srcgan_vggloss_forward_frames")
         ctx.cfg, ctx.ws, ctx.plist, ctx.in_dtype = cfg, ws, plist, output.dtype
         return out
 
@@ -459,8 +441,8 @@ class _VggLossFn(torch.autograd.Function):
         dev = ctx.ws.device
         scratch = N.workspace(lib.srcgan_vggloss_bwd_scratch_bytes(C.byref(cfg)), dev)
         dout = torch.empty((cfg.B, 3, cfg.H, cfg.W), dtype=torch.float32, device=dev)
-        N.check(lib.srcgan_vggloss_backward(C.byref(cfg), gout.data_ptr(), 1.0, N.ptr_array(ctx.plist), ctx.ws.data_ptr(), scratch.data_ptr(),
-                                            dout.data_ptr(), N.stream_ptr(dev)), "srcgan_vggloss_backward")
+        N.check(lib.srcgan_vggloss_backward_frames(C.byref(cfg), gout.data_ptr(), 1.0, 3, 1, 0, 1, N.ptr_array(ctx.plist), ctx.ws.data_ptr(),
+                                                   scratch.data_ptr(), dout.data_ptr(), N.stream_ptr(dev)), "srcgan_vggloss_backward_frames")
         ctx.ws = None
         return dout.to(ctx.in_dtype), None, None, None, None
 
@@ -477,33 +459,33 @@ class _VggLossBase(nn.Module):
         else:
             _load_vgg_weights(self, weights, rename)
 
-    def forward(self, output, target):
-        name = type(self).__name__
-        if output.dim() != 4 or target.dim() != 4 or output.shape != target.shape:
-            raise ValueError(f"{name}: expected two [B,C,H,W] tensors of one shape, got {tuple(output.shape)} and {tuple(target.shape)}")
+    def _checked_params(self, name, output, target):
+        """The channel, frozen-target and device checks of a forward (after its shape checks) -> the parameter list."""
         if output.shape[1] not in (1, 3):
             raise ValueError(f"{name}: inputs must have 1 or 3 channels, got {output.shape[1]}")
         if target.requires_grad and torch.is_grad_enabled():
             raise NotImplementedError(f"{name}: the target branch is frozen (it keeps no activations): detach the target")
         N.require_cuda(output, f"{name} output")
         N.require_cuda(target, f"{name} target")
-        if output.shape[1] == 1:       # losses.py:378-380: autograd sums the three gradients
-            output = torch.cat([output, output, output], dim=1)
-            target = torch.cat([target, target, target], dim=1)
         plist = tuple(p.detach() for p in self.parameters())
         for p in plist:
             if p.device != output.device or p.dtype != torch.float32 or not p.is_contiguous():
                 raise RuntimeError(f"{name}: parameters must be contiguous float32 tensors on {output.device} (move the loss with .to(device))")
+        return plist
+
+    def forward(self, output, target):
+        name = type(self).__name__
+        if output.dim() != 4 or target.dim() != 4 or output.shape != target.shape:
+            raise ValueError(f"{name}: expected two [B,C,H,W] tensors of one shape, got {tuple(output.shape)} and {tuple(target.shape)}")
+        plist = self._checked_params(name, output, target)
+        if output.shape[1] == 1:       # losses.py:378-380: autograd sums the three gradients
+            output = torch.cat([output, output, output], dim=1)
+            target = torch.cat([target, target, target], dim=1)
         if torch.is_grad_enabled() and output.requires_grad:
             return _VggLossFn.apply(output, target, self._kind, self._dtype, plist)
-        lib = N.lib()
         o32, t32 = _as_f32(output, f"{name} output"), _as_f32(target, f"{name} target")
-        B, _, H, W = o32.shape
-        cfg = N.VggLossCfg(self._kind, B, H, W, self._dtype)
-        ws = N.workspace(lib.srcgan_vggloss_infer_ws_bytes(C.byref(cfg)), o32.device)
         out = torch.empty((), dtype=torch.float32, device=o32.device)
-        N.check(lib.srcgan_vggloss_infer(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), N.ptr_array(plist), ws.data_ptr(), out.data_ptr(),
-                                         N.stream_ptr(o32.device)), "srcgan_vggloss_infer")
+        _vgg_infer(self._kind, self._dtype, o32, t32, o32.shape[0], 1, 0, 1, N.ptr_array(plist), out)
         return out
 
 
@@ -583,18 +565,9 @@ class VGG16Loss3D(VGG16Loss):
         name = "VGG16Loss3D"
         _check_5d(name, output, target)
         Bt, Cin, Fr, H, W = (int(v) for v in output.shape)
-        if Cin not in (1, 3):
-            raise ValueError(f"{name}: inputs must have 1 or 3 channels, got {Cin}")
         if H < 8 or W < 8:
             raise ValueError(f"{name}: frames must be at least 8x8 (three max-pools), got {tuple(output.shape)}")
-        if target.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(f"{name}: the target branch is frozen (it keeps no activations): detach the target")
-        N.require_cuda(output, f"{name} output")
-        N.require_cuda(target, f"{name} target")
-        plist = tuple(p.detach() for p in self.parameters())
-        for p in plist:
-            if p.device != output.device or p.dtype != torch.float32 or not p.is_contiguous():
-                raise RuntimeError(f"{name}: parameters must be contiguous float32 tensors on {output.device} (move the loss with .to(device))")
+        plist = self._checked_params(name, output, target)
         lib, dev = N.lib(), output.device
         o32, t32 = _as_f32(output, f"{name} output"), _as_f32(target, f"{name} target")
         need_grad = torch.is_grad_enabled() and output.requires_grad
@@ -607,8 +580,8 @@ class VGG16Loss3D(VGG16Loss):
         for f0 in range(0, Fr, step):
             k = min(step, Fr - f0)
             share = k / Fr
-            cfg = N.VggLossCfg(self._kind, Bt * k, H, W, self._dtype)
             if need_grad:
+                cfg = N.VggLossCfg(self._kind, Bt * k, H, W, self._dtype)
                 ws = N.workspace(lib.srcgan_vggloss_ws_bytes(C.byref(cfg)), dev)
                 N.check(lib.srcgan_vggloss_forward_frames(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), Cin, Fr, f0, k, params, ws.data_ptr(),
                                                           part.data_ptr(), st), "srcgan_vggloss_forward_frames")
@@ -617,10 +590,7 @@ class VGG16Loss3D(VGG16Loss):
                                                            scratch.data_ptr(), grad.data_ptr(), st), "srcgan_vggloss_backward_frames")
                 del ws, scratch               # the next chunk's workspace reuses this memory
             else:
-                ws = N.workspace(lib.srcgan_vggloss_infer_ws_bytes(C.byref(cfg)), dev)
-                N.check(lib.srcgan_vggloss_infer_frames(C.byref(cfg), o32.data_ptr(), t32.data_ptr(), Cin, Fr, f0, k, params, ws.data_ptr(),
-                                                        part.data_ptr(), st), "srcgan_vggloss_infer_frames")
-                del ws
+                _vgg_infer(self._kind, self._dtype, o32, t32, Bt, Fr, f0, k, params, part)
             total = total + part * share      # stream-ordered: `part` is rewritten by the next chunk only after this read
         if not need_grad:
             return total

@@ -98,6 +98,24 @@ def test_one_frame_is_the_2d_loss(case):
     assert _bits(dx[:, :, 0], dx2) and _bits(dt[:, :, 0], dt2)
 
 
+@pytest.mark.parametrize("dname", ["fp32", "bf16"])
+def test_vgg_one_frame_is_the_2d_loss(dname):
+    """VGG16Loss on [2,3,20,28] and VGG16Loss3D on the same data as [2,3,1,20,28] reach one native path: the same bits."""
+    from srcgan_amd import VGG16Loss, VGG16Loss3D
+    sd, out, tgt, _, _ = L.case(VGG_SHAPES[0])
+    o2, t2 = out[:, :, 0].contiguous().cuda(), tgt[:, :, 0].contiguous().cuda()
+    got = []
+    for crit, o, t in ((VGG16Loss(weights=sd, dtype=dname), o2, t2), (VGG16Loss3D(weights=sd, dtype=dname), o2.unsqueeze(2), t2.unsqueeze(2))):
+        o = o.clone().requires_grad_(True)
+        loss = crit(o, t)
+        loss.backward()
+        with torch.no_grad():
+            got.append((loss.detach(), o.grad, crit(o, t)))
+    (l2, dx2, n2), (l3, dx3, n3) = got
+    assert tuple(dx2.shape) == (2, 3, 20, 28) and tuple(dx3.shape) == (2, 3, 1, 20, 28)
+    assert _bits(l3, l2) and _bits(dx3[:, :, 0], dx2) and _bits(n3, n2)
+
+
 def test_deterministic():
     _, x, t = _fixture("mixed_ranges")           # B = 2, C = 3, F = 4, every frame different
     a, b = _native(_crit("dssim"), x, t), _native(_crit("dssim"), x, t)
