@@ -551,7 +551,15 @@ int srcgan_mask_inplace(void* g, const void* act, float slope, long n, int dtype
  *   srcgan_metric_ae:   out[b] = mean over pixels of acos(<p,t>/(|p||t| + 1e-6)) in degrees
  *   srcgan_metric_ssim: out[b][0] = mean SSIM (11x11 gaussian sigma 1.5 "valid" windows, dynamic range from the prediction's
  *                       min / max as metrics.py:100-107), out[b][1] = mean contrast term
- * MSE / PSNR: srcgan_loss_fwd(kind 1) + srcgan_psnr_from_mse.  scratch: srcgan_metric_scratch_floats(B, C, H, W) floats. */
+ * MSE / PSNR: srcgan_loss_fwd(kind 1) + srcgan_psnr_from_mse.  scratch: srcgan_metric_scratch_floats(B, C, H, W) floats.
+ * Pinned by tests/test_gpu_metrics_kernels.py:
+ *   - srcgan_metric_ae: the value of the formula as written, 1e-6 included, per image: 60, 90 and 180 degree pixels, a zero prediction
+ *     and two zero pixels (both 90 degrees) in any mix; pred == truth gives about 0.1 degrees, not 0 (the quotient is 1 - 1e-6 / |p|^2);
+ *     hw = 1, less than a block, one short of and one past 64 blocks of 256.  Within 4 x the error of a float32 restatement.
+ *   - srcgan_metric_ssim: out[b][0] and out[b][1] are image b's own means (a block of unrelated values in one image does not reach the
+ *     other), every window position counted once wherever the block sits: corners, edges, the 16-position tile seam, the last ragged
+ *     tile.  The dynamic range comes from the whole prediction: max > 128 (128.0 itself does not count) -> 255, min < -0.5 (-0.5 itself
+ *     does not) -> floor -1.  Nothing outside out[0 .. 2B) is written; no scratch slot is read before it is written. */
 int srcgan_metric_scratch_floats(int B, int C, int H, int W);
 int srcgan_metric_ae(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* scratch, void* stream);
 int srcgan_metric_ssim(const float* pred, const float* truth, int B, int C, int H, int W, float* out, float* scratch, void* stream);
@@ -569,7 +577,17 @@ int srcgan_metric_ssim(const float* pred, const float* truth, int B, int C, int 
  *                            which enters as gout[0] * (1.0f / F), range the buffer the forward wrote for the same inputs.  dtruth may
  *                            be NULL (no target gradient).  One fused pass per 32x32 output tile; deterministic (every element
  *                            written once, no atomics).
- * The gradient of frame f has the bits of a one-frame backward of that frame at upstream gout[0] * (1.0f / F). */
+ * The gradient of frame f has the bits of a one-frame backward of that frame at upstream gout[0] * (1.0f / F).
+ * Pinned by tests/test_gpu_metrics_kernels.py:
+ *   - srcgan_dssim3d_loss_bwd: EVERY element of dpred and dtruth is within K * 2^-24 * N(q) of float64 autograd, N(q) the gradient's own
+ *     expression with every term replaced by its absolute value (it shrinks at the border as the gradient does: the corner pixel, covered
+ *     by one window position with weight w[0]^2, is held as tightly as an interior one); K = 195 is 4 x what a float32 restatement
+ *     loses.  Shapes from one window position (11x11) to 2x3 output tiles with ragged edges, strips, two planes, two channels, two
+ *     frames of different range, L = 2, near-constant windows and SSIM near 1; with dtruth and with dtruth == NULL.  Every element of
+ *     the outputs is written and nothing around them; pred, truth and gout are not written.
+ *   - srcgan_dssim3d_loss_fwd: range[f] = (amin, amax) of frame f of pred, exactly, wherever the extremes sit (first and last element,
+ *     index 255 and 256, the last plane; more than 256 * 256 elements per frame); the loss counts every window position once (the
+ *     probes of srcgan_metric_ssim, also in one frame of two) and follows the range rule at its thresholds (see srcgan_metric_ssim). */
 long srcgan_dssim3d_scratch_floats(int B, int C, int F, int H, int W);
 int srcgan_dssim3d_loss_fwd(const float* pred, const float* truth, int B, int C, int F, int H, int W, float* out, float* range,
                             float* scratch, void* stream);

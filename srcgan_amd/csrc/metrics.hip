@@ -94,10 +94,11 @@ __global__ __launch_bounds__(256) void ssim_tile_k(const float* __restrict__ p, 
     const size_t plane = (size_t)bc * F + blockIdx.z;
     range += 2 * blockIdx.z;
     const int oy0 = ty * 16, ox0 = tx * 16, OH = H - 10, OW = W - 10;
-    if (threadIdx.x < 11) {
+    const int tid = threadIdx.x;
+    if (tid < 11) {
         float s = 0.f;
         for (int i = 0; i < 11; ++i) s += expf(-(float)((i - 5) * (i - 5)) / 4.5f);
-        gw[threadIdx.x] = expf(-(float)((threadIdx.x - 5) * (threadIdx.x - 5)) / 4.5f) / s;
+        gw[tid] = expf(-(float)((tid - 5) * (tid - 5)) / 4.5f) / s;
     }
     const float* pb = p + plane * H * W; const float* tb = t + plane * H * W;
     for (int i = threadIdx.x; i < 26 * 26; i += 256) {
