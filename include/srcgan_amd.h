@@ -247,6 +247,29 @@ int srcgan_gn_backward(const void* dy, int dy_cs, const void* yact, int ya_cs, c
                        void* dx, int dx_cs, void* dres, int dres_cs, int dres_accumulate, float* dgamma, float* dbeta, int accumulate,
                        float slope, int B, long hw, int C, int G, int dtype, float* scratch, void* stream);
 
+/* Channel attention fused with the block residual, on NHWC activations (rcan.py:11-27 CALayer, :45-49 RCAB.forward):
+ *   p[b][c] = mean_hw t[b][.][c];  h[b] = relu(W1 p[b] + b1);  s[b] = sigmoid(W2 h[b] + b2);  y = t * s[b][c] (+ res)
+ * W1 [Cr][C], b1 [Cr], W2 [C][Cr], b2 [C]: device f32 (the two 1x1 convolutions of conv_du, as stored).  saved: device f32
+ * [B][2C + Cr], per sample { p[C], h[Cr], s[C] } (written by forward, read by backward).  res may be null (y = t * s).
+ * backward, g = dy:  dres (optional) = g (+= when dres_accumulate);  ds = sum_hw g t;  dz2 = ds s (1 - s);  dW2 = sum_b dz2 (x) h;
+ * db2 = sum_b dz2;  dh = (W2^T dz2) [h > 0];  dW1 = sum_b dh (x) p;  db1 = sum_b dh;  dt = g s[b][c] + (W1^T dh)[b][c] / hw.
+ * dw1 / db1 / dw2 / db2: device f32, overwritten; each may be null on its own.
+ * scratch: srcgan_ca_scratch_floats(B, hw, C) floats (no state between calls).
+ *   - C a multiple of 8, at most 1024; 1 <= Cr <= C; every operand has its own channel stride (a multiple of 16 bytes of
+ *     channels, >= C); nothing outside [0, C) of a record is read or written.
+ *   - three launches each way, no host synchronisation, no atomics: the pixel sums are taken per chunk of 256 pixels (a chunking that
+ *     depends on hw alone) and folded in a fixed order, the batch sums of the parameter gradients run in sample order.  A call
+ *     repeated gives the same bits.  Sums and the gate are f32; y, dt and dres are each rounded to the storage type once.
+ *   - no output may alias an input or another output (the kernels take __restrict__ pointers).
+ *   - an error (C no multiple of 8 or > 1024, Cr outside 1..C, a bad stride or dtype, a null required pointer) names the entry
+ *     point in srcgan_last_error() and writes nothing. */
+size_t srcgan_ca_scratch_floats(int B, long hw, int C);
+int srcgan_ca_forward(const void* t, int t_cs, const void* res, int res_cs, void* y, int y_cs, const float* w1, const float* b1,
+                      const float* w2, const float* b2, float* saved, int B, long hw, int C, int Cr, int dtype, float* scratch, void* stream);
+int srcgan_ca_backward(const void* dy, int dy_cs, const void* t, int t_cs, const float* w1, const float* w2, const float* saved, void* dt,
+                       int dt_cs, void* dres, int dres_cs, int dres_accumulate, float* dw1, float* db1, float* dw2, float* db2, int B,
+                       long hw, int C, int Cr, int dtype, float* scratch, void* stream);
+
 /* x2 nearest up-sampling of an NHWC feature map (src may be a channel slice of a blocked buffer: s_plane != 0) and its
  * adjoint: dst[y][x] = sum of the 2x2 block of src, times LeakyReLU'(mz[y][x]) when mz is given.  Replaces
  * F.interpolate(scale_factor=2, mode='nearest') and its backward in the legacy generators (model/model.py:384-386,428-433). */
@@ -489,6 +512,33 @@ int srcgan_srdense_backward(const srcgan_srdense_cfg* c, const float* dy_nchw, c
                             float* const* grads, float* dx_nchw, void* stream);
 size_t srcgan_srdense_infer_ws_bytes(const srcgan_srdense_cfg* c);
 int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
+/* RCAN, the Residual Channel Attention Network (reference src/model/rcan.py:69-116 with common.py:11-21,59-86): sub_mean (MeanShift, a
+ * frozen 1x1 convolution 3 -> 3 + bias) -> head (3x3, 3 -> n_feats) -> n_resgroups x [ n_resblocks x [3x3 + ReLU, 3x3, channel
+ * attention (srcgan_ca_forward) + block input], 3x3 + group input ] -> 3x3 + head output -> Upsampler (per x2 stage 3x3 to 4 n_feats
+ * + PixelShuffle(2); scale 3: 3x3 to 9 n_feats + PixelShuffle(3)) -> 3x3 to 3 -> add_mean (MeanShift).  [B,3,H,W] f32 NCHW ->
+ * [B,3,H*scale,W*scale].  params / grads in parameters() order, which is registration order: sub_mean.{weight,bias}, add_mean.{weight,
+ * bias}, head.0.*, body.<g>.body.<b>.body.{0,2}.*, body.<g>.body.<b>.body.3.conv_du.{0,2}.*, body.<g>.body.<n_resblocks>.*,
+ * body.<n_resgroups>.*, tail.0.<2 stage>.*, tail.1.*.  MeanShift runs from its parameters (params[0..3]) and takes no gradient:
+ * grads[0..3] must be NULL.  Refused: in_ch or out_ch != 3, scale not in {2, 3, 4, 8}, n_feats no multiple of 16 or > 1024,
+ * n_feats / reduction < 1.  The infer entries are those of srcgan_srnet_infer (same launches on the slot-planned workspace, same bits;
+ * one `saved` region serves every attention op; the activation part does not depend on n_resgroups / n_resblocks from 2 x 2 on). */
+typedef struct srcgan_rcan_cfg {
+    int in_ch, out_ch;
+    int B, H, W;
+    int dtype;
+    int n_resgroups, n_resblocks, n_feats, reduction, scale;
+} srcgan_rcan_cfg;
+int srcgan_rcan_num_params(const srcgan_rcan_cfg* c);
+size_t srcgan_rcan_ws_bytes(const srcgan_rcan_cfg* c);
+size_t srcgan_rcan_bwd_scratch_bytes(const srcgan_rcan_cfg* c);
+int srcgan_rcan_forward(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_rcan_backward(const srcgan_rcan_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                         float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_rcan_infer_ws_bytes(const srcgan_rcan_cfg* c);
+size_t srcgan_rcan_infer_act_bytes(const srcgan_rcan_cfg* c);
+int srcgan_rcan_infer_plan(const srcgan_rcan_cfg* c, size_t* ranges, int cap);
+int srcgan_rcan_infer(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
 /* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
  * when strides and bases allow them, element by element otherwise).

@@ -103,6 +103,10 @@ class SrDenseCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "in_ch", "out_ch", "B", "H", "W", "dtype", "growth", "num_blocks", "num_layers", "up")]
 
 
+class RcanCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("in_ch", "out_ch", "B", "H", "W", "dtype", "n_resgroups", "n_resblocks", "n_feats", "reduction", "scale")]
+
+
 class VggLossCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "B", "H", "W", "dtype")]
 
@@ -141,6 +145,9 @@ SIGNATURES = {
     "srcgan_gn_scratch_floats": (_S, [_I, _I]),
     "srcgan_gn_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _L, _I, _I, _F, _I, _F, _I, _P, _P]),
     "srcgan_gn_backward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _F, _I, _L, _I, _I, _I, _P, _P]),
+    "srcgan_ca_scratch_floats": (_S, [_I, _L, _I]),
+    "srcgan_ca_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P]),
+    "srcgan_ca_backward": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P]),
     "srcgan_upsample2_nhwc": (_I, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_sum2x2_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _F, _I, _I, _I, _I, _I, _P]),
     "srcgan_loss_scratch_floats": (_I, []),
@@ -181,6 +188,15 @@ SIGNATURES = {
     "srcgan_srdense_backward": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P, _P, _P]),
     "srcgan_srdense_infer_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
     "srcgan_srdense_infer": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
+    "srcgan_rcan_num_params": (_I, [C.POINTER(RcanCfg)]),
+    "srcgan_rcan_ws_bytes": (_S, [C.POINTER(RcanCfg)]),
+    "srcgan_rcan_bwd_scratch_bytes": (_S, [C.POINTER(RcanCfg)]),
+    "srcgan_rcan_forward": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P]),
+    "srcgan_rcan_backward": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P, _P, _P]),
+    "srcgan_rcan_infer_ws_bytes": (_S, [C.POINTER(RcanCfg)]),
+    "srcgan_rcan_infer_act_bytes": (_S, [C.POINTER(RcanCfg)]),
+    "srcgan_rcan_infer_plan": (_I, [C.POINTER(RcanCfg), C.POINTER(C.c_size_t), _I]),
+    "srcgan_rcan_infer": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P]),
     "srcgan_maxpool2_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_maxpool2_bwd_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_feat_loss_fwd": (_I, [_I, _P, _I, _P, _I, _L, _I, _I, _P, _P, _P]),

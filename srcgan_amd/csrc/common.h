@@ -149,4 +149,7 @@ int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, h
 struct SgFrames { int Cin, F, f0, k; };
 int sg_frames_pack(const float* src5d, void* dst, int cs, int Bt, SgFrames fr, int H, int W, int dtype, hipStream_t st);
 int sg_frames_grad_store(const void* src, int cs, float* dst5d, int Bt, SgFrames fr, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);
+// MeanShift (nets.hip -> chan_attn.hip): y[q][0..2] = M x[q][0..2] (+ bias) on 8-channel image records, M = w [3][3] (f32, device) or its
+// transpose (the input gradient); channels 3..7 of y are written as zero
+int sg_meanshift(const void* x, void* y, const float* w, const float* bias, int transpose, long npix, int dtype, hipStream_t st);
 int sg_fill_zero_guarded(void* p, size_t bytes, const unsigned long long* guard, hipStream_t st);     // guard == nullptr: plain hipMemsetAsync

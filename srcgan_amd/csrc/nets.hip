@@ -1262,6 +1262,9 @@ struct RdOp {
                               // 4 (inference plans only) ConvTranspose2d k2 s2 followed by a bias-free 3x3 conv, folded into four parity 2x2 convs
                               // 5 ConvTranspose2d k3 s2 p1 output_padding 1 + bias + ReLU (deconv_k3s2.hip)
                               // 6 MaxPool2d(2, 2) (vgg_loss.hip)
+                              // 7 channel attention + block residual (chan_attn.hip): in = t, res = the block's input, w = conv_du.0.weight (its bias and
+                              //   conv_du.2.{weight,bias} follow), ngrp = C / reduction, stats = the op's `saved` region
+                              // 8 MeanShift, a frozen 1x1 convolution on the 3 image channels (chan_attn.hip)
     int in, out, res, relu;
     int icoff, iC, ocoff, oC; // type 0 on a dense buffer: reads channels [icoff, icoff + iC) of `in`, writes [ocoff, ocoff + oC) of `out` (iC / oC == 0: the whole tensor)
     int share;                // != 0: a module applied a second time -- op share - 1 owns the packs, this op's weight and bias gradients add to its
@@ -1352,6 +1355,21 @@ struct RdBuilder {
         o.out = tensor(ti.C, ti.cs, ti.H / 2, ti.W / 2);
         P.ops.push_back(o); return o.out;
     }
+    int ca(int in, int res, int cr) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 7; o.in = in; o.res = res; o.out = tensor(ti.C, ti.cs, ti.H, ti.W); o.bias = -1; o.ngrp = cr;
+        o.w = np; np += 4;
+        o.stats = b.take((size_t)B * (2 * ti.C + cr) * sizeof(float));
+        P.ops.push_back(o); return o.out;
+    }
+    int meanshift(int in) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 8; o.in = in; o.res = -1; o.k = 1; o.s = 1; o.w = np++; o.bias = np++;
+        o.out = tensor(3, 8, ti.H, ti.W);
+        P.ops.push_back(o); return o.out;
+    }
     void tap(int t) { P.taps.push_back(t); }
     // BasicBlock (resdeconv.py:56-97).  state_dict order inside a block: conv1, bn1, conv2, bn2, downsample.{0,1}
     int block(int x, int planes, int stride) {
@@ -1371,12 +1389,17 @@ struct RdBuilder {
         P.xin = b.take((size_t)B * H * W * P.in_cs * P.esz);
         P.T.push_back(RdT{in_ch, P.in_cs, H, W, 0, P.xin});
     }
+    size_t ca_scratch() const {       // the largest attention op's scratch (0: the plan has none)
+        size_t v = 0;
+        for (const RdOp& o : P.ops) if (o.type == 7) v = std::max(v, srcgan_ca_scratch_floats(B, (long)P.T[o.in].H * P.T[o.in].W, P.T[o.in].C));
+        return v;
+    }
     void finish(int dtype) {
         P.nparams = np;
         P.maxC = 8;
         for (const RdT& t : P.T) if (t.C > P.maxC) P.maxC = t.C;
         P.out_ch = P.T.back().C; P.out_cs = P.T.back().cs;
-        P.gnfwd = b.take(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC) * sizeof(float));
+        P.gnfwd = b.take(std::max(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC), ca_scratch()) * sizeof(float));
         P.act_bytes = b.off;
         P.wpk = b.off;
         Bump wb;
@@ -1428,7 +1451,7 @@ struct RdBuilder {
             if (v > slab) slab = v;
         }
         P.slab = s.take(slab);
-        P.gnscr = s.take(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC) * sizeof(float));
+        P.gnscr = s.take(std::max(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC), ca_scratch()) * sizeof(float));
         P.colscr = s.take((size_t)2 * srcgan_col_reduce_blocks(maxpix) * P.maxC * sizeof(float));
         P.btmp = 0;           // only plans that apply a module twice carry it (the others keep their size)
         for (const RdOp& o : P.ops) if (o.share && !P.btmp) P.btmp = s.take((size_t)P.maxC * sizeof(float));
@@ -1568,6 +1591,45 @@ static int sd_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
     nb.finish(c->dtype);
     return 0;
 }
+// RCAN (rcan.py:69-116).  Parameter indices follow parameters() order = registration order: sub_mean (:82), add_mean (:100, assigned
+// before head / body / tail at :102-104), head, body, tail -- the two MeanShift ops get their indices by hand.
+static int rcan_plan(const srcgan_rcan_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_rcan: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_rcan"));
+    SG_REQUIRE(c->in_ch == 3 && c->out_ch == 3, "srcgan_rcan: n_colors must be 3 (MeanShift is a 3-channel convolution, common.py:16)");
+    SG_REQUIRE(c->scale == 2 || c->scale == 3 || c->scale == 4 || c->scale == 8, "srcgan_rcan: scale = %d must be 2, 3, 4 or 8 (common.py:63-84)", c->scale);
+    SG_REQUIRE(c->n_feats > 0 && c->n_feats % 16 == 0 && c->n_feats <= 1024, "srcgan_rcan: n_feats = %d must be a multiple of 16, at most 1024", c->n_feats);
+    SG_REQUIRE(c->reduction >= 1 && c->n_feats / c->reduction >= 1, "srcgan_rcan: n_feats / reduction must be at least 1 (n_feats = %d, reduction = %d)",
+               c->n_feats, c->reduction);
+    SG_REQUIRE(c->n_resgroups >= 1 && c->n_resblocks >= 1 && (long)c->n_resgroups * c->n_resblocks <= 100000, "srcgan_rcan: n_resgroups and n_resblocks must be positive");
+    const int F = c->n_feats, cr = F / c->reduction;
+    RdBuilder nb(P, c->B);
+    nb.input(3, c->H, c->W);
+    int t = nb.meanshift(0);                                    // sub_mean: parameters 0, 1
+    nb.np = 4;                                                  // add_mean: parameters 2, 3
+    const int head = nb.conv(t, F, 3, 1, 1, true, false);
+    t = head;
+    for (int g = 0; g < c->n_resgroups; ++g) {
+        const int gin = t;
+        for (int k = 0; k < c->n_resblocks; ++k) {              // RCAB (:30-49)
+            const int x = t;
+            t = nb.conv(x, F, 3, 1, 1, true, true);
+            t = nb.conv(t, F, 3, 1, 1, true, false);
+            t = nb.ca(t, x, cr);
+        }
+        t = nb.conv(t, F, 3, 1, 1, true, false);                // ResidualGroup (:60-66)
+        P.ops.back().res = gin;
+    }
+    t = nb.conv(t, F, 3, 1, 1, true, false);                    // :93, 110-111
+    P.ops.back().res = head;
+    if (c->scale == 3) { t = nb.conv(t, 9 * F, 3, 1, 1, true, false); t = nb.shuffle(t, 3); }
+    else for (int f = 1; f < c->scale; f *= 2) { t = nb.conv(t, 4 * F, 3, 1, 1, true, false); t = nb.shuffle(t, 2); }
+    t = nb.conv(t, 3, 3, 1, 1, true, false);
+    nb.meanshift(t);
+    P.ops.back().w = 2; P.ops.back().bias = 3; nb.np -= 2;
+    nb.finish(c->dtype);
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -1628,6 +1690,12 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
             SG_TRY(cv.run(st));
         } else if (o.type == 6) {
             SG_TRY(srcgan_maxpool2_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, ti.C, dt, st));
+        } else if (o.type == 7) {
+            const void* res = o.res >= 0 ? (w8 + P.T[o.res].off) : nullptr;
+            SG_TRY(srcgan_ca_forward(xin.p, ti.cs, res, o.res >= 0 ? P.T[o.res].cs : 0, out.p, to.cs, params[o.w], params[o.w + 1], params[o.w + 2],
+                                     params[o.w + 3], (float*)(w8 + o.stats), B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
+        } else if (o.type == 8) {
+            SG_TRY(sg_meanshift(xin.p, out.p, params[o.w], params[o.bias], 0, (long)B * ti.H * ti.W, dt, (hipStream_t)st));
         } else {
             // folded tail: output pixel (2i + a, 2j + b) = 2x2 window of the half-resolution input at (i + a - 1, j + b - 1) times the
             // composed weights of parity (a, b) -- the geometry of the 4x4 stride-2 input gradient, so its four-parity kernel serves.
@@ -1698,10 +1766,17 @@ static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare =
     }
     if (spare) b.take(spare);
     size_t stats = 0;
-    for (const RdOp& o : P.ops) if (o.type == 1) stats = std::max(stats, (size_t)P.B * o.ngrp * 2 * sizeof(float));
+    size_t cascr = 0;
+    for (const RdOp& o : P.ops) {
+        if (o.type == 1) stats = std::max(stats, (size_t)P.B * o.ngrp * 2 * sizeof(float));
+        if (o.type == 7) {          // the attention ops' saved {p, h, s}: nothing reads them after the op either
+            stats = std::max(stats, (size_t)P.B * (2 * P.T[o.in].C + o.ngrp) * sizeof(float));
+            cascr = std::max(cascr, srcgan_ca_scratch_floats(P.B, (long)P.T[o.in].H * P.T[o.in].W, P.T[o.in].C));
+        }
+    }
     const size_t stats_off = b.take(stats);
-    for (RdOp& o : P.ops) if (o.type == 1) o.stats = stats_off;
-    P.gnfwd = b.take(srcgan_gn_scratch_floats(P.B, P.maxC > 1024 ? 1024 : P.maxC) * sizeof(float));
+    for (RdOp& o : P.ops) if (o.type == 1 || o.type == 7) o.stats = stats_off;
+    P.gnfwd = b.take(std::max(srcgan_gn_scratch_floats(P.B, P.maxC > 1024 ? 1024 : P.maxC), cascr) * sizeof(float));
     P.act_bytes = b.off;
     P.wpk = b.off;
     Bump wb;
@@ -1737,6 +1812,10 @@ static int sr_infer_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
 static int sd_infer_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
     SG_TRY(sd_plan(c, P));
     return rd_infer_replan(P, false, "srdense");
+}
+static int rcan_infer_plan(const srcgan_rcan_cfg* c, RdPlan& P) {
+    SG_TRY(rcan_plan(c, P));
+    return rd_infer_replan(P, false, "srcgan_rcan");
 }
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -1885,6 +1964,22 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
             SG_TRY(cv.run(st));
             written[o.in] = 1;
+        } else if (o.type == 7) {
+            void* dres = nullptr; int dres_cs = 0, dres_acc = 0;
+            if (o.res >= 0) {       // the block's input: this op stores (or adds to the group convolution's copy), the block's first convolution adds
+                dres = s8 + P.g[o.res]; dres_cs = P.T[o.res].cs; dres_acc = written[o.res]; written[o.res] = 1;
+            }
+            SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (attention input has two consumers or a fused activation)", tag);
+            SG_TRY(srcgan_ca_backward(dy.p, to.cs, xin.p, ti.cs, params[o.w], params[o.w + 2], (const float*)(w8 + o.stats), dx.p, ti.cs, dres, dres_cs,
+                                      dres_acc, G(o.w), G(o.w + 1), G(o.w + 2), G(o.w + 3), B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
+            written[o.in] = 1;
+        } else if (o.type == 8) {
+            SG_REQUIRE(!G(o.w) && !G(o.bias), "%s backward: MeanShift is frozen (its gradient pointers must be null)", tag);
+            SG_REQUIRE(!acc, "%s backward: internal error (MeanShift input with two consumers)", tag);
+            if (need_dx) {
+                SG_TRY(sg_meanshift(dy.p, dx.p, params[o.w], nullptr, 1, (long)B * ti.H * ti.W, dt, (hipStream_t)st));
+                written[o.in] = 1;
+            }
         } else if (o.type == 6) {
             SG_REQUIRE(!acc, "%s backward: internal error (pooled tensor with two consumers)", tag);
             SG_TRY(srcgan_maxpool2_bwd_nhwc(dy.p, to.cs, xin.p, ti.cs, dx.p, ti.cs, B, ti.H, ti.W, ti.C, ti.act && tap_of(o.in) < 0, dt, st));
@@ -1991,6 +2086,34 @@ extern "C" int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_
     RdPlan P;
     SG_TRY(sd_infer_plan(c, P));
     return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind ? "srdenseB_infer" : "srdenseA_infer", st);
+}
+
+// RCAN on the op-list executor (rcan_plan); the inference entries run the same launches on the slot-planned workspace.
+extern "C" int srcgan_rcan_num_params(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_plan(c, P)) return -1; return P.nparams; }
+extern "C" size_t srcgan_rcan_ws_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_plan(c, P)) return 0; return P.total; }
+extern "C" size_t srcgan_rcan_bwd_scratch_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_plan(c, P)) return 0; return P.bwd_total; }
+extern "C" int srcgan_rcan_forward(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(rcan_plan(c, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, "rcan", st);
+}
+extern "C" int srcgan_rcan_backward(const srcgan_rcan_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                                    float* const* grads, float* dx_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(rcan_plan(c, P));
+    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, "rcan", st);
+}
+extern "C" size_t srcgan_rcan_infer_ws_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_infer_plan(c, P)) return 0; return P.total; }
+extern "C" size_t srcgan_rcan_infer_act_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_infer_plan(c, P)) return 0; return P.total - P.wpack; }
+extern "C" int srcgan_rcan_infer_plan(const srcgan_rcan_cfg* c, size_t* ranges, int cap) {
+    RdPlan P;
+    if (rcan_infer_plan(c, P)) return -1;
+    return rd_plan_ranges(P, ranges, cap);
+}
+extern "C" int srcgan_rcan_infer(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(rcan_infer_plan(c, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, "rcan_infer", st);
 }
 
 // ======================================================================================== frozen VGG feature losses

@@ -156,6 +156,8 @@ def _scale(net) -> Optional[int]:
         return int(net._cfg[3])
     if isinstance(net, (M.SRCNN, M.SRDN, M.ResDeconv)):
         return 1
+    if isinstance(net, M.RCAN):
+        return int(net.scale)
     return None
 
 
@@ -191,12 +193,15 @@ def receptive_halo(net) -> int:
                                     2o - 1 .. 2o + 1; reconstruction and conv_last (model.py:761-763) 2 output pixels: x2 2 * 2 + 1 = 5
                                     input pixels, x4 2 * (2 * 2 + 1) + 1 = 11.  (An HR -> LR network: ``upscale_scene`` does not run it.)
 
-    Networks with normalisation layers (ResDeconv, EDSR: GroupNorm / InstanceNorm statistics are taken over the whole image) and
-    unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
+    Networks with normalisation layers (ResDeconv, EDSR: GroupNorm / InstanceNorm statistics are taken over the whole image), RCAN
+    (its channel attention pools over the whole image) and unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
     name = type(net).__name__
     if isinstance(net, (M.ResDeconv, M.EDSR)):
         raise ValueError(f"receptive_halo: {name} has normalisation layers whose per-image statistics make tiles inexact at any halo; "
                          "pass halo= explicitly (and blend='feather')")
+    if isinstance(net, M.RCAN):
+        raise ValueError(f"receptive_halo: {name} gates its channels by a global average pool (rcan.py:24-27) whose per-image value makes "
+                         "tiles inexact at any halo; pass halo= explicitly (and blend='feather')")
     if isinstance(net, M.LegacyRDDBNet):
         return 5 if net.mode == "x1" else 3
     if isinstance(net, M.RDDBNetB):

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
            "get_deconv_params"]
 
 
@@ -789,6 +789,128 @@ class SRDenseNetB(SRDenseNetA):
     @staticmethod
     def _sampler():
         return nn.Conv2d(256, 256, kernel_size=3, stride=2, padding=1)
+
+
+# ------------------------------------------------------------------------------------------------ RCAN
+_DIV2K_MEAN = (0.4488, 0.4371, 0.4040)          # the RGB mean of the DIV2K training set, as a fraction of the value range
+
+
+class _MeanShift(nn.Conv2d):
+    """The colour shift in front of and behind RCAN (common.py:11-21), kept as the frozen 1x1 convolution the reference's state_dict
+    holds: y = x / std + sign * rgb_range * mean / std per colour.  The convolution is first made with torch's default initialisation,
+    so a seeded construction draws the random numbers the reference's draws, and is then overwritten."""
+
+    def __init__(self, rgb_range, sign=-1, rgb_mean=_DIV2K_MEAN, rgb_std=(1.0, 1.0, 1.0)):
+        super().__init__(3, 3, kernel_size=1)
+        mean, std = torch.tensor(rgb_mean, dtype=torch.float32), torch.tensor(rgb_std, dtype=torch.float32)
+        self.weight.requires_grad_(False).copy_(torch.diag(1.0 / std).reshape(3, 3, 1, 1))
+        self.bias.requires_grad_(False).copy_(mean * (sign * rgb_range) / std)
+
+    def forward(self, *a, **k):  # pragma: no cover
+        return _HolderOnly.forward(self, *a, **k)
+
+
+class _CALayer(_HolderOnly):
+    """Parameter holder of rcan.py:11-22 CALayer."""
+
+    def __init__(self, channel, reduction=16):
+        super().__init__()
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.conv_du = nn.Sequential(nn.Conv2d(channel, channel // reduction, 1, padding=0, bias=True), nn.ReLU(inplace=True),
+                                     nn.Conv2d(channel // reduction, channel, 1, padding=0, bias=True), nn.Sigmoid())
+
+
+class _RCAB(_HolderOnly):
+    """Parameter holder of rcan.py:30-43 RCAB: body = [conv, ReLU, conv, CALayer]."""
+
+    def __init__(self, n_feat, reduction):
+        super().__init__()
+        self.body = nn.Sequential(nn.Conv2d(n_feat, n_feat, 3, padding=1), nn.ReLU(True), nn.Conv2d(n_feat, n_feat, 3, padding=1), _CALayer(n_feat, reduction))
+
+
+class _ResidualGroup(_HolderOnly):
+    """Parameter holder of rcan.py:52-61 ResidualGroup: body = n_resblocks RCABs and a convolution."""
+
+    def __init__(self, n_feat, reduction, n_resblocks):
+        super().__init__()
+        self.body = nn.Sequential(*[_RCAB(n_feat, reduction) for _ in range(n_resblocks)], nn.Conv2d(n_feat, n_feat, 3, padding=1))
+
+
+def _rcan_cfg(x, items):
+    n_colors, groups, blocks, feats, reduction, scale, dtype = items
+    _check_input(x, "RCAN", n_colors, f"RCAN expects [B,{n_colors},H,W]")
+    B, _, H, W = x.shape
+    return N.RcanCfg(n_colors, n_colors, B, H, W, dtype, groups, blocks, feats, reduction, scale), (B, n_colors, H * scale, W * scale)
+
+
+_RCAN = _OpList("RCAN", "srcgan_rcan", _rcan_cfg)
+
+
+class RCAN(_NativeRepr, nn.Module):
+    """Residual Channel Attention Network, drop-in for reference ``model.rcan.RCAN`` (src/model/rcan.py:69-142 with common.py):
+    ``RCAN(args)`` with the reference's attribute names (``n_resgroups, n_resblocks, n_feats, reduction, scale`` -- a list, its first
+    entry counts -- ``rgb_range, n_colors, res_scale``), or the same names as keywords.  sub_mean -> head -> n_resgroups residual
+    groups of n_resblocks channel-attention blocks -> + head -> Upsampler (PixelShuffle) -> conv -> add_mean;
+    ``forward(x[B,3,H,W]) -> [B,3,H*scale,W*scale]``.  ``res_scale`` is stored and unused, as in the reference (rcan.py:47).
+    The two MeanShift layers are frozen (``requires_grad=False``) and run from their parameters, so a loaded ``rgb_range`` / ``rgb_std``
+    is honoured.  Default torch initialisation, modules created in the reference's order: the same seed gives the same weights."""
+
+    def __init__(self, args=None, *, n_resgroups=10, n_resblocks=20, n_feats=64, reduction=16, scale=2, rgb_range=255, n_colors=3,
+                 res_scale=1, dtype=None):
+        super().__init__()
+        if args is not None:
+            n_resgroups, n_resblocks = getattr(args, "n_resgroups", n_resgroups), getattr(args, "n_resblocks", n_resblocks)
+            n_feats, reduction = getattr(args, "n_feats", n_feats), getattr(args, "reduction", reduction)
+            scale, rgb_range = getattr(args, "scale", scale), getattr(args, "rgb_range", rgb_range)
+            n_colors, res_scale = getattr(args, "n_colors", n_colors), getattr(args, "res_scale", res_scale)
+        if isinstance(scale, (list, tuple)):
+            scale = scale[0]
+        scale = int(scale)
+        self.compute_dtype = N.dtype_name(dtype)
+        self.scale, self.res_scale = scale, res_scale
+        self._cfg = (int(n_colors), int(n_resgroups), int(n_resblocks), int(n_feats), int(reduction), scale)
+        # the native planner owns the rules (3 colours, scale 2 / 3 / 4 / 8, n_feats % 16, n_feats // reduction >= 1): ask it first
+        probe = N.RcanCfg(self._cfg[0], self._cfg[0], 1, 8, 8, N.dtype_id(self.compute_dtype), *self._cfg[1:])
+        if N.lib().srcgan_rcan_num_params(C.byref(probe)) < 0:
+            raise ValueError("RCAN: " + (N.lib().srcgan_last_error() or b"").decode())
+        # creation order == the reference's (rcan.py:82-100); registration order (= parameters() order) too (:82, 100, 102-104)
+        sub_mean = _MeanShift(rgb_range)
+        head = [nn.Conv2d(n_colors, n_feats, 3, padding=1)]
+        body = [_ResidualGroup(n_feats, reduction, n_resblocks) for _ in range(n_resgroups)]
+        body.append(nn.Conv2d(n_feats, n_feats, 3, padding=1))
+        ups = []
+        for _ in range(1 if scale == 3 else int(math.log2(scale))):
+            r = 3 if scale == 3 else 2
+            ups += [nn.Conv2d(n_feats, r * r * n_feats, 3, padding=1), nn.PixelShuffle(r)]
+        tail = [nn.Sequential(*ups), nn.Conv2d(n_feats, n_colors, 3, padding=1)]
+        self.sub_mean = sub_mean
+        self.add_mean = _MeanShift(rgb_range, sign=1)
+        self.head = nn.Sequential(*head)
+        self.body = nn.Sequential(*body)
+        self.tail = nn.Sequential(*tail)
+
+    def forward(self, x):
+        return _oplist_forward(x, _RCAN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
+
+    def load_state_dict(self, state_dict, strict=False, assign=False):
+        """The reference's tolerant loader (rcan.py:118-142): entries are copied by name; one that does not fit is skipped when it
+        belongs to the tail (a checkpoint trained for another scale) and raises otherwise.  ``strict``: unknown names outside the tail
+        and missing names raise KeyError."""
+        own = self.state_dict()
+        for name, value in state_dict.items():
+            if name in own:
+                try:
+                    own[name].copy_(value.data if isinstance(value, nn.Parameter) else value)
+                except Exception:
+                    if "tail" not in name:
+                        raise RuntimeError(f"RCAN.load_state_dict: {name} has shape {tuple(own[name].shape)} in the model and "
+                                           f"{tuple(value.shape)} in the checkpoint")
+            elif strict and "tail" not in name:
+                raise KeyError(f'unexpected key "{name}" in state_dict')
+        if strict:
+            missing = set(own) - set(state_dict)
+            if missing:
+                raise KeyError(f"missing keys in state_dict: {sorted(missing)}")
 
 
 class _NLayerDFn(torch.autograd.Function):
