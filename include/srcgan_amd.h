@@ -293,6 +293,41 @@ int srcgan_loss_bwd(int kind, const float* a, const float* b, float label, long 
 /* psnr = 10*log10(1/mse) from a device mse scalar (losses.py:144-147) */
 int srcgan_psnr_from_mse(const float* mse, float* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Classification-style losses (losses.py:150-167 CELoss, :258-274 ConLoss, :277-293 CrossLoss, :296-341 FLoss; class_losses.hip).
+ * All tensors f32, contiguous, any 4-byte alignment (16-byte accesses where the pointers allow them); counts are 64-bit.  out: device
+ * f32 scalar.  scratch: srcgan_loss_scratch_floats() floats.  Every forward sums in two stages of fixed order (no atomics: two calls
+ * give the same bits); every backward reads the upstream gradient gout[0] from the device and writes EVERY element of its gradient
+ * exactly once (no memset).  Only the gradient w.r.t. output / feats is produced.
+ *
+ *   srcgan_focal_*: flat over n elements.  o = clamp(output, lo, hi), lo = (float)1e-6, hi = (float)(1.0 - 1e-6);
+ *       binary != 0:  l = -0.9 (1-o)^gamma t log o - 0.1 o^gamma (1-t) log(1-o)      binary == 0:  l = -(1-o)^gamma t log o
+ *     out = sum l / n (mean != 0) or sum l.  doutput = gout * dl/do (/ n) where lo <= output <= hi, bounds included, and exactly 0
+ *     outside (clamp's gradient).  An integer gamma in [0, 8] is taken by repeated multiplication; any other gamma from exp(gamma log b)
+ *     on the logarithms of the formula (no powf).
+ *   srcgan_bce_*: nn.BCELoss, mean: l = -(t max(log o, -100) + (1-t) max(log(1-o), -100)); doutput = gout (o - t) / max(o (1-o), 1e-12) / n.
+ *     No range check: an output outside [0, 1] gives NaN.
+ *   srcgan_nll_argmax_*: output / target [N, C, S].  Per (n, s): k = the FIRST maximum of target[n, :, s] (strict >, lowest channel wins);
+ *     out = mean over the N*S positions of -log output[n, k, s]; doutput = -gout / (output[n, k, s] N S) at channel k, 0 at the others.
+ *   srcgan_batch_range_*: feats [nb, M].  r[m] = max_b - min_b; out = mean_m r^2.  dfeats = +2 r gout / M at the first maximum's sample,
+ *     -2 r gout / M at the first minimum's (lowest sample on ties; the two add where both are one sample), 0 elsewhere; the indices are
+ *     recomputed from feats.  A NaN in a column makes the loss NaN (the gradient is then unspecified).
+ *   srcgan_cross_l1_*: output / target [nb, S], nb >= 2.  out = mean over (nb-1) S elements of |output[b] - target[b+1]|;
+ *     doutput[b] = sign(.) gout * (1 / (float)((nb-1) S)) for b < nb-1 (sign(0) = 0, the expression of srcgan_loss_bwd), zeros for b = nb-1.
+ * ------------------------------------------------------------------------- */
+int srcgan_focal_fwd(const float* output, const float* target, long n, int binary, float gamma, int mean, float* out,
+                     float* scratch, void* stream);
+int srcgan_focal_bwd(const float* output, const float* target, long n, int binary, float gamma, int mean, const float* gout,
+                     float* doutput, void* stream);
+int srcgan_bce_fwd(const float* output, const float* target, long n, float* out, float* scratch, void* stream);
+int srcgan_bce_bwd(const float* output, const float* target, long n, const float* gout, float* doutput, void* stream);
+int srcgan_nll_argmax_fwd(const float* output, const float* target, int N, int C, long S, float* out, float* scratch, void* stream);
+int srcgan_nll_argmax_bwd(const float* output, const float* target, int N, int C, long S, const float* gout, float* doutput, void* stream);
+int srcgan_batch_range_fwd(const float* feats, int nb, long M, float* out, float* scratch, void* stream);
+int srcgan_batch_range_bwd(const float* feats, int nb, long M, const float* gout, float* dfeats, void* stream);
+int srcgan_cross_l1_fwd(const float* output, const float* target, int nb, long S, float* out, float* scratch, void* stream);
+int srcgan_cross_l1_bwd(const float* output, const float* target, int nb, long S, const float* gout, float* doutput, void* stream);
+
 /* In-step preprocessing (trainCas.py:85-90): gray = .2125R+.7154G+.0721B (NCHW f32 in/out),
  * bilinear x(1/up) with align_corners=False == mean of the centre 2x2 of each up x up block. */
 int srcgan_rgb_to_gray(const float* rgb, float* gray, int B, int H, int W, void* stream);

@@ -154,6 +154,16 @@ SIGNATURES = {
     "srcgan_loss_fwd": (_I, [_I, _P, _P, _F, _L, _P, _P, _P]),
     "srcgan_loss_bwd": (_I, [_I, _P, _P, _F, _L, _P, _F, _P, _P]),
     "srcgan_psnr_from_mse": (_I, [_P, _P, _P]),
+    "srcgan_focal_fwd": (_I, [_P, _P, _L, _I, _F, _I, _P, _P, _P]),
+    "srcgan_focal_bwd": (_I, [_P, _P, _L, _I, _F, _I, _P, _P, _P]),
+    "srcgan_bce_fwd": (_I, [_P, _P, _L, _P, _P, _P]),
+    "srcgan_bce_bwd": (_I, [_P, _P, _L, _P, _P, _P]),
+    "srcgan_nll_argmax_fwd": (_I, [_P, _P, _I, _I, _L, _P, _P, _P]),
+    "srcgan_nll_argmax_bwd": (_I, [_P, _P, _I, _I, _L, _P, _P, _P]),
+    "srcgan_batch_range_fwd": (_I, [_P, _I, _L, _P, _P, _P]),
+    "srcgan_batch_range_bwd": (_I, [_P, _I, _L, _P, _P, _P]),
+    "srcgan_cross_l1_fwd": (_I, [_P, _P, _I, _L, _P, _P, _P]),
+    "srcgan_cross_l1_bwd": (_I, [_P, _P, _I, _L, _P, _P, _P]),
     "srcgan_rgb_to_gray": (_I, [_P, _P, _I, _I, _I, _P]),
     "srcgan_bilinear_down": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "srcgan_nearest_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

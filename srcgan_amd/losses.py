@@ -6,6 +6,7 @@
   VGG16Loss / PerceptionLoss   <- reference src/losses.py:344-393, 455-470 (frozen VGG16 / VGG19 features; weights come from the caller)
   NearestSelector              <- reference src/losses.py:199-255 (shift search + crops); NearestL1Loss = its use with L1Loss (:522), fused
   L1Loss3D / DSSIMLoss3D / VGG16Loss3D <- reference src/losses.py:107-120, 183-196, 396-453 (means over the frames of [nb,ch,frame,row,col])
+  CELoss / ConLoss / CrossLoss / FLoss <- reference src/losses.py:150-167, 258-274, 277-293, 296-341
 
 Each forward is one native two-stage reduction (wavefront shuffles + fixed-order final sum,
 elementwise.hip) returning a 0-dim device tensor; backward is one fused elementwise kernel
@@ -19,6 +20,9 @@ the device; NearestL1Loss takes its value from the search and never materialises
 The multi-frame losses read and write the 5-D layout in place: DSSIMLoss3D runs the SSIM kernels with a frame dimension in the grid and one
 dynamic range per frame, VGG16Loss3D packs chunks of frames as images straight from the 5-D tensor and runs each chunk's backward at once.
 Their native entry points (srcgan_dssim3d_*, srcgan_vggloss_*_frames) also serve the 4-D classes, for which a tensor is one frame.
+The classification-style losses (class_losses.hip) are one pass over their inputs forward and one backward each: the focal loss takes
+its powers by multiplication (integer gamma) or from the logarithms of its own formula, the multi-class cross-entropy finds the target's
+arg-max while it reads it, ConLoss recomputes the extreme samples in its backward, CrossLoss addresses the shifted target in place.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ import torch.nn as nn
 from . import _native as N
 
 __all__ = ["L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss", "NearestSelector", "NearestL1Loss",
-           "L1Loss3D", "DSSIMLoss3D", "VGG16Loss3D"]
+           "L1Loss3D", "DSSIMLoss3D", "VGG16Loss3D", "FLoss", "CELoss", "ConLoss", "CrossLoss"]
 
 _K_L1, _K_MSE, _K_LABEL, _K_BCE, _K_SIGNED = 0, 1, 2, 3, 4       # srcgan_loss_fwd kinds; >= 2: scalar label instead of a target tensor
 
@@ -239,6 +243,209 @@ class DSSIMLoss3D(nn.Module):
         N.require_cuda(output, "DSSIMLoss3D output")
         N.require_cuda(target, "DSSIMLoss3D target")
         return _DSSIMFn.apply(output, target)
+
+
+# ------------------------------------------------------------------------------------------------ classification-style losses
+def _check_pair(name, output, target, min_dim=2, dims=None, min_batch=1):
+    """Shape, emptiness and frozen-target checks of the two-tensor class losses, then the device check."""
+    ok = output.dim() == target.dim() and output.shape == target.shape and (output.dim() == dims if dims else output.dim() >= min_dim)
+    if not ok:
+        want = f"{dims}-D" if dims else f"at least {min_dim}-D"
+        raise ValueError(f"{name}: expected two {want} tensors of one shape, got {tuple(output.shape)} and {tuple(target.shape)}")
+    if output.numel() == 0:
+        raise ValueError(f"{name}: empty input {tuple(output.shape)}")
+    if output.shape[0] < min_batch:
+        raise ValueError(f"{name}: needs at least two samples (sample b is compared with sample b+1), got {tuple(output.shape)}")
+    if target.requires_grad:
+        raise ValueError(f"{name}: the native backward produces the output's gradient only: detach the target")
+    N.require_cuda(output, f"{name} output")
+    N.require_cuda(target, f"{name} target")
+
+
+def _loss_buffers(dev):
+    return (torch.empty((), dtype=torch.float32, device=dev),
+            torch.empty(N.lib().srcgan_loss_scratch_floats(), dtype=torch.float32, device=dev))
+
+
+class _FocalFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target, gamma, mean):
+        lib = N.lib()
+        o32, t32 = _as_f32(output, "FLoss output"), _as_f32(target, "FLoss target")
+        out, scratch = _loss_buffers(o32.device)
+        ctx.cfg = (int(o32.shape[1] == 1), float(gamma), int(bool(mean)))
+        N.check(lib.srcgan_focal_fwd(o32.data_ptr(), t32.data_ptr(), o32.numel(), *ctx.cfg, out.data_ptr(), scratch.data_ptr(),
+                                     N.stream_ptr(o32.device)), "srcgan_focal_fwd")
+        ctx.in_dtype = output.dtype
+        ctx.save_for_backward(o32, t32)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        o32, t32 = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        do = torch.empty_like(o32)
+        N.check(N.lib().srcgan_focal_bwd(o32.data_ptr(), t32.data_ptr(), o32.numel(), *ctx.cfg, gout.data_ptr(), do.data_ptr(),
+                                         N.stream_ptr(o32.device)), "srcgan_focal_bwd")
+        return do.to(ctx.in_dtype), None, None, None
+
+
+class _CEFn(torch.autograd.Function):
+    @staticmethod
+    def _dims(o32):
+        n, c = int(o32.shape[0]), int(o32.shape[1])
+        return n, c, o32.numel() // (n * c)
+
+    @staticmethod
+    def forward(ctx, output, target):
+        lib = N.lib()
+        o32, t32 = _as_f32(output, "CELoss output"), _as_f32(target, "CELoss target")
+        out, scratch = _loss_buffers(o32.device)
+        st = N.stream_ptr(o32.device)
+        if o32.shape[1] == 1:
+            N.check(lib.srcgan_bce_fwd(o32.data_ptr(), t32.data_ptr(), o32.numel(), out.data_ptr(), scratch.data_ptr(), st), "srcgan_bce_fwd")
+        else:
+            N.check(lib.srcgan_nll_argmax_fwd(o32.data_ptr(), t32.data_ptr(), *_CEFn._dims(o32), out.data_ptr(), scratch.data_ptr(), st),
+                    "srcgan_nll_argmax_fwd")
+        ctx.in_dtype = output.dtype
+        ctx.save_for_backward(o32, t32)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        lib = N.lib()
+        o32, t32 = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        do = torch.empty_like(o32)
+        st = N.stream_ptr(o32.device)
+        if o32.shape[1] == 1:
+            N.check(lib.srcgan_bce_bwd(o32.data_ptr(), t32.data_ptr(), o32.numel(), gout.data_ptr(), do.data_ptr(), st), "srcgan_bce_bwd")
+        else:
+            N.check(lib.srcgan_nll_argmax_bwd(o32.data_ptr(), t32.data_ptr(), *_CEFn._dims(o32), gout.data_ptr(), do.data_ptr(), st),
+                    "srcgan_nll_argmax_bwd")
+        return do.to(ctx.in_dtype), None
+
+
+class _ConFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feats):
+        f32 = _as_f32(feats, "ConLoss feats")
+        out, scratch = _loss_buffers(f32.device)
+        nb = int(f32.shape[0])
+        N.check(N.lib().srcgan_batch_range_fwd(f32.data_ptr(), nb, f32.numel() // nb, out.data_ptr(), scratch.data_ptr(),
+                                               N.stream_ptr(f32.device)), "srcgan_batch_range_fwd")
+        ctx.in_dtype = feats.dtype
+        ctx.save_for_backward(f32)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        f32, = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        df = torch.empty_like(f32)
+        nb = int(f32.shape[0])
+        N.check(N.lib().srcgan_batch_range_bwd(f32.data_ptr(), nb, f32.numel() // nb, gout.data_ptr(), df.data_ptr(),
+                                               N.stream_ptr(f32.device)), "srcgan_batch_range_bwd")
+        return df.to(ctx.in_dtype)
+
+
+class _CrossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, output, target):
+        o32, t32 = _as_f32(output, "CrossLoss output"), _as_f32(target, "CrossLoss target")
+        out, scratch = _loss_buffers(o32.device)
+        nb = int(o32.shape[0])
+        N.check(N.lib().srcgan_cross_l1_fwd(o32.data_ptr(), t32.data_ptr(), nb, o32.numel() // nb, out.data_ptr(), scratch.data_ptr(),
+                                            N.stream_ptr(o32.device)), "srcgan_cross_l1_fwd")
+        ctx.in_dtype = output.dtype
+        ctx.save_for_backward(o32, t32)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        o32, t32 = ctx.saved_tensors
+        gout = gout.contiguous().float()
+        do = torch.empty_like(o32)
+        nb = int(o32.shape[0])
+        N.check(N.lib().srcgan_cross_l1_bwd(o32.data_ptr(), t32.data_ptr(), nb, o32.numel() // nb, gout.data_ptr(), do.data_ptr(),
+                                            N.stream_ptr(o32.device)), "srcgan_cross_l1_bwd")
+        return do.to(ctx.in_dtype), None
+
+
+class FLoss(nn.Module):
+    """Focal loss (losses.py:296-341), ``FLoss(gamma=2., weight=None, size_average=True)``; ``weight`` is stored and unused, as in the
+    reference.  With o = clamp(output, 1e-6, 1 - 1e-6) (float32 bounds): ``target.shape[1] == 1`` selects the binary form
+    ``-0.9 (1-o)^gamma t log o - 0.1 o^gamma (1-t) log(1-o)`` (alpha = 0.1), anything else ``-(1-o)^gamma t log o``; the mean (or, with
+    ``size_average=False``, the sum) runs over every element, channels included.  Inputs: two CUDA tensors of one shape, at least 2-D
+    (other float dtypes compute in f32).  One pass forward, one backward (srcgan_focal_*); the gradient reaches ``output`` only, is
+    clamp's (zero outside [1e-6, 1 - 1e-6], bounds included), and a target that requires grad is refused."""
+
+    def __init__(self, gamma=2., weight=None, size_average=True):
+        super().__init__()
+        self.gamma = gamma
+        self.weight = weight
+        self.size_average = size_average
+
+    def __repr__(self):
+        return "Focal"
+
+    def forward(self, output, target):
+        _check_pair("FLoss", output, target)
+        return _FocalFn.apply(output, target, self.gamma, self.size_average)
+
+
+class CELoss(nn.Module):
+    """Cross-entropy (losses.py:150-167).  ``target.shape[1] == 1``: ``nn.BCELoss`` (mean, logarithms clamped at -100) between two tensors
+    (srcgan_bce_*).  Otherwise ``nn.NLLLoss(log(output), argmax(target, dim=1))``: the mean over the batch and spatial positions of
+    ``-log output[n, k, s]`` at the first maximum k of the target's channels (srcgan_nll_argmax_*, one pass over both tensors; no index
+    tensor, no log tensor).  Inputs: two CUDA tensors of one shape, at least 2-D.  The gradient reaches ``output`` only; a target that
+    requires grad is refused.  Outputs outside [0, 1] give NaN (the reference asserts on the host instead)."""
+
+    def __repr__(self):
+        return "CE"
+
+    def forward(self, output, target):
+        _check_pair("CELoss", output, target)
+        return _CEFn.apply(output, target)
+
+
+class ConLoss(nn.Module):
+    """Consistency of the samples within a batch (losses.py:258-274): the mean over the positions of ``(max_b feats - min_b feats)^2``.
+    ``forward(feats)``: a CUDA tensor of any dimension >= 1, the batch first.  The gradient goes to the first maximum's and the first
+    minimum's sample of every position (lowest batch index on ties, as the reference on the CPU); srcgan_batch_range_* recompute the
+    indices in the backward and keep no index tensor."""
+
+    def __repr__(self):
+        return "ConLoss"
+
+    def forward(self, feats):
+        if feats.dim() < 1:
+            raise ValueError(f"ConLoss: expected a tensor with a batch dimension, got {tuple(feats.shape)}")
+        if feats.numel() == 0:
+            raise ValueError(f"ConLoss: empty input {tuple(feats.shape)}")
+        N.require_cuda(feats, "ConLoss feats")
+        return _ConFn.apply(feats)
+
+
+class CrossLoss(nn.Module):
+    """Cross comparison between the samples of a batch (losses.py:277-293): ``L1Loss(output[:nb-1], target[1:])`` on [nb,ch,row,col] CUDA
+    tensors of one shape, without the two slice copies (srcgan_cross_l1_*; any ch*row*col, whatever the alignment of ``target[1]``).
+    The gradient reaches ``output`` only (zeros for the last sample); a target that requires grad is refused.
+
+    Deviation from the reference: ``nb == 1`` is a ``ValueError`` here; the reference takes the mean of an empty tensor and returns NaN."""
+
+    def __repr__(self):
+        return "CrossLoss"
+
+    def forward(self, output, target):
+        _check_pair("CrossLoss", output, target, dims=4, min_batch=2)
+        return _CrossFn.apply(output, target)
 
 
 # ------------------------------------------------------------------------------------------------ shift-tolerant pixel loss
