@@ -270,6 +270,34 @@ int srcgan_ca_backward(const void* dy, int dy_cs, const void* t, int t_cs, const
                        int dt_cs, void* dres, int dres_cs, int dres_accumulate, float* dw1, float* db1, float* dw2, float* db2, int B,
                        long hw, int C, int Cr, int dtype, float* scratch, void* stream);
 
+/* Back-projection glue of DDBPN (ddbpn.py:13-66) on NHWC activations; csrc/back_proj.hip, DESIGN.md section 3.9.  An image tensor
+ * y [B][Hy][Wy][C] and a grid tensor g [B][Hg][Wg][s*s*C], channel (a*s + b)*C + c, are tied by the index map
+ *   (m, n, a, b) <-> (oy, ox) = (s*m + a - shift, s*n + b - shift).
+ *   srcgan_s2d_shift:  g[m][n][(a,b,c)] = x[oy][ox][c], zero where (oy, ox) lies outside the image (the whole grid is written).
+ *   srcgan_d2s_shift:  y[oy][ox][c] = g[m][n][(a,b,c)] (+= when accumulate); grid positions that map outside the image are dropped.
+ *     Each is the other's adjoint.  Pure copies: bit-exact.
+ *   srcgan_prelu_forward:  y = PReLU_c(z + bias[c]) + beta * r,  PReLU_c(v) = v > 0 ? v : slope[c] * v.  z is a grid tensor read through
+ *     the map (s == 1, shift == 0, Hg x Wg == Hy x Wy: a plain tensor); bias and r may be null; beta is +1 or -1; slope / bias: device f32 [C].
+ *   srcgan_prelu_backward: dz = dy * (z + bias > 0 ? 1 : slope[c]) in z's layout, zero at grid positions outside the image (the whole
+ *     grid is written);  dres (optional) = beta * dy (+= when dres_accumulate);  dslope[c] = sum of dy * (z + bias) over z + bias <= 0;
+ *     dbias[c] = sum of dz (dslope / dbias: device f32, overwritten, each may be null).  scratch: srcgan_prelu_scratch_floats(B, Hg, Wg, C, s).
+ *   - every operand is a channel slice: its pointer addresses the slice's first channel, *_cs is the channel stride of the buffer it
+ *     lives in.  Nothing outside the slice is read or written.  16-byte accesses when C, the strides and the pointers are multiples of
+ *     16 bytes, element-wise otherwise.  All counts are 64-bit.  The backward needs C / (16-byte vector or 1) <= 256.
+ *   - the parameter sums are taken per chunk of 2048 grid positions and folded in a fixed order: no atomics, a call repeated gives the
+ *     same bits.  Arithmetic is f32; y, dz and dres are rounded to the storage type once.
+ *   - no output may alias an input (dres excepted, which is read when it accumulates).  The grid must cover the image:
+ *     (Hy - 1 + shift) / s < Hg, likewise for the width.  An error names the entry point in srcgan_last_error() and writes nothing. */
+int srcgan_s2d_shift(const void* x, int x_cs, void* g, int g_cs, int B, int Hx, int Wx, int C, int s, int shift, int Hg, int Wg, int dtype, void* stream);
+int srcgan_d2s_shift(const void* g, int g_cs, void* y, int y_cs, int B, int Hy, int Wy, int C, int s, int shift, int Hg, int Wg, int accumulate, int dtype,
+                     void* stream);
+int srcgan_prelu_forward(const void* z, int z_cs, const float* slope, const float* bias, const void* r, int r_cs, float beta, void* y, int y_cs, int B,
+                         int Hy, int Wy, int C, int s, int shift, int Hg, int Wg, int dtype, void* stream);
+size_t srcgan_prelu_scratch_floats(int B, int Hg, int Wg, int C, int s);
+int srcgan_prelu_backward(const void* dy, int dy_cs, const void* z, int z_cs, const float* slope, const float* bias, void* dz, int dz_cs, void* dres,
+                          int dres_cs, float beta, int dres_accumulate, float* dslope, float* dbias, int B, int Hy, int Wy, int C, int s, int shift,
+                          int Hg, int Wg, int dtype, float* scratch, void* stream);
+
 /* x2 nearest up-sampling of an NHWC feature map (src may be a channel slice of a blocked buffer: s_plane != 0) and its
  * adjoint: dst[y][x] = sum of the 2x2 block of src, times LeakyReLU'(mz[y][x]) when mz is given.  Replaces
  * F.interpolate(scale_factor=2, mode='nearest') and its backward in the legacy generators (model/model.py:384-386,428-433). */
@@ -574,6 +602,34 @@ size_t srcgan_rcan_infer_ws_bytes(const srcgan_rcan_cfg* c);
 size_t srcgan_rcan_infer_act_bytes(const srcgan_rcan_cfg* c);
 int srcgan_rcan_infer_plan(const srcgan_rcan_cfg* c, size_t* ranges, int cap);
 int srcgan_rcan_infer(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
+/* DDBPN, the Dense Deep Back-Projection Network (reference src/model/ddbpn.py:68-130): sub_mean (MeanShift) -> 3x3 (3 -> 128) + PReLU ->
+ * 1x1 (128 -> 32) + PReLU -> six up- and five down-modules (DenseProjection, :29-66), alternating, each reading the concatenation of
+ * all earlier outputs at its resolution -> 3x3 (192 -> 3) at HR -> add_mean.  [B,3,H,W] f32 NCHW -> [B,3,H*scale,W*scale].
+ * n0 = 128, nr = 32 and depth = 6 are the reference's constants.  A projection Conv2d / ConvTranspose2d (k, s, 2) with (k, s) = (6, 2),
+ * (8, 4), (12, 8) runs as a stride-1 convolution of ceil(k / s) taps per axis on a space-to-depth view (srcgan_s2d_shift; the
+ * transposed one is cropped inside srcgan_prelu_forward); the two concatenations are one LR buffer of 5 nr and one HR buffer of 6 nr
+ * channels that every module writes its slice of.  params / grads in parameters() order, which is registration order: sub_mean.{weight,
+ * bias}, initial.{0.weight, 0.bias, 1.weight, 2.weight, 2.bias, 3.weight}, upmodules.<i>.[bottleneck.{0.weight, 0.bias, 1.weight},]
+ * conv_<1..3>.{0.weight, 0.bias, 1.weight}, downmodules.<i>. likewise, reconstruction.0.{weight, bias}, add_mean.{weight, bias}.
+ * MeanShift runs from its parameters and takes no gradient: grads[0], grads[1] and the last two must be NULL.
+ * Refused: in_ch or out_ch != 3, scale not in {2, 4, 8}.  The infer entries are those of srcgan_rcan_infer. */
+typedef struct srcgan_ddbpn_cfg {
+    int in_ch, out_ch;
+    int B, H, W;
+    int dtype;
+    int scale;
+} srcgan_ddbpn_cfg;
+int srcgan_ddbpn_num_params(const srcgan_ddbpn_cfg* c);
+size_t srcgan_ddbpn_ws_bytes(const srcgan_ddbpn_cfg* c);
+size_t srcgan_ddbpn_bwd_scratch_bytes(const srcgan_ddbpn_cfg* c);
+int srcgan_ddbpn_forward(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_ddbpn_backward(const srcgan_ddbpn_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                          float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_ddbpn_infer_ws_bytes(const srcgan_ddbpn_cfg* c);
+size_t srcgan_ddbpn_infer_act_bytes(const srcgan_ddbpn_cfg* c);
+int srcgan_ddbpn_infer_plan(const srcgan_ddbpn_cfg* c, size_t* ranges, int cap);
+int srcgan_ddbpn_infer(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
 /* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
  * when strides and bases allow them, element by element otherwise).

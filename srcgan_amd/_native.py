@@ -107,6 +107,10 @@ class RcanCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("in_ch", "out_ch", "B", "H", "W", "dtype", "n_resgroups", "n_resblocks", "n_feats", "reduction", "scale")]
 
 
+class DdbpnCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("in_ch", "out_ch", "B", "H", "W", "dtype", "scale")]
+
+
 class VggLossCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "B", "H", "W", "dtype")]
 
@@ -148,6 +152,11 @@ SIGNATURES = {
     "srcgan_ca_scratch_floats": (_S, [_I, _L, _I]),
     "srcgan_ca_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P]),
     "srcgan_ca_backward": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _L, _I, _I, _I, _P, _P]),
+    "srcgan_s2d_shift": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "srcgan_d2s_shift": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "srcgan_prelu_forward": (_I, [_P, _I, _P, _P, _P, _I, _F, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "srcgan_prelu_scratch_floats": (_S, [_I, _I, _I, _I, _I]),
+    "srcgan_prelu_backward": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _F, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "srcgan_upsample2_nhwc": (_I, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_sum2x2_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _F, _I, _I, _I, _I, _I, _P]),
     "srcgan_loss_scratch_floats": (_I, []),
@@ -207,6 +216,15 @@ SIGNATURES = {
     "srcgan_rcan_infer_act_bytes": (_S, [C.POINTER(RcanCfg)]),
     "srcgan_rcan_infer_plan": (_I, [C.POINTER(RcanCfg), C.POINTER(C.c_size_t), _I]),
     "srcgan_rcan_infer": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P]),
+    "srcgan_ddbpn_num_params": (_I, [C.POINTER(DdbpnCfg)]),
+    "srcgan_ddbpn_ws_bytes": (_S, [C.POINTER(DdbpnCfg)]),
+    "srcgan_ddbpn_bwd_scratch_bytes": (_S, [C.POINTER(DdbpnCfg)]),
+    "srcgan_ddbpn_forward": (_I, [C.POINTER(DdbpnCfg), _P, _P, _P, _P, _P]),
+    "srcgan_ddbpn_backward": (_I, [C.POINTER(DdbpnCfg), _P, _P, _P, _P, _P, _P, _P]),
+    "srcgan_ddbpn_infer_ws_bytes": (_S, [C.POINTER(DdbpnCfg)]),
+    "srcgan_ddbpn_infer_act_bytes": (_S, [C.POINTER(DdbpnCfg)]),
+    "srcgan_ddbpn_infer_plan": (_I, [C.POINTER(DdbpnCfg), C.POINTER(C.c_size_t), _I]),
+    "srcgan_ddbpn_infer": (_I, [C.POINTER(DdbpnCfg), _P, _P, _P, _P, _P]),
     "srcgan_maxpool2_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_maxpool2_bwd_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_feat_loss_fwd": (_I, [_I, _P, _I, _P, _I, _L, _I, _I, _P, _P, _P]),

@@ -152,4 +152,8 @@ int sg_frames_grad_store(const void* src, int cs, float* dst5d, int Bt, SgFrames
 // MeanShift (nets.hip -> chan_attn.hip): y[q][0..2] = M x[q][0..2] (+ bias) on 8-channel image records, M = w [3][3] (f32, device) or its
 // transpose (the input gradient); channels 3..7 of y are written as zero
 int sg_meanshift(const void* x, void* y, const float* w, const float* bias, int transpose, long npix, int dtype, hipStream_t st);
+// DDBPN's projection weights (nets.hip -> back_proj.hip), f32: the stored Conv2d (form 0, w [rows][kdim][k][k]) or ConvTranspose2d (form 1,
+// w [kdim][rows][k][k]) weight <-> its stride-1 form over the space-to-depth view, a Conv2d weight with T = ceil(k / s) taps per axis:
+// form 0 [rows][s*s*kdim][T][T], form 1 [s*s*rows][kdim][T][T] (taps flipped).  back != 0: the stride-1 form's gradient -> the stored layout
+int sg_proj_repack(const float* src, float* dst, int form, int rows, int kdim, int k, int s, int back, hipStream_t st);
 int sg_fill_zero_guarded(void* p, size_t bytes, const unsigned long long* guard, hipStream_t st);     // guard == nullptr: plain hipMemsetAsync

@@ -1265,8 +1265,17 @@ struct RdOp {
                               // 7 channel attention + block residual (chan_attn.hip): in = t, res = the block's input, w = conv_du.0.weight (its bias and
                               //   conv_du.2.{weight,bias} follow), ngrp = C / reduction, stats = the op's `saved` region
                               // 8 MeanShift, a frozen 1x1 convolution on the 3 image channels (chan_attn.hip)
+                              // 9 shifted space-to-depth gather (back_proj.hip): image `in` -> grid `out`, k = the scale, pad = the shift
+                              // 10 per-channel PReLU (+ bias)(+ beta * res) (back_proj.hip): in = the pre-activation z, kept for the backward -- a plain
+                              //    tensor (k = 1) or the grid tensor of a transposed projection, cropped while it is read (k = the scale, pad = the shift);
+                              //    w = the slope, bias = the transposed projection's bias or -1, slope = beta, res at channel rcoff of its tensor
     int in, out, res, relu;
     int icoff, iC, ocoff, oC; // type 0 on a dense buffer: reads channels [icoff, icoff + iC) of `in`, writes [ocoff, ocoff + oC) of `out` (iC / oC == 0: the whole tensor)
+    int rcoff;                // type 10: first channel of the residual in `res`
+    int proj, ps, pk;         // type 0, proj != 0: a DDBPN projection in its stride-1 form over the space-to-depth view (k = ceil(pk / ps) taps): 1 = Conv2d
+                              // pk x pk stride ps (in = the gathered grid), 2 = ConvTranspose2d (out = the grid); w is the stored weight, re-ordered
+                              // into the f32 staging area wst (an offset into the pack region) before it is packed
+    size_t wst;
     int share;                // != 0: a module applied a second time -- op share - 1 owns the packs, this op's weight and bias gradients add to its
     int k, s, pad, w, bias;   // w: parameter index of the weight (GroupNorm: gamma, beta = w + 1; -1 = no affine part); bias: parameter index or -1
     int w2;                   // type 4: parameter index of the 3x3 convolution's weight (w = the transposed convolution's)
@@ -1290,6 +1299,7 @@ struct RdPlan {
     size_t xin, gnfwd, wpk, total, act_bytes;
     size_t wpack;             // inference plans: bytes of the packed-weight part
     std::vector<size_t> g;    // backward: gradient buffer offsets (scratch), same shapes as T
+    size_t projscr, prscr;    // backward: a projection's weight gradient in its stride-1 form; the PReLU partial sums
     size_t slab, gnscr, colscr, btmp, bwd_total;      // btmp: a bias gradient on its way to being added (second use of a shared module)
     std::vector<int> taps;    // tensors whose last reader is a loss behind the walk (frozen feature extractors): the slot planner keeps them
 };
@@ -1370,6 +1380,32 @@ struct RdBuilder {
         o.out = tensor(3, 8, ti.H, ti.W);
         P.ops.push_back(o); return o.out;
     }
+    // convolution with explicit parameter indices reading the channel prefix [0, iC) of `in` (iC == 0: all of it) into a new tensor
+    int conv_at(int in, int iC, int cout, int k, int pad, int widx, int bidx, int proj = 0, int ps = 0, int pk = 0) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 0; o.in = in; o.res = -1; o.k = k; o.s = 1; o.pad = pad; o.w = widx; o.bias = bidx; o.iC = iC; o.proj = proj; o.ps = ps; o.pk = pk;
+        o.out = tensor(cout, cout < 8 ? 8 : cout, ti.H + 2 * pad - k + 1, ti.W + 2 * pad - k + 1);
+        P.ops.push_back(o); return o.out;
+    }
+    int gather(int in, int iC, int s, int shift, int Hg, int Wg) {
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 9; o.in = in; o.res = -1; o.k = s; o.pad = shift; o.w = -1; o.bias = -1; o.iC = iC;
+        o.out = tensor(s * s * iC, s * s * iC, Hg, Wg);
+        P.ops.push_back(o); return o.out;
+    }
+    // out < 0: a new C-channel tensor of H x W; otherwise channels [ocoff, ocoff + C) of `out`
+    int prelu(int in, int C, int H, int W, int s, int shift, int aidx, int bidx, int res, int rcoff, float beta, int out = -1, int ocoff = 0) {
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = 10; o.in = in; o.res = res; o.rcoff = rcoff; o.slope = beta; o.k = s; o.pad = shift; o.w = aidx; o.bias = bidx;
+        o.out = out >= 0 ? out : tensor(C, C, H, W); o.ocoff = ocoff; o.oC = C;
+        P.ops.push_back(o); return o.out;
+    }
+    size_t prelu_scratch() const {
+        size_t v = 0;
+        for (const RdOp& o : P.ops) if (o.type == 10) v = std::max(v, srcgan_prelu_scratch_floats(B, P.T[o.in].H, P.T[o.in].W, o.oC, o.k));
+        return v;
+    }
     void tap(int t) { P.taps.push_back(t); }
     // BasicBlock (resdeconv.py:56-97).  state_dict order inside a block: conv1, bn1, conv2, bn2, downsample.{0,1}
     int block(int x, int planes, int stride) {
@@ -1422,6 +1458,7 @@ struct RdBuilder {
                 for (int q = 0; q < 4; ++q) o.wf[q] = w0 + q * step;
                 o.wd[0] = pk(ti.C, to.C, 9);
             }
+            if (o.type == 0 && o.proj) o.wst = wb.take((size_t)cout * cin * o.k * o.k * sizeof(float));
         }
         P.total = align_up(P.wpk + wb.off + 256, 256);
         // backward scratch
@@ -1432,7 +1469,7 @@ struct RdBuilder {
             for (const RdT& t : P.T) mx = std::max(mx, (size_t)B * t.H * t.W * t.cs * P.esz);
             const size_t g0 = s.take(mx), g1 = s.take(mx);
             for (size_t i = 0; i < P.T.size(); ++i) P.g[i] = (i & 1) ? g1 : g0;
-            P.slab = P.gnscr = P.colscr = P.btmp = 0;
+            P.slab = P.gnscr = P.colscr = P.btmp = P.projscr = P.prscr = 0;
             P.bwd_total = s.off + 256;
             return;
         }
@@ -1451,6 +1488,10 @@ struct RdBuilder {
             if (v > slab) slab = v;
         }
         P.slab = s.take(slab);
+        size_t projscr = 0;
+        for (const RdOp& o : P.ops) if (o.type == 0 && o.proj) projscr = std::max(projscr, (size_t)rd_cout(o, P.T[o.out]) * rd_cin(o, P.T[o.in]) * o.k * o.k * sizeof(float));
+        P.projscr = projscr ? s.take(projscr) : 0;
+        P.prscr = prelu_scratch() ? s.take(prelu_scratch() * sizeof(float)) : 0;
         P.gnscr = s.take(std::max(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC), ca_scratch()) * sizeof(float));
         P.colscr = s.take((size_t)2 * srcgan_col_reduce_blocks(maxpix) * P.maxC * sizeof(float));
         P.btmp = 0;           // only plans that apply a module twice carry it (the others keep their size)
@@ -1630,6 +1671,71 @@ static int rcan_plan(const srcgan_rcan_cfg* c, RdPlan& P) {
     nb.finish(c->dtype);
     return 0;
 }
+// DDBPN (ddbpn.py:68-130).  n0, nr and depth are the reference's constants (:73-75).  Parameter indices follow parameters() order =
+// registration order (sub_mean, initial, upmodules, downmodules, reconstruction, add_mean), not the order the modules run in (up 0,
+// down 0, up 1, ...), so every op gets its indices by hand.  Inside a DenseProjection: [bottleneck.0.{w,b}, bottleneck.1.weight,]
+// conv_1.0.{w,b}, conv_1.1.weight, conv_2..., conv_3... (:32-53).
+//
+// A projection (k, s, p = 2) in its stride-1 form, T = ceil(k / s) taps, LR h x w, HR s h x s w:
+//   up   (ConvTranspose2d): T x T convolution, pad 1, to s^2 nr channels on the grid; PReLU reads it through the crop and adds the bias
+//   down (Conv2d):          gather to the grid (s^2 nr channels); T x T convolution, pad 0 (scale 2: 1), + bias; plain PReLU
+// The grid is (h + 1) x (w + 1) with shift 2; at scale 2 its border rows are all padding, so it is h x w with shift 0 (plain
+// space-to-depth / PixelShuffle) and 3x3 pad-1 convolutions.  PReLU's fused residual carries e = b_0 - x and out = a_0 + a_1 (:61-64);
+// `out` goes straight into its slice of the concatenation buffer (l_list: LR, 5 nr channels; h_list: HR, 6 nr), whose consumers read
+// the prefix.  Backward: the reconstruction's input gradient is the first writer of the whole HR gradient buffer, the last up-module's
+// bottleneck that of the LR one; every other consumer adds to the range it read.
+static int ddbpn_plan(const srcgan_ddbpn_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_ddbpn: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_ddbpn"));
+    SG_REQUIRE(c->in_ch == 3 && c->out_ch == 3, "srcgan_ddbpn: n_colors must be 3 (MeanShift is a 3-channel convolution, common.py:16)");
+    SG_REQUIRE(c->scale == 2 || c->scale == 4 || c->scale == 8, "srcgan_ddbpn: scale = %d must be 2, 4 or 8 (ddbpn.py:14-18)", c->scale);
+    SG_REQUIRE((long)c->H * c->scale < (1 << 24) && (long)c->W * c->scale < (1 << 24), "srcgan_ddbpn: image too large");
+    const int n0 = 128, nr = 32, depth = 6;
+    const int s = c->scale, k = s == 2 ? 6 : s == 4 ? 8 : 12, T = (k + s - 1) / s;
+    const int shift = s == 2 ? 0 : 2, h = c->H, w = c->W, Hg = h + (s == 2 ? 0 : 1), Wg = w + (s == 2 ? 0 : 1);
+    RdBuilder nb(P, c->B);
+    nb.input(3, h, w);
+    int t = nb.meanshift(0);                                    // sub_mean: parameters 0, 1
+    t = nb.conv_at(t, 0, n0, 3, 1, 2, 3);
+    t = nb.prelu(t, n0, h, w, 1, 0, 4, -1, -1, 0, 1.f);
+    t = nb.conv_at(t, 0, nr, 1, 0, 5, 6);
+    const int x0 = nb.prelu(t, nr, h, w, 1, 0, 7, -1, -1, 0, 1.f);
+    const int L = nb.tensor((depth - 1) * nr, (depth - 1) * nr, h, w), Hh = nb.tensor(depth * nr, depth * nr, s * h, s * w);
+    // x: channels [0, nr) of its tensor; returns PReLU(projection(x)) + beta * res, a new tensor or the slice ocoff of `out`
+    auto proj = [&](bool up, int x, int pb, int res, float beta, int out, int ocoff) {
+        if (up) {
+            const int g = nb.conv_at(x, nr, s * s * nr, T, 1, pb, -1, 2, s, k);
+            return nb.prelu(g, nr, s * h, s * w, s, shift, pb + 2, pb + 1, res, 0, beta, out, ocoff);
+        }
+        const int g = nb.gather(x, nr, s, shift, Hg, Wg);
+        const int z = nb.conv_at(g, 0, nr, T, s == 2 ? 1 : 0, pb, pb + 1, 1, s, k);
+        return nb.prelu(z, nr, h, w, 1, 0, pb + 2, -1, res, 0, beta, out, ocoff);
+    };
+    auto module = [&](bool up, int in, int iC, bool bneck, int pb, int out, int ocoff) {       // DenseProjection.forward (:55-66)
+        int x = in;
+        if (bneck) {
+            const int z = nb.conv_at(in, iC, nr, 1, 0, pb, pb + 1);
+            x = nb.prelu(z, nr, P.T[z].H, P.T[z].W, 1, 0, pb + 2, -1, -1, 0, 1.f);
+            pb += 3;
+        }
+        const int a0 = proj(up, x, pb, -1, 1.f, -1, 0);
+        const int e = proj(!up, a0, pb + 3, x, -1.f, -1, 0);
+        proj(up, e, pb + 6, a0, 1.f, out, ocoff);
+    };
+    int up_pb[6], down_pb[5], pb = 8;
+    for (int i = 0; i < depth; ++i) { up_pb[i] = pb; pb += i > 1 ? 12 : 9; }                   // bottleneck: i > 1 (:93)
+    for (int i = 0; i < depth - 1; ++i) { down_pb[i] = pb; pb += i != 0 ? 12 : 9; }            // bottleneck: i != 0 (:101)
+    for (int i = 0; i < depth - 1; ++i) {                                                       // :118-124
+        module(true, i == 0 ? x0 : L, i * nr, i > 1, up_pb[i], Hh, i * nr);
+        module(false, Hh, (i + 1) * nr, i != 0, down_pb[i], L, i * nr);
+    }
+    module(true, L, (depth - 1) * nr, true, up_pb[depth - 1], Hh, (depth - 1) * nr);           // :126
+    t = nb.conv_at(Hh, 0, 3, 3, 1, pb, pb + 1);                                                 // reconstruction
+    nb.np = pb + 2;
+    nb.meanshift(t);                                                                            // add_mean: the last two parameters
+    nb.finish(c->dtype);
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -1642,6 +1748,11 @@ static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, co
         const RdT ti = P.T[o.in], to = P.T[o.out];
         const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
         if (o.share) continue;          // packed by the module's first use
+        if (o.type == 0 && o.proj) {    // the stored weight in its stride-1 form: an f32 Conv2d weight [cout][cin][k][k] in the staging area
+            SG_TRY(sg_proj_repack(params[o.w], (float*)(wp + o.wst), o.proj - 1, o.proj == 1 ? cout : cout / (o.ps * o.ps), o.proj == 1 ? cin / (o.ps * o.ps) : cin,
+                                  o.pk, o.ps, 0, (hipStream_t)st));
+            packs.add((const float*)(wp + o.wst), wp + o.wf[0], cout, cin, o.k, o.k, lay_fwd(cin, o.k, o.k));
+        } else
         if (o.type == 0) packs.add(params[o.w], wp + o.wf[0], cout, cin, o.k, o.k, (long)cin * o.k * o.k, (long)o.k * o.k, o.k, 1, 0);
         else if (o.type == 2)
             for (int q = 0; q < 4; ++q) packs.add(params[o.w], wp + o.wf[q], to.C, ti.C, 1, 1, 4, (long)to.C * 4, 0, 0, q);
@@ -1696,6 +1807,12 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
                                      params[o.w + 3], (float*)(w8 + o.stats), B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
         } else if (o.type == 8) {
             SG_TRY(sg_meanshift(xin.p, out.p, params[o.w], params[o.bias], 0, (long)B * ti.H * ti.W, dt, (hipStream_t)st));
+        } else if (o.type == 9) {
+            SG_TRY(srcgan_s2d_shift(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, o.iC, o.k, o.pad, to.H, to.W, dt, st));
+        } else if (o.type == 10) {
+            const void* res = o.res >= 0 ? (w8 + P.T[o.res].off + (size_t)o.rcoff * P.esz) : nullptr;
+            SG_TRY(srcgan_prelu_forward(xin.p, ti.cs, params[o.w], o.bias >= 0 ? params[o.bias] : nullptr, res, o.res >= 0 ? P.T[o.res].cs : 0, o.slope,
+                                        (char*)out.p + (size_t)o.ocoff * P.esz, to.cs, B, to.H, to.W, o.oC, o.k, o.pad, ti.H, ti.W, dt, st));
         } else {
             // folded tail: output pixel (2i + a, 2j + b) = 2x2 window of the half-resolution input at (i + a - 1, j + b - 1) times the
             // composed weights of parity (a, b) -- the geometry of the 4x4 stride-2 input gradient, so its four-parity kernel serves.
@@ -1791,6 +1908,7 @@ static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare =
             const size_t step = srcgan_packed_weight_bytes(to.C, ti.C, 4, P.dtype), w0 = wb.take(4 * step);
             for (int q = 0; q < 4; ++q) o.wf[q] = w0 + q * step;
         }
+        if (o.type == 0 && o.proj && !o.share) o.wst = wb.take((size_t)rd_cout(o, to) * rd_cin(o, ti) * o.k * o.k * sizeof(float));
     }
     P.wpack = wb.off;
     P.total = align_up(P.wpk + wb.off + 256, 256);
@@ -1816,6 +1934,10 @@ static int sd_infer_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
 static int rcan_infer_plan(const srcgan_rcan_cfg* c, RdPlan& P) {
     SG_TRY(rcan_plan(c, P));
     return rd_infer_replan(P, false, "srcgan_rcan");
+}
+static int ddbpn_infer_plan(const srcgan_ddbpn_cfg* c, RdPlan& P) {
+    SG_TRY(ddbpn_plan(c, P));
+    return rd_infer_replan(P, false, "srcgan_ddbpn");
 }
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -1850,7 +1972,8 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
             if (o.share) continue;
             if (o.type == 0 && (o.in != 0 || dx_nchw)) {
-                if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));
+                if (o.proj) packs.add((const float*)(wp + o.wst), wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));     // staged by the forward
+                else if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));
                 else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, 1, 1, 1, (long)cin, 0, 0, 0);
                 else o.s2(cin, cout).pack(packs, params[o.w], wp, o.wd);
             } else if (o.type == 2) {
@@ -1907,9 +2030,14 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                 acc = need_dx && written[o.in];
             }
             const bool fused_bias = o.bias >= 0 && o.k == 3 && G(o.w);
-            if (G(o.w))
-                SG_TRY(wgrad_call(dt, dy, to.H, to.W, cout, xin, B, ti.H, ti.W, cin, o.k, o.k, o.s, o.pad, o.pad, lay_fwd(cin, o.k, o.k), 1.f, slab, G(o.w), st,
+            if (G(o.w)) {       // a projection: the gradient of the stride-1 form, then back into the stored layout
+                float* gw = o.proj ? (float*)(s8 + P.projscr) : G(o.w);
+                SG_TRY(wgrad_call(dt, dy, to.H, to.W, cout, xin, B, ti.H, ti.W, cin, o.k, o.k, o.s, o.pad, o.pad, lay_fwd(cin, o.k, o.k), 1.f, slab, gw, st,
                                   fused_bias ? G(o.bias) : nullptr, pacc0));
+                if (o.proj)
+                    SG_TRY(sg_proj_repack(gw, G(o.w), o.proj - 1, o.proj == 1 ? cout : cout / (o.ps * o.ps), o.proj == 1 ? cin / (o.ps * o.ps) : cin, o.pk, o.ps, 1,
+                                          (hipStream_t)st));
+            }
             if (o.bias >= 0 && G(o.bias) && !fused_bias) SG_TRY(bias_sum(dy, (long)B * to.H * to.W, cout, G(o.bias)));
             seen_param[o.w] = 1;
             if (need_dx) {
@@ -1980,6 +2108,17 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                 SG_TRY(sg_meanshift(dy.p, dx.p, params[o.w], nullptr, 1, (long)B * ti.H * ti.W, dt, (hipStream_t)st));
                 written[o.in] = 1;
             }
+        } else if (o.type == 9) {       // the gather's adjoint is the crop; a second consumer's contribution is added
+            SG_TRY(srcgan_d2s_shift(dy.p, to.cs, dx.p, ti.cs, B, ti.H, ti.W, o.iC, o.k, o.pad, to.H, to.W, acc, dt, st));
+            written[o.in] = 1;
+        } else if (o.type == 10) {
+            void* dres = nullptr; int dres_cs = 0, dres_acc = 0;
+            if (o.res >= 0) { dres = s8 + P.g[o.res] + (size_t)o.rcoff * P.esz; dres_cs = P.T[o.res].cs; dres_acc = written[o.res]; written[o.res] = 1; }
+            SG_REQUIRE(!acc && !ti.act && o.in != o.res, "%s backward: internal error (PReLU input with two consumers or a fused activation)", tag);
+            SG_TRY(srcgan_prelu_backward((char*)dy.p + (size_t)dy.coff * P.esz, to.cs, xin.p, ti.cs, params[o.w], o.bias >= 0 ? params[o.bias] : nullptr, dx.p, ti.cs,
+                                         dres, dres_cs, o.slope, dres_acc, G(o.w), G(o.bias), B, to.H, to.W, o.oC, o.k, o.pad, ti.H, ti.W, dt,
+                                         (float*)(s8 + P.prscr), st));
+            written[o.in] = 1;
         } else if (o.type == 6) {
             SG_REQUIRE(!acc, "%s backward: internal error (pooled tensor with two consumers)", tag);
             SG_TRY(srcgan_maxpool2_bwd_nhwc(dy.p, to.cs, xin.p, ti.cs, dx.p, ti.cs, B, ti.H, ti.W, ti.C, ti.act && tap_of(o.in) < 0, dt, st));
@@ -2114,6 +2253,34 @@ extern "C" int srcgan_rcan_infer(const srcgan_rcan_cfg* c, const float* x_nchw, 
     RdPlan P;
     SG_TRY(rcan_infer_plan(c, P));
     return rd_forward(P, x_nchw, params, ws, y_nchw, "rcan_infer", st);
+}
+
+// DDBPN on the op-list executor (ddbpn_plan); the inference entries run the same launches on the slot-planned workspace.
+extern "C" int srcgan_ddbpn_num_params(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_plan(c, P)) return -1; return P.nparams; }
+extern "C" size_t srcgan_ddbpn_ws_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_plan(c, P)) return 0; return P.total; }
+extern "C" size_t srcgan_ddbpn_bwd_scratch_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_plan(c, P)) return 0; return P.bwd_total; }
+extern "C" int srcgan_ddbpn_forward(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(ddbpn_plan(c, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, "ddbpn", st);
+}
+extern "C" int srcgan_ddbpn_backward(const srcgan_ddbpn_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                                     float* const* grads, float* dx_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(ddbpn_plan(c, P));
+    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, "ddbpn", st);
+}
+extern "C" size_t srcgan_ddbpn_infer_ws_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_infer_plan(c, P)) return 0; return P.total; }
+extern "C" size_t srcgan_ddbpn_infer_act_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_infer_plan(c, P)) return 0; return P.total - P.wpack; }
+extern "C" int srcgan_ddbpn_infer_plan(const srcgan_ddbpn_cfg* c, size_t* ranges, int cap) {
+    RdPlan P;
+    if (ddbpn_infer_plan(c, P)) return -1;
+    return rd_plan_ranges(P, ranges, cap);
+}
+extern "C" int srcgan_ddbpn_infer(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
+    RdPlan P;
+    SG_TRY(ddbpn_infer_plan(c, P));
+    return rd_forward(P, x_nchw, params, ws, y_nchw, "ddbpn_infer", st);
 }
 
 // ======================================================================================== frozen VGG feature losses

@@ -156,9 +156,48 @@ def _scale(net) -> Optional[int]:
         return int(net._cfg[3])
     if isinstance(net, (M.SRCNN, M.SRDN, M.ResDeconv)):
         return 1
-    if isinstance(net, M.RCAN):
+    if isinstance(net, (M.RCAN, M.DDBPN)):
         return int(net.scale)
     return None
+
+
+def _ddbpn_halo(scale: int) -> int:
+    """DDBPN's receptive radius in input pixels, by propagating index intervals backwards through its graph (ddbpn.py:112-130).
+
+    A projection has (k, s, p) = (6, 2, 2), (8, 4, 2) or (12, 8, 2).  Up (ConvTranspose2d): HR pixel o reads the LR pixels i with
+    0 <= o + p - s i <= k - 1, so an HR interval [a, b] needs U[a, b] = [ceil((a + p - k + 1) / s), floor((b + p) / s)].  Down (Conv2d):
+    LR pixel q reads HR [s q - p, s q - p + k - 1], so D[a, b] = [s a - p, s b - p + k - 1].  PReLU and the 1x1 bottleneck spread
+    nothing.  An up-module computes a_0 = up(x), e = down(a_0) - x, out = a_0 + up(e) (:59-64): ``out`` on I needs x on
+    U(I + D(U(I))), where + is the interval hull; a down-module likewise needs D(I + U(D(I))).  The walk starts from one HR pixel o
+    widened by the 3x3 reconstruction, visits the eleven modules in reverse order -- every module's need is added to each slice of
+    the concatenation it reads -- and ends at the initial 1x1 (0) and 3x3 (1) convolutions.  The radius is the largest distance
+    between the needed interval's ends and the LR pixel o // s that owns o, over the s phases of o (the graph is periodic in s)."""
+    k, s, p = M._DDBPN_PROJ[scale]
+    depth = 6
+    hull = lambda a, b: b if a is None else (a if b is None else (min(a[0], b[0]), max(a[1], b[1])))
+    U = lambda I: (-((-(I[0] + p - k + 1)) // s), (I[1] + p) // s)
+    D = lambda I: (s * I[0] - p, s * I[1] - p + k - 1)
+    up_mod = lambda I: U(hull(I, D(U(I))))
+    down_mod = lambda I: D(hull(I, U(D(I))))
+    radius = 0
+    for o in range(s):
+        need_h = [(o - 1, o + 1)] * depth                      # reconstruction: 3x3 over all six HR outputs
+        need_l = [None] * (depth - 1)
+        x0 = None
+        for j in range(depth - 1):                              # the last up-module reads l_0 .. l_4
+            need_l[j] = hull(need_l[j], up_mod(need_h[depth - 1]))
+        for i in range(depth - 2, -1, -1):
+            d = down_mod(need_l[i])                             # down-module i reads h_0 .. h_i
+            for j in range(i + 1):
+                need_h[j] = hull(need_h[j], d)
+            u = up_mod(need_h[i])                               # up-module i reads x (i = 0) or l_0 .. l_{i-1}
+            if i == 0:
+                x0 = hull(x0, u)
+            for j in range(i):
+                need_l[j] = hull(need_l[j], u)
+        lo, hi = x0[0] - 1, x0[1] + 1                           # initial: 1x1 (0), 3x3 (1)
+        radius = max(radius, (o // s) - lo, hi - (o // s))
+    return radius
 
 
 def receptive_halo(net) -> int:
@@ -193,6 +232,8 @@ def receptive_halo(net) -> int:
                                     2o - 1 .. 2o + 1; reconstruction and conv_last (model.py:761-763) 2 output pixels: x2 2 * 2 + 1 = 5
                                     input pixels, x4 2 * (2 * 2 + 1) + 1 = 11.  (An HR -> LR network: ``upscale_scene`` does not run it.)
 
+      DDBPN          by interval propagation through its eleven projection modules: ``_ddbpn_halo`` holds the derivation
+
     Networks with normalisation layers (ResDeconv, EDSR: GroupNorm / InstanceNorm statistics are taken over the whole image), RCAN
     (its channel attention pools over the whole image) and unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
     name = type(net).__name__
@@ -202,6 +243,8 @@ def receptive_halo(net) -> int:
     if isinstance(net, M.RCAN):
         raise ValueError(f"receptive_halo: {name} gates its channels by a global average pool (rcan.py:24-27) whose per-image value makes "
                          "tiles inexact at any halo; pass halo= explicitly (and blend='feather')")
+    if isinstance(net, M.DDBPN):
+        return _ddbpn_halo(net.scale)
     if isinstance(net, M.LegacyRDDBNet):
         return 5 if net.mode == "x1" else 3
     if isinstance(net, M.RDDBNetB):

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
            "get_deconv_params"]
 
 
@@ -911,6 +911,86 @@ class RCAN(_NativeRepr, nn.Module):
             missing = set(own) - set(state_dict)
             if missing:
                 raise KeyError(f"missing keys in state_dict: {sorted(missing)}")
+
+
+# ------------------------------------------------------------------------------------------------ DDBPN
+_DDBPN_PROJ = {2: (6, 2, 2), 4: (8, 4, 2), 8: (12, 8, 2)}      # scale -> (kernel, stride, padding) of a projection (ddbpn.py:14-18)
+
+
+class _DenseProjection(_HolderOnly):
+    """Parameter holder of ddbpn.py:29-53 DenseProjection: [bottleneck = 1x1 conv + PReLU,] conv_1 .. conv_3 = projection + PReLU, the
+    projections alternating ConvTranspose2d / Conv2d (up) or Conv2d / ConvTranspose2d (down)."""
+
+    def __init__(self, in_channels, nr, scale, up=True, bottleneck=True):
+        super().__init__()
+        k, s, p = _DDBPN_PROJ[scale]
+        proj = lambda ci, co, t: (nn.ConvTranspose2d if t else nn.Conv2d)(ci, co, k, stride=s, padding=p)
+        if bottleneck:
+            self.bottleneck = nn.Sequential(nn.Conv2d(in_channels, nr, 1), nn.PReLU(nr))
+            inter = nr
+        else:
+            self.bottleneck = None
+            inter = in_channels
+        self.conv_1 = nn.Sequential(proj(inter, nr, up), nn.PReLU(nr))
+        self.conv_2 = nn.Sequential(proj(nr, inter, not up), nn.PReLU(inter))
+        self.conv_3 = nn.Sequential(proj(inter, nr, up), nn.PReLU(nr))
+
+
+def _ddbpn_cfg(x, items):
+    n_colors, scale, dtype = items
+    _check_input(x, "DDBPN", n_colors, f"DDBPN expects [B,{n_colors},H,W]")
+    B, _, H, W = x.shape
+    return N.DdbpnCfg(n_colors, n_colors, B, H, W, dtype, scale), (B, n_colors, H * scale, W * scale)
+
+
+_DDBPN = _OpList("DDBPN", "srcgan_ddbpn", _ddbpn_cfg)
+
+
+class DDBPN(_NativeRepr, nn.Module):
+    """Dense Deep Back-Projection Network (arXiv 1803.02735), drop-in for reference ``model.ddbpn.DDBPN`` (src/model/ddbpn.py:68-130):
+    ``DDBPN(args)`` with the reference's attribute names (``scale`` -- a list, its first entry counts -- ``rgb_range, n_colors``), or the
+    same names as keywords.  sub_mean -> initial (3x3 + PReLU, 1x1 + PReLU) -> six up- and five down-projection modules, each fed the
+    concatenation of all earlier outputs at its resolution -> 3x3 reconstruction over the six HR outputs -> add_mean;
+    ``forward(x[B,3,H,W]) -> [B,3,H*scale,W*scale]``, scale 2, 4 or 8.  n0 = 128, nr = 32 and depth = 6 are the reference's constants.
+    The two MeanShift layers are frozen and run from their parameters.  Default torch initialisation, modules created in the
+    reference's order: the same seed gives the same weights, and ``state_dict`` has the reference's keys."""
+
+    def __init__(self, args=None, *, scale=2, rgb_range=255, n_colors=3, dtype=None):
+        super().__init__()
+        if args is not None:
+            scale, rgb_range = getattr(args, "scale", scale), getattr(args, "rgb_range", rgb_range)
+            n_colors = getattr(args, "n_colors", n_colors)
+        if isinstance(scale, (list, tuple)):
+            scale = scale[0]
+        scale = int(scale)
+        self.compute_dtype = N.dtype_name(dtype)
+        self.scale, self.depth = scale, 6
+        self._cfg = (int(n_colors), scale)
+        # the native planner owns the rules (3 colours, scale 2 / 4 / 8): ask it first
+        probe = N.DdbpnCfg(self._cfg[0], self._cfg[0], 1, 8, 8, N.dtype_id(self.compute_dtype), scale)
+        if N.lib().srcgan_ddbpn_num_params(C.byref(probe)) < 0:
+            raise ValueError("DDBPN: " + (N.lib().srcgan_last_error() or b"").decode())
+        n0, nr = 128, 32
+        rgb_mean, rgb_std = _DIV2K_MEAN, (1.0, 1.0, 1.0)
+        # creation order == registration order == the reference's (ddbpn.py:79-110)
+        self.sub_mean = _MeanShift(rgb_range, rgb_mean=rgb_mean, rgb_std=rgb_std, sign=-1)
+        self.initial = nn.Sequential(nn.Conv2d(n_colors, n0, 3, padding=1), nn.PReLU(n0), nn.Conv2d(n0, nr, 1), nn.PReLU(nr))
+        self.upmodules = nn.ModuleList()
+        self.downmodules = nn.ModuleList()
+        channels = nr
+        for i in range(self.depth):
+            self.upmodules.append(_DenseProjection(channels, nr, scale, True, i > 1))
+            if i != 0:
+                channels += nr
+        channels = nr
+        for i in range(self.depth - 1):
+            self.downmodules.append(_DenseProjection(channels, nr, scale, False, i != 0))
+            channels += nr
+        self.reconstruction = nn.Sequential(nn.Conv2d(self.depth * nr, n_colors, 3, padding=1))
+        self.add_mean = _MeanShift(rgb_range, rgb_mean=rgb_mean, rgb_std=rgb_std, sign=1)
+
+    def forward(self, x):
+        return _oplist_forward(x, _DDBPN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class _NLayerDFn(torch.autograd.Function):
