@@ -179,52 +179,8 @@ SIGNATURES = {
     "srcgan_bilinear_up": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "srcgan_gray_nearest_down": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "srcgan_rep3_nearest_up": (_I, [_P, _P, _I, _I, _I, _I, _P]),
-    "srcgan_resdeconv_num_params": (_I, [C.POINTER(ResDeconvCfg)]),
-    "srcgan_resdeconv_ws_bytes": (_S, [C.POINTER(ResDeconvCfg)]),
-    "srcgan_resdeconv_bwd_scratch_bytes": (_S, [C.POINTER(ResDeconvCfg)]),
-    "srcgan_resdeconv_forward": (_I, [C.POINTER(ResDeconvCfg), _P, _P, _P, _P, _P]),
-    "srcgan_resdeconv_backward": (_I, [C.POINTER(ResDeconvCfg), _P, _P, _P, _P, _P, _P, _P]),
-    "srcgan_resdeconv_infer_ws_bytes": (_S, [C.POINTER(ResDeconvCfg), _I]),
-    "srcgan_resdeconv_infer_act_bytes": (_S, [C.POINTER(ResDeconvCfg), _I]),
-    "srcgan_resdeconv_infer_plan": (_I, [C.POINTER(ResDeconvCfg), _I, C.POINTER(C.c_size_t), _I]),
-    "srcgan_resdeconv_infer": (_I, [C.POINTER(ResDeconvCfg), _P, _P, _P, _P, _I, _P]),
     "srcgan_fold_tail_pack_bytes": (_S, [_I]),
     "srcgan_fold_tail_pack": (_I, [_P, _P, _P, _I, _I, _P]),
-    "srcgan_srnet_num_params": (_I, [C.POINTER(SrNetCfg)]),
-    "srcgan_srnet_ws_bytes": (_S, [C.POINTER(SrNetCfg)]),
-    "srcgan_srnet_bwd_scratch_bytes": (_S, [C.POINTER(SrNetCfg)]),
-    "srcgan_srnet_forward": (_I, [C.POINTER(SrNetCfg), _P, _P, _P, _P, _P]),
-    "srcgan_srnet_backward": (_I, [C.POINTER(SrNetCfg), _P, _P, _P, _P, _P, _P, _P]),
-    "srcgan_srnet_infer_ws_bytes": (_S, [C.POINTER(SrNetCfg)]),
-    "srcgan_srnet_infer_act_bytes": (_S, [C.POINTER(SrNetCfg)]),
-    "srcgan_srnet_infer_plan": (_I, [C.POINTER(SrNetCfg), C.POINTER(C.c_size_t), _I]),
-    "srcgan_srnet_infer": (_I, [C.POINTER(SrNetCfg), _P, _P, _P, _P, _P]),
-    "srcgan_srdense_num_params": (_I, [C.POINTER(SrDenseCfg)]),
-    "srcgan_srdense_out_hw": (_I, [C.POINTER(SrDenseCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "srcgan_srdense_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
-    "srcgan_srdense_bwd_scratch_bytes": (_S, [C.POINTER(SrDenseCfg)]),
-    "srcgan_srdense_forward": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
-    "srcgan_srdense_backward": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P, _P, _P]),
-    "srcgan_srdense_infer_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
-    "srcgan_srdense_infer": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
-    "srcgan_rcan_num_params": (_I, [C.POINTER(RcanCfg)]),
-    "srcgan_rcan_ws_bytes": (_S, [C.POINTER(RcanCfg)]),
-    "srcgan_rcan_bwd_scratch_bytes": (_S, [C.POINTER(RcanCfg)]),
-    "srcgan_rcan_forward": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P]),
-    "srcgan_rcan_backward": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P, _P, _P]),
-    "srcgan_rcan_infer_ws_bytes": (_S, [C.POINTER(RcanCfg)]),
-    "srcgan_rcan_infer_act_bytes": (_S, [C.POINTER(RcanCfg)]),
-    "srcgan_rcan_infer_plan": (_I, [C.POINTER(RcanCfg), C.POINTER(C.c_size_t), _I]),
-    "srcgan_rcan_infer": (_I, [C.POINTER(RcanCfg), _P, _P, _P, _P, _P]),
-    "srcgan_ddbpn_num_params": (_I, [C.POINTER(DdbpnCfg)]),
-    "srcgan_ddbpn_ws_bytes": (_S, [C.POINTER(DdbpnCfg)]),
-    "srcgan_ddbpn_bwd_scratch_bytes": (_S, [C.POINTER(DdbpnCfg)]),
-    "srcgan_ddbpn_forward": (_I, [C.POINTER(DdbpnCfg), _P, _P, _P, _P, _P]),
-    "srcgan_ddbpn_backward": (_I, [C.POINTER(DdbpnCfg), _P, _P, _P, _P, _P, _P, _P]),
-    "srcgan_ddbpn_infer_ws_bytes": (_S, [C.POINTER(DdbpnCfg)]),
-    "srcgan_ddbpn_infer_act_bytes": (_S, [C.POINTER(DdbpnCfg)]),
-    "srcgan_ddbpn_infer_plan": (_I, [C.POINTER(DdbpnCfg), C.POINTER(C.c_size_t), _I]),
-    "srcgan_ddbpn_infer": (_I, [C.POINTER(DdbpnCfg), _P, _P, _P, _P, _P]),
     "srcgan_maxpool2_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_maxpool2_bwd_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_feat_loss_fwd": (_I, [_I, _P, _I, _P, _I, _L, _I, _I, _P, _P, _P]),
@@ -290,6 +246,35 @@ SIGNATURES = {
     "srcgan_nlayerd_forward": (_I, [C.POINTER(NLayerDCfg), _P, _P, _P, _P, _P, _P, _P]),
     "srcgan_nlayerd_backward": (_I, [C.POINTER(NLayerDCfg), _P, _P, _P, _P, _P, _P, _P]),
 }
+
+
+# The op-list families (csrc/oplist.hip): the rows of the entry points its RD_TRAIN_ENTRIES / RD_INFER_ENTRIES macros stamp out, generated
+# from (stem, config struct) pairs like them; what a family has beyond or short of those is listed by hand.
+def _train_rows(stem, cfg):
+    c = C.POINTER(cfg)
+    return {f"srcgan_{stem}_num_params": (_I, [c]), f"srcgan_{stem}_ws_bytes": (_S, [c]), f"srcgan_{stem}_bwd_scratch_bytes": (_S, [c]),
+            f"srcgan_{stem}_forward": (_I, [c, _P, _P, _P, _P, _P]), f"srcgan_{stem}_backward": (_I, [c, _P, _P, _P, _P, _P, _P, _P])}
+
+
+def _infer_rows(stem, cfg):
+    c = C.POINTER(cfg)
+    return {f"srcgan_{stem}_infer_ws_bytes": (_S, [c]), f"srcgan_{stem}_infer_act_bytes": (_S, [c]),
+            f"srcgan_{stem}_infer_plan": (_I, [c, C.POINTER(C.c_size_t), _I]), f"srcgan_{stem}_infer": (_I, [c, _P, _P, _P, _P, _P])}
+
+
+for _stem, _cfg in (("resdeconv", ResDeconvCfg), ("srnet", SrNetCfg), ("srdense", SrDenseCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg)):
+    SIGNATURES.update(_train_rows(_stem, _cfg))
+for _stem, _cfg in (("srnet", SrNetCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg)):
+    SIGNATURES.update(_infer_rows(_stem, _cfg))
+SIGNATURES.update({
+    "srcgan_resdeconv_infer_ws_bytes": (_S, [C.POINTER(ResDeconvCfg), _I]),       # ResDeconv: fold_tail
+    "srcgan_resdeconv_infer_act_bytes": (_S, [C.POINTER(ResDeconvCfg), _I]),
+    "srcgan_resdeconv_infer_plan": (_I, [C.POINTER(ResDeconvCfg), _I, C.POINTER(C.c_size_t), _I]),
+    "srcgan_resdeconv_infer": (_I, [C.POINTER(ResDeconvCfg), _P, _P, _P, _P, _I, _P]),
+    "srcgan_srdense_out_hw": (_I, [C.POINTER(SrDenseCfg), C.POINTER(C.c_int), C.POINTER(C.c_int)]),       # SRDenseNet: out_hw, no act_bytes / infer_plan
+    "srcgan_srdense_infer_ws_bytes": (_S, [C.POINTER(SrDenseCfg)]),
+    "srcgan_srdense_infer": (_I, [C.POINTER(SrDenseCfg), _P, _P, _P, _P, _P]),
+})
 
 _lib = None
 

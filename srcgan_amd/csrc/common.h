@@ -125,7 +125,7 @@ static inline const char* sg_env(const char*) { return nullptr; }
 int sg_prof_start(const char* cls, double flops, double bytes, hipStream_t st);   // returns token or -1
 void sg_prof_stop(int token, hipStream_t st);
 
-// ---------------------------------------------------------------- batched weight packing (nets.hip -> elementwise.hip)
+// ---------------------------------------------------------------- batched weight packing (net_common.h -> elementwise.hip)
 struct SgPackJob {
     const float* w; size_t wp_off;
     int rows, kdim, tys, txs;
@@ -140,7 +140,7 @@ int sg_fold_tail_pack(const float* w_deconv, const float* w_conv, void* wp, int 
 // value range (metrics.hip; also scene_score.hip): range[2f .. 2f+1] = min / max of frame f of a contiguous f32 [planes, frames, n] tensor
 // over all its planes, left on the device by two launches.  nblk = the caller's partial blocks per frame; partial = frames * nblk * 2 floats
 void sg_minmax_frames(const float* x, int planes, int frames, long n, int nblk, float* partial, float* range, hipStream_t st);
-// frozen VGG feature path (nets.hip -> vgg_loss.hip): out = sum_k sums[k] * weights[k] (host weights, n <= 4)
+// frozen VGG feature path (oplist.hip -> vgg_loss.hip): out = sum_k sums[k] * weights[k] (host weights, n <= 4)
 int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, hipStream_t st);
 // its images are frames of 5-D tensors: frames [f0, f0 + k) of a contiguous f32 [Bt, Cin, F, H, W] tensor (Cin = 1 or 3; a [Bt, Cin, H, W]
 // tensor is F = 1, f0 = 0, k = 1) <-> the 8-channel NHWC records of Bt * k images (image j * Bt + b = frame f0 + j of sample b).  The pack
@@ -149,10 +149,10 @@ int sg_vgg_combine(const float* sums, const float* weights, int n, float* out, h
 struct SgFrames { int Cin, F, f0, k; };
 int sg_frames_pack(const float* src5d, void* dst, int cs, int Bt, SgFrames fr, int H, int W, int dtype, hipStream_t st);
 int sg_frames_grad_store(const void* src, int cs, float* dst5d, int Bt, SgFrames fr, int H, int W, const float* gout, float gscale, int dtype, hipStream_t st);
-// MeanShift (nets.hip -> chan_attn.hip): y[q][0..2] = M x[q][0..2] (+ bias) on 8-channel image records, M = w [3][3] (f32, device) or its
+// MeanShift (oplist.hip -> chan_attn.hip): y[q][0..2] = M x[q][0..2] (+ bias) on 8-channel image records, M = w [3][3] (f32, device) or its
 // transpose (the input gradient); channels 3..7 of y are written as zero
 int sg_meanshift(const void* x, void* y, const float* w, const float* bias, int transpose, long npix, int dtype, hipStream_t st);
-// DDBPN's projection weights (nets.hip -> back_proj.hip), f32: the stored Conv2d (form 0, w [rows][kdim][k][k]) or ConvTranspose2d (form 1,
+// DDBPN's projection weights (oplist.hip -> back_proj.hip), f32: the stored Conv2d (form 0, w [rows][kdim][k][k]) or ConvTranspose2d (form 1,
 // w [kdim][rows][k][k]) weight <-> its stride-1 form over the space-to-depth view, a Conv2d weight with T = ceil(k / s) taps per axis:
 // form 0 [rows][s*s*kdim][T][T], form 1 [s*s*rows][kdim][T][T] (taps flipped).  back != 0: the stride-1 form's gradient -> the stored layout
 int sg_proj_repack(const float* src, float* dst, int form, int rows, int kdim, int k, int s, int back, hipStream_t st);

@@ -5,7 +5,8 @@
 //
 //   RRDB generators (RDDBNet, RDDBNetA, RDDBNetB, legacy RDDBNet, SRDN)   reference src/model/rddb.py:48-114, model.py:347-440, srdn.py
 //   NLayerDiscriminator (PatchGAN, BatchNorm2d / InstanceNorm2d)          reference src/model/model.py:595-639
-//   op-list networks: ResDeconv, ESPCN, SRCNN, EDSR                        reference src/model/{resdeconv,espcn,srcnn,edsr}.py
+// The op-list networks (ResDeconv, ESPCN, SRCNN, EDSR, SRDenseNetA/B, RCAN, DDBPN, the frozen VGG features) are sequenced by oplist.hip;
+// net_common.h holds what the two files share, and this file defines its two pieces of per-process state.
 //
 // Memory design (HBM): activations live in NHWC.  Each ResidualDenseBlock_5 owns ONE dense buffer of
 // nf+4*gc channels; conv k reads the channel prefix [0, nf+(k-1)gc) and writes its own slice, so the
@@ -13,198 +14,61 @@
 // "x5*0.2 + x" (rddb.py:68), and for RDB3 also the RRDB residual (rddb.py:82), writing straight into
 // channels [0,nf) of the next block's dense buffer.  Backward mirrors this with a dense *gradient*
 // buffer per block that the dgrads of conv5..conv1 accumulate into in place.
-#include "common.h"
-#include <algorithm>
-#include <vector>
+#include "net_common.h"
 #include <map>
-#include <string>
 #include <mutex>
+#include <string>
+
+// ---- the per-process state behind net_common.h
+int sg_zigzag_next() {
+    static const bool zig = sg_env("SRCGAN_NO_ZIGZAG") == nullptr;
+    static int flip = 0;
+    const int rev = flip;
+    flip ^= 1;
+    return zig ? rev : 0;
+}
 
 namespace {
-
-struct TRef { void* p; int cs; int coff; long plane; };     // plane: blocked-layout plane stride in bytes (0 = NHWC)
-static inline TRef tref(void* p, int cs, int coff = 0, long plane = 0) { return TRef{p, cs, coff, plane}; }
-static inline TRef sl(TRef t, int coff) { return TRef{t.p, t.cs, t.coff + coff, t.plane}; }
-static const TRef TNULL = {nullptr, 0, 0, 0};
-
-static inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
-static inline int img_cs(int c) { return round_up(c, 8); }     // image-like tensors: channels padded to 8
-
-struct Conv {
-    srcgan_conv_desc d;
-    Conv(int dtype, int kh, int kw, int stride) {
-        memset(&d, 0, sizeof(d));
-        d.dtype = dtype; d.kh = kh; d.kw = kw; d.stride = stride;
-        d.os = 1; d.alpha = 1.f; d.slope = 0.2f; d.mslope = 0.2f;
-    }
-    Conv& in(TRef x, int B, int H, int W, int Cin) { d.x = x.p; d.x_cs = x.cs; d.x_coff = x.coff; d.x_plane = x.plane; d.B = B; d.H = H; d.W = W; d.Cin = Cin; return *this; }
-    Conv& w(const void* wp, const float* bias = nullptr) { d.wp = wp; d.bias = bias; return *this; }
-    Conv& out(TRef y, int OH, int OW, int Cout) { d.y = y.p; d.y_cs = y.cs; d.y_coff = y.coff; d.y_plane = y.plane; d.OH = OH; d.OW = OW; d.Cout = Cout; d.YH = OH; d.YW = OW; return *this; }
-    Conv& pad(int py, int px) { d.pad_y = py; d.pad_x = px; return *this; }
-    Conv& scatter(int os, int oa, int ob, int YH, int YW) { d.os = os; d.oa = oa; d.ob = ob; d.YH = YH; d.YW = YW; return *this; }
-    Conv& alpha(float a) { d.alpha = a; return *this; }
-    Conv& res1(TRef r, int cend, float beta) { d.r1 = r.p; d.r1_cs = r.cs; d.r1_coff = r.coff; d.r1_plane = r.plane; d.r1_cend = cend; d.beta1 = beta; return *this; }
-    Conv& res2(TRef r, int cend, float beta) { d.r2 = r.p; d.r2_cs = r.cs; d.r2_coff = r.coff; d.r2_plane = r.plane; d.r2_cend = cend; d.beta2 = beta; return *this; }
-    Conv& lrelu() { d.act = 1; return *this; }
-    Conv& sign_out(void* m) { d.sign_out = m; return *this; }                  // write / read the LeakyReLU sign mask (u32 per pixel)
-    Conv& sign_in(const void* m) { d.sign_in = m; return *this; }
-    Conv& mask(TRef z, int c0) { d.mz = z.p; d.mz_cs = z.cs; d.mz_coff = z.coff; d.mz_plane = z.plane; d.mz_c0 = c0; return *this; }
-    // consecutive 3x3 s1 launches walk the batch in alternating directions (SRCGAN_NO_ZIGZAG=1 disables): see srcgan_conv_desc.rev_batch
-    int run(void* st) {
-        static const bool zig = sg_env("SRCGAN_NO_ZIGZAG") == nullptr;
-        static int flip = 0;
-        if (zig && d.kh == 3 && d.kw == 3 && d.stride == 1) { d.rev_batch = flip; flip ^= 1; }
-        return srcgan_conv_igemm(&d, st);
-    }
-};
-
-// canonical weight layouts
-struct WLayout { long sr, sk, sty, stx, off; };
-// Conv2d weight [co][ci][kh][kw]: forward pack rows = co
-static inline WLayout lay_fwd(int cin, int kh, int kw) { return {(long)cin * kh * kw, (long)kh * kw, kw, 1, 0}; }
-// Conv2d dgrad for stride 1: rows = ci, k = co, taps flipped
-static inline WLayout lay_dgrad_s1(int cin, int kh, int kw) { return {(long)kh * kw, (long)cin * kh * kw, -kw, -1, (long)kh * kw - 1}; }
-// Input gradient of a k x k stride-2 convolution with padding `pad`, by output parity a (0 / 1) along one axis:
-//   dx[2 j + a] = sum over the kernel rows ky == (a + pad) mod 2 of dy[j + (a + pad - ky) / 2] * w[ky]
-// -> a stride-1 sub-convolution with n taps; tap t (ascending dy row) uses ky = ky_max - 2 t and needs `lead` rows above row j.
-// (4x4 p1: 2 taps, ky_max 3 / 2, lead 1 / 0;  3x3 p1: 1 / 2 taps, lead 0;  7x7 p3: 3 / 4 taps)
-struct Par2 { int n, ky_max, lead; };
-static inline Par2 par2(int k, int pad, int a) {
-    int ky_max = k - 1;
-    if (((ky_max ^ (a + pad)) & 1) != 0) --ky_max;
-    Par2 r; r.ky_max = ky_max; r.n = ky_max >= 0 ? ky_max / 2 + 1 : 0; r.lead = (ky_max - a - pad) / 2;
-    return r;
-}
-
-struct Bump {   // workspace bump allocator (256-byte aligned)
-    size_t off = 0;
-    size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; }
-};
-
-static int wgrad_call(int dtype, TRef dy, int OH, int OW, int Cout, TRef x, int B, int H, int W, int Cin, int kh, int kw,
-                      int stride, int pad_y, int pad_x, WLayout lay, float alpha, float* slab, float* grad, void* st,
-                      float* bias_grad = nullptr, int accumulate = 0) {
-    srcgan_wgrad_desc d;
-    memset(&d, 0, sizeof(d));
-    d.dy = dy.p; d.dy_cs = dy.cs; d.dy_coff = dy.coff; d.x = x.p; d.x_cs = x.cs; d.x_coff = x.coff;
-    d.slab = slab; d.grad = grad; d.bias_grad = bias_grad; d.dtype = dtype; d.kh = kh; d.kw = kw; d.stride = stride;
-    d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.OH = OH; d.OW = OW; d.Cout = Cout; d.pad_y = pad_y; d.pad_x = pad_x;
-    d.nsplit = srcgan_conv_wgrad_nsplit(B, OH, OW, Cout, Cin, stride);
-    d.sr = lay.sr; d.sk = lay.sk; d.sty = lay.sty; d.stx = lay.stx; d.off = lay.off;
-    d.alpha = alpha; d.accumulate = accumulate;
-    return srcgan_conv_wgrad(&d, st);
-}
-static size_t wgrad_slab(int B, int OH, int OW, int Cout, int Cin, int kh, int kw, int stride) {
-    return srcgan_conv_wgrad_slab_bytes(Cout, Cin, kh, kw, srcgan_conv_wgrad_nsplit(B, OH, OW, Cout, Cin, stride));
-}
-static int bias_grad(int dtype, TRef dy, long npix, int C, float scale, float* out, float* scratch, void* st) {
-    return srcgan_col_reduce(0, dy.p, dy.cs, dy.coff, nullptr, 0, 0, nullptr, nullptr, npix, C, scale, out, nullptr, scratch, dtype, st);
-}
-
-// ---- batched weight packing with a cached device-side job table
 struct PackCache { std::vector<SgPackJob> host; SgPackJob* dev = nullptr; SgPackJob* pinned = nullptr; size_t cap = 0; hipEvent_t staged = nullptr; };
-static std::map<std::string, PackCache> g_pack_cache;
-static std::mutex g_pack_mutex;
+std::map<std::string, PackCache> g_pack_cache;
+std::mutex g_pack_mutex;
+}  // namespace
 
-struct PackList {
-    std::vector<SgPackJob> jobs; long nblk = 0; int dtype; char* base;
-    PackList(int dt, void* wp_base) : dtype(dt), base((char*)wp_base) {}
-    void add(const float* w, void* wp, int rows, int kdim, int tys, int txs, long sr, long sk, long sty, long stx, long off,
-             int k_off = 0, int k_total = -1, float scale = 1.f) {
-        SgPackJob j;
-        memset(&j, 0, sizeof(j));
-        j.w = w; j.wp_off = (size_t)((char*)wp - base); j.rows = rows; j.kdim = kdim; j.tys = tys; j.txs = txs;
-        j.sr = sr; j.sk = sk; j.sty = sty; j.stx = stx; j.off = off; j.k_off = k_off; j.k_total = k_total < 0 ? kdim : k_total; j.scale = scale;
-        sg_pack_job_finish(j, dtype, nblk);
-        jobs.push_back(j);
-    }
-    void add(const float* w, void* wp, int rows, int kdim, int tys, int txs, WLayout L) { add(w, wp, rows, kdim, tys, txs, L.sr, L.sk, L.sty, L.stx, L.off); }
-    int run(const char* tag, const void* key_ptr, void* st, const unsigned long long* guard = nullptr) {
-        if (jobs.empty()) return 0;
-        int dev = 0;
-        SG_HIP(hipGetDevice(&dev));
-        char key[112];
-        snprintf(key, sizeof(key), "%s:%d:%p:%d:%zu", tag, dev, key_ptr, dtype, jobs.size());
-        std::lock_guard<std::mutex> lock(g_pack_mutex);
-        PackCache& c = g_pack_cache[key];
-        const size_t bytes = jobs.size() * sizeof(SgPackJob);
-        if (c.host.size() != jobs.size() || memcmp(c.host.data(), jobs.data(), bytes) != 0) {
-            // cold path (first call / parameters or buffers moved).  The table is staged in pinned memory and copied on the
-            // call's stream: stream order puts the copy behind every earlier pack kernel that still reads the old table and in
-            // front of this call's -- no host synchronisation.  Only a table that outgrows its buffers allocates (first call,
-            // behind a stream drain: the old device table may still be in use), and a second re-staging waits for the first
-            // one's copy to have left the pinned buffer.
-            if (c.cap < bytes) {
-                SG_HIP(hipStreamSynchronize((hipStream_t)st));
-                if (c.dev) SG_HIP(hipFree(c.dev));
-                if (c.pinned) SG_HIP(hipHostFree(c.pinned));
-                SG_HIP(hipMalloc((void**)&c.dev, bytes));
-                SG_HIP(hipHostMalloc((void**)&c.pinned, bytes, hipHostMallocDefault));
-                c.cap = bytes;
-            }
-            if (!c.staged) SG_HIP(hipEventCreateWithFlags(&c.staged, hipEventDisableTiming));
-            else SG_HIP(hipEventSynchronize(c.staged));
-            memcpy(c.pinned, jobs.data(), bytes);
-            SG_HIP(hipMemcpyAsync(c.dev, c.pinned, bytes, hipMemcpyHostToDevice, (hipStream_t)st));
-            SG_HIP(hipEventRecord(c.staged, (hipStream_t)st));
-            c.host = jobs;
+int sg_pack_list_run(const std::vector<SgPackJob>& jobs, long nblk, void* wp_base, int dtype, const char* tag, const void* key_ptr, void* st,
+                     const unsigned long long* guard) {
+    if (jobs.empty()) return 0;
+    int dev = 0;
+    SG_HIP(hipGetDevice(&dev));
+    char key[112];
+    snprintf(key, sizeof(key), "%s:%d:%p:%d:%zu", tag, dev, key_ptr, dtype, jobs.size());
+    std::lock_guard<std::mutex> lock(g_pack_mutex);
+    PackCache& c = g_pack_cache[key];
+    const size_t bytes = jobs.size() * sizeof(SgPackJob);
+    if (c.host.size() != jobs.size() || memcmp(c.host.data(), jobs.data(), bytes) != 0) {
+        // cold path (first call / parameters or buffers moved).  The table is staged in pinned memory and copied on the
+        // call's stream: stream order puts the copy behind every earlier pack kernel that still reads the old table and in
+        // front of this call's -- no host synchronisation.  Only a table that outgrows its buffers allocates (first call,
+        // behind a stream drain: the old device table may still be in use), and a second re-staging waits for the first
+        // one's copy to have left the pinned buffer.
+        if (c.cap < bytes) {
+            SG_HIP(hipStreamSynchronize((hipStream_t)st));
+            if (c.dev) SG_HIP(hipFree(c.dev));
+            if (c.pinned) SG_HIP(hipHostFree(c.pinned));
+            SG_HIP(hipMalloc((void**)&c.dev, bytes));
+            SG_HIP(hipHostMalloc((void**)&c.pinned, bytes, hipHostMallocDefault));
+            c.cap = bytes;
         }
-        return sg_pack_multi_launch(c.dev, (int)jobs.size(), nblk, base, dtype, (hipStream_t)st, guard);
+        if (!c.staged) SG_HIP(hipEventCreateWithFlags(&c.staged, hipEventDisableTiming));
+        else SG_HIP(hipEventSynchronize(c.staged));
+        memcpy(c.pinned, jobs.data(), bytes);
+        SG_HIP(hipMemcpyAsync(c.dev, c.pinned, bytes, hipMemcpyHostToDevice, (hipStream_t)st));
+        SG_HIP(hipEventRecord(c.staged, (hipStream_t)st));
+        c.host = jobs;
     }
-};
-
-// opts.pack == 2: the persistent pack is re-made only if the device-side guard words differ (srcgan_net_opts)
-static inline const unsigned long long* pack_guard(const srcgan_net_opts* o) {
-    return (o && o->wpack && o->pack == 2) ? (const unsigned long long*)o->guard : nullptr;
+    return sg_pack_multi_launch(c.dev, (int)jobs.size(), nblk, wp_base, dtype, (hipStream_t)st, guard);
 }
 
-// ---- the input gradient of a k x k, stride 2, padding `pad` convolution cin -> cout: four stride-1 sub-convolutions over dy, one
-// per output parity q = (a, b) = (q >> 1, q & 1), each with its own pack of par2() taps per axis (rows = cin, k = cout), made
-// from the canonical weight w [cout][cin][k][k]
-struct S2Dgrad {
-    int k, pad, cin, cout;
-    void plan(Bump& wb, int dtype, size_t wd[4]) const {
-        for (int q = 0; q < 4; ++q) wd[q] = wb.take(srcgan_packed_weight_bytes(cin, cout, par2(k, pad, q >> 1).n * par2(k, pad, q & 1).n, dtype));
-    }
-    void pack(PackList& packs, const float* w, char* wp, const size_t wd[4]) const {
-        const long kk = (long)k * k;
-        for (int q = 0; q < 4; ++q) {
-            const Par2 py = par2(k, pad, q >> 1), px = par2(k, pad, q & 1);
-            packs.add(w, wp + wd[q], cin, cout, py.n, px.n, kk, (long)cin * kk, -2 * k, -2, (long)py.ky_max * k + px.ky_max);
-        }
-    }
-    // dy [B, OH, OW, cout] -> dx [B, H, W, cin].  acc: dx already holds a contribution, add to it; mz: multiply by LeakyReLU' of
-    // this tensor (either may be TNULL).  fuse: all four parities from one staged dy tile in ONE launch (conv_par4.hip: 4x4 p1,
-    // equally spaced packs, 16-byte accessible operands) where that applies; SRCGAN_NO_PAR4 (diagnostic builds) keeps the four.
-    int run(int dt, TRef dy, int B, int OH, int OW, TRef dx, int H, int W, const char* wp, const size_t wd[4], TRef acc, TRef mz,
-            bool fuse, void* st, float mslope = 0.2f) const {
-        static const bool no_par4 = sg_env("SRCGAN_NO_PAR4") != nullptr;
-        auto launch = [&](Conv& cv) {
-            if (acc.p) cv.res1(acc, cin, 1.f);
-            if (mz.p) { cv.mask(mz, 0); cv.d.mslope = mslope; }
-            return cv.run(st);
-        };
-        const int vec = 16 / (dt == SRCGAN_F32 ? 4 : 2);
-        const size_t wstep = wd[1] - wd[0];
-        const bool even = wd[2] - wd[1] == wstep && wd[3] - wd[2] == wstep;
-        if (fuse && !no_par4 && k == 4 && pad == 1 && even && H >= 2 && W >= 2 && cin % vec == 0 && dx.cs % vec == 0) {
-            Conv cv(dt, 2, 2, 1);
-            cv.in(dy, B, OH, OW, cout).w(wp + wd[0]).out(dx, (H + 1) / 2, (W + 1) / 2, cin).scatter(2, 0, 0, H, W);
-            cv.d.npar = 4; cv.d.wpar_stride = (long)wstep;
-            return launch(cv);
-        }
-        for (int q = 0; q < 4; ++q) {
-            const int a = q >> 1, b = q & 1;
-            const int mh = (H - a + 1) / 2, mw = (W - b + 1) / 2;
-            if (mh <= 0 || mw <= 0) continue;
-            const Par2 py = par2(k, pad, a), px = par2(k, pad, b);
-            Conv cv(dt, py.n, px.n, 1);
-            cv.in(dy, B, OH, OW, cout).w(wp + wd[q]).out(dx, mh, mw, cin).pad(py.lead, px.lead).scatter(2, a, b, H, W);
-            SG_TRY(launch(cv));
-        }
-        return 0;
-    }
-};
+namespace {
 
 // ======================================================================================== RDDBNet
 // The generator families: the values of srcgan_rddbnet_cfg.legacy (include/srcgan_amd.h describes each)
@@ -1241,1198 +1105,4 @@ extern "C" int srcgan_nlayerd_backward_ex(const srcgan_nlayerd_cfg* c, const flo
     DBwdPlan Q;
     d_bwd_plan(c, P, Q);
     return DCall(c, P, params, ws, opt, st, &Q, scratch, grads).backward(dy_nchw, dx_nchw);
-}
-
-// ======================================================================================== op-list networks
-// ResDeconv colouriser -- reference src/model/resdeconv.py:99-195 (the second network of every trainCas step,
-// trainCas.py:31,99-100): ResNet-18-style encoder (7x7 s2 stem, BasicBlocks 64-128-256-512 with 3x3 s2 + 1x1 s2 shortcut at
-// each widening) and a mirrored decoder (ConvTranspose2d k2 s2 + two BasicBlocks per scale), GroupNorm(32) + ReLU, no biases.
-// ESPCN -- src/model/espcn.py:18-51 (the CLI default --SRModel, trainCas.py:169): 5x5, 3x3, 3x3 convs + ReLU, 3x3 conv to
-// 64 r^2 channels, PixelShuffle(r), 3x3 conv.   SRCNN -- src/model/srcnn.py:17-42: 9x9, 1x1, 5x5 convs, each + ReLU.
-//
-// Each network is a short op list built once per call; forward walks it, backward walks it in reverse.  A tensor with two
-// consumers (a block's input: first convolution + shortcut) gets its first gradient contribution by a plain store and the
-// second through the convolution epilogue's in-place residual operand.  The gradient stored for the output of a
-// convolution with a fused ReLU is the gradient w.r.t. its pre-activation: whoever writes it applies the mask (the consumer's
-// dgrad epilogue, or srcgan_mask_inplace for the gradient arriving from the loss).
-namespace {
-struct RdT { int C, cs, H, W, act; size_t off; };       // act: produced by a convolution with a fused ReLU
-struct RdOp {
-    int type;                 // 0 conv (+bias)(+ReLU), 1 GroupNorm(+res)(+ReLU), 2 ConvTranspose2d k2 s2, 3 PixelShuffle(r),
-                              // 4 (inference plans only) ConvTranspose2d k2 s2 followed by a bias-free 3x3 conv, folded into four parity 2x2 convs
-                              // 5 ConvTranspose2d k3 s2 p1 output_padding 1 + bias + ReLU (deconv_k3s2.hip)
-                              // 6 MaxPool2d(2, 2) (vgg_loss.hip)
-                              // 7 channel attention + block residual (chan_attn.hip): in = t, res = the block's input, w = conv_du.0.weight (its bias and
-                              //   conv_du.2.{weight,bias} follow), ngrp = C / reduction, stats = the op's `saved` region
-                              // 8 MeanShift, a frozen 1x1 convolution on the 3 image channels (chan_attn.hip)
-                              // 9 shifted space-to-depth gather (back_proj.hip): image `in` -> grid `out`, k = the scale, pad = the shift
-                              // 10 per-channel PReLU (+ bias)(+ beta * res) (back_proj.hip): in = the pre-activation z, kept for the backward -- a plain
-                              //    tensor (k = 1) or the grid tensor of a transposed projection, cropped while it is read (k = the scale, pad = the shift);
-                              //    w = the slope, bias = the transposed projection's bias or -1, slope = beta, res at channel rcoff of its tensor
-    int in, out, res, relu;
-    int icoff, iC, ocoff, oC; // type 0 on a dense buffer: reads channels [icoff, icoff + iC) of `in`, writes [ocoff, ocoff + oC) of `out` (iC / oC == 0: the whole tensor)
-    int rcoff;                // type 10: first channel of the residual in `res`
-    int proj, ps, pk;         // type 0, proj != 0: a DDBPN projection in its stride-1 form over the space-to-depth view (k = ceil(pk / ps) taps): 1 = Conv2d
-                              // pk x pk stride ps (in = the gathered grid), 2 = ConvTranspose2d (out = the grid); w is the stored weight, re-ordered
-                              // into the f32 staging area wst (an offset into the pack region) before it is packed
-    size_t wst;
-    int share;                // != 0: a module applied a second time -- op share - 1 owns the packs, this op's weight and bias gradients add to its
-    int k, s, pad, w, bias;   // w: parameter index of the weight (GroupNorm: gamma, beta = w + 1; -1 = no affine part); bias: parameter index or -1
-    int w2;                   // type 4: parameter index of the 3x3 convolution's weight (w = the transposed convolution's)
-    int ngrp;                 // GroupNorm: groups (InstanceNorm2d: = channels)
-    float slope;              // GroupNorm activation: 0 = ReLU, 0.2 = LeakyReLU (edsr.py:42)
-    size_t wf[4], wd[4], stats;
-    S2Dgrad s2(int cin, int cout) const { return S2Dgrad{k, pad, cin, cout}; }      // input gradient of a stride-2 convolution with k > 1
-};
-static inline int rd_cin(const RdOp& o, const RdT& ti) { return o.iC ? o.iC : ti.C; }
-static inline int rd_cout(const RdOp& o, const RdT& to) { return o.oC ? o.oC : to.C; }
-// ConvTranspose2d weight [ci][co][3][3], output parity q = (a, b): rows = co, k = ci, taps (wy, wx) in [0, a] x [0, b] with ky = a ? 2 - 2 wy : 1
-static inline void deconv3_pack(PackList& packs, const float* w, char* wp, const size_t wf[4], int cin, int cout) {
-    for (int q = 0; q < 4; ++q) {
-        const int a = q >> 1, b = q & 1;
-        packs.add(w, wp + wf[q], cout, cin, a + 1, b + 1, 9, (long)cout * 9, -6, -2, (a ? 2 : 1) * 3 + (b ? 2 : 1));
-    }
-}
-struct RdPlan {
-    int dtype, esz, B, H, W, in_ch, out_ch, in_cs, out_cs, nparams, maxC;
-    std::vector<RdT> T; std::vector<RdOp> ops;
-    size_t xin, gnfwd, wpk, total, act_bytes;
-    size_t wpack;             // inference plans: bytes of the packed-weight part
-    std::vector<size_t> g;    // backward: gradient buffer offsets (scratch), same shapes as T
-    size_t projscr, prscr;    // backward: a projection's weight gradient in its stride-1 form; the PReLU partial sums
-    size_t slab, gnscr, colscr, btmp, bwd_total;      // btmp: a bias gradient on its way to being added (second use of a shared module)
-    std::vector<int> taps;    // tensors whose last reader is a loss behind the walk (frozen feature extractors): the slot planner keeps them
-};
-
-struct RdBuilder {
-    RdPlan& P; Bump b; int np = 0; int B;
-    int inorm = 0;            // normalisation layers are InstanceNorm2d (no parameters) instead of GroupNorm(32, C)
-    int frozen = 0;           // no parameter takes a gradient and the ops form a chain: the backward scratch is two alternating gradient buffers
-    RdBuilder(RdPlan& p, int B_) : P(p), B(B_) {}
-    int tensor(int C, int cs, int H, int W, int act = 0) { P.T.push_back(RdT{C, cs, H, W, act, b.take((size_t)B * H * W * cs * P.esz)}); return (int)P.T.size() - 1; }
-    int conv(int in, int cout, int k, int s, int pad, bool bias = false, bool relu = false) {
-        const RdT ti = P.T[in];
-        const int oh = (ti.H + 2 * pad - k) / s + 1, ow = (ti.W + 2 * pad - k) / s + 1;
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 0; o.in = in; o.res = -1; o.k = k; o.s = s; o.pad = pad; o.relu = relu; o.w = np++; o.bias = bias ? np++ : -1;
-        o.out = tensor(cout, cout < 8 ? 8 : cout, oh, ow, relu);
-        P.ops.push_back(o); return o.out;
-    }
-    // convolution between channel slices of dense buffers (the concat-free dense blocks of SRDenseNet)
-    void conv_slice(int in, int icoff, int iC, int out, int ocoff, int oC, int k, int pad) {
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 0; o.in = in; o.out = out; o.res = -1; o.k = k; o.s = 1; o.pad = pad; o.relu = 1; o.w = np++; o.bias = np++;
-        o.icoff = icoff; o.iC = iC; o.ocoff = ocoff; o.oC = oC;
-        P.ops.push_back(o);
-    }
-    int deconv3(int in, int cout) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 5; o.in = in; o.out = tensor(cout, cout, 2 * ti.H, 2 * ti.W, 1); o.res = -1; o.k = 3; o.s = 2; o.pad = 1; o.relu = 1; o.w = np++; o.bias = np++;
-        P.ops.push_back(o); return o.out;
-    }
-    // the last op applies the module of op `first` again (same parameters, same packs)
-    void share_last(int first) {
-        RdOp& o = P.ops.back();
-        o.w = P.ops[first].w; o.bias = P.ops[first].bias; o.share = first + 1;
-        np -= 2;
-    }
-    int gn(int in, int res, int relu) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 1; o.in = in; o.out = tensor(ti.C, ti.cs, ti.H, ti.W); o.res = res; o.relu = relu; o.bias = -1;
-        if (inorm) { o.w = -1; o.ngrp = ti.C; } else { o.w = np; np += 2; o.ngrp = 32; }
-        o.stats = b.take((size_t)B * o.ngrp * 2 * sizeof(float));
-        P.ops.push_back(o); return o.out;
-    }
-    int deconv(int in, int cout) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 2; o.in = in; o.out = tensor(cout, cout, 2 * ti.H, 2 * ti.W); o.res = -1; o.k = 2; o.s = 2; o.w = np++; o.bias = -1;
-        P.ops.push_back(o); return o.out;
-    }
-    int shuffle(int in, int r) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 3; o.in = in; o.res = -1; o.k = r; o.w = -1; o.bias = -1;
-        o.out = tensor(ti.C / (r * r), ti.C / (r * r), ti.H * r, ti.W * r);
-        P.ops.push_back(o); return o.out;
-    }
-    int pool(int in) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 6; o.in = in; o.res = -1; o.k = 2; o.s = 2; o.w = -1; o.bias = -1;
-        o.out = tensor(ti.C, ti.cs, ti.H / 2, ti.W / 2);
-        P.ops.push_back(o); return o.out;
-    }
-    int ca(int in, int res, int cr) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 7; o.in = in; o.res = res; o.out = tensor(ti.C, ti.cs, ti.H, ti.W); o.bias = -1; o.ngrp = cr;
-        o.w = np; np += 4;
-        o.stats = b.take((size_t)B * (2 * ti.C + cr) * sizeof(float));
-        P.ops.push_back(o); return o.out;
-    }
-    int meanshift(int in) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 8; o.in = in; o.res = -1; o.k = 1; o.s = 1; o.w = np++; o.bias = np++;
-        o.out = tensor(3, 8, ti.H, ti.W);
-        P.ops.push_back(o); return o.out;
-    }
-    // convolution with explicit parameter indices reading the channel prefix [0, iC) of `in` (iC == 0: all of it) into a new tensor
-    int conv_at(int in, int iC, int cout, int k, int pad, int widx, int bidx, int proj = 0, int ps = 0, int pk = 0) {
-        const RdT ti = P.T[in];
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 0; o.in = in; o.res = -1; o.k = k; o.s = 1; o.pad = pad; o.w = widx; o.bias = bidx; o.iC = iC; o.proj = proj; o.ps = ps; o.pk = pk;
-        o.out = tensor(cout, cout < 8 ? 8 : cout, ti.H + 2 * pad - k + 1, ti.W + 2 * pad - k + 1);
-        P.ops.push_back(o); return o.out;
-    }
-    int gather(int in, int iC, int s, int shift, int Hg, int Wg) {
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 9; o.in = in; o.res = -1; o.k = s; o.pad = shift; o.w = -1; o.bias = -1; o.iC = iC;
-        o.out = tensor(s * s * iC, s * s * iC, Hg, Wg);
-        P.ops.push_back(o); return o.out;
-    }
-    // out < 0: a new C-channel tensor of H x W; otherwise channels [ocoff, ocoff + C) of `out`
-    int prelu(int in, int C, int H, int W, int s, int shift, int aidx, int bidx, int res, int rcoff, float beta, int out = -1, int ocoff = 0) {
-        RdOp o; memset(&o, 0, sizeof(o));
-        o.type = 10; o.in = in; o.res = res; o.rcoff = rcoff; o.slope = beta; o.k = s; o.pad = shift; o.w = aidx; o.bias = bidx;
-        o.out = out >= 0 ? out : tensor(C, C, H, W); o.ocoff = ocoff; o.oC = C;
-        P.ops.push_back(o); return o.out;
-    }
-    size_t prelu_scratch() const {
-        size_t v = 0;
-        for (const RdOp& o : P.ops) if (o.type == 10) v = std::max(v, srcgan_prelu_scratch_floats(B, P.T[o.in].H, P.T[o.in].W, o.oC, o.k));
-        return v;
-    }
-    void tap(int t) { P.taps.push_back(t); }
-    // BasicBlock (resdeconv.py:56-97).  state_dict order inside a block: conv1, bn1, conv2, bn2, downsample.{0,1}
-    int block(int x, int planes, int stride) {
-        const bool ds = stride != 1 || P.T[x].C != planes;
-        int t = conv(x, planes, 3, stride, 1);
-        t = gn(t, -1, 1);
-        t = conv(t, planes, 3, 1, 1);
-        const int gn2_param = np; if (!inorm) np += 2;      // bn2's parameters precede the shortcut's in the state_dict
-        int idn = x;
-        if (ds) { idn = conv(x, planes, 1, stride, 0); idn = gn(idn, -1, 0); }
-        const int out = gn(t, idn, 1);
-        if (!inorm) { P.ops.back().w = gn2_param; np -= 2; }
-        return out;
-    }
-    void input(int in_ch, int H, int W) {
-        P.in_ch = in_ch; P.in_cs = img_cs(in_ch); P.H = H; P.W = W;
-        P.xin = b.take((size_t)B * H * W * P.in_cs * P.esz);
-        P.T.push_back(RdT{in_ch, P.in_cs, H, W, 0, P.xin});
-    }
-    size_t ca_scratch() const {       // the largest attention op's scratch (0: the plan has none)
-        size_t v = 0;
-        for (const RdOp& o : P.ops) if (o.type == 7) v = std::max(v, srcgan_ca_scratch_floats(B, (long)P.T[o.in].H * P.T[o.in].W, P.T[o.in].C));
-        return v;
-    }
-    void finish(int dtype) {
-        P.nparams = np;
-        P.maxC = 8;
-        for (const RdT& t : P.T) if (t.C > P.maxC) P.maxC = t.C;
-        P.out_ch = P.T.back().C; P.out_cs = P.T.back().cs;
-        P.gnfwd = b.take(std::max(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC), ca_scratch()) * sizeof(float));
-        P.act_bytes = b.off;
-        P.wpk = b.off;
-        Bump wb;
-        auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, dtype)); };
-        for (RdOp& o : P.ops) {
-            const RdT ti = P.T[o.in], to = P.T[o.out];
-            const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
-            if (o.share) {
-                memcpy(o.wf, P.ops[o.share - 1].wf, sizeof(o.wf)); memcpy(o.wd, P.ops[o.share - 1].wd, sizeof(o.wd));
-            } else if (o.type == 0) {
-                o.wf[0] = pk(cout, cin, o.k * o.k);
-                if (o.s == 1) o.wd[0] = pk(cin, cout, o.k * o.k);
-                else if (o.k == 1) o.wd[0] = pk(cin, cout, 1);
-                else o.s2(cin, cout).plan(wb, dtype, o.wd);
-            } else if (o.type == 2) {
-                for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.C, ti.C, 1);
-                o.wd[0] = pk(ti.C, to.C, 4);
-            } else if (o.type == 5) {       // four parity packs, equally spaced (the 4-tap pack's size)
-                const size_t step = srcgan_packed_weight_bytes(to.C, ti.C, 4, dtype), w0 = wb.take(4 * step);
-                for (int q = 0; q < 4; ++q) o.wf[q] = w0 + q * step;
-                o.wd[0] = pk(ti.C, to.C, 9);
-            }
-            if (o.type == 0 && o.proj) o.wst = wb.take((size_t)cout * cin * o.k * o.k * sizeof(float));
-        }
-        P.total = align_up(P.wpk + wb.off + 256, 256);
-        // backward scratch
-        Bump s;
-        P.g.resize(P.T.size());
-        if (frozen) {       // op k maps tensor k to tensor k + 1, and a gradient is dead once its op has run: even and odd tensors share a buffer each
-            size_t mx = 0;
-            for (const RdT& t : P.T) mx = std::max(mx, (size_t)B * t.H * t.W * t.cs * P.esz);
-            const size_t g0 = s.take(mx), g1 = s.take(mx);
-            for (size_t i = 0; i < P.T.size(); ++i) P.g[i] = (i & 1) ? g1 : g0;
-            P.slab = P.gnscr = P.colscr = P.btmp = P.projscr = P.prscr = 0;
-            P.bwd_total = s.off + 256;
-            return;
-        }
-        long maxpix = 1;
-        for (size_t i = 0; i < P.T.size(); ++i) {
-            P.g[i] = s.take((size_t)B * P.T[i].H * P.T[i].W * P.T[i].cs * P.esz);
-            if ((long)B * P.T[i].H * P.T[i].W > maxpix) maxpix = (long)B * P.T[i].H * P.T[i].W;
-        }
-        size_t slab = 0;
-        for (const RdOp& o : P.ops) {
-            const RdT ti = P.T[o.in], to = P.T[o.out];
-            size_t v = 0;
-            if (o.type == 0) v = wgrad_slab(B, to.H, to.W, rd_cout(o, to), rd_cin(o, ti), o.k, o.k, o.s);
-            else if (o.type == 2) v = wgrad_slab(B, ti.H, ti.W, ti.C, to.C, 2, 2, 2);
-            else if (o.type == 5) v = wgrad_slab(B, ti.H, ti.W, ti.C, to.C, 3, 3, 2);
-            if (v > slab) slab = v;
-        }
-        P.slab = s.take(slab);
-        size_t projscr = 0;
-        for (const RdOp& o : P.ops) if (o.type == 0 && o.proj) projscr = std::max(projscr, (size_t)rd_cout(o, P.T[o.out]) * rd_cin(o, P.T[o.in]) * o.k * o.k * sizeof(float));
-        P.projscr = projscr ? s.take(projscr) : 0;
-        P.prscr = prelu_scratch() ? s.take(prelu_scratch() * sizeof(float)) : 0;
-        P.gnscr = s.take(std::max(srcgan_gn_scratch_floats(B, P.maxC > 1024 ? 1024 : P.maxC), ca_scratch()) * sizeof(float));
-        P.colscr = s.take((size_t)2 * srcgan_col_reduce_blocks(maxpix) * P.maxC * sizeof(float));
-        P.btmp = 0;           // only plans that apply a module twice carry it (the others keep their size)
-        for (const RdOp& o : P.ops) if (o.share && !P.btmp) P.btmp = s.take((size_t)P.maxC * sizeof(float));
-        P.bwd_total = s.off + 256;
-    }
-};
-
-static int rd_common(int dtype, int B, int H, int W, RdPlan& P, const char* who) {
-    SG_REQUIRE(sg_dtype_ok(dtype), "%s: bad dtype %d", who, dtype);
-    SG_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad B/H/W", who);
-    P.dtype = dtype; P.esz = dtype == SRCGAN_F32 ? 4 : 2; P.B = B;
-    return 0;
-}
-
-static int rd_plan(const srcgan_resdeconv_cfg* c, RdPlan& P) {
-    SG_REQUIRE(c, "resdeconv: null cfg");
-    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "resdeconv"));
-    SG_REQUIRE(c->in_ch == 3 && c->out_ch > 0 && c->out_ch <= 8, "resdeconv: the stem takes 3 channels (resdeconv.py:113), tar_ch must be in 1..8");
-    SG_REQUIRE(c->H % 16 == 0 && c->W % 16 == 0, "resdeconv: H and W must be multiples of 16 (four stride-2 stages mirrored by four x2 deconvolutions)");
-    int layers[4];
-    const bool dflt = c->layers[0] == 0 && c->layers[1] == 0 && c->layers[2] == 0 && c->layers[3] == 0;
-    for (int l = 0; l < 4; ++l) {
-        layers[l] = dflt ? 2 : c->layers[l];
-        SG_REQUIRE(layers[l] >= 1 && layers[l] <= 64, "resdeconv: layers[%d] = %d (1..64 BasicBlocks per stage)", l, layers[l]);
-    }
-    SG_REQUIRE(c->norm == 0 || c->norm == 1, "resdeconv: norm must be 0 (GroupNorm(32, C)) or 1 (InstanceNorm2d)");
-    RdBuilder nb(P, c->B);
-    nb.inorm = c->norm == 1;
-    nb.input(c->in_ch, c->H, c->W);
-    int t = nb.conv(0, 64, 7, 2, 3);
-    t = nb.gn(t, -1, 1);
-    const int widths[4] = {64, 128, 256, 512};
-    for (int l = 0; l < 4; ++l)                 // _make_layer (resdeconv.py:148-163): the first block carries the stride / shortcut
-        for (int k = 0; k < layers[l]; ++k) t = nb.block(t, widths[l], (k == 0 && l > 0) ? 2 : 1);
-    const int up_w[3] = {256, 128, 64};
-    for (int l = 0; l < 3; ++l) {               // upRes1..3 use layers[2], layers[1], layers[0] (resdeconv.py:131-137)
-        t = nb.deconv(t, up_w[l]);
-        for (int k = 0; k < layers[2 - l]; ++k) t = nb.block(t, up_w[l], 1);
-    }
-    t = nb.deconv(t, 64);
-    nb.conv(t, c->out_ch, 3, 1, 1);
-    nb.finish(c->dtype);
-    return 0;
-}
-
-// kind 0: ESPCN(in_ch, ou_ch, upscale_factor, base_kernel) espcn.py:18-51;  kind 1: SRCNN(in_ch, ou_ch, ., base_kernel) srcnn.py:17-42
-static int sr_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
-    SG_REQUIRE(c, "srnet: null cfg");
-    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srnet"));
-    SG_REQUIRE(c->kind >= 0 && c->kind <= 2, "srnet: kind must be 0 (ESPCN), 1 (SRCNN) or 2 (EDSR)");
-    SG_REQUIRE(c->kind != 2 || (c->nres >= 1 && c->base % 32 == 0 && (c->up & (c->up - 1)) == 0), "srnet: EDSR needs num_residuals >= 1, base_channel % 32 == 0 and a power-of-two upscale factor");
-    SG_REQUIRE(c->in_ch > 0 && c->in_ch <= 8 && c->out_ch > 0 && c->out_ch <= 8, "srnet: in/out channels must be in 1..8");
-    SG_REQUIRE(c->base > 0 && c->base % 16 == 0, "srnet: base_kernel must be a multiple of 16");
-    SG_REQUIRE(c->up >= 1 && c->up <= 8, "srnet: upscale_factor must be in 1..8");
-    RdBuilder nb(P, c->B);
-    nb.input(c->in_ch, c->H, c->W);
-    if (c->kind == 0) {
-        int t = nb.conv(0, c->base, 5, 1, 2, true, true);
-        t = nb.conv(t, c->base, 3, 1, 1, true, true);
-        t = nb.conv(t, c->base / 2, 3, 1, 1, true, true);
-        t = nb.conv(t, c->base * c->up * c->up, 3, 1, 1, true, false);
-        t = nb.shuffle(t, c->up);
-        nb.conv(t, c->out_ch, 3, 1, 1, true, false);
-    } else if (c->kind == 1) {
-        int t = nb.conv(0, c->base, 9, 1, 4, true, true);
-        t = nb.conv(t, c->base / 2, 1, 1, 0, true, true);
-        nb.conv(t, c->out_ch, 5, 1, 2, true, true);
-    } else {
-        // EDSR (edsr.py:37-110): input_conv; num_residuals x [conv1 -> gn -> LeakyReLU(0.2) -> conv2 -> gn (the SAME GroupNorm
-        // module) -> + x]; mid_conv + input_conv's output; ConvTranspose2d k2 s2 per x2 stage; output_conv.  state_dict order
-        // inside a block: conv1.{w,b}, conv2.{w,b}, gn.{w,b}.
-        const int feat = nb.conv(0, c->base, 3, 1, 1, true, false);
-        int t = feat;
-        for (int i = 0; i < c->nres; ++i) {
-            const int base = nb.np, x = t;
-            t = nb.conv(x, c->base, 3, 1, 1, true, false);
-            P.ops.back().w = base; P.ops.back().bias = base + 1;
-            t = nb.gn(t, -1, 1);
-            P.ops.back().w = base + 4; P.ops.back().slope = 0.2f;
-            t = nb.conv(t, c->base, 3, 1, 1, true, false);
-            P.ops.back().w = base + 2; P.ops.back().bias = base + 3;
-            t = nb.gn(t, x, 0);
-            P.ops.back().w = base + 4;
-            nb.np = base + 6;
-        }
-        t = nb.conv(t, c->base, 3, 1, 1, true, false);
-        P.ops.back().res = feat;
-        for (int f = 1; f < c->up; f *= 2) t = nb.deconv(t, c->base);
-        nb.conv(t, c->out_ch, 3, 1, 1, true, false);
-    }
-    nb.finish(c->dtype);
-    return 0;
-}
-// SRDenseNetA (kind 0, LR -> HR) / SRDenseNetB (kind 1, HR -> LR) -- reference src/model/model.py:643-786.  conv_first (in -> 1
-// channel) -> conv (1 -> g L) + ReLU -> num_blocks DenseBlocks -> 1x1 bottleneck to 256 + ReLU -> the shared up- / down-sampler once
-// ('x2') or twice ('x4') -> reconstruction (256 -> 1) -> conv_last.  state_dict order = the order the ops are built in.
-//
-// Concat-free dense blocks, in-place prefixing: DenseBlock i maps its input x (C_i = g L (i + 1) channels) to cat[x, c_1 .. c_L], and
-// that is exactly the next block's input, so ALL blocks share ONE buffer of g L (num_blocks + 1) channels: the block's first layer reads
-// the prefix [0, C_i), layer j > 1 reads [C_i, C_i + g (j - 1)) (the block-local concatenation: model.py:666-669 does not feed x to its
-// DenseLayers), each writes its own g-channel slice, and the bottleneck reads the whole buffer.  No copy, no torch.cat, no CatBackward.
-// Backward: the bottleneck's input gradient is the first writer of the whole gradient buffer; every layer's dgrad adds to the
-// slice range it read through the epilogue's in-place residual, masked by ReLU' of the stored activation.
-static int sd_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
-    SG_REQUIRE(c, "srdense: null cfg");
-    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srdense"));
-    SG_REQUIRE(c->kind == 0 || c->kind == 1, "srdense: kind must be 0 (SRDenseNetA) or 1 (SRDenseNetB)");
-    SG_REQUIRE(c->in_ch > 0 && c->in_ch <= 8 && c->out_ch > 0 && c->out_ch <= 8, "srdense: in/out channels must be in 1..8");
-    SG_REQUIRE(c->num_blocks >= 1 && c->num_layers >= 1 && c->growth >= 1, "srdense: growth_rate, num_blocks and num_layers must be positive");
-    SG_REQUIRE(c->up == 2 || c->up == 4, "srdense: mode must be 'x2' or 'x4' (up = 2 or 4)");
-    SG_REQUIRE(c->growth % 8 == 0, "srdense: growth_rate must be a multiple of 8 (growth_rate = %d): every layer writes a growth_rate-channel slice, and slices are "
-               "addressed in 16-byte pieces", c->growth);
-    const int g = c->growth, L = c->num_layers, nB = c->num_blocks, gL = g * L, kce = 64 / P.esz;
-    SG_REQUIRE(gL % kce == 0, "srdense: growth_rate * num_layers = %d must be a multiple of the 64-byte K chunk (%d channels in this dtype): a dense block's "
-               "slice offset growth_rate * num_layers * (i + 1) has to start a chunk", gL, kce);
-    SG_REQUIRE(c->kind == 0 || (c->H >= 2 && c->W >= 2), "srdense: SRDenseNetB needs H, W >= 2");
-    SG_REQUIRE((long)gL * (nB + 1) <= 8192, "srdense: more than 8192 concatenated channels");
-    RdBuilder nb(P, c->B);
-    nb.input(c->in_ch, c->H, c->W);
-    const int t1 = nb.conv(0, 1, 3, 1, 1, true, false);                      // conv_first
-    const int Ctot = gL * (nB + 1);
-    const int D = nb.tensor(Ctot, Ctot, c->H, c->W, 1);
-    nb.conv_slice(t1, 0, 0, D, 0, gL, 3, 1);                                 // conv
-    for (int i = 0; i < nB; ++i) {
-        const int Ci = gL * (i + 1);
-        nb.conv_slice(D, 0, Ci, D, Ci, g, 3, 1);                             // ConvLayer: the whole block input
-        for (int j = 1; j < L; ++j) nb.conv_slice(D, Ci, g * j, D, Ci + g * j, g, 3, 1);     // DenseLayer j: c_1 .. c_j
-    }
-    int t = nb.conv(D, 256, 1, 1, 0, true, true);                            // bottleneck
-    int first = -1;
-    for (int f = 1; f < c->up; f *= 2) {                                     // deconv: ONE module, applied once or twice
-        t = c->kind == 0 ? nb.deconv3(t, 256) : nb.conv(t, 256, 3, 2, 1, true, true);
-        if (first < 0) first = (int)P.ops.size() - 1; else nb.share_last(first);
-    }
-    t = nb.conv(t, 1, 3, 1, 1, true, false);                                 // reconstruction
-    nb.conv(t, c->out_ch, 3, 1, 1, true, false);                             // conv_last
-    nb.finish(c->dtype);
-    return 0;
-}
-// RCAN (rcan.py:69-116).  Parameter indices follow parameters() order = registration order: sub_mean (:82), add_mean (:100, assigned
-// before head / body / tail at :102-104), head, body, tail -- the two MeanShift ops get their indices by hand.
-static int rcan_plan(const srcgan_rcan_cfg* c, RdPlan& P) {
-    SG_REQUIRE(c, "srcgan_rcan: null cfg");
-    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_rcan"));
-    SG_REQUIRE(c->in_ch == 3 && c->out_ch == 3, "srcgan_rcan: n_colors must be 3 (MeanShift is a 3-channel convolution, common.py:16)");
-    SG_REQUIRE(c->scale == 2 || c->scale == 3 || c->scale == 4 || c->scale == 8, "srcgan_rcan: scale = %d must be 2, 3, 4 or 8 (common.py:63-84)", c->scale);
-    SG_REQUIRE(c->n_feats > 0 && c->n_feats % 16 == 0 && c->n_feats <= 1024, "srcgan_rcan: n_feats = %d must be a multiple of 16, at most 1024", c->n_feats);
-    SG_REQUIRE(c->reduction >= 1 && c->n_feats / c->reduction >= 1, "srcgan_rcan: n_feats / reduction must be at least 1 (n_feats = %d, reduction = %d)",
-               c->n_feats, c->reduction);
-    SG_REQUIRE(c->n_resgroups >= 1 && c->n_resblocks >= 1 && (long)c->n_resgroups * c->n_resblocks <= 100000, "srcgan_rcan: n_resgroups and n_resblocks must be positive");
-    const int F = c->n_feats, cr = F / c->reduction;
-    RdBuilder nb(P, c->B);
-    nb.input(3, c->H, c->W);
-    int t = nb.meanshift(0);                                    // sub_mean: parameters 0, 1
-    nb.np = 4;                                                  // add_mean: parameters 2, 3
-    const int head = nb.conv(t, F, 3, 1, 1, true, false);
-    t = head;
-    for (int g = 0; g < c->n_resgroups; ++g) {
-        const int gin = t;
-        for (int k = 0; k < c->n_resblocks; ++k) {              // RCAB (:30-49)
-            const int x = t;
-            t = nb.conv(x, F, 3, 1, 1, true, true);
-            t = nb.conv(t, F, 3, 1, 1, true, false);
-            t = nb.ca(t, x, cr);
-        }
-        t = nb.conv(t, F, 3, 1, 1, true, false);                // ResidualGroup (:60-66)
-        P.ops.back().res = gin;
-    }
-    t = nb.conv(t, F, 3, 1, 1, true, false);                    // :93, 110-111
-    P.ops.back().res = head;
-    if (c->scale == 3) { t = nb.conv(t, 9 * F, 3, 1, 1, true, false); t = nb.shuffle(t, 3); }
-    else for (int f = 1; f < c->scale; f *= 2) { t = nb.conv(t, 4 * F, 3, 1, 1, true, false); t = nb.shuffle(t, 2); }
-    t = nb.conv(t, 3, 3, 1, 1, true, false);
-    nb.meanshift(t);
-    P.ops.back().w = 2; P.ops.back().bias = 3; nb.np -= 2;
-    nb.finish(c->dtype);
-    return 0;
-}
-// DDBPN (ddbpn.py:68-130).  n0, nr and depth are the reference's constants (:73-75).  Parameter indices follow parameters() order =
-// registration order (sub_mean, initial, upmodules, downmodules, reconstruction, add_mean), not the order the modules run in (up 0,
-// down 0, up 1, ...), so every op gets its indices by hand.  Inside a DenseProjection: [bottleneck.0.{w,b}, bottleneck.1.weight,]
-// conv_1.0.{w,b}, conv_1.1.weight, conv_2..., conv_3... (:32-53).
-//
-// A projection (k, s, p = 2) in its stride-1 form, T = ceil(k / s) taps, LR h x w, HR s h x s w:
-//   up   (ConvTranspose2d): T x T convolution, pad 1, to s^2 nr channels on the grid; PReLU reads it through the crop and adds the bias
-//   down (Conv2d):          gather to the grid (s^2 nr channels); T x T convolution, pad 0 (scale 2: 1), + bias; plain PReLU
-// The grid is (h + 1) x (w + 1) with shift 2; at scale 2 its border rows are all padding, so it is h x w with shift 0 (plain
-// space-to-depth / PixelShuffle) and 3x3 pad-1 convolutions.  PReLU's fused residual carries e = b_0 - x and out = a_0 + a_1 (:61-64);
-// `out` goes straight into its slice of the concatenation buffer (l_list: LR, 5 nr channels; h_list: HR, 6 nr), whose consumers read
-// the prefix.  Backward: the reconstruction's input gradient is the first writer of the whole HR gradient buffer, the last up-module's
-// bottleneck that of the LR one; every other consumer adds to the range it read.
-static int ddbpn_plan(const srcgan_ddbpn_cfg* c, RdPlan& P) {
-    SG_REQUIRE(c, "srcgan_ddbpn: null cfg");
-    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_ddbpn"));
-    SG_REQUIRE(c->in_ch == 3 && c->out_ch == 3, "srcgan_ddbpn: n_colors must be 3 (MeanShift is a 3-channel convolution, common.py:16)");
-    SG_REQUIRE(c->scale == 2 || c->scale == 4 || c->scale == 8, "srcgan_ddbpn: scale = %d must be 2, 4 or 8 (ddbpn.py:14-18)", c->scale);
-    SG_REQUIRE((long)c->H * c->scale < (1 << 24) && (long)c->W * c->scale < (1 << 24), "srcgan_ddbpn: image too large");
-    const int n0 = 128, nr = 32, depth = 6;
-    const int s = c->scale, k = s == 2 ? 6 : s == 4 ? 8 : 12, T = (k + s - 1) / s;
-    const int shift = s == 2 ? 0 : 2, h = c->H, w = c->W, Hg = h + (s == 2 ? 0 : 1), Wg = w + (s == 2 ? 0 : 1);
-    RdBuilder nb(P, c->B);
-    nb.input(3, h, w);
-    int t = nb.meanshift(0);                                    // sub_mean: parameters 0, 1
-    t = nb.conv_at(t, 0, n0, 3, 1, 2, 3);
-    t = nb.prelu(t, n0, h, w, 1, 0, 4, -1, -1, 0, 1.f);
-    t = nb.conv_at(t, 0, nr, 1, 0, 5, 6);
-    const int x0 = nb.prelu(t, nr, h, w, 1, 0, 7, -1, -1, 0, 1.f);
-    const int L = nb.tensor((depth - 1) * nr, (depth - 1) * nr, h, w), Hh = nb.tensor(depth * nr, depth * nr, s * h, s * w);
-    // x: channels [0, nr) of its tensor; returns PReLU(projection(x)) + beta * res, a new tensor or the slice ocoff of `out`
-    auto proj = [&](bool up, int x, int pb, int res, float beta, int out, int ocoff) {
-        if (up) {
-            const int g = nb.conv_at(x, nr, s * s * nr, T, 1, pb, -1, 2, s, k);
-            return nb.prelu(g, nr, s * h, s * w, s, shift, pb + 2, pb + 1, res, 0, beta, out, ocoff);
-        }
-        const int g = nb.gather(x, nr, s, shift, Hg, Wg);
-        const int z = nb.conv_at(g, 0, nr, T, s == 2 ? 1 : 0, pb, pb + 1, 1, s, k);
-        return nb.prelu(z, nr, h, w, 1, 0, pb + 2, -1, res, 0, beta, out, ocoff);
-    };
-    auto module = [&](bool up, int in, int iC, bool bneck, int pb, int out, int ocoff) {       // DenseProjection.forward (:55-66)
-        int x = in;
-        if (bneck) {
-            const int z = nb.conv_at(in, iC, nr, 1, 0, pb, pb + 1);
-            x = nb.prelu(z, nr, P.T[z].H, P.T[z].W, 1, 0, pb + 2, -1, -1, 0, 1.f);
-            pb += 3;
-        }
-        const int a0 = proj(up, x, pb, -1, 1.f, -1, 0);
-        const int e = proj(!up, a0, pb + 3, x, -1.f, -1, 0);
-        proj(up, e, pb + 6, a0, 1.f, out, ocoff);
-    };
-    int up_pb[6], down_pb[5], pb = 8;
-    for (int i = 0; i < depth; ++i) { up_pb[i] = pb; pb += i > 1 ? 12 : 9; }                   // bottleneck: i > 1 (:93)
-    for (int i = 0; i < depth - 1; ++i) { down_pb[i] = pb; pb += i != 0 ? 12 : 9; }            // bottleneck: i != 0 (:101)
-    for (int i = 0; i < depth - 1; ++i) {                                                       // :118-124
-        module(true, i == 0 ? x0 : L, i * nr, i > 1, up_pb[i], Hh, i * nr);
-        module(false, Hh, (i + 1) * nr, i != 0, down_pb[i], L, i * nr);
-    }
-    module(true, L, (depth - 1) * nr, true, up_pb[depth - 1], Hh, (depth - 1) * nr);           // :126
-    t = nb.conv_at(Hh, 0, 3, 3, 1, pb, pb + 1);                                                 // reconstruction
-    nb.np = pb + 2;
-    nb.meanshift(t);                                                                            // add_mean: the last two parameters
-    nb.finish(c->dtype);
-    return 0;
-}
-static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
-static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
-
-// the forward in three parts (a frozen feature extractor packs once and walks twice, on two inputs)
-static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, const char* tag, void* st) {
-    const int dt = P.dtype;
-    char* w8 = (char*)ws; char* wp = w8 + P.wpk;
-    PackList packs(dt, wp);
-    for (const RdOp& o : P.ops) {
-        const RdT ti = P.T[o.in], to = P.T[o.out];
-        const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
-        if (o.share) continue;          // packed by the module's first use
-        if (o.type == 0 && o.proj) {    // the stored weight in its stride-1 form: an f32 Conv2d weight [cout][cin][k][k] in the staging area
-            SG_TRY(sg_proj_repack(params[o.w], (float*)(wp + o.wst), o.proj - 1, o.proj == 1 ? cout : cout / (o.ps * o.ps), o.proj == 1 ? cin / (o.ps * o.ps) : cin,
-                                  o.pk, o.ps, 0, (hipStream_t)st));
-            packs.add((const float*)(wp + o.wst), wp + o.wf[0], cout, cin, o.k, o.k, lay_fwd(cin, o.k, o.k));
-        } else
-        if (o.type == 0) packs.add(params[o.w], wp + o.wf[0], cout, cin, o.k, o.k, (long)cin * o.k * o.k, (long)o.k * o.k, o.k, 1, 0);
-        else if (o.type == 2)
-            for (int q = 0; q < 4; ++q) packs.add(params[o.w], wp + o.wf[q], to.C, ti.C, 1, 1, 4, (long)to.C * 4, 0, 0, q);
-        else if (o.type == 5) deconv3_pack(packs, params[o.w], wp, o.wf, ti.C, to.C);
-    }
-    char key[64]; snprintf(key, sizeof(key), "%s_fwd", tag);
-    SG_TRY(packs.run(key, params[0], st));
-    for (const RdOp& o : P.ops)      // composed weights of a folded tail: made from both sources on every call, like the packs above
-        if (o.type == 4) SG_TRY(sg_fold_tail_pack(params[o.w], params[o.w2], wp + o.wf[0], P.T[o.out].C, dt, (hipStream_t)st));
-    return 0;
-}
-// fr != nullptr: x_nchw is a 5-D tensor whose frames [f0, f0 + k) are the B images (common.h, SgFrames)
-static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, void* st, const SgFrames* fr = nullptr) {
-    const int dt = P.dtype, B = P.B;
-    char* w8 = (char*)ws; char* wp = w8 + P.wpk;
-    if (fr) SG_TRY(sg_frames_pack(x_nchw, w8 + P.xin, P.in_cs, B / fr->k, *fr, P.H, P.W, dt, (hipStream_t)st));
-    else SG_TRY(srcgan_nchw_f32_to_nhwc(x_nchw, w8 + P.xin, B, P.in_ch, P.H, P.W, P.in_cs, dt, st));
-    float* gnscr = (float*)(w8 + P.gnfwd);
-    for (const RdOp& o : P.ops) {
-        const RdT ti = P.T[o.in], to = P.T[o.out];
-        TRef xin = rd_t(w8, ti), out = rd_t(w8, to);
-        if (o.type == 0) {
-            if (to.C < to.cs) SG_HIP(hipMemsetAsync(out.p, 0, (size_t)B * to.H * to.W * to.cs * P.esz, (hipStream_t)st));
-            Conv cv(dt, o.k, o.k, o.s);
-            cv.in(sl(xin, o.icoff), B, ti.H, ti.W, ti.C < 8 ? ti.cs : rd_cin(o, ti)).w(wp + o.wf[0], o.bias >= 0 ? params[o.bias] : nullptr)
-                .out(sl(out, o.ocoff), to.H, to.W, rd_cout(o, to)).pad(o.pad, o.pad);
-            if (o.relu) { cv.lrelu(); cv.d.slope = 0.f; }
-            if (o.res >= 0) cv.res1(rd_t(w8, P.T[o.res]), to.C, 1.f);          // y = conv(x) + res (edsr.py:97-98)
-            SG_TRY(cv.run(st));
-        } else if (o.type == 1) {
-            const void* res = o.res >= 0 ? (w8 + P.T[o.res].off) : nullptr;
-            SG_TRY(srcgan_gn_forward(xin.p, ti.cs, res, o.res >= 0 ? P.T[o.res].cs : 0, out.p, to.cs, o.w >= 0 ? params[o.w] : nullptr,
-                                     o.w >= 0 ? params[o.w + 1] : nullptr, (float*)(w8 + o.stats), B, (long)ti.H * ti.W, ti.C, o.ngrp, 1e-5f, o.relu,
-                                     o.slope, dt, gnscr, st));
-        } else if (o.type == 2) {
-            for (int q = 0; q < 4; ++q)
-                SG_TRY(Conv(dt, 1, 1, 1).in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[q]).out(out, ti.H, ti.W, to.C)
-                           .scatter(2, q >> 1, q & 1, to.H, to.W).run(st));
-        } else if (o.type == 3) {
-            SG_TRY(srcgan_pixel_shuffle_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, to.C, o.k, 0, dt, st));
-        } else if (o.type == 5) {
-            // output pixel (2i + a, 2j + b) = the 1, 2, 2 or 4 taps of parity (a, b) over x[i..i+1][j..j+1]: all four in one launch
-            Conv cv(dt, 3, 3, 2);
-            cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0], params[o.bias]).out(out, ti.H, ti.W, to.C).pad(1, 1).scatter(2, 0, 0, to.H, to.W).lrelu();
-            cv.d.slope = 0.f; cv.d.npar = 4; cv.d.wpar_stride = (long)(o.wf[1] - o.wf[0]);
-            SG_TRY(cv.run(st));
-        } else if (o.type == 6) {
-            SG_TRY(srcgan_maxpool2_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, ti.C, dt, st));
-        } else if (o.type == 7) {
-            const void* res = o.res >= 0 ? (w8 + P.T[o.res].off) : nullptr;
-            SG_TRY(srcgan_ca_forward(xin.p, ti.cs, res, o.res >= 0 ? P.T[o.res].cs : 0, out.p, to.cs, params[o.w], params[o.w + 1], params[o.w + 2],
-                                     params[o.w + 3], (float*)(w8 + o.stats), B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
-        } else if (o.type == 8) {
-            SG_TRY(sg_meanshift(xin.p, out.p, params[o.w], params[o.bias], 0, (long)B * ti.H * ti.W, dt, (hipStream_t)st));
-        } else if (o.type == 9) {
-            SG_TRY(srcgan_s2d_shift(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, o.iC, o.k, o.pad, to.H, to.W, dt, st));
-        } else if (o.type == 10) {
-            const void* res = o.res >= 0 ? (w8 + P.T[o.res].off + (size_t)o.rcoff * P.esz) : nullptr;
-            SG_TRY(srcgan_prelu_forward(xin.p, ti.cs, params[o.w], o.bias >= 0 ? params[o.bias] : nullptr, res, o.res >= 0 ? P.T[o.res].cs : 0, o.slope,
-                                        (char*)out.p + (size_t)o.ocoff * P.esz, to.cs, B, to.H, to.W, o.oC, o.k, o.pad, ti.H, ti.W, dt, st));
-        } else {
-            // folded tail: output pixel (2i + a, 2j + b) = 2x2 window of the half-resolution input at (i + a - 1, j + b - 1) times the
-            // composed weights of parity (a, b) -- the geometry of the 4x4 stride-2 input gradient, so its four-parity kernel serves.
-            // All to.cs channels are written (the pack's rows >= to.C are zero): no memset of the padded channels.
-            Conv cv(dt, 2, 2, 1);
-            cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0]).out(out, ti.H, ti.W, to.cs).scatter(2, 0, 0, to.H, to.W);
-            cv.d.npar = 4; cv.d.wpar_stride = (long)(o.wf[1] - o.wf[0]);
-            SG_TRY(cv.run(st));
-        }
-    }
-    return 0;
-}
-static int rd_forward(const RdPlan& P, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, const char* tag, void* st) {
-    SG_REQUIRE(x_nchw && params && ws && y_nchw, "%s forward: null pointer", tag);
-    SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s forward: workspace must be 256-byte aligned", tag);
-    SG_TRY(rd_pack_fwd(P, params, ws, tag, st));
-    SG_TRY(rd_walk(P, x_nchw, params, ws, st));
-    const RdT& last = P.T.back();
-    SG_TRY(srcgan_nhwc_to_nchw_f32((char*)ws + last.off, y_nchw, P.B, P.out_ch, last.H, last.W, last.cs, 0, P.dtype, st));
-    return 0;
-}
-
-// ---- inference: the same op list on a liveness-planned workspace.  rd_forward walks whatever offsets the plan holds, so an
-// inference plan is the training plan with its addresses rewritten: a tensor's slot is handed back after its last reader (as `in`
-// or as `res`) and reused by later tensors of the same byte size -- one pool per size: a network's stages each cycle through a
-// handful of equal tensors, so the pool sizes do not depend on the depth.  An op's output slot is taken BEFORE its inputs are
-// handed back: it never aliases them (the kernels take __restrict__ pointers).  GroupNorm statistics share one region (nothing reads
-// them after the op), and only the forward packs are laid out.  fold: the trailing ConvTranspose2d k2 s2 -> bias-free 3x3 conv pair
-// becomes one op of type 4, and the full-resolution tensor between them gets no slot.
-static inline size_t rd_bytes(const RdPlan& P, const RdT& t) { return (size_t)P.B * t.H * t.W * t.cs * P.esz; }
-
-static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare = 0) {
-    if (fold) {
-        const int n = (int)P.ops.size();
-        SG_REQUIRE(n >= 2, "%s: no tail to fold", who);
-        const RdOp d = P.ops[n - 2], c = P.ops[n - 1];
-        SG_REQUIRE(d.type == 2 && c.type == 0 && c.in == d.out && c.k == 3 && c.s == 1 && c.pad == 1 && c.bias < 0 && !c.relu && c.res < 0 &&
-                   P.T[d.in].C == 64 && P.T[d.out].C == 64 && P.T[c.out].cs == 8,
-                   "%s: the tail is not ConvTranspose2d(64, 64, k2 s2) -> bias-free 3x3 convolution to <= 8 channels", who);
-        RdOp f; memset(&f, 0, sizeof(f));
-        f.type = 4; f.in = d.in; f.out = c.out; f.res = -1; f.k = 2; f.s = 1; f.w = d.w; f.w2 = c.w; f.bias = -1;
-        P.ops.resize(n - 2);
-        P.ops.push_back(f);
-    }
-    const int nops = (int)P.ops.size(), nt = (int)P.T.size();
-    std::vector<int> last(nt, -1);
-    for (int k = 0; k < nops; ++k) { last[P.ops[k].in] = k; if (P.ops[k].res >= 0) last[P.ops[k].res] = k; }
-    last[nt - 1] = nops;                                       // the output conversion reads the last tensor
-    for (int t : P.taps) last[t] = nops;                       // a tap's last reader is the loss, behind the walk
-    Bump b;
-    std::map<size_t, std::vector<size_t>> pool;                // byte size -> free slots
-    auto get = [&](int t) {
-        const size_t sz = align_up(rd_bytes(P, P.T[t]), 256);
-        std::vector<size_t>& f = pool[sz];
-        if (f.empty()) P.T[t].off = b.take(sz);
-        else { P.T[t].off = f.back(); f.pop_back(); }
-    };
-    auto put = [&](int t) { pool[align_up(rd_bytes(P, P.T[t]), 256)].push_back(P.T[t].off); };
-    for (RdT& t : P.T) t.off = 0;
-    std::vector<char> have(nt, 0);          // a dense buffer is the output of many ops: it takes its slot at the first
-    get(0); have[0] = 1;
-    P.xin = P.T[0].off;
-    for (int k = 0; k < nops; ++k) {
-        const RdOp& o = P.ops[k];
-        if (!have[o.out]) { get(o.out); have[o.out] = 1; }
-        if (last[o.in] == k) put(o.in);
-        if (o.res >= 0 && o.res != o.in && last[o.res] == k) put(o.res);
-    }
-    if (spare) b.take(spare);
-    size_t stats = 0;
-    size_t cascr = 0;
-    for (const RdOp& o : P.ops) {
-        if (o.type == 1) stats = std::max(stats, (size_t)P.B * o.ngrp * 2 * sizeof(float));
-        if (o.type == 7) {          // the attention ops' saved {p, h, s}: nothing reads them after the op either
-            stats = std::max(stats, (size_t)P.B * (2 * P.T[o.in].C + o.ngrp) * sizeof(float));
-            cascr = std::max(cascr, srcgan_ca_scratch_floats(P.B, (long)P.T[o.in].H * P.T[o.in].W, P.T[o.in].C));
-        }
-    }
-    const size_t stats_off = b.take(stats);
-    for (RdOp& o : P.ops) if (o.type == 1 || o.type == 7) o.stats = stats_off;
-    P.gnfwd = b.take(std::max(srcgan_gn_scratch_floats(P.B, P.maxC > 1024 ? 1024 : P.maxC), cascr) * sizeof(float));
-    P.act_bytes = b.off;
-    P.wpk = b.off;
-    Bump wb;
-    auto pk = [&](int rows, int k, int taps) { return wb.take(srcgan_packed_weight_bytes(rows, k, taps, P.dtype)); };
-    for (RdOp& o : P.ops) {
-        const RdT ti = P.T[o.in], to = P.T[o.out];
-        if (o.share) memcpy(o.wf, P.ops[o.share - 1].wf, sizeof(o.wf));
-        else if (o.type == 0) o.wf[0] = pk(rd_cout(o, to), rd_cin(o, ti), o.k * o.k);
-        else if (o.type == 2) { for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.C, ti.C, 1); }
-        else if (o.type == 4) { for (int q = 0; q < 4; ++q) o.wf[q] = pk(to.cs, ti.C, 4); }
-        else if (o.type == 5) {
-            const size_t step = srcgan_packed_weight_bytes(to.C, ti.C, 4, P.dtype), w0 = wb.take(4 * step);
-            for (int q = 0; q < 4; ++q) o.wf[q] = w0 + q * step;
-        }
-        if (o.type == 0 && o.proj && !o.share) o.wst = wb.take((size_t)rd_cout(o, to) * rd_cin(o, ti) * o.k * o.k * sizeof(float));
-    }
-    P.wpack = wb.off;
-    P.total = align_up(P.wpk + wb.off + 256, 256);
-    return 0;
-}
-static int rd_infer_plan(const srcgan_resdeconv_cfg* c, int fold, RdPlan& P) {
-    SG_TRY(rd_plan(c, P));
-    SG_REQUIRE(fold == 0 || fold == 1, "resdeconv: fold_tail must be 0 or 1");
-    return rd_infer_replan(P, fold != 0, "resdeconv");
-}
-static int sr_infer_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
-    SG_TRY(sr_plan(c, P));
-    // EDSR with ONE residual block: its input is input_conv's output, which the global skip keeps alive anyway, so it needs one
-    // feature slot fewer than every deeper stack (4).  It gets the fourth as a spare: the activation part is then a function of
-    // the shapes alone, and a caller can size one workspace for a family of depths.
-    const size_t spare = (c->kind == 2 && c->nres == 1) ? (size_t)c->B * c->H * c->W * c->base * P.esz : 0;
-    return rd_infer_replan(P, false, "srnet", spare);
-}
-static int sd_infer_plan(const srcgan_srdense_cfg* c, RdPlan& P) {
-    SG_TRY(sd_plan(c, P));
-    return rd_infer_replan(P, false, "srdense");
-}
-static int rcan_infer_plan(const srcgan_rcan_cfg* c, RdPlan& P) {
-    SG_TRY(rcan_plan(c, P));
-    return rd_infer_replan(P, false, "srcgan_rcan");
-}
-static int ddbpn_infer_plan(const srcgan_ddbpn_cfg* c, RdPlan& P) {
-    SG_TRY(ddbpn_plan(c, P));
-    return rd_infer_replan(P, false, "srcgan_ddbpn");
-}
-// per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
-static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
-    const int n = (int)P.ops.size();
-    for (int k = 0; k < n && k < cap && ranges; ++k) {
-        const RdOp& o = P.ops[k];
-        size_t* r = ranges + 6 * k;
-        r[0] = P.T[o.in].off; r[1] = rd_bytes(P, P.T[o.in]);
-        r[2] = o.res >= 0 ? P.T[o.res].off : 0; r[3] = o.res >= 0 ? rd_bytes(P, P.T[o.res]) : 0;
-        r[4] = P.T[o.out].off; r[5] = rd_bytes(P, P.T[o.out]);
-    }
-    return n;
-}
-
-// A loss that sits behind the walk and reads the plan's taps (P.taps[k]) against a second branch's: the backward starts from it instead of
-// from dy_nchw.  Tap k adds scale[k] * d|a - b| (kind 0) or scale[k] * d(a - b)^2 (kind 1) to its tensor's gradient; the input gradient
-// leaves times gout[0] * gscale on the frames fr of the 5-D tensor dx_nchw (rd_walk).
-struct RdTapLoss { int kind; const RdPlan* Pb; float scale[4]; const float* gout; float gscale; SgFrames fr; };
-
-static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, const float* const* params, void* ws, void* scratch, float* const* grads,
-                       const char* tag, void* st, const RdTapLoss* tl = nullptr) {
-    SG_REQUIRE((dy_nchw || tl) && params && ws && scratch && grads, "%s backward: null pointer", tag);
-    SG_REQUIRE(((uintptr_t)ws % 256) == 0 && ((uintptr_t)scratch % 256) == 0, "%s backward: buffers must be 256-byte aligned", tag);
-    const int dt = P.dtype, B = P.B;
-    char* w8 = (char*)ws; char* s8 = (char*)scratch; char* wp = w8 + P.wpk;
-    float* slab = (float*)(s8 + P.slab); float* gnscr = (float*)(s8 + P.gnscr); float* colscr = (float*)(s8 + P.colscr);
-    auto G = [&](int idx) { return idx >= 0 ? grads[idx] : nullptr; };
-    {   // dgrad weight packs
-        PackList packs(dt, wp);
-        for (const RdOp& o : P.ops) {
-            const RdT ti = P.T[o.in], to = P.T[o.out];
-            const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
-            if (o.share) continue;
-            if (o.type == 0 && (o.in != 0 || dx_nchw)) {
-                if (o.proj) packs.add((const float*)(wp + o.wst), wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));     // staged by the forward
-                else if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));
-                else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, 1, 1, 1, (long)cin, 0, 0, 0);
-                else o.s2(cin, cout).pack(packs, params[o.w], wp, o.wd);
-            } else if (o.type == 2) {
-                packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 2, 2, (long)to.C * 4, 4, 2, 1, 0);
-            } else if (o.type == 5) {       // the input gradient is a 3x3 s2 p1 convolution of dy: rows = ci, k = co, taps as stored
-                packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 3, 3, lay_fwd(to.C, 3, 3));
-            }
-        }
-        char key[64]; snprintf(key, sizeof(key), "%s_bwd", tag);
-        SG_TRY(packs.run(key, params[0], st));
-    }
-    std::vector<char> written(P.T.size(), 0), seen_param(P.nparams + 2, 0);
-    auto gt = [&](int id) { return tref(s8 + P.g[id], P.T[id].cs); };
-    if (!tl) {
-        const RdT& last = P.T.back();
-        const int id = (int)P.T.size() - 1;
-        SG_TRY(srcgan_nchw_f32_to_nhwc(dy_nchw, s8 + P.g[id], B, P.out_ch, last.H, last.W, last.cs, dt, st));
-        if (last.act) SG_TRY(srcgan_mask_inplace(s8 + P.g[id], w8 + last.off, 0.f, (long)B * last.H * last.W * last.cs, dt, st));
-        written[id] = 1;
-    }
-    for (int k = (int)P.ops.size() - 1; k >= 0; --k) {
-        const RdOp& o = P.ops[k];
-        const RdT ti = P.T[o.in], to = P.T[o.out];
-        auto tap_of = [&](int t) { if (tl) for (size_t i = 0; i < P.taps.size(); ++i) if (P.taps[i] == t) return (int)i; return -1; };
-        if (const int tk = tap_of(o.out); tk >= 0) {       // (a frozen chain: one op per tensor, so this runs once per tap)
-            const RdT tb = tl->Pb->T[o.out];
-            SG_TRY(srcgan_feat_loss_bwd(tl->kind, w8 + to.off, to.cs, w8 + tb.off, tb.cs, s8 + P.g[o.out], to.cs, written[o.out], tl->scale[tk],
-                                        (long)B * to.H * to.W, to.C, dt, st));
-            // the stored gradient of an activated tensor is the one w.r.t. its pre-activation (a pool behind a tap leaves the mask to this pass)
-            if (to.act) SG_TRY(srcgan_mask_inplace(s8 + P.g[o.out], w8 + to.off, 0.f, (long)B * to.H * to.W * to.cs, dt, st));
-            written[o.out] = 1;
-        }
-        SG_REQUIRE(written[o.out], "%s backward: internal error (gradient of tensor %d missing)", tag, o.out);
-        const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
-        TRef xin = sl(rd_t(w8, ti), o.icoff), dy = sl(gt(o.out), o.ocoff);
-        const bool need_dx = o.in != 0 || dx_nchw;
-        TRef dx = need_dx ? sl(gt(o.in), o.icoff) : TNULL;
-        bool acc = need_dx && written[o.in];
-        // a module applied twice (SRDenseNet's shared up- / down-sampler): the later use's parameter gradients add to the earlier one's
-        const int pacc0 = (o.type == 0 || o.type == 5) ? seen_param[o.w] : 0;
-        auto bias_sum = [&](TRef g, long npix, int C, float* out) -> int {
-            if (!pacc0) return bias_grad(dt, g, npix, C, 1.f, out, colscr, st);
-            float* tmp = (float*)(s8 + P.btmp);
-            SG_TRY(bias_grad(dt, g, npix, C, 1.f, tmp, colscr, st));
-            return srcgan_add_inplace(out, C, 0, tmp, C, 0, nullptr, 0, 0, 0.f, 1, C, SRCGAN_F32, st);
-        };
-        if (o.type == 0) {
-            if (o.res >= 0) {       // y = conv(x) + res: the residual's gradient is dy itself
-                const RdT tr = P.T[o.res];
-                TRef dr = gt(o.res);
-                if (!written[o.res]) SG_HIP(hipMemcpyAsync(dr.p, dy.p, (size_t)B * tr.H * tr.W * tr.cs * P.esz, hipMemcpyDeviceToDevice, (hipStream_t)st));
-                else SG_TRY(srcgan_add_inplace(dr.p, tr.cs, 0, dy.p, to.cs, 0, nullptr, 0, 0, 0.f, (long)B * tr.H * tr.W, tr.C, dt, st));
-                written[o.res] = 1;
-                acc = need_dx && written[o.in];
-            }
-            const bool fused_bias = o.bias >= 0 && o.k == 3 && G(o.w);
-            if (G(o.w)) {       // a projection: the gradient of the stride-1 form, then back into the stored layout
-                float* gw = o.proj ? (float*)(s8 + P.projscr) : G(o.w);
-                SG_TRY(wgrad_call(dt, dy, to.H, to.W, cout, xin, B, ti.H, ti.W, cin, o.k, o.k, o.s, o.pad, o.pad, lay_fwd(cin, o.k, o.k), 1.f, slab, gw, st,
-                                  fused_bias ? G(o.bias) : nullptr, pacc0));
-                if (o.proj)
-                    SG_TRY(sg_proj_repack(gw, G(o.w), o.proj - 1, o.proj == 1 ? cout : cout / (o.ps * o.ps), o.proj == 1 ? cin / (o.ps * o.ps) : cin, o.pk, o.ps, 1,
-                                          (hipStream_t)st));
-            }
-            if (o.bias >= 0 && G(o.bias) && !fused_bias) SG_TRY(bias_sum(dy, (long)B * to.H * to.W, cout, G(o.bias)));
-            seen_param[o.w] = 1;
-            if (need_dx) {
-                // (a slice of a dense buffer has several consumers: every contribution is masked by the same ReLU', and the mask of a sum
-                //  that already holds masked terms leaves them as they are)
-                SG_REQUIRE(!(acc && ti.act) || o.iC, "%s backward: internal error (activated tensor with two consumers)", tag);
-                if ((o.in == 0 || ti.C < ti.cs) && !acc) SG_HIP(hipMemsetAsync(dx.p, 0, (size_t)B * ti.H * ti.W * ti.cs * P.esz, (hipStream_t)st));    // padded image channels
-                if (o.s == 1) {
-                    Conv cv(dt, o.k, o.k, 1);
-                    cv.in(dy, B, to.H, to.W, to.C < 8 ? to.cs : cout).w(wp + o.wd[0]).out(dx, ti.H, ti.W, cin).pad(o.k - 1 - o.pad, o.k - 1 - o.pad);
-                    if (acc) cv.res1(dx, cin, 1.f);
-                    if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
-                    SG_TRY(cv.run(st));
-                } else if (o.k == 1) {
-                    if (!acc) SG_HIP(hipMemsetAsync(dx.p, 0, (size_t)B * ti.H * ti.W * ti.cs * P.esz, (hipStream_t)st));
-                    Conv cv(dt, 1, 1, 1);
-                    cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, to.H, to.W, ti.C).pad(0, 0).scatter(2, 0, 0, ti.H, ti.W);
-                    if (acc) cv.res1(dx, ti.C, 1.f);
-                    SG_TRY(cv.run(st));
-                } else
-                    SG_TRY(o.s2(ti.C, to.C).run(dt, dy, B, to.H, to.W, dx, ti.H, ti.W, wp, o.wd, acc ? dx : TNULL, ti.act ? xin : TNULL, false, st, 0.f));
-                written[o.in] = 1;
-            }
-        } else if (o.type == 1) {
-            void* dres = nullptr; int dres_cs = 0, dres_acc = 0;
-            if (o.res >= 0) {       // first contribution to the shortcut's source: plain store, later ones add
-                dres = s8 + P.g[o.res]; dres_cs = P.T[o.res].cs; dres_acc = written[o.res]; written[o.res] = 1;
-            }
-            SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (GroupNorm input has two consumers or a fused activation)", tag);
-            const int pacc = o.w >= 0 ? seen_param[o.w] : 0;       // a GroupNorm module applied more than once (edsr.py:41,47,49): gradients add
-            if (o.w >= 0) seen_param[o.w] = 1;
-            SG_TRY(srcgan_gn_backward(dy.p, to.cs, o.relu ? (w8 + to.off) : nullptr, to.cs, xin.p, ti.cs, o.w >= 0 ? params[o.w] : nullptr,
-                                      (const float*)(w8 + o.stats), dx.p, ti.cs, dres, dres_cs, dres_acc, o.w >= 0 ? G(o.w) : nullptr,
-                                      o.w >= 0 ? G(o.w + 1) : nullptr, pacc, o.slope, B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
-            written[o.in] = 1;
-        } else if (o.type == 2) {
-            if (G(o.w))     // dW[ci][co][a][b] = sum x[y,x,ci] * dy[2y+a,2x+b,co]: wgrad with roles (dy := x, x := dy), k2 s2
-                SG_TRY(wgrad_call(dt, xin, ti.H, ti.W, ti.C, dy, B, to.H, to.W, to.C, 2, 2, 2, 0, 0, WLayout{(long)to.C * 4, 4, 2, 1, 0}, 1.f, slab, G(o.w), st));
-            SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (deconvolution input)", tag);
-            SG_TRY(Conv(dt, 2, 2, 2).in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(0, 0).run(st));
-            written[o.in] = 1;
-        } else if (o.type == 5) {
-            // dW[ci][co][ky][kx] = sum x[i][j][ci] * dy[2i + ky - 1][2j + kx - 1][co]: the stride-2 wgrad with the roles of x and dy exchanged
-            if (G(o.w))
-                SG_TRY(wgrad_call(dt, xin, ti.H, ti.W, ti.C, dy, B, to.H, to.W, to.C, 3, 3, 2, 1, 1, lay_fwd(to.C, 3, 3), 1.f, slab, G(o.w), st, nullptr, pacc0));
-            if (G(o.bias)) SG_TRY(bias_sum(dy, (long)B * to.H * to.W, to.C, G(o.bias)));
-            seen_param[o.w] = 1;
-            SG_REQUIRE(!acc, "%s backward: internal error (transposed convolution input with two consumers)", tag);
-            // dx[i][j][ci] = sum dy[2i + ky - 1][2j + kx - 1][co] * W[ci][co][ky][kx]: the forward 3x3 stride-2 pad-1 convolution
-            Conv cv(dt, 3, 3, 2);
-            cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(1, 1);
-            if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
-            SG_TRY(cv.run(st));
-            written[o.in] = 1;
-        } else if (o.type == 7) {
-            void* dres = nullptr; int dres_cs = 0, dres_acc = 0;
-            if (o.res >= 0) {       // the block's input: this op stores (or adds to the group convolution's copy), the block's first convolution adds
-                dres = s8 + P.g[o.res]; dres_cs = P.T[o.res].cs; dres_acc = written[o.res]; written[o.res] = 1;
-            }
-            SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (attention input has two consumers or a fused activation)", tag);
-            SG_TRY(srcgan_ca_backward(dy.p, to.cs, xin.p, ti.cs, params[o.w], params[o.w + 2], (const float*)(w8 + o.stats), dx.p, ti.cs, dres, dres_cs,
-                                      dres_acc, G(o.w), G(o.w + 1), G(o.w + 2), G(o.w + 3), B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
-            written[o.in] = 1;
-        } else if (o.type == 8) {
-            SG_REQUIRE(!G(o.w) && !G(o.bias), "%s backward: MeanShift is frozen (its gradient pointers must be null)", tag);
-            SG_REQUIRE(!acc, "%s backward: internal error (MeanShift input with two consumers)", tag);
-            if (need_dx) {
-                SG_TRY(sg_meanshift(dy.p, dx.p, params[o.w], nullptr, 1, (long)B * ti.H * ti.W, dt, (hipStream_t)st));
-                written[o.in] = 1;
-            }
-        } else if (o.type == 9) {       // the gather's adjoint is the crop; a second consumer's contribution is added
-            SG_TRY(srcgan_d2s_shift(dy.p, to.cs, dx.p, ti.cs, B, ti.H, ti.W, o.iC, o.k, o.pad, to.H, to.W, acc, dt, st));
-            written[o.in] = 1;
-        } else if (o.type == 10) {
-            void* dres = nullptr; int dres_cs = 0, dres_acc = 0;
-            if (o.res >= 0) { dres = s8 + P.g[o.res] + (size_t)o.rcoff * P.esz; dres_cs = P.T[o.res].cs; dres_acc = written[o.res]; written[o.res] = 1; }
-            SG_REQUIRE(!acc && !ti.act && o.in != o.res, "%s backward: internal error (PReLU input with two consumers or a fused activation)", tag);
-            SG_TRY(srcgan_prelu_backward((char*)dy.p + (size_t)dy.coff * P.esz, to.cs, xin.p, ti.cs, params[o.w], o.bias >= 0 ? params[o.bias] : nullptr, dx.p, ti.cs,
-                                         dres, dres_cs, o.slope, dres_acc, G(o.w), G(o.bias), B, to.H, to.W, o.oC, o.k, o.pad, ti.H, ti.W, dt,
-                                         (float*)(s8 + P.prscr), st));
-            written[o.in] = 1;
-        } else if (o.type == 6) {
-            SG_REQUIRE(!acc, "%s backward: internal error (pooled tensor with two consumers)", tag);
-            SG_TRY(srcgan_maxpool2_bwd_nhwc(dy.p, to.cs, xin.p, ti.cs, dx.p, ti.cs, B, ti.H, ti.W, ti.C, ti.act && tap_of(o.in) < 0, dt, st));
-            written[o.in] = 1;
-        } else {
-            SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (PixelShuffle input)", tag);
-            SG_TRY(srcgan_pixel_shuffle_nhwc(dy.p, to.cs, dx.p, ti.cs, B, ti.H, ti.W, to.C, o.k, 1, dt, st));
-            written[o.in] = 1;
-        }
-    }
-    if (dx_nchw) {       // gradient w.r.t. the network input (an end-to-end cascade: trainCas.py:108 feeds one network's output to the next)
-        SG_REQUIRE(written[0], "%s backward: internal error (no input gradient was produced)", tag);
-        if (tl) return sg_frames_grad_store(s8 + P.g[0], P.in_cs, dx_nchw, B / tl->fr.k, tl->fr, P.H, P.W, tl->gout, tl->gscale, dt, (hipStream_t)st);
-        SG_TRY(srcgan_nhwc_to_nchw_f32(s8 + P.g[0], dx_nchw, B, P.in_ch, P.H, P.W, P.in_cs, 0, dt, st));
-    }
-    return 0;
-}
-}  // namespace
-
-extern "C" int srcgan_resdeconv_num_params(const srcgan_resdeconv_cfg* c) { RdPlan P; if (rd_plan(c, P)) return -1; return P.nparams; }
-extern "C" size_t srcgan_resdeconv_ws_bytes(const srcgan_resdeconv_cfg* c) { RdPlan P; if (rd_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_resdeconv_bwd_scratch_bytes(const srcgan_resdeconv_cfg* c) { RdPlan P; if (rd_plan(c, P)) return 0; return P.bwd_total; }
-extern "C" int srcgan_resdeconv_forward(const srcgan_resdeconv_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(rd_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, "resdeconv", st);
-}
-extern "C" int srcgan_resdeconv_backward(const srcgan_resdeconv_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
-                                         float* const* grads, float* dx_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(rd_plan(c, P));
-    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, "resdeconv", st);
-}
-
-extern "C" int srcgan_srnet_num_params(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_plan(c, P)) return -1; return P.nparams; }
-extern "C" size_t srcgan_srnet_ws_bytes(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_srnet_bwd_scratch_bytes(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_plan(c, P)) return 0; return P.bwd_total; }
-extern "C" int srcgan_srnet_forward(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(sr_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, sr_tag(c->kind), st);
-}
-extern "C" int srcgan_srnet_backward(const srcgan_srnet_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
-                                     float* const* grads, float* dx_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(sr_plan(c, P));
-    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, sr_tag(c->kind), st);
-}
-
-// Inference forwards of the op-list networks: rd_forward on the liveness-planned workspace (same launches, same arguments apart from
-// buffer addresses -> the same bits), and for ResDeconv optionally the folded tail.  The job tables are cached under tags of their
-// own: the packs sit at other offsets than the training forward's (no dgrad packs between them).
-extern "C" size_t srcgan_resdeconv_infer_ws_bytes(const srcgan_resdeconv_cfg* c, int fold_tail) { RdPlan P; if (rd_infer_plan(c, fold_tail, P)) return 0; return P.total; }
-extern "C" size_t srcgan_resdeconv_infer_act_bytes(const srcgan_resdeconv_cfg* c, int fold_tail) { RdPlan P; if (rd_infer_plan(c, fold_tail, P)) return 0; return P.total - P.wpack; }
-extern "C" int srcgan_resdeconv_infer_plan(const srcgan_resdeconv_cfg* c, int fold_tail, size_t* ranges, int cap) {
-    RdPlan P;
-    if (rd_infer_plan(c, fold_tail, P)) return -1;
-    return rd_plan_ranges(P, ranges, cap);
-}
-extern "C" int srcgan_resdeconv_infer(const srcgan_resdeconv_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw,
-                                      int fold_tail, void* st) {
-    RdPlan P;
-    SG_TRY(rd_infer_plan(c, fold_tail, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, fold_tail ? "resdeconv_fold" : "resdeconv_infer", st);
-}
-extern "C" size_t srcgan_srnet_infer_ws_bytes(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_infer_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_srnet_infer_act_bytes(const srcgan_srnet_cfg* c) { RdPlan P; if (sr_infer_plan(c, P)) return 0; return P.total - P.wpack; }
-extern "C" int srcgan_srnet_infer_plan(const srcgan_srnet_cfg* c, size_t* ranges, int cap) {
-    RdPlan P;
-    if (sr_infer_plan(c, P)) return -1;
-    return rd_plan_ranges(P, ranges, cap);
-}
-extern "C" int srcgan_srnet_infer(const srcgan_srnet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(sr_infer_plan(c, P));
-    char tag[32]; snprintf(tag, sizeof(tag), "%s_infer", sr_tag(c->kind));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, tag, st);
-}
-
-// SRDenseNetA / SRDenseNetB on the op-list executor (sd_plan); the inference entry runs the same launches on the slot-planned workspace.
-extern "C" int srcgan_srdense_num_params(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_plan(c, P)) return -1; return P.nparams; }
-extern "C" size_t srcgan_srdense_ws_bytes(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_srdense_bwd_scratch_bytes(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_plan(c, P)) return 0; return P.bwd_total; }
-extern "C" int srcgan_srdense_out_hw(const srcgan_srdense_cfg* c, int* oh, int* ow) {
-    RdPlan P;
-    SG_TRY(sd_plan(c, P));
-    SG_REQUIRE(oh && ow, "srcgan_srdense_out_hw: null pointer");
-    *oh = P.T.back().H; *ow = P.T.back().W;
-    return 0;
-}
-extern "C" int srcgan_srdense_forward(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(sd_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind ? "srdenseB" : "srdenseA", st);
-}
-extern "C" int srcgan_srdense_backward(const srcgan_srdense_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
-                                       float* const* grads, float* dx_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(sd_plan(c, P));
-    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, c->kind ? "srdenseB" : "srdenseA", st);
-}
-extern "C" size_t srcgan_srdense_infer_ws_bytes(const srcgan_srdense_cfg* c) { RdPlan P; if (sd_infer_plan(c, P)) return 0; return P.total; }
-extern "C" int srcgan_srdense_infer(const srcgan_srdense_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(sd_infer_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, c->kind ? "srdenseB_infer" : "srdenseA_infer", st);
-}
-
-// RCAN on the op-list executor (rcan_plan); the inference entries run the same launches on the slot-planned workspace.
-extern "C" int srcgan_rcan_num_params(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_plan(c, P)) return -1; return P.nparams; }
-extern "C" size_t srcgan_rcan_ws_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_rcan_bwd_scratch_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_plan(c, P)) return 0; return P.bwd_total; }
-extern "C" int srcgan_rcan_forward(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(rcan_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, "rcan", st);
-}
-extern "C" int srcgan_rcan_backward(const srcgan_rcan_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
-                                    float* const* grads, float* dx_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(rcan_plan(c, P));
-    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, "rcan", st);
-}
-extern "C" size_t srcgan_rcan_infer_ws_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_infer_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_rcan_infer_act_bytes(const srcgan_rcan_cfg* c) { RdPlan P; if (rcan_infer_plan(c, P)) return 0; return P.total - P.wpack; }
-extern "C" int srcgan_rcan_infer_plan(const srcgan_rcan_cfg* c, size_t* ranges, int cap) {
-    RdPlan P;
-    if (rcan_infer_plan(c, P)) return -1;
-    return rd_plan_ranges(P, ranges, cap);
-}
-extern "C" int srcgan_rcan_infer(const srcgan_rcan_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(rcan_infer_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, "rcan_infer", st);
-}
-
-// DDBPN on the op-list executor (ddbpn_plan); the inference entries run the same launches on the slot-planned workspace.
-extern "C" int srcgan_ddbpn_num_params(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_plan(c, P)) return -1; return P.nparams; }
-extern "C" size_t srcgan_ddbpn_ws_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_ddbpn_bwd_scratch_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_plan(c, P)) return 0; return P.bwd_total; }
-extern "C" int srcgan_ddbpn_forward(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(ddbpn_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, "ddbpn", st);
-}
-extern "C" int srcgan_ddbpn_backward(const srcgan_ddbpn_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
-                                     float* const* grads, float* dx_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(ddbpn_plan(c, P));
-    return rd_backward(P, dy_nchw, dx_nchw, params, ws, scratch, grads, "ddbpn", st);
-}
-extern "C" size_t srcgan_ddbpn_infer_ws_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_infer_plan(c, P)) return 0; return P.total; }
-extern "C" size_t srcgan_ddbpn_infer_act_bytes(const srcgan_ddbpn_cfg* c) { RdPlan P; if (ddbpn_infer_plan(c, P)) return 0; return P.total - P.wpack; }
-extern "C" int srcgan_ddbpn_infer_plan(const srcgan_ddbpn_cfg* c, size_t* ranges, int cap) {
-    RdPlan P;
-    if (ddbpn_infer_plan(c, P)) return -1;
-    return rd_plan_ranges(P, ranges, cap);
-}
-extern "C" int srcgan_ddbpn_infer(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* st) {
-    RdPlan P;
-    SG_TRY(ddbpn_infer_plan(c, P));
-    return rd_forward(P, x_nchw, params, ws, y_nchw, "ddbpn_infer", st);
-}
-
-// ======================================================================================== frozen VGG feature losses
-// losses.VGG16Loss (reference src/losses.py:344-393) and losses.PerceptionLoss (:455-470): torchvision's VGG16 / VGG19 `features` prefix as an
-// op list of 3x3 convolutions (+ bias + ReLU) and max-pools, walked twice with one set of packs -- on the network's output, whose
-// activations stay for the backward, and on the target, on a slot-planned region that keeps only the taps -- and one feature-distance
-// reduction per tap.  Frozen: the backward launches input gradients only, on two alternating gradient buffers, at unit scale (see
-// include/srcgan_amd.h).
-namespace {
-struct VggPlan {
-    RdPlan P, Pt;             // output branch (every activation kept) / target branch (slot-planned, offsets inside the same workspace)
-    int kind, ntap;
-    size_t sums, lscr, total;
-    float wsum[4];            // loss = sum_k wsum[k] * sum|a_k - b_k|  (1 / (ntaps N_k))
-    float gscale[4], gfinal;  // tap k's gradient factor inside the backward (N_1 / N_k), and the one of the final store (1 / (ntaps N_1))
-};
-
-// move a slot-planned plan's activation part to `base` of a workspace whose packs are another plan's
-static void vgg_rebase(RdPlan& Q, size_t base, const RdPlan& packs) {
-    for (RdT& t : Q.T) t.off += base;
-    Q.xin += base; Q.gnfwd += base;
-    for (size_t k = 0; k < Q.ops.size(); ++k) memcpy(Q.ops[k].wf, packs.ops[k].wf, sizeof(Q.ops[k].wf));
-    Q.wpk = packs.wpk;
-}
-
-static int vgg_plan(const srcgan_vggloss_cfg* c, bool infer, VggPlan& V) {
-    SG_REQUIRE(c, "vggloss: null cfg");
-    RdPlan& P = V.P;
-    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "vggloss"));
-    SG_REQUIRE(c->kind == 0 || c->kind == 1, "vggloss: kind must be 0 (VGG16Loss) or 1 (PerceptionLoss)");
-    const int minhw = c->kind == 0 ? 8 : 16;
-    SG_REQUIRE(c->H >= minhw && c->W >= minhw, "vggloss: H and W must be at least %d (%d max-pools)", minhw, c->kind == 0 ? 3 : 4);
-    V.kind = c->kind;
-    RdBuilder nb(P, c->B);
-    nb.frozen = 1;
-    nb.input(3, c->H, c->W);
-    int t = 0;
-    if (c->kind == 0) {       // vgg16.features[0:23]; taps behind indices 3, 8, 15, 22 (losses.py:354-361, 381-393)
-        const int width[4] = {64, 128, 256, 512}, nconv[4] = {2, 2, 3, 3};
-        for (int s = 0; s < 4; ++s) {
-            if (s) t = nb.pool(t);
-            for (int k = 0; k < nconv[s]; ++k) t = nb.conv(t, width[s], 3, 1, 1, true, true);
-            nb.tap(t);
-        }
-    } else {                  // vgg19.features[0:35]: conv5_4 without its ReLU (losses.py:459-468)
-        const int width[5] = {64, 128, 256, 512, 512}, nconv[5] = {2, 2, 4, 4, 4};
-        for (int s = 0; s < 5; ++s) {
-            if (s) t = nb.pool(t);
-            for (int k = 0; k < nconv[s]; ++k) t = nb.conv(t, width[s], 3, 1, 1, true, !(s == 4 && k == 3));
-        }
-        nb.tap(t);
-    }
-    nb.finish(c->dtype);
-    V.ntap = (int)P.taps.size();
-    const RdT t1 = P.T[P.taps[0]];
-    const double n1 = (double)c->B * t1.C * t1.H * t1.W;
-    for (int k = 0; k < V.ntap; ++k) {
-        const RdT tk = P.T[P.taps[k]];
-        const double nk = (double)c->B * tk.C * tk.H * tk.W;
-        V.wsum[k] = (float)(1.0 / (V.ntap * nk));
-        V.gscale[k] = (float)(n1 / nk);
-    }
-    V.gfinal = (float)(1.0 / (V.ntap * n1));
-    const size_t packs = P.total - P.wpk;
-    V.Pt = P;
-    SG_TRY(rd_infer_replan(V.Pt, false, "vggloss"));
-    const size_t slot_bytes = V.Pt.act_bytes;
-    if (infer) {              // both branches on slot-planned regions, the packs laid out by the replan (forward packs only)
-        const size_t ipacks = V.Pt.total - V.Pt.wpk;
-        P = V.Pt;
-        Bump b;
-        b.take(slot_bytes);
-        const size_t tgt = b.take(slot_bytes);
-        V.sums = b.take(4 * sizeof(float));
-        V.lscr = b.take((size_t)srcgan_loss_scratch_floats() * sizeof(float));
-        P.wpk = b.off;
-        vgg_rebase(V.Pt, tgt, P);
-        V.total = align_up(b.off + ipacks, 256);
-        return 0;
-    }
-    Bump b;
-    b.take(P.act_bytes);
-    const size_t tgt = b.take(slot_bytes);
-    V.sums = b.take(4 * sizeof(float));
-    V.lscr = b.take((size_t)srcgan_loss_scratch_floats() * sizeof(float));
-    P.wpk = b.off;
-    vgg_rebase(V.Pt, tgt, P);
-    V.total = align_up(b.off + packs, 256);
-    return 0;
-}
-
-static int vgg_forward(const VggPlan& V, const float* out5d, const float* tgt5d, const float* const* params, void* ws, float* loss_out,
-                       const char* tag, void* st, const SgFrames& fr) {
-    SG_REQUIRE(out5d && tgt5d && params && ws && loss_out, "%s: null pointer", tag);
-    SG_REQUIRE(((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", tag);
-    const RdPlan& P = V.P;
-    char* w8 = (char*)ws;
-    SG_TRY(rd_pack_fwd(P, params, ws, tag, st));
-    SG_TRY(rd_walk(P, out5d, params, ws, st, &fr));
-    SG_TRY(rd_walk(V.Pt, tgt5d, params, ws, st, &fr));
-    float* sums = (float*)(w8 + V.sums);
-    for (int k = 0; k < V.ntap; ++k) {
-        const RdT a = P.T[P.taps[k]], b = V.Pt.T[P.taps[k]];
-        SG_TRY(srcgan_feat_loss_fwd(V.kind, w8 + a.off, a.cs, w8 + b.off, b.cs, (long)P.B * a.H * a.W, a.C, P.dtype, sums + k, (float*)(w8 + V.lscr), st));
-    }
-    return sg_vgg_combine(sums, V.wsum, V.ntap, loss_out, (hipStream_t)st);
-}
-
-static int vgg_backward(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, const float* const* params, void* ws, void* scratch,
-                        float* dout, void* st, const SgFrames& fr) {
-    VggPlan V;
-    SG_TRY(vgg_plan(c, false, V));
-    SG_REQUIRE(gout_dev && dout, "vggloss backward: null pointer");
-    RdTapLoss tl;
-    tl.kind = V.kind; tl.Pb = &V.Pt; tl.gout = gout_dev; tl.gscale = gscale * V.gfinal; tl.fr = fr;
-    for (int k = 0; k < 4; ++k) tl.scale[k] = k < V.ntap ? V.gscale[k] : 0.f;
-    std::vector<float*> nograds(V.P.nparams, nullptr);       // frozen: every parameter gradient is skipped
-    return rd_backward(V.P, nullptr, dout, params, ws, scratch, nograds.data(), c->kind ? "vgg19loss" : "vgg16loss", st, &tl);
-}
-
-// the frames [f0, f0 + k) of a [Bt, C_in, F, H, W] tensor as the c->B = Bt * k images of a call
-static int vgg_frames(const srcgan_vggloss_cfg* c, int C_in, int F, int f0, int k, SgFrames& fr) {
-    SG_REQUIRE(c, "vggloss frames: null cfg");
-    SG_REQUIRE(C_in == 1 || C_in == 3, "vggloss frames: C_in must be 1 or 3, got %d", C_in);
-    SG_REQUIRE(F > 0 && k > 0 && f0 >= 0 && f0 <= F - k, "vggloss frames: frames [%d, %d + %d) leave the %d frames of the tensor", f0, f0, k, F);
-    SG_REQUIRE(c->B > 0 && c->B % k == 0, "vggloss frames: cfg.B = %d is not a multiple of the %d frames of the call", c->B, k);
-    fr.Cin = C_in; fr.F = F; fr.f0 = f0; fr.k = k;
-    return 0;
-}
-}  // namespace
-
-extern "C" int srcgan_vggloss_num_params(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return -1; return V.P.nparams; }
-extern "C" size_t srcgan_vggloss_ws_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return 0; return V.total; }
-extern "C" size_t srcgan_vggloss_infer_ws_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, true, V)) return 0; return V.total; }
-extern "C" size_t srcgan_vggloss_bwd_scratch_bytes(const srcgan_vggloss_cfg* c) { VggPlan V; if (vgg_plan(c, false, V)) return 0; return V.P.bwd_total; }
-extern "C" int srcgan_vggloss_forward_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
-                                             const float* const* params, void* ws, float* loss_out, void* st) {
-    SgFrames fr; VggPlan V;
-    SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
-    SG_TRY(vgg_plan(c, false, V));
-    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss" : "vgg16loss", st, fr);
-}
-extern "C" int srcgan_vggloss_infer_frames(const srcgan_vggloss_cfg* c, const float* out5d, const float* tgt5d, int C_in, int F, int f0, int k,
-                                           const float* const* params, void* ws, float* loss_out, void* st) {
-    SgFrames fr; VggPlan V;
-    SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
-    SG_TRY(vgg_plan(c, true, V));
-    return vgg_forward(V, out5d, tgt5d, params, ws, loss_out, c->kind ? "vgg19loss_infer" : "vgg16loss_infer", st, fr);
-}
-extern "C" int srcgan_vggloss_backward_frames(const srcgan_vggloss_cfg* c, const float* gout_dev, float gscale, int C_in, int F, int f0, int k,
-                                              const float* const* params, void* ws, void* scratch, float* dout5d, void* st) {
-    SgFrames fr;
-    SG_TRY(vgg_frames(c, C_in, F, f0, k, fr));
-    return vgg_backward(c, gout_dev, gscale, params, ws, scratch, dout5d, st, fr);
 }

@@ -13,7 +13,7 @@ elementwise.hip) returning a 0-dim device tensor; backward is one fused elementw
 (sign(a-b)/N or 2(a-b)/N times the upstream gradient read from device memory -> no host sync).
 DSSIMLoss reuses the SSIM metric's range and tile kernels plus one fold for its forward; its backward is one fused
 stencil pass (metrics.hip, dssim_bwd_k) that recomputes the window statistics per output tile.
-The perceptual losses run a frozen VGG feature extractor on the op-list executor (nets.hip, srcgan_vggloss_*): one native forward
+The perceptual losses run a frozen VGG feature extractor on the op-list executor (oplist.hip, srcgan_vggloss_*): one native forward
 over both branches and one native backward that carries input gradients only.
 The shift search (shift_select.hip) reads both tensors once, accumulates every candidate offset in registers and leaves the selection on
 the device; NearestL1Loss takes its value from the search and never materialises a crop.

@@ -442,7 +442,7 @@ class LegacyRDDBNet(RDDBNetB):
 
 # ------------------------------------------------------------------------------------------------ op-list networks
 class _OpList(NamedTuple):
-    """One network family of the native op-list executor (``rd_forward`` / ``rd_backward`` in csrc/nets.hip).  Its C entry points
+    """One network family of the native op-list executor (``rd_forward`` / ``rd_backward`` in csrc/oplist.hip).  Its C entry points
     are ``<stem>_ws_bytes`` / ``_forward`` / ``_bwd_scratch_bytes`` / ``_backward`` / ``_infer_ws_bytes`` / ``_infer``."""
     name: str                 # in messages
     stem: str                 # C symbol stem
