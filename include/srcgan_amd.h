@@ -414,7 +414,10 @@ typedef struct srcgan_rddbnet_cfg {
  *                   to first; the call with hi == number of RRDBs also runs everything behind the trunk (conv_last, up-sampler,
  *                   trunk_conv), the call with lo == 0 everything in front of it (conv_first, dx).  Calls come in descending,
  *                   gap-free order on one stream with the same ws / scratch / grads; when a call returns, the gradients of the
- *                   parameters it covers are final (data parallel: their all-reduce starts while earlier blocks still compute). */
+ *                   parameters it covers are final (data parallel: their all-reduce starts while earlier blocks still compute).
+ * The `ws` / `scratch` parameters of every whole-network entry point below (and `wpack`, `grads`, a weight-gradient `slab`): the
+ * contents on entry are unspecified.  A call reads no byte of them that it (or, for a backward, its forward on the same `ws`) has not
+ * written, and writes nothing outside the first *_bytes bytes: results do not depend on what the buffers held. */
 typedef struct srcgan_net_opts {
     void* wpack;
     int pack;

@@ -17,6 +17,7 @@ import torch
 
 import conv_exact as CE
 from conv_exact import conv_case, par_case, wgrad_case, dense_case, DTS, TDT
+from ws_guard import NAN, guarded_slabs
 
 pytestmark = pytest.mark.gpu
 
@@ -313,6 +314,14 @@ def ops():
     return o
 
 
+@pytest.fixture(autouse=True)
+def _guarded_slabs(ops):
+    """Every srcgan_conv_wgrad / srcgan_wgrad_dense call of this file gets a NaN-filled split-K slab between guards, checked after the
+    call (tests/ws_guard.py): the slab's contents on entry are unspecified, like those of the networks' scratch."""
+    with guarded_slabs(NAN, "cuda") as g:
+        yield g
+
+
 @pytest.fixture(scope="module")
 def ncu(ops):
     return torch.cuda.get_device_properties(0).multi_processor_count
@@ -594,20 +603,22 @@ def test_four_parities_exact(ops, c, dt):
 
 
 @pytest.mark.parametrize("c,dt", _params(WGRAD_CASES))
-def test_wgrad_exact(ops, c, dt):
+def test_wgrad_exact(ops, c, dt, _guarded_slabs):
     b = built(c, dt)
     exact_conditions(c, dt, b)
     _, grad, gb = run_wgrad(ops, c, dt, b)
+    assert _guarded_slabs.calls >= 1          # the call above ran on the guarded slab
     same(grad, b["want"], "grad")
     if gb is not None:
         same(gb, b["bias_want"], "bias_grad")
 
 
 @pytest.mark.parametrize("c,dt", _params(DENSE_CASES))
-def test_wgrad_dense_exact(ops, c, dt):
+def test_wgrad_dense_exact(ops, c, dt, _guarded_slabs):
     b = built(c, dt)
     exact_conditions(c, dt, b)
     _, outs = run_dense(ops, c, dt, b)
+    assert _guarded_slabs.calls >= 1
     for s, (gw, gb) in zip(b["segs"], outs):
         if gw is not None:
             same(gw, s["w_want"], f"grad of rows [{s['g0']}, {s['g1']})")

@@ -24,6 +24,15 @@ def ops():
     return o
 
 
+@pytest.fixture(autouse=True)
+def _guarded_slabs(ops):
+    """Every srcgan_conv_wgrad / srcgan_wgrad_dense call of this file gets a NaN-filled split-K slab between guards, checked after the
+    call (tests/ws_guard.py)."""
+    from ws_guard import NAN, guarded_slabs
+    with guarded_slabs(NAN, "cuda"):
+        yield
+
+
 def _q(t, dt):
     """quantise reference inputs like the kernel sees them"""
     return t.to(torch.bfloat16).float() if dt == "bf16" else t.to(torch.float16).float() if dt == "fp16" else t
