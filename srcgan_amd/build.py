@@ -1,5 +1,6 @@
 """Build the native library: hipcc cross-compiles every .hip source for gfx950 (no GPU needed)
 into srcgan_amd/lib/libsrcgan_amd.so, in-tree so it travels with the repo snapshot."""
+import glob
 import os
 import subprocess
 import sys
@@ -9,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsrcgan_amd.so")
-SOURCES = ["conv_igemm.hip", "conv_par4.hip", "deconv_k3s2.hip", "conv3x3_dma.hip", "conv_wgrad.hip", "wgrad_dense.hip", "elementwise.hip", "class_losses.hip", "groupnorm.hip", "chan_attn.hip", "back_proj.hip", "metrics.hip", "shift_select.hip", "scene_score.hip", "colour.hip", "tiles.hip", "vgg_loss.hip", "nets.hip", "oplist.hip"]
+SOURCES = ["conv_entry.hip", "conv_igemm.hip", "conv_par4.hip", "deconv_k3s2.hip", "conv3x3_dma.hip", "conv_wgrad.hip", "wgrad_dense.hip", "elementwise.hip", "class_losses.hip", "groupnorm.hip", "chan_attn.hip", "back_proj.hip", "metrics.hip", "shift_select.hip", "scene_score.hip", "colour.hip", "tiles.hip", "vgg_loss.hip", "nets.hip", "oplist.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 
@@ -30,7 +31,7 @@ def _stale(target, deps):
 def build(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_params.h"), os.path.join(CSRC, "pixel_ops.h"), os.path.join(CSRC, "net_common.h"), os.path.join(HERE, "..", "include", "srcgan_amd.h")]
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "srcgan_amd.h")]
     objs, jobs = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)

@@ -13,9 +13,9 @@
 //     LDS: the DMA of chunk c+1 is in flight during the MFMAs of chunk c; one barrier per chunk.
 //     (tile twice as large as the generic kernel -> weight traffic per FLOP halves.)
 //   * out-of-image / past-Cin pieces are fetched from a 64-byte zero page instead of being branched on.
-#include "conv_params.h"
+#include "conv_epilogue.h"
+#include "launch.h"
 #include <type_traits>
-#include <stdlib.h>
 
 static __device__ __attribute__((aligned(64))) unsigned int sg_zero_page[16];
 
@@ -624,29 +624,25 @@ static int launch_ls_dir(const ConvP& p, int ctiles, hipStream_t st) {
     constexpr int HB = (((18 * 34 * 64 + 1023) / 1024 + NLW - 1) / NLW) * NLW * 1024, WB = WRES ? 0 : ((9 * 32 * MT * 64 / 1024 + NLW - 1) / NLW) * NLW * 1024;
     constexpr size_t SMEM = WRES ? 160 * 1024 : 2 * ((size_t)HB + (size_t)WB) + 4096 + 256;  // + bias copy (<= 1024 output channels) + prefetch dummy
     static_assert(NSTG == 2 || WRES, "three stages only beside resident weights");
-    auto kern = conv3x3_ls_k<T, MT, NLW, WRES, EM, NSTG, PT, DIR>;
-    static bool attr_set = false;
-    static int ncu = 0;
-    if (!attr_set) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        int dev = 0; hipDeviceProp_t prop;
-        SG_HIP(hipGetDevice(&dev)); SG_HIP(hipGetDeviceProperties(&prop, dev));
-        ncu = prop.multiProcessorCount;
-        attr_set = true;
-    }
+    constexpr auto kern = conv3x3_ls_k<T, MT, NLW, WRES, EM, NSTG, PT, DIR>;
     if constexpr (DIR == 3 && ConvRowsPre<T, MT, PT, EM>::ON) {       // 32-bit per-lane offsets of the residual operands' buffer loads (conv_lds_rows_request)
         const long lim = (1L << 31) - (1L << 20);
         SG_REQUIRE((!p.r1 || p.r1plane < lim) && (!p.r2 || p.r2plane < lim) && p.r1pix < (1 << 16) && p.r2pix < (1 << 16),
                    "conv3x3: a residual operand's channel plane must be below 2 GiB");
     }
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
+    SG_TRY(sg_allow_lds<kern>(SMEM, dev));
+    const int ncu = sg_cu_count(dev);
+    if (!ncu) return 1;
     ConvP q = p;
     q.tiles_x = cdiv(p.OW, 32); q.tiles_y = cdiv(p.OH, 16); q.ctiles = ctiles;
-    { static const char* e = sg_env("SRCGAN_DBG"); q.dbg = e ? atoi(e) : 0; }
+    q.dbg = sg_dbg_flags();
     const size_t nunits = (size_t)q.tiles_x * q.tiles_y * p.B * ctiles;
     size_t nwg = (size_t)ncu; if (nwg > nunits) nwg = nunits;
     if (const char* e = sg_env("SRCGAN_CONV_CUS")) { const int v = atoi(e); if (v > 0 && (size_t)v < nwg) nwg = (size_t)v; }     // diagnostic builds: share the chip with a concurrent kernel
     char cls[96];
-    snprintf(cls, sizeof(cls), "conv3x3_ls<%s,MT%d,W%d+%d%s%s,e%d%s>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"), MT, 16 / PT, NLW, WRES ? ",wres" : "", NSTG == 3 ? ",s3" : "", EM,
+    snprintf(cls, sizeof(cls), "conv3x3_ls<%s,MT%d,W%d+%d%s%s,e%d%s>", sg_dtype_tag<T>(), MT, 16 / PT, NLW, WRES ? ",wres" : "", NSTG == 3 ? ",s3" : "", EM,
              DIR == 2 ? ",d16" : DIR == 1 ? ",d8" : DIR == 0 ? ",gen" : "");
     const double px = (double)p.B * p.OH * p.OW;
     const int tok = sg_prof_start(cls, 2.0 * px * 9 * p.Cin * p.Cout, ((double)p.B * p.H * p.W * p.Cin + px * p.Cout) * sizeof(T), st);
@@ -690,37 +686,42 @@ static int launch_dma(const ConvP& p, int ctiles, hipStream_t st) {
     constexpr int HB = (((TH + 2) * 34 * 64 + 1023) / 1024) * 1024, WB = 9 * 32 * MT * 64;
     constexpr size_t SMEM = NBUF * ((size_t)HB + (size_t)WB);
     static_assert(SMEM <= 160 * 1024, "LDS budget");
-    auto kern = conv3x3_dma_k<T, MT, NWV, NBUF, PT, NLW>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        attr_set = true;
-    }
+    constexpr auto kern = conv3x3_dma_k<T, MT, NWV, NBUF, PT, NLW>;
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
+    SG_TRY(sg_allow_lds<kern>(SMEM, dev));
+    const int ncu = sg_cu_count(dev);
+    if (!ncu) return 1;
     ConvP q = p;
-    { static const char* e = sg_env("SRCGAN_DBG"); q.dbg = e ? atoi(e) : 0; }
+    q.dbg = sg_dbg_flags();
     q.tiles_x = cdiv(p.OW, 32);
     q.tiles_y = cdiv(p.OH, TH);
     q.ctiles = ctiles;
     const size_t nunits = (size_t)q.tiles_x * q.tiles_y * p.B * ctiles;
-    static int wg_per_cu = 0, ncu = 0;
-    if (!wg_per_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        SG_HIP(hipGetDevice(&dev)); SG_HIP(hipGetDeviceProperties(&prop, dev));
-        ncu = prop.multiProcessorCount;
-        wg_per_cu = (int)((160 * 1024) / SMEM); if (wg_per_cu < 1) wg_per_cu = 1;
-        if (wg_per_cu * (NWV + NLW) > 16) wg_per_cu = 16 / (NWV + NLW) > 0 ? 16 / (NWV + NLW) : 1;
-    }
+    int wg_per_cu = (int)((160 * 1024) / SMEM); if (wg_per_cu < 1) wg_per_cu = 1;
+    if (wg_per_cu * (NWV + NLW) > 16) wg_per_cu = 16 / (NWV + NLW) > 0 ? 16 / (NWV + NLW) : 1;
     size_t nwg = (size_t)ncu * wg_per_cu;
     if (nwg > nunits) nwg = nunits;
     dim3 grid((unsigned)nwg, 1, 1);
     char cls[96];
-    snprintf(cls, sizeof(cls), "conv3x3_dma<%s,MT%d,W%d+%d,PT%d>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"), MT, NWV, NLW, PT);
+    snprintf(cls, sizeof(cls), "conv3x3_dma<%s,MT%d,W%d+%d,PT%d>", sg_dtype_tag<T>(), MT, NWV, NLW, PT);
     const double px = (double)p.B * p.OH * p.OW;
     const int tok = sg_prof_start(cls, 2.0 * px * 9 * p.Cin * p.Cout, ((double)p.B * p.H * p.W * p.Cin + px * p.Cout) * sizeof(T), st);
     hipLaunchKernelGGL(kern, grid, dim3((NWV + NLW) * 64), SMEM, st, q);
     sg_prof_stop(tok, st);
     SG_LAUNCH_CHECK();
     return 0;
+}
+
+// launch_ls<T, MT, NLW, WRES, EM, NSTG> with EM = the member of the compile-time list that equals em, the launch's set of optional
+// epilogue operands (bits as for conv_epilogue_lds_rows); -1, with nothing launched, if em is not in the list -- the caller then
+// takes the all-operand instance (EM = 7).  Only the listed sets are instantiated.
+template <int... EMS> struct EmSets {};
+template <typename T, int MT, int NLW, bool WRES, int NSTG, int... EMS>
+static int launch_ls_em(EmSets<EMS...>, int em, const ConvP& p, int ctiles, hipStream_t st) {
+    int rc = -1;
+    (void)((em == EMS && ((rc = launch_ls<T, MT, NLW, WRES, EMS, NSTG>(p, ctiles, st)), true)) || ...);
+    return rc;
 }
 
 template <typename T>
@@ -747,44 +748,33 @@ static int dispatch_dma(const ConvP& p, hipStream_t st) {
             const int em = (p.r1 ? 1 : 0) | (p.r2 ? 2 : 0) | (p.mz ? 4 : 0) | (p.sgn_in ? 8 : 0) | (p.sgn_out ? 16 : 0);
             SG_REQUIRE(em < 8 || em == 8 || em == 16, "conv3x3: a sign mask cannot be combined with other epilogue operands");
             static const bool no_s3 = sg_env("SRCGAN_NO_S3") != nullptr;
-            if (!no_wres && !no_s3 && p.nchunk == 2) {           // Cin = 64: three 40 KiB stages + 36 KiB of weights + bias = 160 KiB
-                if (em == 0) return launch_ls<T, 1, SG_NLW1, true, 0, 3>(p, 1, st);
-                if (em == 4) return launch_ls<T, 1, SG_NLW1, true, 4, 3>(p, 1, st);
-                if (em == 8) return launch_ls<T, 1, SG_NLW1, true, 8, 3>(p, 1, st);
-                if (em == 16) return launch_ls<T, 1, SG_NLW1, true, 16, 3>(p, 1, st);
-            }
+            using Dense = EmSets<0, 4, 8, 16>;                   // forward, gradient slice with mz, sign mask read, sign mask written
+            int rc = -1;
+            if (!no_wres && !no_s3 && p.nchunk == 2)             // Cin = 64: three 40 KiB stages + 36 KiB of weights + bias = 160 KiB
+                rc = launch_ls_em<T, 1, SG_NLW1, true, 3>(Dense{}, em, p, 1, st);
+            if (rc >= 0) return rc;
             // (PT = 4: four MFMA waves with 4 rows each read 36 % fewer fragments per MFMA, but one MFMA wave per SIMD does not
             //  keep the matrix pipe fed: 96->32 68 -> 74 us, 128->32 90 -> 98 us.  launch_ls<T, 1, SG_NLW1, true, EM, 2, 4> to retry.)
             if (!no_wres && 2 * 40 * 1024 + p.nchunk * 9 * 32 * 64 + 4096 <= 160 * 1024) {
-                if (em == 0) return launch_ls<T, 1, SG_NLW1, true, 0>(p, 1, st);
-                if (em == 4) return launch_ls<T, 1, SG_NLW1, true, 4>(p, 1, st);
-                if (em == 8) return launch_ls<T, 1, SG_NLW1, true, 8>(p, 1, st);
-                if (em == 16) return launch_ls<T, 1, SG_NLW1, true, 16>(p, 1, st);
-                return launch_ls<T, 1, SG_NLW1, true, 7>(p, 1, st);
+                rc = launch_ls_em<T, 1, SG_NLW1, true, 2>(Dense{}, em, p, 1, st);
+                return rc >= 0 ? rc : launch_ls<T, 1, SG_NLW1, true, 7>(p, 1, st);
             }
-            if (em == 0) return launch_ls<T, 1, SG_NLW1, false, 0>(p, 1, st);
-            if (em == 4) return launch_ls<T, 1, SG_NLW1, false, 4>(p, 1, st);
-            if (em == 8) return launch_ls<T, 1, SG_NLW1, false, 8>(p, 1, st);
-            if (em == 16) return launch_ls<T, 1, SG_NLW1, false, 16>(p, 1, st);
-            return launch_ls<T, 1, SG_NLW1, false, 7>(p, 1, st);
+            rc = launch_ls_em<T, 1, SG_NLW1, false, 2>(Dense{}, em, p, 1, st);
+            return rc >= 0 ? rc : launch_ls<T, 1, SG_NLW1, false, 7>(p, 1, st);
         }
     }
     const int ctiles = cdiv(p.Cout, 64);
     if (cfg == 'a') return launch_dma<T, 2, 8, 2, 2>(p, ctiles, st);
     if constexpr (sizeof(T) == 2) {
-        const int em = (p.r1 ? 1 : 0) | (p.r2 ? 2 : 0) | (p.mz ? 4 : 0);
-        if (p.sgn_in) return launch_ls<T, 2, 4, false, 8>(p, ctiles, st);       // conv_last's input gradient: 8 mask bytes per pixel instead of the 64-channel activation
-        if (em == 0) return launch_ls<T, 2, 4, false, 0>(p, ctiles, st);
-        if (em == 1) return launch_ls<T, 2, 4, false, 1>(p, ctiles, st);
-        if (em == 3) return launch_ls<T, 2, 4, false, 3>(p, ctiles, st);
-        if (em == 4) return launch_ls<T, 2, 4, false, 4>(p, ctiles, st);
+        // sign mask read = conv_last's input gradient: 8 mask bytes per pixel instead of the 64-channel activation (no other operand beside it)
+        const int em = p.sgn_in ? 8 : (p.r1 ? 1 : 0) | (p.r2 ? 2 : 0) | (p.mz ? 4 : 0);
+        const int rc = launch_ls_em<T, 2, 4, false, 2>(EmSets<8, 0, 1, 3, 4>{}, em, p, ctiles, st);
+        if (rc >= 0) return rc;
     }
     return launch_ls<T, 2, 4>(p, ctiles, st);
 }
 
 // entry used by srcgan_conv_igemm for kh == kw == 3, stride 1
 int sg_conv3x3_dma(const ConvP& p, int dtype, hipStream_t st) {
-    if (dtype == SRCGAN_F32) return dispatch_dma<float>(p, st);
-    if (dtype == SRCGAN_F16) return dispatch_dma<_Float16>(p, st);
-    return dispatch_dma<__bf16>(p, st);
+    return sg_dtype_dispatch(dtype, [&](auto t) { return dispatch_dma<decltype(t)>(p, st); });
 }

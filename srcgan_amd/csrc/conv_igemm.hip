@@ -15,11 +15,11 @@
 // of 32 consecutive pixels is bank-conflict free (stride 5 slots of 16 B, coprime with 16).
 // Both dtypes use the same byte layout: 64 B = 32 bf16 (2 x mfma_32x32x16_bf16 k-steps)
 //                                            = 16 f32  (8 x mfma_32x32x2_f32).
-#include "common.h"
+//
+// Reached through sg_conv_generic (bottom of the file); srcgan_conv_igemm itself is in conv_entry.hip.
+#include "conv_epilogue.h"
+#include "launch.h"
 #include <type_traits>
-#include <stdlib.h>
-
-#include "conv_params.h"
 
 // Cost-removal switches of this kernel's hot loop (scripts/microbench_generic.py): only in a -DSG_DIAG -DSG_IG_DIAG variant --
 // as run-time branches they stop the compiler from hoisting fragment reads over MFMAs, so even other SG_DIAG variants leave them out.
@@ -313,20 +313,18 @@ static int launch_igemm(const ConvP& p, int ctiles, hipStream_t st) {
     constexpr int COT = 32 * MT, NTAP = KH * KW;
     constexpr size_t STAGE = (size_t)IHT * IWT * 80 + (size_t)(WPK ? KW : NTAP) * COT * 80, EPI = (size_t)4 * 32 * (COT * 4 + 16);
     constexpr size_t SMEM = STAGE > EPI ? STAGE : EPI;       // the LDS-transposed epilogue reuses the stage buffers
-    static bool attr_set = false;
-    auto kern = conv_igemm_k<T, KH, KW, S, MT, PT, WPK>;
-    if (!attr_set) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        attr_set = true;
-    }
+    constexpr auto kern = conv_igemm_k<T, KH, KW, S, MT, PT, WPK>;
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
+    SG_TRY(sg_allow_lds<kern>(SMEM, dev));
     ConvP q = p;
     q.tiles_x = cdiv(p.OW, TW);
     q.tiles_y = cdiv(p.OH, TH);
     q.ctiles = ctiles;
-    { static const char* e = sg_env("SRCGAN_DBG"); q.dbg = e ? atoi(e) : 0; }
+    q.dbg = sg_dbg_flags();
     dim3 grid((unsigned)((size_t)q.tiles_x * q.tiles_y * p.B * ctiles), 1, 1);
     char cls[96];
-    snprintf(cls, sizeof(cls), "conv_igemm<%s,%dx%d,s%d,MT%d>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"), KH, KW, S, MT);
+    snprintf(cls, sizeof(cls), "conv_igemm<%s,%dx%d,s%d,MT%d>", sg_dtype_tag<T>(), KH, KW, S, MT);
     // algorithmic work: 2*pixels*taps*Cin*Cout flop; bytes: input read once + output written once
     const double px = (double)p.B * p.OH * p.OW * (p.npar ? p.npar : 1);
     const int tok = sg_prof_start(cls, 2.0 * px * NTAP * p.Cin * p.Cout,
@@ -366,120 +364,26 @@ static int dispatch_shape(const ConvP& p, int kh, int kw, int s, int ctiles, hip
     SG_FAIL("srcgan_conv_igemm: unsupported kernel %dx%d stride %d", kh, kw, s);
 }
 
-int sg_conv3x3_dma(const ConvP& p, int dtype, hipStream_t st);      // conv3x3_dma.hip
-int sg_dgrad_s2k4(const ConvP& p, int dtype, hipStream_t st);       // conv_par4.hip
-int sg_deconv_k3s2(const ConvP& p, int dtype, hipStream_t st);      // deconv_k3s2.hip
-static const bool g_force_generic = sg_env("SRCGAN_GENERIC_3X3") != nullptr;   // A/B switch for benchmarking
-
-extern "C" int srcgan_conv_igemm(const srcgan_conv_desc* d, void* stream) {
-    SG_REQUIRE(d && d->x && d->wp && d->y, "srcgan_conv_igemm: null pointer");
-    SG_REQUIRE(sg_dtype_ok(d->dtype), "srcgan_conv_igemm: bad dtype %d", d->dtype);
-    const int esz = d->dtype == SRCGAN_F32 ? 4 : 2;
-    const int epp = 16 / esz;
-    SG_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->OH > 0 && d->OW > 0 && d->Cin > 0 && d->Cout > 0,
-               "srcgan_conv_igemm: non-positive dimension");
-    SG_REQUIRE(d->Cin % epp == 0 && d->x_cs % epp == 0 && d->x_coff % epp == 0,
-               "srcgan_conv_igemm: input channels/stride/offset (%d,%d,%d) must be multiples of %d", d->Cin, d->x_cs, d->x_coff, epp);
-    SG_REQUIRE((d->x_plane || d->x_coff + d->Cin <= d->x_cs) && (d->y_plane || d->y_coff + d->Cout <= d->y_cs),
-               "srcgan_conv_igemm: channel slice exceeds stride");
-    SG_REQUIRE(!d->x_plane || (d->kh == 3 && d->kw == 3 && d->stride == 1), "srcgan_conv_igemm: a blocked-layout input is supported by the 3x3 stride-1 kernel only");
-    SG_REQUIRE(((uintptr_t)d->x % 16) == 0 && ((uintptr_t)d->wp % 16) == 0, "srcgan_conv_igemm: x/wp must be 16-byte aligned");
-    SG_REQUIRE(d->os >= 1 && d->oa >= 0 && d->ob >= 0 && d->oa < d->os && d->ob < d->os, "srcgan_conv_igemm: bad output scale/offset");
-    SG_REQUIRE((d->OH - 1) * d->os + d->oa < d->YH && (d->OW - 1) * d->os + d->ob < d->YW, "srcgan_conv_igemm: output extent exceeds tensor");
-    ConvP p;
-    memset(&p, 0, sizeof(p));
-    p.x = d->x; p.wp = d->wp; p.bias = d->bias; p.y = d->y; p.r1 = d->r1; p.r2 = d->r2; p.mz = d->mz;
-    p.B = d->B; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.xcoff = d->x_coff;
-    p.OH = d->OH; p.OW = d->OW; p.Cout = d->Cout; p.YH = d->YH; p.YW = d->YW; p.ycoff = d->y_coff;
-    p.pad_y = d->pad_y; p.pad_x = d->pad_x; p.os = d->os; p.oa = d->oa; p.ob = d->ob;
-    p.r1coff = d->r1_coff; p.r1cend = d->r1_cend;
-    p.r2coff = d->r2_coff; p.r2cend = d->r2_cend;
-    p.mzcoff = d->mz_coff; p.mzc0 = d->mz_c0;
-    auto pl = [](long v) { return v ? v : 64L; };      // plane stride 0 = interleaved NHWC
-    p.xpix = (long)d->x_cs * esz; p.xplane = pl(d->x_plane); p.ypix = (long)d->y_cs * esz; p.yplane = pl(d->y_plane);
-    p.r1pix = (long)d->r1_cs * esz; p.r1plane = pl(d->r1_plane); p.r2pix = (long)d->r2_cs * esz; p.r2plane = pl(d->r2_plane);
-    p.mzpix = (long)d->mz_cs * esz; p.mzplane = pl(d->mz_plane);
-    p.rev = d->rev_batch;
-    p.sgn_out = (unsigned char*)d->sign_out; p.sgn_in = (const unsigned char*)d->sign_in;
-    if (d->sign_out || d->sign_in) {
-        const bool dense32 = d->kh == 3 && d->kw == 3 && d->stride == 1 && sg_is16(d->dtype) && d->Cout == 32 && d->os == 1 && d->oa == 0 && d->ob == 0 &&
-                             d->YH == d->OH && d->YW == d->OW && d->x_plane && !(d->sign_in && d->mz) && (!d->sign_out || d->act);
-        // 64 channels (8 mask bytes per pixel): written by the up-sampler's 1x1 parity form, read by a 3x3 s1 convolution without other operands
-        const bool up_out = d->sign_out && !d->sign_in && d->kh == 1 && d->kw == 1 && d->npar == 4 && sg_is16(d->dtype) && d->Cout == 64 && d->act;
-        const bool in64 = d->sign_in && !d->sign_out && d->kh == 3 && d->kw == 3 && d->stride == 1 && sg_is16(d->dtype) && d->Cout == 64 && d->os == 1 &&
-                          d->YH == d->OH && d->YW == d->OW && !d->mz && !d->r1 && !d->r2;
-        SG_REQUIRE(dense32 || up_out || in64,
-                   "srcgan_conv_igemm: sign masks need a 3x3 s1 16-bit conv with Cout == 32 on a blocked input, unscaled output (act for sign_out, no mz beside sign_in); "
-                   "or Cout == 64: sign_out of the 1x1 four-parity form with act, sign_in of a 3x3 s1 conv without other operands");
+// entry used by srcgan_conv_igemm for every shape that has no kernel of its own; p.npar == 4: the 1x1 four-parity form
+int sg_conv_generic(const ConvP& p, int dtype, int kh, int kw, int stride, hipStream_t st) {
+    // pixel-pair form: 64 channels of 2 bytes, dense interleaved output -> one 128-row tile per ROW parity writes both column parities
+    // (yplane == 64 stands for interleaved NHWC: the entry turns a plane stride of 0 into the 64-byte chunk, and a descriptor that
+    //  passes 64 itself addresses the same bytes)
+    if (p.npar == 4 && kh == 1 && kw == 1 && sg_is16(dtype) && p.Cout == 64 && p.ypix == 128 && p.ycoff == 0 && p.yplane == 64 && p.YW == 2 * p.OW &&
+        p.buf16 && !p.bias && !p.r1 && !p.r2 && !p.mz && p.Cin % 32 == 0) {
+        ConvP q = p;
+        q.npar = 2; q.wpar = 2 * p.wpar; q.wsplit = p.wpar;
+        q.Cout = 128; q.ypix *= 2; q.YW = p.YW / 2; q.osx = 1;
+        return sg_dtype_dispatch16(dtype, [&](auto t) { return launch_igemm<decltype(t), 1, 1, 1, 4, SG_UP_PT, false>(q, 2, st); });
     }
-    p.alpha = d->alpha; p.beta1 = d->beta1; p.beta2 = d->beta2; p.slope = d->slope; p.mslope = d->mslope;
-    p.act = d->act;
-    const int kce = 64 / esz;
-    p.nchunk = cdiv(d->Cin, kce);
-    auto m4 = [](int v) { return (v & 3) == 0; };
-    p.vec = m4(d->Cout) && m4(d->y_cs) && m4(d->y_coff) && ((uintptr_t)d->y % 16 == 0) &&
-            (!d->bias || ((uintptr_t)d->bias % 16 == 0)) &&
-            (!d->r1 || (m4(d->r1_cs) && m4(d->r1_coff) && m4(d->r1_cend) && (uintptr_t)d->r1 % 16 == 0)) &&
-            (!d->r2 || (m4(d->r2_cs) && m4(d->r2_coff) && m4(d->r2_cend) && (uintptr_t)d->r2 % 16 == 0)) &&
-            (!d->mz || (m4(d->mz_cs) && m4(d->mz_coff) && m4(d->mz_c0) && (uintptr_t)d->mz % 16 == 0));
-    {
-        auto me = [&](int v) { return v % epp == 0; };
-        p.vec16 = p.vec && me(d->Cout) && me(d->y_cs) && me(d->y_coff) &&
-                  (!d->r1 || (me(d->r1_cs) && me(d->r1_coff) && me(d->r1_cend))) &&
-                  (!d->r2 || (me(d->r2_cs) && me(d->r2_coff) && me(d->r2_cend))) &&
-                  (!d->mz || (me(d->mz_cs) && me(d->mz_coff) && me(d->mz_c0)));
-    }
-    {
-        const long lim = (1L << 31) - (1L << 20);
-        p.buf16 = p.vec16 && p.yplane < lim && p.ypix < (1 << 20) && (!d->r1 || (p.r1plane < lim && p.r1pix < (1 << 20))) &&
-                  (!d->r2 || (p.r2plane < lim && p.r2pix < (1 << 20))) && (!d->mz || (p.mzplane < lim && p.mzpix < (1 << 20)));
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (d->npar && d->kh == 3) {
-        // ConvTranspose2d(k3, s2, p1, output_padding 1): the four output parities (1, 2, 2 and 4 taps) in one launch (deconv_k3s2.hip)
-        SG_REQUIRE(d->npar == 4 && d->kw == 3 && d->stride == 2 && d->pad_y == 1 && d->pad_x == 1 && d->os == 2 && d->oa == 0 && d->ob == 0 &&
-                   d->OH == d->H && d->OW == d->W && d->YH == 2 * d->H && d->YW == 2 * d->W && d->wpar_stride > 0 && d->wpar_stride % 16 == 0 &&
-                   !d->x_plane && !d->y_plane && !d->sign_in && !d->sign_out,
-                   "srcgan_conv_igemm: npar == 4 with a 3x3 kernel is the transposed stride-2 form: stride 2, pad 1, os 2, oa == ob == 0, OH x OW = H x W, "
-                   "YH x YW = 2H x 2W, the four parity packs wpar_stride bytes apart, interleaved tensors, no sign masks");
-        p.npar = 4; p.wpar = d->wpar_stride;
-        return sg_deconv_k3s2(p, d->dtype, st);
-    } else if (d->npar && d->kh == 1 && d->kw == 1) {
-        // four output parities of a stride-2 scatter in one launch: parity q = (oa, ob) = (q >> 1, q & 1) uses the pack at wp + q * wpar_stride
-        SG_REQUIRE(d->npar == 4 && d->stride == 1 && d->os == 2 && d->oa == 0 && d->ob == 0 && d->wpar_stride > 0 && d->wpar_stride % 16 == 0 &&
-                   !d->sign_in, "srcgan_conv_igemm: npar == 4 with a 1x1 kernel needs os == 2, oa == ob == 0 and the four packs wpar_stride bytes apart");
-        SG_REQUIRE(!d->sign_out || p.buf16, "srcgan_conv_igemm: sign_out of the 1x1 four-parity form needs 16-byte accessible output channels");
-        p.npar = 4; p.wpar = d->wpar_stride;
-        // pixel-pair form: 64 channels of 2 bytes, dense interleaved output -> one 128-row tile per ROW parity writes both column parities
-        if (sg_is16(d->dtype) && d->Cout == 64 && d->y_cs == 64 && d->y_coff == 0 && !d->y_plane && d->YW % 2 == 0 && d->YW == 2 * d->OW && p.buf16 &&
-            !d->bias && !d->r1 && !d->r2 && !d->mz && d->Cin % 32 == 0) {
-            p.npar = 2; p.wpar = 2 * d->wpar_stride; p.wsplit = d->wpar_stride;
-            p.Cout = 128; p.ypix *= 2; p.YW = d->YW / 2; p.osx = 1;
-            if (d->dtype == SRCGAN_F16) return launch_igemm<_Float16, 1, 1, 1, 4, SG_UP_PT, false>(p, 2, st);
-            return launch_igemm<__bf16, 1, 1, 1, 4, SG_UP_PT, false>(p, 2, st);
-        }
-    } else if (d->npar) {
-        SG_REQUIRE(d->npar == 4 && d->kh == 2 && d->kw == 2 && d->stride == 1 && d->wpar_stride > 0 && d->wpar_stride % 16 == 0 && !d->x_plane && !d->y_plane &&
-                   !d->sign_in && !d->sign_out && !d->bias,
-                   "srcgan_conv_igemm: npar must be 0 or 4 (2x2 stride-1 parity packs wpar_stride bytes apart, interleaved tensors, no bias / sign masks)");
-        p.wpar = d->wpar_stride;
-        return sg_dgrad_s2k4(p, d->dtype, st);
-    }
-    if (d->kh == 3 && d->kw == 3 && d->stride == 1 && (!g_force_generic || d->x_plane)) return sg_conv3x3_dma(p, d->dtype, st);
     // Cout <= 32 -> one 32-row M tile per workgroup, otherwise 64-row tiles.
     const int npm = p.npar ? p.npar : 1;        // channel tiles = parities x tiles of one parity
-    if (d->Cout <= 32) {
-        if (d->dtype == SRCGAN_F32) return dispatch_shape<float, 1>(p, d->kh, d->kw, d->stride, npm, st);
-        if (d->dtype == SRCGAN_F16) return dispatch_shape<_Float16, 1>(p, d->kh, d->kw, d->stride, npm, st);
-        return dispatch_shape<__bf16, 1>(p, d->kh, d->kw, d->stride, npm, st);
-    }
+    if (p.Cout <= 32) return sg_dtype_dispatch(dtype, [&](auto t) { return dispatch_shape<decltype(t), 1>(p, kh, kw, stride, npm, st); });
 #ifdef SG_MT4_22
     // (variant) stride-2 parity gradients with >= 128 output rows: one 128-row tile per workgroup halves the dy staging per FLOP
-    if (d->dtype == SRCGAN_BF16 && d->kh == 2 && d->kw == 2 && d->stride == 1 && d->Cout % 128 == 0)       // (the variant instantiates bf16 only)
-        return launch_igemm<__bf16, 2, 2, 1, 4, SG_PT22, false>(p, d->Cout / 128, st);
+    if (dtype == SRCGAN_BF16 && kh == 2 && kw == 2 && stride == 1 && p.Cout % 128 == 0)       // (the variant instantiates bf16 only)
+        return launch_igemm<__bf16, 2, 2, 1, 4, SG_PT22, false>(p, p.Cout / 128, st);
 #endif
-    const int ctiles = cdiv(d->Cout, 64) * npm;
-    if (d->dtype == SRCGAN_F32) return dispatch_shape<float, 2>(p, d->kh, d->kw, d->stride, ctiles, st);
-    if (d->dtype == SRCGAN_F16) return dispatch_shape<_Float16, 2>(p, d->kh, d->kw, d->stride, ctiles, st);
-    return dispatch_shape<__bf16, 2>(p, d->kh, d->kw, d->stride, ctiles, st);
+    const int ctiles = cdiv(p.Cout, 64) * npm;
+    return sg_dtype_dispatch(dtype, [&](auto t) { return dispatch_shape<decltype(t), 2>(p, kh, kw, stride, ctiles, st); });
 }

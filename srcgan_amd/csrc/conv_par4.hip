@@ -11,7 +11,8 @@
 // from LDS once for every parity that uses it (9 fragment reads per k-step instead of 16).
 //   GEMM orientation as conv_igemm.hip: D[M = 32 input channels][N = 32 positions u] per parity; a wave owns PT rows t.
 //   LDS: window (80 B per pixel: conflict-free ds_read_b128 of 32 consecutive pixels) + 16 x 32 weight rows of the K chunk.
-#include "conv_params.h"
+#include "conv_epilogue.h"
+#include "launch.h"
 #include <type_traits>
 
 template <typename T, int PT, bool VEC16>
@@ -144,19 +145,17 @@ static int launch_par4v(const ConvP& p, hipStream_t st) {
     constexpr int TH = 4 * PT, IHT = TH + 2, IWT = 34;
     constexpr size_t STAGE = (size_t)IHT * IWT * 80 + (size_t)16 * 32 * 80, EPI = (size_t)4 * 32 * (32 * 4 + 16);
     constexpr size_t SMEM = STAGE > EPI ? STAGE : EPI;
-    auto kern = dgrad_s2k4_k<T, PT, VEC16>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        attr_set = true;
-    }
+    constexpr auto kern = dgrad_s2k4_k<T, PT, VEC16>;
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
+    SG_TRY(sg_allow_lds<kern>(SMEM, dev));
     ConvP q = p;
     q.tiles_x = cdiv((p.YW + 1) / 2, 32);
     q.tiles_y = cdiv((p.YH + 1) / 2, TH);
     q.ctiles = cdiv(p.Cout, 32);
     dim3 grid((unsigned)((size_t)q.tiles_x * q.tiles_y * p.B * q.ctiles), 1, 1);
     char cls[96];
-    snprintf(cls, sizeof(cls), "dgrad_s2k4<%s,4 parities>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"));
+    snprintf(cls, sizeof(cls), "dgrad_s2k4<%s,4 parities>", sg_dtype_tag<T>());
     const double px = (double)p.B * p.YH * p.YW;
     const int tok = sg_prof_start(cls, 2.0 * px * 4 * p.Cin * p.Cout, ((double)p.B * p.H * p.W * p.Cin + px * p.Cout) * sizeof(T), st);
     hipLaunchKernelGGL(kern, grid, dim3(256), SMEM, st, q);
@@ -178,7 +177,5 @@ static int launch_par4(const ConvP& p, hipStream_t st) {
 #endif
 // entry used by srcgan_conv_igemm for descriptors with npar == 4
 int sg_dgrad_s2k4(const ConvP& p, int dtype, hipStream_t st) {
-    if (dtype == SRCGAN_F32) return launch_par4<float, SG_P4PT>(p, st);
-    if (dtype == SRCGAN_F16) return launch_par4<_Float16, SG_P4PT>(p, st);
-    return launch_par4<__bf16, SG_P4PT>(p, st);
+    return sg_dtype_dispatch(dtype, [&](auto t) { return launch_par4<decltype(t), SG_P4PT>(p, st); });
 }

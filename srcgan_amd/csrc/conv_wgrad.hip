@@ -14,7 +14,7 @@
 // so bf16 fragments are read with ds_read_b64_tr_b16 (4 pixels x 16 channels transposed per 16 lanes;
 // 4 consecutive 64-B pixels = one 256-B bank row -> conflict free).  f32 uses plain ds_read_b32
 // (mfma_32x32x2_f32 takes one element per lane).
-#include "common.h"
+#include "launch.h"
 #include <type_traits>
 
 struct WgradP {
@@ -439,12 +439,10 @@ static int launch_wgrad(WgradP p, hipStream_t st) {
     constexpr int IHT = (TH - 1) * S + KH, IWT = (TW - 1) * S + KW;
     constexpr size_t SMEM = (size_t)MT * TH * TW * PB + (size_t)IHT * IWT * PB;
     static_assert(SMEM <= 160 * 1024, "wgrad tile exceeds LDS");
-    auto kern = conv_wgrad_k<T, KH, KW, S, MT, TH, NCW, BIASW>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        attr_set = true;
-    }
+    constexpr auto kern = conv_wgrad_k<T, KH, KW, S, MT, TH, NCW, BIASW>;
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
+    SG_TRY(sg_allow_lds<kern>(SMEM, dev));
     p.tiles_x = cdiv(p.OW, TW);
     p.tiles_y = cdiv(p.OH, TH);
     p.ntiles = p.B * p.tiles_x * p.tiles_y;
@@ -452,7 +450,7 @@ static int launch_wgrad(WgradP p, hipStream_t st) {
     dim3 grid((unsigned)p.citiles, (unsigned)p.ctiles, (unsigned)p.nsplit);
     if (SG_WG_XCD) grid = dim3((unsigned)(p.citiles * p.ctiles * ((p.nsplit + 7) / 8) * 8), 1, 1);
     char cls[96];
-    snprintf(cls, sizeof(cls), "conv_wgrad<%s,%dx%d,s%d,MT%d>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"), KH, KW, S, MT);
+    snprintf(cls, sizeof(cls), "conv_wgrad<%s,%dx%d,s%d,MT%d>", sg_dtype_tag<T>(), KH, KW, S, MT);
     const double px = (double)p.B * p.OH * p.OW;
     const int tok = sg_prof_start(cls, 2.0 * px * KH * KW * p.Cin * p.Cout,
                                   ((double)p.B * p.H * p.W * p.Cin + px * p.Cout) * sizeof(T), st);
@@ -520,26 +518,19 @@ extern "C" int srcgan_conv_wgrad(const srcgan_wgrad_desc* d, void* stream) {
         if (p.nsplit > p.ntiles) p.nsplit = p.ntiles;
         const dim3 grid((unsigned)(p.citiles * ((p.nsplit + 7) / 8) * 8), 1, 1);
         const double px = (double)p.B * p.OH * p.OW;
-        const int tok = sg_prof_start(d->dtype == SRCGAN_F16 ? (c3 ? "conv_wgrad<f16,3x3,s1,c3>" : "conv_wgrad<f16,4x4,s1,c1>") : (c3 ? "conv_wgrad<bf16,3x3,s1,c3>" : "conv_wgrad<bf16,4x4,s1,c1>"),
-                                      2.0 * px * d->kh * d->kw * d->Cin * d->Cout,
-                                      ((double)p.B * p.H * p.W * d->Cin + px * d->Cout) * 2, st);
-        if (c3) {
-            if (d->dtype == SRCGAN_F16) hipLaunchKernelGGL((wgrad_c3_k<_Float16, 3, 3>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((wgrad_c3_k<__bf16, 3, 3>), grid, dim3(256), 0, st, p);
-        } else {
-            if (d->dtype == SRCGAN_F16) hipLaunchKernelGGL((wgrad_c3_k<_Float16, 4, 1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((wgrad_c3_k<__bf16, 4, 1>), grid, dim3(256), 0, st, p);
-        }
-        sg_prof_stop(tok, st);
-        SG_LAUNCH_CHECK();
-        rc = 0;
-    } else
-    if (cot == 32) rc = d->dtype == SRCGAN_F32 ? dispatch_wgrad<float, 1>(p, d->kh, d->kw, d->stride, st)
-                      : d->dtype == SRCGAN_F16 ? dispatch_wgrad<_Float16, 1>(p, d->kh, d->kw, d->stride, st)
-                                               : dispatch_wgrad<__bf16, 1>(p, d->kh, d->kw, d->stride, st);
-    else rc = d->dtype == SRCGAN_F32 ? dispatch_wgrad<float, 2>(p, d->kh, d->kw, d->stride, st)
-            : d->dtype == SRCGAN_F16 ? dispatch_wgrad<_Float16, 2>(p, d->kh, d->kw, d->stride, st)
-                                     : dispatch_wgrad<__bf16, 2>(p, d->kh, d->kw, d->stride, st);
+        rc = sg_dtype_dispatch16(d->dtype, [&](auto t) {
+            using T = decltype(t);
+            char cls[96];
+            snprintf(cls, sizeof(cls), "conv_wgrad<%s,%s>", sg_dtype_tag<T>(), c3 ? "3x3,s1,c3" : "4x4,s1,c1");
+            const int tok = sg_prof_start(cls, 2.0 * px * d->kh * d->kw * d->Cin * d->Cout, ((double)p.B * p.H * p.W * d->Cin + px * d->Cout) * 2, st);
+            if (c3) hipLaunchKernelGGL((wgrad_c3_k<T, 3, 3>), grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((wgrad_c3_k<T, 4, 1>), grid, dim3(256), 0, st, p);
+            sg_prof_stop(tok, st);
+            SG_LAUNCH_CHECK();
+            return 0;
+        });
+    } else if (cot == 32) rc = sg_dtype_dispatch(d->dtype, [&](auto t) { return dispatch_wgrad<decltype(t), 1>(p, d->kh, d->kw, d->stride, st); });
+    else rc = sg_dtype_dispatch(d->dtype, [&](auto t) { return dispatch_wgrad<decltype(t), 2>(p, d->kh, d->kw, d->stride, st); });
     if (rc) return rc;
     WredP q;
     q.slab = d->slab; q.grad = d->grad; q.bias_grad = d->bias_grad; q.nsplit = p.nsplit; q.ctiles = p.ctiles; q.citiles = p.citiles;

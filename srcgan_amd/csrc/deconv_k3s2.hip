@@ -12,7 +12,8 @@
 //   LDS: window (80 B per pixel: conflict-free ds_read_b128 of 32 consecutive pixels) + 9 x 32 weight rows of the K chunk.
 //   Weights: pack q = a * 2 + b at wp + q * wpar bytes, Wp[row tile][chunk][tap wy * (b + 1) + wx][row][k] (srcgan_pack_weight with
 //   tys = a + 1, txs = b + 1); LDS slot of (q, tap) = {0, 1, 3, 5}[q] + tap.
-#include "conv_params.h"
+#include "conv_epilogue.h"
+#include "launch.h"
 #include <type_traits>
 
 template <typename T, int PT>
@@ -154,19 +155,17 @@ static int launch_deconv_k3s2(const ConvP& p, hipStream_t st) {
     constexpr size_t SMEM = STAGE > EPI ? STAGE : EPI;
     // only the LDS-transposed epilogue is instantiated (the per-element form spills beside the 128 accumulator registers)
     SG_REQUIRE(p.buf16, "srcgan_conv_igemm: the transposed 3x3 stride-2 form needs output channels, strides and offsets that are multiples of 16 bytes");
-    auto kern = deconv_k3s2_k<T, PT>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        attr_set = true;
-    }
+    constexpr auto kern = deconv_k3s2_k<T, PT>;
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
+    SG_TRY(sg_allow_lds<kern>(SMEM, dev));
     ConvP q = p;
     q.tiles_x = cdiv(p.W, 32);
     q.tiles_y = cdiv(p.H, TH);
     q.ctiles = cdiv(p.Cout, 32);
     dim3 grid((unsigned)((size_t)q.tiles_x * q.tiles_y * p.B * q.ctiles), 1, 1);
     char cls[96];
-    snprintf(cls, sizeof(cls), "deconv_k3s2<%s,4 parities>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"));
+    snprintf(cls, sizeof(cls), "deconv_k3s2<%s,4 parities>", sg_dtype_tag<T>());
     const double px = (double)p.B * p.H * p.W;
     const int tok = sg_prof_start(cls, 2.0 * px * 9 * p.Cin * p.Cout, (px * p.Cin + 4 * px * p.Cout) * sizeof(T), st);
     hipLaunchKernelGGL(kern, grid, dim3(256), SMEM, st, q);
@@ -177,7 +176,5 @@ static int launch_deconv_k3s2(const ConvP& p, hipStream_t st) {
 
 // entry used by srcgan_conv_igemm for descriptors with npar == 4, kh == kw == 3, stride == 2
 int sg_deconv_k3s2(const ConvP& p, int dtype, hipStream_t st) {
-    if (dtype == SRCGAN_F32) return launch_deconv_k3s2<float, 2>(p, st);
-    if (dtype == SRCGAN_F16) return launch_deconv_k3s2<_Float16, 2>(p, st);
-    return launch_deconv_k3s2<__bf16, 2>(p, st);
+    return sg_dtype_dispatch(dtype, [&](auto t) { return launch_deconv_k3s2<decltype(t), 2>(p, st); });
 }

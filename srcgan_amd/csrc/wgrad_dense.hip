@@ -9,9 +9,8 @@
 // accumulators (+ the bias pseudo-tap, B operand = ones) in registers across its pixel range; split-K over pixel
 // ranges into an f32 slab; a segment-aware reduce scatters rows to the five canonical [Cout,Cin,3,3] gradients
 // (rows of a tile may belong to different convolutions with different Cin; surplus columns are dropped).
-#include "common.h"
+#include "launch.h"
 #include <type_traits>
-#include <stdlib.h>
 
 struct WdSeg { int g0, g1; float* grad; float* bias; int Cin; float alpha; };
 struct WdP {
@@ -578,7 +577,10 @@ static int launch_wd(WdP p, hipStream_t st) {
     constexpr int PB = 32 * (int)sizeof(T), PXP = 64 / (PB / 16);
     constexpr size_t SMEM = 2 * 1024 * ((size_t)MT * ((TH * 32 + PXP - 1) / PXP) + (size_t)NT * (((TH + 2) * 34 + PXP - 1) / PXP));
     static_assert(SMEM <= 160 * 1024, "wgrad_dense tile exceeds LDS");
-    void (*kern)(const WdP) = wgrad_dense_k<T, MT, NT, TH>;
+    constexpr auto slow_kern = wgrad_dense_k<T, MT, NT, TH>;
+    void (*kern)(const WdP) = slow_kern;
+    int dev = 0;
+    SG_TRY(sg_current_device(dev));
     bool fast = false;
     if constexpr (!std::is_same<T, float>::value) {
         // whole tiles, 32-channel-aligned slices when planar, and every byte offset within 31 bits
@@ -589,20 +591,18 @@ static int launch_wd(WdP p, hipStream_t st) {
         fast = !no_fast && p.H % TH == 0 && p.W % 32 == 0 && span_dy < 2.0e9 && span_x < 2.0e9 &&
                (p.dyplane == 64 || (p.dycoff + p.g_base) % 32 == 0) && (p.xplane == 64 || p.xcoff % 32 == 0);
         constexpr int IPWF = (MT * (TH * 2) + NT * (((TH + 2) * 34 + 15) / 16) + MT * NT - 1) / (MT * NT);      // pieces per wave
-        if constexpr (IPWF <= 10) { if (fast) kern = wgrad_dense_fast_k<T, MT, NT, TH>; }   // larger tables would spill beside 160 accumulators
-        else fast = false;
+        if constexpr (IPWF <= 10) {                                                         // larger tables would spill beside 160 accumulators
+            constexpr auto fast_kern = wgrad_dense_fast_k<T, MT, NT, TH>;
+            if (fast) { kern = fast_kern; SG_TRY(sg_allow_lds<fast_kern>(SMEM, dev)); }
+        } else fast = false;
     }
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[fast]) {
-        SG_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM));
-        attr_set[fast] = true;
-    }
+    if (!fast) SG_TRY(sg_allow_lds<slow_kern>(SMEM, dev));
     p.tiles_x = cdiv(p.W, 32);
     p.tiles_y = cdiv(p.H, TH);
     p.ntiles = p.B * p.tiles_x * p.tiles_y;
     if (p.nsplit > p.ntiles) p.nsplit = p.ntiles;
     char cls[96];
-    snprintf(cls, sizeof(cls), "wgrad_dense<%s,MT%d,NT%d%s>", sizeof(T) == 4 ? "f32" : (__is_same(T, __bf16) ? "bf16" : "f16"), MT, NT, fast ? ",fast" : "");
+    snprintf(cls, sizeof(cls), "wgrad_dense<%s,MT%d,NT%d%s>", sg_dtype_tag<T>(), MT, NT, fast ? ",fast" : "");
     const double px = (double)p.B * p.H * p.W;
     const int rows = (p.G - p.g_base) < 32 * MT ? (p.G - p.g_base) : 32 * MT;
     // algorithmic work = the (gradient channel, input channel) pairs some convolution of the block owns (the triangle), not
@@ -758,9 +758,7 @@ extern "C" int srcgan_wgrad_dense(const srcgan_wgrad_dense_desc* d, void* stream
         }
         p.nsplit = wd_nsplit(mt, nt, p.ncit, d->dtype, d->B, d->H, d->W);
         int ns = 0;
-        if (d->dtype == SRCGAN_F32) SG_TRY(dispatch_wd<float>(p, mt, nt, st, ns));
-        else if (d->dtype == SRCGAN_F16) SG_TRY(dispatch_wd<_Float16>(p, mt, nt, st, ns));
-        else SG_TRY(dispatch_wd<__bf16>(p, mt, nt, st, ns));
+        SG_TRY(sg_dtype_dispatch(d->dtype, [&](auto t) { return dispatch_wd<decltype(t)>(p, mt, nt, st, ns); }));
         WdRedP q;
         memset(&q, 0, sizeof(q));
         q.slab = d->slab; q.nsplit = ns; q.ncit = p.ncit; q.COT = 32 * mt; q.g_base = g_base; q.nseg = d->nseg; q.accumulate = d->accumulate;

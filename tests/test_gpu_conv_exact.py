@@ -258,8 +258,8 @@ def _params(cases):
 
 # --------------------------------------------------------------------------------------------- the classes the dispatch can reach
 def _expected_classes():
-    """Read off srcgan_conv_igemm (conv_igemm.hip), dispatch_dma / launch_ls (conv3x3_dma.hip), dispatch_shape, sg_dgrad_s2k4
-    (conv_par4.hip), sg_deconv_k3s2 (deconv_k3s2.hip), srcgan_conv_wgrad / dispatch_wgrad (conv_wgrad.hip) and dispatch_wd / launch_wd
+    """Read off srcgan_conv_igemm's routing (conv_entry.hip), dispatch_dma / launch_ls_em / launch_ls (conv3x3_dma.hip), sg_conv_generic /
+    dispatch_shape (conv_igemm.hip), sg_dgrad_s2k4 (conv_par4.hip), sg_deconv_k3s2 (deconv_k3s2.hip), srcgan_conv_wgrad / dispatch_wgrad (conv_wgrad.hip) and dispatch_wd / launch_wd
     (wgrad_dense.hip), default environment.  3x3 stride 1 always goes to conv3x3_dma.hip, so conv_igemm<.,3x3,s1,.> is not reachable."""
     E = set()
     for t in ("f32", "bf16", "f16"):
