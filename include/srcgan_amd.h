@@ -123,6 +123,11 @@ typedef struct srcgan_conv_desc {
      * the canonical weight [Cin][Cout][3][3].  bias and act are fused; 16-byte accessible output channels are required. */
     int npar; long wpar_stride;
 } srcgan_conv_desc;
+/* Extents.  Tensors may be of any size (image bases and plane offsets are 64-bit; tested past 4 GiB).  Refused before launch:
+ *   - one image of the input (H * W pixel records) of 2 GiB or more, except for the loader-specialised 3x3 stride-1 kernel (pad 1,
+ *     Cin in whole 64-byte chunks or a single chunk, 18 input rows below 2 GiB), which takes images of any size;
+ *   - a residual operand (r1 / r2) in channel planes of 2 GiB - 1 MiB or more beside a 3x3 stride-1 convolution with more than 32
+ *     output channels. */
 int srcgan_conv_igemm(const srcgan_conv_desc* d, void* stream);
 
 /* ---------------------------------------------------------------------------

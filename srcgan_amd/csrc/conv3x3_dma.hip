@@ -735,6 +735,7 @@ static int dispatch_dma(const ConvP& p, hipStream_t st) {
         SG_REQUIRE(ls_ok && cfg != 'a' && sizeof(T) == 2 && (p.Cout == 32 || (p.Cout == 64 && !p.sgn_out && !p.r1 && !p.r2 && !p.mz && p.vec16)),
                    "conv3x3: sign masks are only handled by the loader-specialised 16-bit kernel (Cout == 32, or Cout == 64 read-only without other operands)");
     if (!ls_ok) cfg = 'a';
+    if (cfg == 'a') SG_TRY(sg_require_image_31(p));      // the self-loading kernel's h_goff is a 32-bit offset inside the image
     if (p.Cout <= 32) {
         if (cfg == 'a') return launch_dma<T, 1, 8, 2, 2>(p, 1, st);
 #ifndef SG_NLW1

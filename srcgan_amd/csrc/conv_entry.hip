@@ -77,6 +77,16 @@ static ConvP build_params(const srcgan_conv_desc* d) {
     return p;
 }
 
+// The generic, four-parity and self-loading kernels carry a halo piece's byte offset inside its image in 32 bits (h_goff): one image of the
+// input, H * W pixel records, must stay below 2 GiB.  Only the loader-specialised 3x3 stride-1 kernel rebases per tile (conv3x3_dma.hip,
+// which applies this check itself where it falls back to the self-loading kernel).  Any number of such images is fine: the image base is 64-bit.
+int sg_require_image_31(const ConvP& p) {
+    SG_REQUIRE((long)p.H * p.W * p.xpix < (1L << 31),
+               "srcgan_conv_igemm: one image of the input must be below 2 GiB for this kernel (%d x %d pixels of %ld bytes); only the loader-specialised "
+               "3x3 stride-1 form (pad 1, whole 64-byte input chunks, 18 rows below 2 GiB) takes larger images", p.H, p.W, p.xpix);
+    return 0;
+}
+
 // ---- step 3: the kernel family.  The parity forms (npar != 0) come first, each with the rule its kernel sets
 static int route(const srcgan_conv_desc* d, ConvP& p, hipStream_t st) {
     if (d->npar && d->kh == 3) {
@@ -86,6 +96,7 @@ static int route(const srcgan_conv_desc* d, ConvP& p, hipStream_t st) {
                    !d->x_plane && !d->y_plane && !d->sign_in && !d->sign_out,
                    "srcgan_conv_igemm: npar == 4 with a 3x3 kernel is the transposed stride-2 form: stride 2, pad 1, os 2, oa == ob == 0, OH x OW = H x W, "
                    "YH x YW = 2H x 2W, the four parity packs wpar_stride bytes apart, interleaved tensors, no sign masks");
+        SG_TRY(sg_require_image_31(p));
         p.npar = 4; p.wpar = d->wpar_stride;
         return sg_deconv_k3s2(p, d->dtype, st);
     }
@@ -99,10 +110,12 @@ static int route(const srcgan_conv_desc* d, ConvP& p, hipStream_t st) {
         SG_REQUIRE(d->npar == 4 && d->kh == 2 && d->kw == 2 && d->stride == 1 && d->wpar_stride > 0 && d->wpar_stride % 16 == 0 && !d->x_plane && !d->y_plane &&
                    !d->sign_in && !d->sign_out && !d->bias,
                    "srcgan_conv_igemm: npar must be 0 or 4 (2x2 stride-1 parity packs wpar_stride bytes apart, interleaved tensors, no bias / sign masks)");
+        SG_TRY(sg_require_image_31(p));
         p.wpar = d->wpar_stride;
         return sg_dgrad_s2k4(p, d->dtype, st);
     }
     if (d->kh == 3 && d->kw == 3 && d->stride == 1 && (!g_force_generic || d->x_plane)) return sg_conv3x3_dma(p, d->dtype, st);
+    SG_TRY(sg_require_image_31(p));
     return sg_conv_generic(p, d->dtype, d->kh, d->kw, d->stride, st);
 }
 

@@ -43,3 +43,4 @@ int sg_conv3x3_dma(const ConvP& p, int dtype, hipStream_t st);      // conv3x3_d
 int sg_dgrad_s2k4(const ConvP& p, int dtype, hipStream_t st);       // conv_par4.hip: npar == 4, 2x2 parity packs of a 4x4 stride-2 input gradient
 int sg_deconv_k3s2(const ConvP& p, int dtype, hipStream_t st);      // deconv_k3s2.hip: npar == 4, transposed 3x3 stride 2
 int sg_conv_generic(const ConvP& p, int dtype, int kh, int kw, int stride, hipStream_t st);      // conv_igemm.hip: every other shape
+int sg_require_image_31(const ConvP& p);                            // conv_entry.hip: one image of the input below 2 GiB (all but the loader-specialised 3x3 kernel)

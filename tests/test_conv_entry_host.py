@@ -18,6 +18,11 @@ SIGN_RULE = ("srcgan_conv_igemm: sign masks need a 3x3 s1 16-bit conv with Cout 
              "no mz beside sign_in); or Cout == 64: sign_out of the 1x1 four-parity form with act, sign_in of a 3x3 s1 conv without other operands")
 UP = dict(kh=1, kw=1, pad_y=0, pad_x=0, os=2, YH=16, YW=16, npar=4, wpar_stride=4096)          # the 1x1 four-parity form, well-formed
 
+# a single image of 8185 x 4100 pixels with 64 bf16 channels: 4,295,488,000 bytes
+BIG = dict(H=8185, W=4100, Cin=64, x_cs=64, OH=8185, OW=4100, YH=8185, YW=4100)
+IMAGE_RULE = ("srcgan_conv_igemm: one image of the input must be below 2 GiB for this kernel (%d x %d pixels of %d bytes); only the loader-specialised "
+              "3x3 stride-1 form (pad 1, whole 64-byte input chunks, 18 rows below 2 GiB) takes larger images")
+
 CASES = [
     ("null_pointer", dict(y=None), "srcgan_conv_igemm: null pointer"),
     ("bad_dtype", dict(dtype=7), "srcgan_conv_igemm: bad dtype 7"),
@@ -45,6 +50,13 @@ CASES = [
      "srcgan_conv_igemm: the transposed 3x3 stride-2 form needs output channels, strides and offsets that are multiples of 16 bytes"),
     ("sign_mask_needs_loader_kernel", dict(sign_in=AUX, x_plane=4096, pad_y=0, pad_x=0),
      "conv3x3: sign masks are only handled by the loader-specialised 16-bit kernel (Cout == 32, or Cout == 64 read-only without other operands)"),
+    # one image of 2 GiB or more: every kernel family but the loader-specialised 3x3 stride-1 one carries 32-bit offsets inside an image
+    ("image_2gib_generic", dict(BIG, kh=2, kw=2, stride=2, pad_y=0, pad_x=0, OH=4092, OW=2050, YH=4092, YW=2050), IMAGE_RULE % (8185, 4100, 128)),
+    ("image_2gib_1x1_pair", dict(BIG, **dict(UP, YH=16370, YW=8200)), IMAGE_RULE % (8185, 4100, 128)),
+    ("image_2gib_par4", dict(BIG, kh=2, kw=2, npar=4, wpar_stride=4096, os=2, YH=16370, YW=8200), IMAGE_RULE % (8185, 4100, 128)),
+    ("image_2gib_deconv", dict(BIG, stride=2, npar=4, wpar_stride=4096, os=2, YH=16370, YW=8200), IMAGE_RULE % (8185, 4100, 128)),
+    ("image_2gib_3x3_pad0", dict(BIG, pad_y=0, pad_x=0, OH=8183, OW=4098), IMAGE_RULE % (8185, 4100, 128)),
+    ("image_2gib_3x3_wide_rows", dict(BIG, H=18, W=310700, Cin=192, x_cs=192, OH=18, OW=310700, YH=18, YW=310700), IMAGE_RULE % (18, 310700, 384)),
     ("unsupported_kernel", dict(kh=6, kw=6, pad_y=2, pad_x=2), "srcgan_conv_igemm: unsupported kernel 6x6 stride 1"),
 ]
 
