@@ -639,6 +639,37 @@ size_t srcgan_ddbpn_infer_act_bytes(const srcgan_ddbpn_cfg* c);
 int srcgan_ddbpn_infer_plan(const srcgan_ddbpn_cfg* c, size_t* ranges, int cap);
 int srcgan_ddbpn_infer(const srcgan_ddbpn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
+/* RDN, the Residual Dense Network (reference src/model/rdn.py:45-105, arXiv 1802.08797): SFENet1 (3x3, n_colors -> G0) -> SFENet2 (3x3) ->
+ * D residual dense blocks [ C x (3x3 + ReLU, G0 + c G -> G, on the concatenation of the block's input and all earlier layers), 1x1 LFF
+ * (G0 + C G -> G0) + the block's input ] -> GFF.0 (1x1 over the concatenation of the D block outputs) -> GFF.1 (3x3) + SFENet1's output
+ * -> UPNet (3x3 to r^2 G + PixelShuffle(r) for r = 2, 3; twice with r = 2 at scale 4) -> 3x3 to n_colors.
+ * [B,n_colors,H,W] f32 NCHW -> [B,n_colors,H*scale,W*scale].  The reference's RDNconfig 'A' is (D, C, G) = (20, 6, 32), 'B' (16, 8, 64).
+ * No concatenation is made: block d owns one buffer of G0 + C G channels whose layers read a prefix and write their slice, the LFF
+ * writes the prefix of the next block's buffer, and GFF.0 runs as D 1x1 convolutions over K slices of its weight, one behind each
+ * block, summing into two alternating G0-channel accumulators (in a 16-bit dtype the running sum is rounded D times where the
+ * reference rounds once).  params / grads in parameters() order: SFENet1.{weight,bias}, SFENet2.*, RDBs.<d>.convs.<c>.conv.0.* for
+ * c < C then RDBs.<d>.LFF.*, GFF.0.*, GFF.1.*, UPNet.0.*, UPNet.2.* and at scale 4 UPNet.4.*: 4 + D (2 C + 2) + 8 tensors, two more at
+ * scale 4.  Refused: in_ch outside 1..8, scale not in {2, 3, 4}, D, C, G or G0 < 1, G0 or G no multiple of 32 (a slice starts at
+ * G0 + c G and has to start a K chunk of the 16-bit types), G0 + C G > 8192.  The infer entries are those of srcgan_rcan_infer; the
+ * activation part holds two dense buffers and a handful of G0-channel tensors and does not depend on D from 2 on. */
+typedef struct srcgan_rdn_cfg {
+    int in_ch;                  /* n_colors, also the output's channels */
+    int B, H, W;
+    int dtype;
+    int scale;
+    int G0, D, C, G;
+} srcgan_rdn_cfg;
+int srcgan_rdn_num_params(const srcgan_rdn_cfg* c);
+size_t srcgan_rdn_ws_bytes(const srcgan_rdn_cfg* c);
+size_t srcgan_rdn_bwd_scratch_bytes(const srcgan_rdn_cfg* c);
+int srcgan_rdn_forward(const srcgan_rdn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_rdn_backward(const srcgan_rdn_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                        float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_rdn_infer_ws_bytes(const srcgan_rdn_cfg* c);
+size_t srcgan_rdn_infer_act_bytes(const srcgan_rdn_cfg* c);
+int srcgan_rdn_infer_plan(const srcgan_rdn_cfg* c, size_t* ranges, int cap);
+int srcgan_rdn_infer(const srcgan_rdn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
 /* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
  * when strides and bases allow them, element by element otherwise).
  *   srcgan_maxpool2_nhwc:     nn.MaxPool2d(2, 2), ceil_mode = False: [B,H,W,C] -> [B,H/2,W/2,C]; an odd last row / column is dropped.

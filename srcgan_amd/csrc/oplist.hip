@@ -4,7 +4,7 @@
 //
 //   ResDeconv, ESPCN, SRCNN, EDSR     reference src/model/{resdeconv,espcn,srcnn,edsr}.py
 //   SRDenseNetA / SRDenseNetB         reference src/model/model.py:643-786
-//   RCAN, DDBPN                       reference src/model/{rcan,ddbpn}.py
+//   RCAN, DDBPN, RDN                  reference src/model/{rcan,ddbpn,rdn}.py
 //   frozen VGG16 / VGG19 features     reference src/losses.py:344-393, 455-470 (VGG16Loss, PerceptionLoss)
 #include "net_common.h"
 #include <map>
@@ -21,7 +21,8 @@
 // convolution with a fused ReLU is the gradient w.r.t. its pre-activation: whoever writes it applies the mask (the consumer's
 // dgrad epilogue, or srcgan_mask_inplace for the gradient arriving from the loss).
 namespace {
-struct RdT { int C, cs, H, W, act; size_t off; };       // act: produced by a convolution with a fused ReLU
+struct RdT { int C, cs, H, W, act; size_t off; int act0; };      // act: produced by a convolution with a fused ReLU -- its channels from act0 on
+                                                                  // (RDN's dense buffers: the prefix [0, G0) is a block's input, a plain sum)
 // What an op does.  Every place that branches on the kind is a switch over this enum WITHOUT a default, so -Wswitch names the switch a
 // new kind is missing from: a kind a walker has nothing to do for gets an explicit empty case, one it must never meet an "internal error".
 enum RdKind {
@@ -45,6 +46,8 @@ struct RdOp {
     int in, out, res, relu;
     int icoff, iC, ocoff, oC; // RD_CONV on a dense buffer: reads channels [icoff, icoff + iC) of `in`, writes [ocoff, ocoff + oC) of `out` (iC / oC == 0: the whole tensor)
     int rcoff;                // RD_PRELU: first channel of the residual in `res`
+    int wkoff, wktot;         // RD_CONV, wktot != 0: the weight is the K slice [wkoff, wkoff + cin) of a parameter [cout][wktot][k][k] (RDN's GFF.0, one slice
+                              // per block); the slices of one parameter cover its columns once, so each stores its part of the gradient
     // RD_CONV, proj_form != 0: a DDBPN projection in its stride-1 form over the space-to-depth view (k = ceil(proj_kernel / proj_stride) taps):
     // 1 = Conv2d proj_kernel x proj_kernel stride proj_stride (in = the gathered grid), 2 = ConvTranspose2d (out = the grid); w is the stored
     // weight, re-ordered into the f32 staging area wst (an offset into the pack region) before it is packed
@@ -63,6 +66,9 @@ struct RdOp {
 };
 static inline int rd_cin(const RdOp& o, const RdT& ti) { return o.iC ? o.iC : ti.C; }
 static inline int rd_cout(const RdOp& o, const RdT& to) { return o.oC ? o.oC : to.C; }
+// the canonical Conv2d layouts of an op's weight (forward pack / weight gradient; stride-1 input-gradient pack), K-sliced where the op says so
+static inline WLayout rd_lay_fwd(const RdOp& o, int cin) { WLayout L = lay_fwd(o.wktot ? o.wktot : cin, o.k, o.k); L.off += (long)o.wkoff * o.k * o.k; return L; }
+static inline WLayout rd_lay_dgrad(const RdOp& o, int cin) { WLayout L = lay_dgrad_s1(o.wktot ? o.wktot : cin, o.k, o.k); L.off += (long)o.wkoff * o.k * o.k; return L; }
 // ConvTranspose2d weight [ci][co][3][3], output parity q = (a, b): rows = co, k = ci, taps (wy, wx) in [0, a] x [0, b] with ky = a ? 2 - 2 wy : 1
 static inline void deconv3_pack(PackList& packs, const float* w, char* wp, const size_t wf[4], int cin, int cout) {
     for (int q = 0; q < 4; ++q) {
@@ -162,6 +168,7 @@ struct RdBuilder {
     RdPlan& P; Bump b; int np = 0; int B;
     int inorm = 0;            // normalisation layers are InstanceNorm2d (no parameters) instead of GroupNorm(32, C)
     int frozen = 0;           // no parameter takes a gradient and the ops form a chain: the backward scratch is two alternating gradient buffers
+    std::vector<std::pair<int, int>> gshare;      // (t, owner < t): tensor t's gradient lives in owner's buffer (equal shapes; never alive together)
     RdBuilder(RdPlan& p, int B_) : P(p), B(B_) {}
     int tensor(int C, int cs, int H, int W, int act = 0) { P.T.push_back(RdT{C, cs, H, W, act, b.take((size_t)B * H * W * cs * P.esz)}); return (int)P.T.size() - 1; }
     int conv(int in, int cout, int k, int s, int pad, bool bias = false, bool relu = false) {
@@ -178,6 +185,13 @@ struct RdBuilder {
         o.type = RD_CONV; o.in = in; o.out = out; o.res = -1; o.k = k; o.s = 1; o.pad = pad; o.relu = 1; o.w = np++; o.bias = np++;
         o.icoff = icoff; o.iC = iC; o.ocoff = ocoff; o.oC = oC;
         P.ops.push_back(o);
+    }
+    // convolution with explicit parameter indices between channel ranges of existing tensors (iC / oC == 0: the whole tensor)
+    RdOp& conv_to(int in, int icoff, int iC, int out, int ocoff, int oC, int k, int pad, int widx, int bidx, bool relu) {
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_CONV; o.in = in; o.out = out; o.res = -1; o.k = k; o.s = 1; o.pad = pad; o.relu = relu; o.w = widx; o.bias = bidx;
+        o.icoff = icoff; o.iC = iC; o.ocoff = ocoff; o.oC = oC;
+        P.ops.push_back(o); return P.ops.back();
     }
     int deconv3(int in, int cout) {
         const RdT ti = P.T[in];
@@ -297,8 +311,10 @@ struct RdBuilder {
             return;
         }
         long maxpix = 1;
+        std::vector<int> owner(P.T.size(), -1);
+        for (const auto& gs : gshare) owner[gs.first] = gs.second;
         for (size_t i = 0; i < P.T.size(); ++i) {
-            P.g[i] = s.take((size_t)B * P.T[i].H * P.T[i].W * P.T[i].cs * P.esz);
+            P.g[i] = owner[i] >= 0 ? P.g[owner[i]] : s.take((size_t)B * P.T[i].H * P.T[i].W * P.T[i].cs * P.esz);
             if ((long)B * P.T[i].H * P.T[i].W > maxpix) maxpix = (long)B * P.T[i].H * P.T[i].W;
         }
         RdBwdNeed need = {0, 0, 0};
@@ -553,6 +569,62 @@ static int ddbpn_plan(const srcgan_ddbpn_cfg* c, RdPlan& P) {
     nb.finish();
     return 0;
 }
+// RDN (rdn.py:45-105): SFENet1, SFENet2, D residual dense blocks of C 3x3 + ReLU layers and a 1x1 local fusion (LFF) + the block's input,
+// GFF = 1x1 over the concatenation of all D block outputs and a 3x3, + SFENet1's output, UPNet (PixelShuffle).  Parameter indices follow
+// parameters() order: SFENet1, SFENet2, per block convs.<c>.conv.0 and LFF, GFF.0, GFF.1, UPNet -- the GFF.0 slices run inside the block
+// loop, so every op of the trunk gets its indices by hand.
+//
+// No concatenation anywhere.  Block d owns a dense buffer of G0 + C G channels: layer c reads the prefix [0, G0 + c G) and writes the
+// slice [G0 + c G, + G); the LFF reads the whole buffer, takes the prefix [0, G0) -- the block's input -- as its residual and writes the
+// prefix of block d + 1's buffer (the last one a plain G0-channel tensor).  GFF.0 is linear, so it runs as D 1x1 convolutions over K
+// slices of its weight, acc_d = W[:, d G0 : (d + 1) G0] x_{d+1} (+ bias at d = 0) + acc_{d-1}, each right behind its block's LFF, on two
+// alternating accumulators (an op's output must not alias its operands).  Under the slot planner a dense buffer is dead once the next
+// block's LFF has read it: two dense buffers and a handful of G0-channel tensors, whatever D is.
+// Backward: the LFF's input gradient is the first writer of the whole gradient buffer of its block (the residual's share, dy on the
+// prefix, rides in the epilogue); the layers and the GFF slice add to the range they read, under ReLU' from channel G0 on.  The
+// accumulators share ONE gradient buffer (the residual's factor is 1: the gradient passes through), the dense buffers two.
+static int rdn_plan(const srcgan_rdn_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_rdn: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_rdn"));
+    SG_REQUIRE(c->in_ch >= 1 && c->in_ch <= 8, "srcgan_rdn: n_colors = %d must be in 1..8", c->in_ch);
+    SG_REQUIRE(c->scale == 2 || c->scale == 3 || c->scale == 4, "srcgan_rdn: scale = %d must be 2 or 3 or 4 (rdn.py:76-91)", c->scale);
+    SG_REQUIRE(c->D >= 1 && c->C >= 1 && c->G >= 1 && c->G0 >= 1, "srcgan_rdn: D, C, G and G0 must be positive (D = %d, C = %d, G = %d, G0 = %d)", c->D, c->C, c->G, c->G0);
+    SG_REQUIRE(c->G0 % 32 == 0 && c->G % 32 == 0, "srcgan_rdn: G0 = %d and G = %d must be multiples of 32 channels (the K chunk of the 16-bit types): layer c's "
+               "slice starts at channel G0 + c G", c->G0, c->G);
+    SG_REQUIRE((long)c->G0 + (long)c->C * c->G <= 8192, "srcgan_rdn: more than 8192 channels in a dense buffer (G0 + C G = %ld)", (long)c->G0 + (long)c->C * c->G);
+    SG_REQUIRE(c->D <= 4096, "srcgan_rdn: D = %d blocks (at most 4096)", c->D);
+    const int G0 = c->G0, D = c->D, C = c->C, G = c->G, Cb = G0 + C * G, r = c->scale, H = c->H, W = c->W;
+    const int per_block = 2 * C + 2, gff = 4 + D * per_block;
+    RdBuilder nb(P, c->B);
+    nb.input(c->in_ch, H, W);
+    const int f1 = nb.conv(0, G0, 3, 1, 1, true, false);                                   // SFENet1: parameters 0, 1
+    std::vector<int> buf(D);
+    for (int d = 0; d < D; ++d) {
+        buf[d] = nb.tensor(Cb, Cb, H, W, 1);
+        P.T[buf[d]].act0 = G0;
+        if (d >= 2) nb.gshare.push_back({buf[d], buf[d - 2]});
+    }
+    const int xD = nb.tensor(G0, G0, H, W), acc[2] = {nb.tensor(G0, G0, H, W), nb.tensor(G0, G0, H, W)};
+    nb.gshare.push_back({acc[1], acc[0]});
+    nb.conv_to(f1, 0, 0, buf[0], 0, G0, 3, 1, 2, 3, false);                                 // SFENet2
+    for (int d = 0; d < D; ++d) {
+        const int pb = 4 + d * per_block, out = d + 1 < D ? buf[d + 1] : xD;
+        for (int l = 0; l < C; ++l) nb.conv_to(buf[d], 0, G0 + l * G, buf[d], G0 + l * G, G, 3, 1, pb + 2 * l, pb + 2 * l + 1, true);
+        nb.conv_to(buf[d], 0, 0, out, 0, G0, 1, 0, pb + 2 * C, pb + 2 * C + 1, false).res = buf[d];           // LFF + x (rdn.py:43)
+        RdOp& g = nb.conv_to(out, 0, G0, acc[d & 1], 0, 0, 1, 0, gff, d == 0 ? gff + 1 : -1, false);           // GFF.0, slice d
+        g.res = d ? acc[(d - 1) & 1] : -1; g.wkoff = d * G0; g.wktot = D * G0;
+    }
+    nb.np = gff + 2;
+    int t = nb.conv(acc[(D - 1) & 1], G0, 3, 1, 1, true, false);                             // GFF.1, + f__1 (rdn.py:102-103)
+    P.ops.back().res = f1;
+    for (int f = 1; f < (r == 3 ? 2 : r); f *= 2) {                                          // UPNet (rdn.py:76-89)
+        t = nb.conv(t, G * (r == 3 ? 9 : 4), 3, 1, 1, true, false);
+        t = nb.shuffle(t, r == 3 ? 3 : 2);
+    }
+    nb.conv(t, c->in_ch, 3, 1, 1, true, false);
+    nb.finish();
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -574,7 +646,7 @@ static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, co
                                       o.proj_kernel, o.proj_stride, 0, (hipStream_t)st));
                 packs.add((const float*)(wp + o.wst), wp + o.wf[0], cout, cin, o.k, o.k, lay_fwd(cin, o.k, o.k));
             } else
-                packs.add(params[o.w], wp + o.wf[0], cout, cin, o.k, o.k, (long)cin * o.k * o.k, (long)o.k * o.k, o.k, 1, 0);
+                packs.add(params[o.w], wp + o.wf[0], cout, cin, o.k, o.k, rd_lay_fwd(o, cin));
             break;
         case RD_DECONV2:
             for (int q = 0; q < 4; ++q) packs.add(params[o.w], wp + o.wf[q], to.C, ti.C, 1, 1, 4, (long)to.C * 4, 0, 0, q);
@@ -608,7 +680,7 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
             cv.in(sl(xin, o.icoff), B, ti.H, ti.W, ti.C < 8 ? ti.cs : rd_cin(o, ti)).w(wp + o.wf[0], o.bias >= 0 ? params[o.bias] : nullptr)
                 .out(sl(out, o.ocoff), to.H, to.W, rd_cout(o, to)).pad(o.pad, o.pad);
             if (o.relu) { cv.lrelu(); cv.d.slope = 0.f; }
-            if (o.res >= 0) cv.res1(rd_t(w8, P.T[o.res]), to.C, 1.f);          // y = conv(x) + res (edsr.py:97-98)
+            if (o.res >= 0) cv.res1(rd_t(w8, P.T[o.res]), rd_cout(o, to), 1.f);        // y = conv(x) + res (edsr.py:97-98); a wider `res`: its prefix
             SG_TRY(cv.run(st));
             break;
         }
@@ -757,6 +829,7 @@ static int sr_infer_plan(const srcgan_srnet_cfg* c, RdPlan& P) {
 RD_INFER_PLAN(sd_infer_plan, srcgan_srdense_cfg, sd_plan, "srdense")
 RD_INFER_PLAN(rcan_infer_plan, srcgan_rcan_cfg, rcan_plan, "srcgan_rcan")
 RD_INFER_PLAN(ddbpn_infer_plan, srcgan_ddbpn_cfg, ddbpn_plan, "srcgan_ddbpn")
+RD_INFER_PLAN(rdn_infer_plan, srcgan_rdn_cfg, rdn_plan, "srcgan_rdn")
 #undef RD_INFER_PLAN
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -794,7 +867,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             case RD_CONV:
                 if (o.in == 0 && !dx_nchw) break;       // the network input's gradient is not wanted
                 if (o.proj_form) packs.add((const float*)(wp + o.wst), wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));     // staged by the forward
-                else if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));
+                else if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, rd_lay_dgrad(o, cin));
                 else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, 1, 1, 1, (long)cin, 0, 0, 0);
                 else o.s2(cin, cout).pack(packs, params[o.w], wp, o.wd);
                 break;
@@ -849,8 +922,10 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
         };
         switch (o.type) {
         case RD_CONV: {
-            const int pacc0 = seen_param[o.w];
-            if (o.res >= 0) {       // y = conv(x) + res: the residual's gradient is dy itself
+            const int pacc0 = o.wktot ? 0 : seen_param[o.w];       // (K slices of one parameter: disjoint columns, each stored once)
+            const bool res_in = o.res >= 0 && o.res == o.in;       // the residual is the input's own prefix (RDN's LFF): its gradient joins dx below
+            if (o.res >= 0 && !res_in && P.g[o.res] == P.g[o.out]) written[o.res] = 1;        // an accumulator chain on one gradient buffer: dy is it
+            else if (o.res >= 0 && !res_in) {       // y = conv(x) + res: the residual's gradient is dy itself
                 const RdT tr = P.T[o.res];
                 TRef dr = gt(o.res);
                 if (!written[o.res]) SG_HIP(hipMemcpyAsync(dr.p, dy.p, (size_t)B * tr.H * tr.W * tr.cs * P.esz, hipMemcpyDeviceToDevice, (hipStream_t)st));
@@ -861,7 +936,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             const bool fused_bias = o.bias >= 0 && o.k == 3 && G(o.w);
             if (G(o.w)) {       // a projection: the gradient of the stride-1 form, then back into the stored layout
                 float* gw = o.proj_form ? (float*)(s8 + P.projscr) : G(o.w);
-                SG_TRY(wgrad_call(dt, dy, to.H, to.W, cout, xin, B, ti.H, ti.W, cin, o.k, o.k, o.s, o.pad, o.pad, lay_fwd(cin, o.k, o.k), 1.f, slab, gw, st,
+                SG_TRY(wgrad_call(dt, dy, to.H, to.W, cout, xin, B, ti.H, ti.W, cin, o.k, o.k, o.s, o.pad, o.pad, rd_lay_fwd(o, cin), 1.f, slab, gw, st,
                                   fused_bias ? G(o.bias) : nullptr, pacc0));
                 if (o.proj_form) {
                     const int s2 = o.proj_stride * o.proj_stride;
@@ -879,8 +954,11 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                 if (o.s == 1) {
                     Conv cv(dt, o.k, o.k, 1);
                     cv.in(dy, B, to.H, to.W, to.C < 8 ? to.cs : cout).w(wp + o.wd[0]).out(dx, ti.H, ti.W, cin).pad(o.k - 1 - o.pad, o.k - 1 - o.pad);
+                    SG_REQUIRE(!(acc && res_in), "%s backward: internal error (a residual that is its op's input needs the first write)", tag);
                     if (acc) cv.res1(dx, cin, 1.f);
-                    if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
+                    else if (res_in) cv.res1(dy, cout, 1.f);        // dx[:, :cout] += dy
+                    const int c0 = std::max(0, ti.act0 - o.icoff);
+                    if (ti.act && c0 < cin) { cv.mask(xin, c0); cv.d.mslope = 0.f; }
                     SG_TRY(cv.run(st));
                 } else if (o.k == 1) {
                     if (!acc) SG_HIP(hipMemsetAsync(dx.p, 0, (size_t)B * ti.H * ti.W * ti.cs * P.esz, (hipStream_t)st));
@@ -1026,6 +1104,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
 RD_FAMILY(srnet, srcgan_srnet_cfg, sr_plan, sr_infer_plan, sr_tag(c->kind))
 RD_FAMILY(rcan, srcgan_rcan_cfg, rcan_plan, rcan_infer_plan, "rcan")
 RD_FAMILY(ddbpn, srcgan_ddbpn_cfg, ddbpn_plan, ddbpn_infer_plan, "ddbpn")
+RD_FAMILY(rdn, srcgan_rdn_cfg, rdn_plan, rdn_infer_plan, "rdn")
 
 // ResDeconv: the inference entry points take fold_tail, and the folded plan's job table has a tag of its own
 RD_TRAIN_ENTRIES(resdeconv, srcgan_resdeconv_cfg, rd_plan, "resdeconv")

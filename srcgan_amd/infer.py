@@ -156,7 +156,7 @@ def _scale(net) -> Optional[int]:
         return int(net._cfg[3])
     if isinstance(net, (M.SRCNN, M.SRDN, M.ResDeconv)):
         return 1
-    if isinstance(net, (M.RCAN, M.DDBPN)):
+    if isinstance(net, (M.RCAN, M.DDBPN, M.RDN)):
         return int(net.scale)
     return None
 
@@ -233,6 +233,10 @@ def receptive_halo(net) -> int:
                                     input pixels, x4 2 * (2 * 2 + 1) + 1 = 11.  (An HR -> LR network: ``upscale_scene`` does not run it.)
 
       DDBPN          by interval propagation through its eleven projection modules: ``_ddbpn_halo`` holds the derivation
+      RDN            D C + 5        SFENet1, SFENet2 (rdn.py:59-60) 2; one 3x3 per dense layer (rdn.py:18-20, 35-37): C per block, D blocks;
+                                    LFF and GFF.0 1x1 (rdn.py:40, 71) 0; GFF.1 (rdn.py:72) 1; UPNet.0 (rdn.py:78, 84) 1; PixelShuffle 0; x2 / x3:
+                                    the last convolution at HR (rdn.py:80): 1 HR pixel = 1 input pixel; x4: UPNet.2 at 2x (rdn.py:86) 1 and
+                                    the last convolution at 4x (rdn.py:88) 1 -> 1 at 2x: 2 pixels at 2x = 1 input pixel.  'A': 125, 'B': 133
 
     Networks with normalisation layers (ResDeconv, EDSR: GroupNorm / InstanceNorm statistics are taken over the whole image), RCAN
     (its channel attention pools over the whole image) and unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
@@ -245,6 +249,8 @@ def receptive_halo(net) -> int:
                          "tiles inexact at any halo; pass halo= explicitly (and blend='feather')")
     if isinstance(net, M.DDBPN):
         return _ddbpn_halo(net.scale)
+    if isinstance(net, M.RDN):
+        return net.D * net.C + 5
     if isinstance(net, M.LegacyRDDBNet):
         return 5 if net.mode == "x1" else 3
     if isinstance(net, M.RDDBNetB):

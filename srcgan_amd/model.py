@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
            "get_deconv_params"]
 
 
@@ -991,6 +991,89 @@ class DDBPN(_NativeRepr, nn.Module):
 
     def forward(self, x):
         return _oplist_forward(x, _DDBPN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
+
+
+# ------------------------------------------------------------------------------------------------ RDN
+_RDN_CONFIG = {"A": (20, 6, 32), "B": (16, 8, 64)}       # RDNconfig -> (D blocks, C layers per block, G growth) (rdn.py:53-56)
+
+
+class _RDBConv(_HolderOnly):
+    """Parameter holder of rdn.py:13-21 RDB_Conv: conv = [3x3, ReLU]."""
+
+    def __init__(self, in_channels, grow_rate):
+        super().__init__()
+        self.conv = nn.Sequential(nn.Conv2d(in_channels, grow_rate, 3, padding=1, stride=1), nn.ReLU())
+
+
+class _RDB(_HolderOnly):
+    """Parameter holder of rdn.py:27-40 RDB: convs = C dense layers, LFF = the 1x1 local feature fusion."""
+
+    def __init__(self, G0, G, C):
+        super().__init__()
+        self.convs = nn.Sequential(*[_RDBConv(G0 + c * G, G) for c in range(C)])
+        self.LFF = nn.Conv2d(G0 + C * G, G0, 1, padding=0, stride=1)
+
+
+def _rdn_cfg(x, items):
+    n_colors, scale, G0, D, Cl, G, dtype = items
+    _check_input(x, "RDN", n_colors, f"RDN expects [B,{n_colors},H,W]")
+    B, _, H, W = x.shape
+    return N.RdnCfg(n_colors, B, H, W, dtype, scale, G0, D, Cl, G), (B, n_colors, H * scale, W * scale)
+
+
+_RDN = _OpList("RDN", "srcgan_rdn", _rdn_cfg)
+
+
+class RDN(_NativeRepr, nn.Module):
+    """Residual Dense Network (arXiv 1802.08797), drop-in for reference ``model.rdn.RDN`` (src/model/rdn.py:45-105): ``RDN(args)`` with the
+    reference's attribute names (``scale`` -- a list, its first entry counts -- ``G0, RDNkSize, RDNconfig, n_colors``), or the same names as
+    keywords.  SFENet1 -> SFENet2 -> D residual dense blocks (C 3x3 + ReLU layers on the growing concatenation, a 1x1 local fusion, + the
+    block's input) -> GFF (1x1 over all D block outputs, 3x3) + SFENet1's output -> UPNet (PixelShuffle);
+    ``forward(x[B,n_colors,H,W]) -> [B,n_colors,H*scale,W*scale]``, scale 2, 3 or 4.  ``RDNconfig`` is 'A' (D, C, G = 20, 6, 32), 'B'
+    (16, 8, 64) or, beyond the reference, a tuple ``(D, C, G)``; G0 and G must be multiples of 32.  No concatenation is made (DESIGN.md
+    section 3.11).  Default torch initialisation, modules created in the reference's order: the same seed gives the same weights, and
+    ``state_dict`` has the reference's keys."""
+
+    def __init__(self, args=None, *, scale=2, G0=64, RDNkSize=3, RDNconfig="B", n_colors=3, dtype=None):
+        super().__init__()
+        if args is not None:
+            scale, G0, RDNkSize = getattr(args, "scale", scale), getattr(args, "G0", G0), getattr(args, "RDNkSize", RDNkSize)
+            RDNconfig, n_colors = getattr(args, "RDNconfig", RDNconfig), getattr(args, "n_colors", n_colors)
+        if isinstance(scale, (list, tuple)):
+            scale = scale[0]
+        scale, G0, n_colors = int(scale), int(G0), int(n_colors)
+        if int(RDNkSize) != 3:
+            raise NotImplementedError(f"RDN: RDNkSize = {RDNkSize}; the native network has the reference's default, 3x3 convolutions")
+        if isinstance(RDNconfig, str):
+            if RDNconfig not in _RDN_CONFIG:
+                raise KeyError(RDNconfig)          # the reference's own failure (rdn.py:53-56)
+            RDNconfig = _RDN_CONFIG[RDNconfig]
+        D, Cl, G = (int(v) for v in RDNconfig)
+        if scale not in (2, 3, 4):
+            raise ValueError("scale must be 2 or 3 or 4.")      # rdn.py:91
+        self.compute_dtype = N.dtype_name(dtype)
+        self.scale, self.D, self.C, self.G, self.G0 = scale, D, Cl, G, G0
+        self._cfg = (n_colors, scale, G0, D, Cl, G)
+        # the native planner owns the rules (1..8 colours, G0 and G multiples of 32, at most 8192 channels in a dense buffer): ask it first
+        probe = N.RdnCfg(n_colors, 1, 8, 8, N.dtype_id(self.compute_dtype), scale, G0, D, Cl, G)
+        if N.lib().srcgan_rdn_num_params(C.byref(probe)) < 0:
+            raise ValueError("RDN: " + (N.lib().srcgan_last_error() or b"").decode())
+        # creation order == registration order == the reference's (rdn.py:59-89)
+        self.SFENet1 = nn.Conv2d(n_colors, G0, 3, padding=1, stride=1)
+        self.SFENet2 = nn.Conv2d(G0, G0, 3, padding=1, stride=1)
+        self.RDBs = nn.ModuleList()
+        for _ in range(D):
+            self.RDBs.append(_RDB(G0, G, Cl))
+        self.GFF = nn.Sequential(nn.Conv2d(D * G0, G0, 1, padding=0, stride=1), nn.Conv2d(G0, G0, 3, padding=1, stride=1))
+        if scale == 4:
+            self.UPNet = nn.Sequential(nn.Conv2d(G0, G * 4, 3, padding=1, stride=1), nn.PixelShuffle(2), nn.Conv2d(G, G * 4, 3, padding=1, stride=1),
+                                       nn.PixelShuffle(2), nn.Conv2d(G, n_colors, 3, padding=1, stride=1))
+        else:
+            self.UPNet = nn.Sequential(nn.Conv2d(G0, G * scale * scale, 3, padding=1, stride=1), nn.PixelShuffle(scale),
+                                       nn.Conv2d(G, n_colors, 3, padding=1, stride=1))
+
+    def forward(self, x):
+        return _oplist_forward(x, _RDN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class _NLayerDFn(torch.autograd.Function):
