@@ -670,6 +670,60 @@ size_t srcgan_rdn_infer_act_bytes(const srcgan_rdn_cfg* c);
 int srcgan_rdn_infer_plan(const srcgan_rdn_cfg* c, size_t* ranges, int cap);
 int srcgan_rdn_infer(const srcgan_rdn_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
+/* MDSR, the multi-scale EDSR (reference src/model/mdsr.py:13-66 with common.py, arXiv 1707.02921): sub_mean -> head (3x3, 3 -> F) ->
+ * pre_process[idx] (two ResBlocks of 5x5 convolutions: conv + ReLU, conv, + the block's input) -> body (n_resblocks 3x3 ResBlocks and a
+ * 3x3 convolution) + the pre_process output -> upsample[idx] (3x3 to r^2 F + PixelShuffle(r): r = 3 once, r = 2 once / twice / three
+ * times for scale 2 / 4 / 8) -> tail (3x3, F -> 3) -> add_mean.  [B,3,H,W] f32 NCHW -> [B,3,H*s,W*s], s = scales[scale_idx].
+ * One module, several graphs: pre_process and upsample exist once per entry of scales, and scale_idx says which pair the call runs.
+ * params / grads hold ALL parameters in parameters() order (registration order, mdsr.py:22-23, 27, 41, 47-49): sub_mean.{weight,bias},
+ * add_mean.*, pre_process.<i>.{0,1}.body.{0,2}.* for every i, upsample.<i>.{0[,2[,4]]}.* for every i, head.0.*, body.<k>.body.{0,2}.*,
+ * body.<n_resblocks>.*, tail.0.*: 4 + 8 nscale + (2, 2, 4 or 6 per scale 2, 3, 4, 8) + 2 + 4 n_resblocks + 2 + 2 tensors.  The branches
+ * off the graph cost nothing: their weights are not packed, they take no gradient pass and no zero fill, their entries of grads (and of
+ * params) are never read and may be null, and every size query of {scales = {.., s, ..}, scale_idx -> s} equals that of {scales = {s},
+ * scale_idx = 0}.  The MeanShift layers are frozen (their grads entries must be null).  Refused: in_ch or out_ch != 3, nscale outside
+ * 1..4, a scale not in {2, 3, 4, 8}, scale_idx outside [0, nscale), n_feats no multiple of 16 or above 1024, n_resblocks < 1.  All ranks
+ * of a data-parallel step must use the same scale_idx.  The 5x5 convolutions run on the generic implicit-GEMM kernel.
+ *
+ * VDSR (reference src/model/vdsr.py:13-45): sub_mean -> 3x3 (3 -> F) + ReLU -> n_resblocks - 2 times 3x3 (F -> F) + ReLU -> 3x3 (F -> 3)
+ * + the sub_mean output -> add_mean.  [B,3,H,W] -> [B,3,H,W].  params / grads: sub_mean.*, add_mean.*, body.<k>.0.{weight,bias} for
+ * k < n_resblocks: 4 + 2 n_resblocks tensors.  Refused: in_ch != 3, n_resblocks < 2, n_feats no multiple of 16 or above 1024.
+ * The entry points of both families are those of srcgan_rcan_*. */
+typedef struct srcgan_mdsr_cfg {
+    int in_ch, out_ch;          /* both 3: MeanShift is a 3-channel convolution (common.py:16) */
+    int B, H, W;
+    int dtype;
+    int n_resblocks, n_feats;
+    int nscale;                 /* 1..4 */
+    int scales[4];              /* each 2, 3, 4 or 8 (common.py:63-84) */
+    int scale_idx;              /* the branch on the graph */
+} srcgan_mdsr_cfg;
+typedef struct srcgan_vdsr_cfg {
+    int in_ch;                  /* 3, also the output's channels */
+    int B, H, W;
+    int dtype;
+    int n_resblocks, n_feats;   /* n_resblocks >= 2 */
+} srcgan_vdsr_cfg;
+int srcgan_mdsr_num_params(const srcgan_mdsr_cfg* c);
+size_t srcgan_mdsr_ws_bytes(const srcgan_mdsr_cfg* c);
+size_t srcgan_mdsr_bwd_scratch_bytes(const srcgan_mdsr_cfg* c);
+int srcgan_mdsr_forward(const srcgan_mdsr_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_mdsr_backward(const srcgan_mdsr_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                         float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_mdsr_infer_ws_bytes(const srcgan_mdsr_cfg* c);
+size_t srcgan_mdsr_infer_act_bytes(const srcgan_mdsr_cfg* c);
+int srcgan_mdsr_infer_plan(const srcgan_mdsr_cfg* c, size_t* ranges, int cap);
+int srcgan_mdsr_infer(const srcgan_mdsr_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_vdsr_num_params(const srcgan_vdsr_cfg* c);
+size_t srcgan_vdsr_ws_bytes(const srcgan_vdsr_cfg* c);
+size_t srcgan_vdsr_bwd_scratch_bytes(const srcgan_vdsr_cfg* c);
+int srcgan_vdsr_forward(const srcgan_vdsr_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_vdsr_backward(const srcgan_vdsr_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                         float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_vdsr_infer_ws_bytes(const srcgan_vdsr_cfg* c);
+size_t srcgan_vdsr_infer_act_bytes(const srcgan_vdsr_cfg* c);
+int srcgan_vdsr_infer_plan(const srcgan_vdsr_cfg* c, size_t* ranges, int cap);
+int srcgan_vdsr_infer(const srcgan_vdsr_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
 /* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
  * when strides and bases allow them, element by element otherwise).
  *   srcgan_maxpool2_nhwc:     nn.MaxPool2d(2, 2), ceil_mode = False: [B,H,W,C] -> [B,H/2,W/2,C]; an odd last row / column is dropped.

@@ -115,6 +115,15 @@ class RdnCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("in_ch", "B", "H", "W", "dtype", "scale", "G0", "D", "C", "G")]
 
 
+class MdsrCfg(C.Structure):
+    _fields_ = ([(n, C.c_int) for n in ("in_ch", "out_ch", "B", "H", "W", "dtype", "n_resblocks", "n_feats", "nscale")]
+                + [("scales", C.c_int * 4), ("scale_idx", C.c_int)])
+
+
+class VdsrCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("in_ch", "B", "H", "W", "dtype", "n_resblocks", "n_feats")]
+
+
 class VggLossCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "B", "H", "W", "dtype")]
 
@@ -266,9 +275,11 @@ def _infer_rows(stem, cfg):
             f"srcgan_{stem}_infer_plan": (_I, [c, C.POINTER(C.c_size_t), _I]), f"srcgan_{stem}_infer": (_I, [c, _P, _P, _P, _P, _P])}
 
 
-for _stem, _cfg in (("resdeconv", ResDeconvCfg), ("srnet", SrNetCfg), ("srdense", SrDenseCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg), ("rdn", RdnCfg)):
+for _stem, _cfg in (("resdeconv", ResDeconvCfg), ("srnet", SrNetCfg), ("srdense", SrDenseCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg), ("rdn", RdnCfg),
+                    ("mdsr", MdsrCfg), ("vdsr", VdsrCfg)):
     SIGNATURES.update(_train_rows(_stem, _cfg))
-for _stem, _cfg in (("srnet", SrNetCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg), ("rdn", RdnCfg)):
+for _stem, _cfg in (("srnet", SrNetCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg), ("rdn", RdnCfg),
+                    ("mdsr", MdsrCfg), ("vdsr", VdsrCfg)):
     SIGNATURES.update(_infer_rows(_stem, _cfg))
 SIGNATURES.update({
     "srcgan_resdeconv_infer_ws_bytes": (_S, [C.POINTER(ResDeconvCfg), _I]),       # ResDeconv: fold_tail

@@ -4,7 +4,7 @@
 //
 //   ResDeconv, ESPCN, SRCNN, EDSR     reference src/model/{resdeconv,espcn,srcnn,edsr}.py
 //   SRDenseNetA / SRDenseNetB         reference src/model/model.py:643-786
-//   RCAN, DDBPN, RDN                  reference src/model/{rcan,ddbpn,rdn}.py
+//   RCAN, DDBPN, RDN, MDSR, VDSR      reference src/model/{rcan,ddbpn,rdn,mdsr,vdsr}.py
 //   frozen VGG16 / VGG19 features     reference src/losses.py:344-393, 455-470 (VGG16Loss, PerceptionLoss)
 #include "net_common.h"
 #include <map>
@@ -625,6 +625,82 @@ static int rdn_plan(const srcgan_rdn_cfg* c, RdPlan& P) {
     nb.finish();
     return 0;
 }
+// MDSR (mdsr.py:13-66).  One module, several graphs: pre_process[i] and upsample[i] exist once per entry of scales, and the plan holds the
+// ops of the pair scale_idx alone -- the other branches are parameter indices nobody refers to: not packed, no gradient pass, no zero
+// fill, their params / grads entries never read.  So every size of {scales, scale_idx = k} is that of {scales = {scales[k]}, 0}.
+// Parameter indices follow parameters() order = registration order: sub_mean, add_mean (:22-23), pre_process, upsample (the ModuleLists
+// of :27, 41 are assigned before head / body / tail at :47-49), head, body, tail -- every op gets its indices by hand.
+// A ResBlock (common.py:36-57) is conv + bias + ReLU, then conv + bias with `res` = the block's input; its input therefore has two
+// consumers (three for the pre_process output, which the body's last convolution adds: mdsr.py:56-57), and the backward gives it the
+// residual's share by a plain store and the convolutions' through the in-place residual operand, as for EDSR and RCAN.
+static int mdsr_up_params(int s) { return s == 8 ? 6 : s == 4 ? 4 : 2; }     // Upsampler (common.py:59-86): one conv per x2 stage, one for x3
+static int mdsr_plan(const srcgan_mdsr_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_mdsr: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_mdsr"));
+    SG_REQUIRE(c->in_ch == 3 && c->out_ch == 3, "srcgan_mdsr: n_colors must be 3 (MeanShift is a 3-channel convolution, common.py:16)");
+    SG_REQUIRE(c->nscale >= 1 && c->nscale <= 4, "srcgan_mdsr: nscale = %d must be in 1..4 (the scale list has at most 4 entries)", c->nscale);
+    for (int i = 0; i < c->nscale; ++i)
+        SG_REQUIRE(c->scales[i] == 2 || c->scales[i] == 3 || c->scales[i] == 4 || c->scales[i] == 8,
+                   "srcgan_mdsr: scales[%d] = %d must be 2, 3, 4 or 8 (common.py:63-84)", i, c->scales[i]);
+    SG_REQUIRE(c->scale_idx >= 0 && c->scale_idx < c->nscale, "srcgan_mdsr: scale_idx = %d must be in [0, nscale = %d)", c->scale_idx, c->nscale);
+    SG_REQUIRE(c->n_feats > 0 && c->n_feats % 16 == 0 && c->n_feats <= 1024, "srcgan_mdsr: n_feats = %d must be a multiple of 16, at most 1024", c->n_feats);
+    SG_REQUIRE(c->n_resblocks >= 1 && c->n_resblocks <= 100000, "srcgan_mdsr: n_resblocks = %d must be in 1..100000", c->n_resblocks);
+    const int F = c->n_feats, idx = c->scale_idx, s = c->scales[idx];
+    const int pre = 4 + 8 * idx;
+    int up = 4 + 8 * c->nscale, head = up;
+    for (int i = 0; i < c->nscale; ++i) { if (i < idx) up += mdsr_up_params(c->scales[i]); head += mdsr_up_params(c->scales[i]); }
+    const int body = head + 2, tail = body + 4 * c->n_resblocks + 2;
+    RdBuilder nb(P, c->B);
+    nb.input(3, c->H, c->W);
+    // a convolution with bias at parameters (w, w + 1)
+    auto cv = [&](int in, int cout, int k, int w, bool relu, int res) {
+        const int t = nb.conv(in, cout, k, 1, k / 2, true, relu);
+        RdOp& o = P.ops.back();
+        o.w = w; o.bias = w + 1; o.res = res;
+        return t;
+    };
+    auto resblock = [&](int x, int k, int w) { return cv(cv(x, F, k, w, true, -1), F, k, w + 2, false, x); };
+    int t = nb.meanshift(0);                                    // sub_mean: parameters 0, 1; add_mean: 2, 3
+    t = cv(t, F, 3, head, false, -1);
+    t = resblock(t, 5, pre);                                    // pre_process[idx] (:27-32, 54)
+    const int x = resblock(t, 5, pre + 4);
+    t = x;
+    for (int k = 0; k < c->n_resblocks; ++k) t = resblock(t, 3, body + 4 * k);
+    t = cv(t, F, 3, body + 4 * c->n_resblocks, false, x);       // res += x (:56-57): the pre_process output, not the head's
+    if (s == 3) { t = cv(t, 9 * F, 3, up, false, -1); t = nb.shuffle(t, 3); }
+    else for (int f = 1, w = up; f < s; f *= 2, w += 2) { t = cv(t, 4 * F, 3, w, false, -1); t = nb.shuffle(t, 2); }
+    t = cv(t, 3, 3, tail, false, -1);
+    nb.meanshift(t);
+    P.ops.back().w = 2; P.ops.back().bias = 3;
+    nb.np = tail + 2;
+    nb.finish();
+    return 0;
+}
+// the pack-cache tag stem of a branch: one job table per scale_idx, so set_scale between two steps re-stages none
+static inline const char* mdsr_tag(int idx) { return idx == 0 ? "mdsr0" : idx == 1 ? "mdsr1" : idx == 2 ? "mdsr2" : "mdsr3"; }
+// VDSR (vdsr.py:13-45): sub_mean, n_resblocks - 1 times 3x3 + ReLU (the first from the 3 colours), 3x3 to the 3 colours + the sub_mean
+// output (:41-42), add_mean.  parameters() order: sub_mean, add_mean (:21-22), body.<k>.0.  The sub_mean output has two consumers: the
+// last convolution's residual stores its gradient, the first convolution's input gradient adds to it in place.
+static int vdsr_plan(const srcgan_vdsr_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_vdsr: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_vdsr"));
+    SG_REQUIRE(c->in_ch == 3, "srcgan_vdsr: n_colors must be 3 (MeanShift is a 3-channel convolution, common.py:16)");
+    SG_REQUIRE(c->n_feats > 0 && c->n_feats % 16 == 0 && c->n_feats <= 1024, "srcgan_vdsr: n_feats = %d must be a multiple of 16, at most 1024", c->n_feats);
+    SG_REQUIRE(c->n_resblocks >= 2 && c->n_resblocks <= 100000, "srcgan_vdsr: n_resblocks = %d must be in 2..100000 (the first and the last convolution, vdsr.py:32-35)",
+               c->n_resblocks);
+    RdBuilder nb(P, c->B);
+    nb.input(3, c->H, c->W);
+    const int x = nb.meanshift(0);                              // sub_mean: parameters 0, 1
+    nb.np = 4;                                                  // add_mean: parameters 2, 3
+    int t = x;
+    for (int k = 0; k < c->n_resblocks - 1; ++k) t = nb.conv(t, c->n_feats, 3, 1, 1, true, true);
+    t = nb.conv(t, 3, 3, 1, 1, true, false);
+    P.ops.back().res = x;                                       // res += x (:41-42)
+    nb.meanshift(t);
+    P.ops.back().w = 2; P.ops.back().bias = 3; nb.np -= 2;
+    nb.finish();
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -830,6 +906,8 @@ RD_INFER_PLAN(sd_infer_plan, srcgan_srdense_cfg, sd_plan, "srdense")
 RD_INFER_PLAN(rcan_infer_plan, srcgan_rcan_cfg, rcan_plan, "srcgan_rcan")
 RD_INFER_PLAN(ddbpn_infer_plan, srcgan_ddbpn_cfg, ddbpn_plan, "srcgan_ddbpn")
 RD_INFER_PLAN(rdn_infer_plan, srcgan_rdn_cfg, rdn_plan, "srcgan_rdn")
+RD_INFER_PLAN(mdsr_infer_plan, srcgan_mdsr_cfg, mdsr_plan, "srcgan_mdsr")
+RD_INFER_PLAN(vdsr_infer_plan, srcgan_vdsr_cfg, vdsr_plan, "srcgan_vdsr")
 #undef RD_INFER_PLAN
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -1105,6 +1183,8 @@ RD_FAMILY(srnet, srcgan_srnet_cfg, sr_plan, sr_infer_plan, sr_tag(c->kind))
 RD_FAMILY(rcan, srcgan_rcan_cfg, rcan_plan, rcan_infer_plan, "rcan")
 RD_FAMILY(ddbpn, srcgan_ddbpn_cfg, ddbpn_plan, ddbpn_infer_plan, "ddbpn")
 RD_FAMILY(rdn, srcgan_rdn_cfg, rdn_plan, rdn_infer_plan, "rdn")
+RD_FAMILY(mdsr, srcgan_mdsr_cfg, mdsr_plan, mdsr_infer_plan, mdsr_tag(c->scale_idx))
+RD_FAMILY(vdsr, srcgan_vdsr_cfg, vdsr_plan, vdsr_infer_plan, "vdsr")
 
 // ResDeconv: the inference entry points take fold_tail, and the folded plan's job table has a tag of its own
 RD_TRAIN_ENTRIES(resdeconv, srcgan_resdeconv_cfg, rd_plan, "resdeconv")

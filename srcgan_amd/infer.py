@@ -158,6 +158,10 @@ def _scale(net) -> Optional[int]:
         return 1
     if isinstance(net, (M.RCAN, M.DDBPN, M.RDN)):
         return int(net.scale)
+    if isinstance(net, M.MDSR):
+        return int(net.scale[net.scale_idx])            # the branch ``set_scale`` chose
+    if isinstance(net, M.VDSR):
+        return 1                                        # three colours in and out: a ``cascade_scene(const=True)`` SR network on 3-channel input only
     return None
 
 
@@ -237,6 +241,13 @@ def receptive_halo(net) -> int:
                                     LFF and GFF.0 1x1 (rdn.py:40, 71) 0; GFF.1 (rdn.py:72) 1; UPNet.0 (rdn.py:78, 84) 1; PixelShuffle 0; x2 / x3:
                                     the last convolution at HR (rdn.py:80): 1 HR pixel = 1 input pixel; x4: UPNet.2 at 2x (rdn.py:86) 1 and
                                     the last convolution at 4x (rdn.py:88) 1 -> 1 at 2x: 2 pixels at 2x = 1 input pixel.  'A': 125, 'B': 133
+      MDSR           2 n_resblocks + 12
+                                    MeanShift 1x1 (common.py:16) 0; head (mdsr.py:25) 1; pre_process: two ResBlocks of two 5x5 (mdsr.py:27-32,
+                                    common.py:43-44) 4 * 2 = 8; body: two 3x3 per ResBlock and one 3x3 (mdsr.py:34-39) 2 n_resblocks + 1; the
+                                    skips spread nothing; Upsampler (common.py:63-82): its first 3x3 at LR 1; x2 / x3: the tail at HR
+                                    (mdsr.py:45): 1 HR pixel = 1 input pixel; x4: a 3x3 at 2x and the tail at 4x: 1 -> 1 at 2x, 2 at 2x = 1
+                                    input pixel; x8: one level more, again 1: the sampler and the tail cost 2 at every scale.  r16: 44
+      VDSR           n_resblocks    one 3x3 per BasicBlock (vdsr.py:24-35), all at the input's resolution; the skip spreads nothing.  r20: 20
 
     Networks with normalisation layers (ResDeconv, EDSR: GroupNorm / InstanceNorm statistics are taken over the whole image), RCAN
     (its channel attention pools over the whole image) and unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
@@ -251,6 +262,10 @@ def receptive_halo(net) -> int:
         return _ddbpn_halo(net.scale)
     if isinstance(net, M.RDN):
         return net.D * net.C + 5
+    if isinstance(net, M.MDSR):
+        return 2 * net.n_resblocks + 12
+    if isinstance(net, M.VDSR):
+        return net.n_resblocks
     if isinstance(net, M.LegacyRDDBNet):
         return 5 if net.mode == "x1" else 3
     if isinstance(net, M.RDDBNetB):

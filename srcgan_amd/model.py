@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
            "get_deconv_params"]
 
 
@@ -1074,6 +1074,143 @@ class RDN(_NativeRepr, nn.Module):
 
     def forward(self, x):
         return _oplist_forward(x, _RDN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
+
+
+# ------------------------------------------------------------------------------------------------ MDSR, VDSR
+# the reference's checkpoint addresses (mdsr.py:5-8, vdsr.py:6-8); never fetched
+_MDSR_URL = {"r16f64": "https://cv.snu.ac.kr/research/EDSR/models/mdsr_baseline-a00cab12.pt",
+             "r80f64": "https://cv.snu.ac.kr/research/EDSR/models/mdsr-4a78bedf.pt"}
+_VDSR_URL = {"r20f64": ""}
+
+
+class _ResBlock(_HolderOnly):
+    """Parameter holder of common.py:36-57 ResBlock (no BatchNorm, res_scale 1): body = [conv, ReLU, conv]."""
+
+    def __init__(self, n_feats, kernel_size):
+        super().__init__()
+        pad = kernel_size // 2
+        self.body = nn.Sequential(nn.Conv2d(n_feats, n_feats, kernel_size, padding=pad), nn.ReLU(True), nn.Conv2d(n_feats, n_feats, kernel_size, padding=pad))
+        self.res_scale = 1
+
+
+def _upsampler(scale, n_feats):
+    """common.py:59-86 Upsampler without BatchNorm or activation: [3x3 to 4 F, PixelShuffle(2)] per x2 stage, [3x3 to 9 F, PixelShuffle(3)]."""
+    m = []
+    for _ in range(1 if scale == 3 else int(math.log2(scale))):
+        r = 3 if scale == 3 else 2
+        m += [nn.Conv2d(n_feats, r * r * n_feats, 3, padding=1), nn.PixelShuffle(r)]
+    return nn.Sequential(*m)
+
+
+def _mdsr_cfg(x, items):
+    n_resblocks, n_feats, scales, scale_idx, dtype = items
+    _check_input(x, "MDSR", 3, "MDSR expects [B,3,H,W]")
+    B, _, H, W = x.shape
+    s = scales[scale_idx]
+    return (N.MdsrCfg(3, 3, B, H, W, dtype, n_resblocks, n_feats, len(scales), (C.c_int * 4)(*scales), scale_idx), (B, 3, H * s, W * s))
+
+
+def _vdsr_cfg(x, items):
+    n_resblocks, n_feats, dtype = items
+    _check_input(x, "VDSR", 3, "VDSR expects [B,3,H,W]")
+    B, _, H, W = x.shape
+    return N.VdsrCfg(3, B, H, W, dtype, n_resblocks, n_feats), (B, 3, H, W)
+
+
+_MDSR = _OpList("MDSR", "srcgan_mdsr", _mdsr_cfg)
+_VDSR = _OpList("VDSR", "srcgan_vdsr", _vdsr_cfg)
+
+
+class MDSR(_NativeRepr, nn.Module):
+    """Multi-scale EDSR (arXiv 1707.02921), drop-in for reference ``model.mdsr.MDSR`` (src/model/mdsr.py:13-66 with common.py): ``MDSR(args)``
+    with the reference's attribute names (``n_resblocks, n_feats, scale`` -- the list of scales -- ``rgb_range, n_colors``), or the same
+    names as keywords.  sub_mean -> head -> pre_process[scale_idx] (two 5x5 ResBlocks) -> body (n_resblocks 3x3 ResBlocks, a 3x3) + the
+    pre_process output -> upsample[scale_idx] (PixelShuffle) -> tail -> add_mean; ``forward(x[B,3,H,W]) -> [B,3,H*s,W*s]`` with
+    ``s = scale[scale_idx]``, each scale 2, 3, 4 or 8, at most four of them.  ``set_scale(i)`` chooses the branch of the next forward;
+    the other branches stay in the ``state_dict``, cost nothing and their ``.grad`` stays None, as in the reference.  In a data-parallel
+    step all ranks must use the same ``scale_idx`` (``GradSync`` reduces the gradients that exist).
+
+    Unlike the reference, which looks ``url['r{}f{}']`` up and so raises KeyError for every size but r16f64 / r80f64, any size the native
+    plan accepts is built: ``url`` is the reference's string where the key exists and None otherwise; nothing is ever fetched.
+    Default torch initialisation with the modules CREATED in the reference's order (head, pre_process, body, upsample, tail:
+    mdsr.py:25-45) and REGISTERED in its other one (pre_process, upsample, head, body, tail: :27, 41, 47-49): the same seed gives the
+    same weights, and ``state_dict`` has the reference's keys in its order."""
+
+    def __init__(self, args=None, *, n_resblocks=16, n_feats=64, scale=(2, 3, 4), rgb_range=255, n_colors=3, dtype=None):
+        super().__init__()
+        if args is not None:
+            n_resblocks, n_feats = getattr(args, "n_resblocks", n_resblocks), getattr(args, "n_feats", n_feats)
+            scale, rgb_range, n_colors = getattr(args, "scale", scale), getattr(args, "rgb_range", rgb_range), getattr(args, "n_colors", n_colors)
+        scale = [int(s) for s in (scale if isinstance(scale, (list, tuple)) else [scale])]
+        n_resblocks, n_feats = int(n_resblocks), int(n_feats)
+        if int(n_colors) != 3:
+            raise ValueError(f"MDSR: n_colors = {n_colors}; MeanShift is a 3-channel convolution (common.py:16)")
+        self.compute_dtype = N.dtype_name(dtype)
+        self.scale, self.n_resblocks, self.n_feats = scale, n_resblocks, n_feats
+        self.scale_idx = 0
+        self.url = _MDSR_URL.get(f"r{n_resblocks}f{n_feats}")
+        # the native planner owns the rules (1..4 scales of 2 / 3 / 4 / 8, n_feats % 16, n_resblocks >= 1): ask it first
+        probe = N.MdsrCfg(3, 3, 1, 8, 8, N.dtype_id(self.compute_dtype), n_resblocks, n_feats, len(scale), (C.c_int * 4)(*scale[:4]), 0)
+        if N.lib().srcgan_mdsr_num_params(C.byref(probe)) < 0:
+            raise ValueError("MDSR: " + (N.lib().srcgan_last_error() or b"").decode())
+        # creation order: the reference's (mdsr.py:22-45); registration order (= parameters() order): its other one (:22-23, 27, 41, 47-49)
+        self.sub_mean = _MeanShift(rgb_range)
+        self.add_mean = _MeanShift(rgb_range, sign=1)
+        head = [nn.Conv2d(3, n_feats, 3, padding=1)]
+        self.pre_process = nn.ModuleList([nn.Sequential(_ResBlock(n_feats, 5), _ResBlock(n_feats, 5)) for _ in scale])
+        body = [_ResBlock(n_feats, 3) for _ in range(n_resblocks)]
+        body.append(nn.Conv2d(n_feats, n_feats, 3, padding=1))
+        self.upsample = nn.ModuleList([_upsampler(s, n_feats) for s in scale])
+        tail = [nn.Conv2d(n_feats, 3, 3, padding=1)]
+        self.head = nn.Sequential(*head)
+        self.body = nn.Sequential(*body)
+        self.tail = nn.Sequential(*tail)
+
+    def set_scale(self, scale_idx):
+        self.scale_idx = scale_idx
+
+    def forward(self, x):
+        idx = int(self.scale_idx)
+        if not 0 <= idx < len(self.scale):
+            raise IndexError(f"MDSR: scale_idx = {self.scale_idx} with {len(self.scale)} scales")       # the reference's ModuleList would raise it
+        # the other branches are not on the graph (mdsr.py:54, 59): pass their parameters detached so autograd leaves their .grad at None
+        on = {id(p) for m in (self.pre_process[idx], self.upsample[idx]) for p in m.parameters()}
+        off = {id(p) for m in (self.pre_process, self.upsample) for p in m.parameters()} - on
+        ps = [p.detach() if id(p) in off else p for p in self.parameters()]
+        return _oplist_forward(x, _MDSR, (self.n_resblocks, self.n_feats, tuple(self.scale), idx, N.dtype_id(self.compute_dtype)), ps)
+
+
+class VDSR(_NativeRepr, nn.Module):
+    """Very Deep Super-Resolution network (arXiv 1511.04587), drop-in for reference ``model.vdsr.VDSR`` (src/model/vdsr.py:13-45):
+    ``VDSR(args)`` with the reference's attribute names (``n_resblocks, n_feats, rgb_range, n_colors``), or the same names as keywords.
+    sub_mean -> n_resblocks 3x3 convolutions, all but the last with ReLU, + the sub_mean output -> add_mean; ``forward(x[B,3,H,W])`` has
+    the input's size (the reference feeds it an interpolated image).  ``n_resblocks >= 2``.  ``url`` is the reference's string for r20f64
+    and None for every other size, which the reference refuses with KeyError; nothing is ever fetched.  Default torch initialisation in the
+    reference's order: the same seed gives the same weights, and ``state_dict`` has the reference's keys."""
+
+    def __init__(self, args=None, *, n_resblocks=20, n_feats=64, rgb_range=255, n_colors=3, dtype=None):
+        super().__init__()
+        if args is not None:
+            n_resblocks, n_feats = getattr(args, "n_resblocks", n_resblocks), getattr(args, "n_feats", n_feats)
+            rgb_range, n_colors = getattr(args, "rgb_range", rgb_range), getattr(args, "n_colors", n_colors)
+        n_resblocks, n_feats = int(n_resblocks), int(n_feats)
+        if int(n_colors) != 3:
+            raise ValueError(f"VDSR: n_colors = {n_colors}; MeanShift is a 3-channel convolution (common.py:16)")
+        self.compute_dtype = N.dtype_name(dtype)
+        self.n_resblocks, self.n_feats = n_resblocks, n_feats
+        self.url = _VDSR_URL.get(f"r{n_resblocks}f{n_feats}")
+        probe = N.VdsrCfg(3, 1, 8, 8, N.dtype_id(self.compute_dtype), n_resblocks, n_feats)
+        if N.lib().srcgan_vdsr_num_params(C.byref(probe)) < 0:
+            raise ValueError("VDSR: " + (N.lib().srcgan_last_error() or b"").decode())
+        self.sub_mean = _MeanShift(rgb_range)
+        self.add_mean = _MeanShift(rgb_range, sign=1)
+        # BasicBlock (common.py:23-34) without BatchNorm: [conv, ReLU], the last one [conv]
+        widths = [3] + [n_feats] * (n_resblocks - 1) + [3]
+        self.body = nn.Sequential(*[nn.Sequential(nn.Conv2d(widths[k], widths[k + 1], 3, padding=1), *([nn.ReLU(True)] if k < n_resblocks - 1 else []))
+                                    for k in range(n_resblocks)])
+
+    def forward(self, x):
+        return _oplist_forward(x, _VDSR, (self.n_resblocks, self.n_feats, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class _NLayerDFn(torch.autograd.Function):
