@@ -724,6 +724,48 @@ size_t srcgan_vdsr_infer_act_bytes(const srcgan_vdsr_cfg* c);
 int srcgan_vdsr_infer_plan(const srcgan_vdsr_cfg* c, size_t* ranges, int cap);
 int srcgan_vdsr_infer(const srcgan_vdsr_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
+/* nn.ReflectionPad2d and nn.Tanh (csrc/reflect_pad.hip), NHWC, channel stride *_cs elements, all three dtypes: 16-byte accesses along the
+ * channels when C, strides and bases allow them, element by element otherwise; 64-bit addresses, no atomics, every output element
+ * written exactly once.
+ *   srcgan_reflect_pad_nhwc:     y [B, H+2p, W+2p, C], y[i][j] = x[r(i, H)][r(j, W)], r(i, H) = p - i for i < p, 2 (H-1) - (i - p) for
+ *                                i >= H + p, i - p otherwise.  Refused before the launch: p < 1, p >= H, p >= W.
+ *   srcgan_reflect_pad_bwd_nhwc: the adjoint as a gather: dx[i][j] = sum of dy over R(i, H) x R(j, W); R(i, H) holds i + p, p - i when
+ *                                1 <= i <= p, and p + 2 (H-1) - i when H-1-p <= i <= H-2 (up to 9 terms on a small image).  Summed in f32,
+ *                                rows outer, ascending index; accumulate != 0: the old dx is added last; rounded once.
+ *   srcgan_tanh_forward:         y = tanh(z), computed in f32, on npix records of C channels.
+ *   srcgan_tanh_backward:        dz = dy (1 - y^2) from the saved y; accumulate != 0: added to the old dz (last), rounded once. */
+int srcgan_reflect_pad_nhwc(const void* x, int x_cs, void* y, int y_cs, int B, int H, int W, int C, int p, int dtype, void* stream);
+int srcgan_reflect_pad_bwd_nhwc(const void* dy, int dy_cs, void* dx, int dx_cs, int B, int H, int W, int C, int p, int accumulate, int dtype, void* stream);
+int srcgan_tanh_forward(const void* z, int z_cs, void* y, int y_cs, long npix, int C, int dtype, void* stream);
+int srcgan_tanh_backward(const void* dy, int dy_cs, const void* y, int y_cs, void* dz, int dz_cs, long npix, int C, int accumulate, int dtype, void* stream);
+
+/* ResnetGenerator (reference src/model/basicModel.py:141-254, the translator of multi-task.py's define_G(.., 'resnet_9blocks', 'instance'))
+ * with InstanceNorm2d (no parameters) and use_bias = True: ReflectionPad2d(3) -> 7x7 (in -> ngf) -> IN -> ReLU -> two 3x3 s2 p1
+ * (ngf -> 2 ngf -> 4 ngf), each IN + ReLU -> n_blocks x [pad 1, 3x3 p0, IN, ReLU, pad 1, 3x3 p0, IN, + the block's input] -> two
+ * ConvTranspose2d(k3, s2, p1, output_padding 1) (4 ngf -> 2 ngf -> ngf), each IN + ReLU -> ReflectionPad2d(3) -> 7x7 (ngf -> out) -> tanh.
+ * [B,in_ch,H,W] f32 NCHW -> [B,out_ch,H,W].  The padded tensors are materialised (srcgan_reflect_pad_nhwc) and the convolutions behind
+ * them run with pad 0.  padding = 0: 'reflect'; 1: 'zero' (the block convolutions take pad 1, their pad ops drop out; the pads around
+ * the 7x7 layers stay).  params / grads in parameters() order: every convolution's {weight, bias}: 2 (6 + 2 n_blocks) tensors.
+ * Refused: H or W no multiple of 4 or below 8 (the quarter-resolution pad 1 needs two pixels; an odd size gives the reference another
+ * output size), ngf no multiple of 16, in_ch or out_ch outside 1..8, n_blocks < 0, padding not 0 / 1.  Entry points as srcgan_rcan_*. */
+typedef struct srcgan_resnetgen_cfg {
+    int in_ch, out_ch;
+    int B, H, W;
+    int dtype;
+    int ngf, n_blocks;
+    int padding;                /* 0 = 'reflect', 1 = 'zero' */
+} srcgan_resnetgen_cfg;
+int srcgan_resnetgen_num_params(const srcgan_resnetgen_cfg* c);
+size_t srcgan_resnetgen_ws_bytes(const srcgan_resnetgen_cfg* c);
+size_t srcgan_resnetgen_bwd_scratch_bytes(const srcgan_resnetgen_cfg* c);
+int srcgan_resnetgen_forward(const srcgan_resnetgen_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_resnetgen_backward(const srcgan_resnetgen_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                              float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_resnetgen_infer_ws_bytes(const srcgan_resnetgen_cfg* c);
+size_t srcgan_resnetgen_infer_act_bytes(const srcgan_resnetgen_cfg* c);
+int srcgan_resnetgen_infer_plan(const srcgan_resnetgen_cfg* c, size_t* ranges, int cap);
+int srcgan_resnetgen_infer(const srcgan_resnetgen_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
 /* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
  * when strides and bases allow them, element by element otherwise).
  *   srcgan_maxpool2_nhwc:     nn.MaxPool2d(2, 2), ceil_mode = False: [B,H,W,C] -> [B,H/2,W/2,C]; an odd last row / column is dropped.

@@ -477,6 +477,7 @@ static int dispatch_wgrad(const WgradP& p, int kh, int kw, int s, hipStream_t st
     SG_CASE(5, 5, 1, 8, 7, false)
     if constexpr (MT == 1) { SG_CASE(9, 9, 1, 8, 9, false) }
     if constexpr (MT == 1) { SG_CASE(7, 7, 2, 4, 8, false) }     // 49 taps: 7 per wave x 16 accumulator registers, 32-row tiles only
+    if constexpr (MT == 1) { SG_CASE(7, 7, 1, 8, 7, false) }     // ResnetGenerator's 7x7 layers: 7 taps per wave on 7 waves
 #undef SG_CASE
     SG_FAIL("srcgan_conv_wgrad: unsupported kernel %dx%d stride %d", kh, kw, s);
 }

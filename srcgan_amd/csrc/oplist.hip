@@ -5,6 +5,7 @@
 //   ResDeconv, ESPCN, SRCNN, EDSR     reference src/model/{resdeconv,espcn,srcnn,edsr}.py
 //   SRDenseNetA / SRDenseNetB         reference src/model/model.py:643-786
 //   RCAN, DDBPN, RDN, MDSR, VDSR      reference src/model/{rcan,ddbpn,rdn,mdsr,vdsr}.py
+//   ResnetGenerator                   reference src/model/basicModel.py:141-254
 //   frozen VGG16 / VGG19 features     reference src/losses.py:344-393, 455-470 (VGG16Loss, PerceptionLoss)
 #include "net_common.h"
 #include <map>
@@ -31,7 +32,7 @@ enum RdKind {
     RD_DECONV2,       // ConvTranspose2d k2 s2
     RD_SHUFFLE,       // PixelShuffle(k)
     RD_FOLD_TAIL,     // (inference plans only) ConvTranspose2d k2 s2 followed by a bias-free 3x3 conv, folded into four parity 2x2 convs
-    RD_DECONV3,       // ConvTranspose2d k3 s2 p1 output_padding 1 + bias + ReLU (deconv_k3s2.hip)
+    RD_DECONV3,       // ConvTranspose2d k3 s2 p1 output_padding 1 + bias (+ ReLU) (deconv_k3s2.hip)
     RD_POOL,          // MaxPool2d(2, 2) (vgg_loss.hip)
     RD_ATTN,          // channel attention + block residual (chan_attn.hip): in = t, res = the block's input, w = conv_du.0.weight (its bias and
                       // conv_du.2.{weight,bias} follow), stats = the op's `saved` region
@@ -40,6 +41,8 @@ enum RdKind {
     RD_PRELU,         // per-channel PReLU (+ bias)(+ beta * res) (back_proj.hip): in = the pre-activation z, kept for the backward -- a plain
                       // tensor (scale 1) or the grid tensor of a transposed projection, cropped while it is read (scale, shift of the grid);
                       // w = the slope's parameter, bias = the transposed projection's bias or -1, res at channel rcoff of its tensor
+    RD_REFLECT,       // ReflectionPad2d(pad) (reflect_pad.hip): the padded tensor is materialised, the convolution behind it runs with pad 0
+    RD_TANH,          // Tanh (reflect_pad.hip); the backward reads the saved output
 };
 struct RdOp {
     RdKind type;
@@ -95,6 +98,7 @@ static RdFwdNeed rd_fwd_need(const RdPlan& P, const RdOp& o) {
     case RD_NORM: return {(size_t)P.B * o.ngrp * 2 * sizeof(float), 0};
     case RD_ATTN: return {(size_t)P.B * (2 * ti.C + o.attn_width) * sizeof(float), srcgan_ca_scratch_floats(P.B, (long)ti.H * ti.W, ti.C)};      // saved {p, h, s}
     case RD_CONV: case RD_DECONV2: case RD_SHUFFLE: case RD_FOLD_TAIL: case RD_DECONV3: case RD_POOL: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU:
+    case RD_REFLECT: case RD_TANH:
         break;
     }
     return {0, 0};
@@ -110,7 +114,7 @@ static RdBwdNeed rd_bwd_need(const RdPlan& P, const RdOp& o) {
     case RD_DECONV2: return {wgrad_slab(P.B, ti.H, ti.W, ti.C, to.C, 2, 2, 2), 0, 0};
     case RD_DECONV3: return {wgrad_slab(P.B, ti.H, ti.W, ti.C, to.C, 3, 3, 2), 0, 0};
     case RD_PRELU: return {0, 0, srcgan_prelu_scratch_floats(P.B, ti.H, ti.W, o.oC, o.scale)};
-    case RD_NORM: case RD_SHUFFLE: case RD_FOLD_TAIL: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER:
+    case RD_NORM: case RD_SHUFFLE: case RD_FOLD_TAIL: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_REFLECT: case RD_TANH:
         break;
     }
     return {0, 0, 0};
@@ -157,7 +161,7 @@ static size_t rd_layout_packs(RdPlan& P, bool train) {
             if (train) o.wd[0] = pk(ti.C, to.C, 9);
             break;
         }
-        case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU:
+        case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU: case RD_REFLECT: case RD_TANH:
             break;              // no packed weights
         }
     }
@@ -193,10 +197,24 @@ struct RdBuilder {
         o.icoff = icoff; o.iC = iC; o.ocoff = ocoff; o.oC = oC;
         P.ops.push_back(o); return P.ops.back();
     }
-    int deconv3(int in, int cout) {
+    int deconv3(int in, int cout, bool relu = true) {
         const RdT ti = P.T[in];
         RdOp o; memset(&o, 0, sizeof(o));
-        o.type = RD_DECONV3; o.in = in; o.out = tensor(cout, cout, 2 * ti.H, 2 * ti.W, 1); o.res = -1; o.k = 3; o.s = 2; o.pad = 1; o.relu = 1; o.w = np++; o.bias = np++;
+        o.type = RD_DECONV3; o.in = in; o.out = tensor(cout, cout, 2 * ti.H, 2 * ti.W, relu); o.res = -1; o.k = 3; o.s = 2; o.pad = 1; o.relu = relu; o.w = np++; o.bias = np++;
+        P.ops.push_back(o); return o.out;
+    }
+    int reflect(int in, int p) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_REFLECT; o.in = in; o.res = -1; o.pad = p; o.w = -1; o.bias = -1;
+        o.out = tensor(ti.C, ti.cs, ti.H + 2 * p, ti.W + 2 * p);
+        P.ops.push_back(o); return o.out;
+    }
+    int tanh(int in) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_TANH; o.in = in; o.res = -1; o.w = -1; o.bias = -1;
+        o.out = tensor(ti.C, ti.cs, ti.H, ti.W);
         P.ops.push_back(o); return o.out;
     }
     // the last op applies the module of op `first` again (same parameters, same packs)
@@ -701,6 +719,51 @@ static int vdsr_plan(const srcgan_vdsr_cfg* c, RdPlan& P) {
     nb.finish();
     return 0;
 }
+// ResnetGenerator (basicModel.py:141-254) with InstanceNorm2d (no parameters) and use_bias = True: pad 3, 7x7, IN, ReLU; two 3x3 s2 p1,
+// each IN + ReLU; n_blocks x [pad 1, 3x3 p0, IN, ReLU, pad 1, 3x3 p0, IN, + x]; two ConvTranspose2d k3 s2 p1 op1 WITHOUT the fused ReLU,
+// each IN + ReLU; pad 3, 7x7 + bias, tanh.  parameters() order = the order the ops are built in.  The padded tensors are materialised and
+// the convolutions behind them run with pad 0.  A block's input has two consumers: the closing norm's residual stores its gradient
+// first (the backward walks in reverse), the pad's backward -- or, with padding 'zero', the convolution's input gradient -- adds.
+// Every bias but the last sits in front of an InstanceNorm: its gradient is zero in exact arithmetic and is computed like any other.
+static int resnetgen_plan(const srcgan_resnetgen_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_resnetgen: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_resnetgen"));
+    SG_REQUIRE(c->in_ch >= 1 && c->in_ch <= 8 && c->out_ch >= 1 && c->out_ch <= 8, "srcgan_resnetgen: input_nc = %d and output_nc = %d must be in 1..8", c->in_ch, c->out_ch);
+    SG_REQUIRE(c->H >= 8 && c->W >= 8 && c->H % 4 == 0 && c->W % 4 == 0, "srcgan_resnetgen: H = %d and W = %d must be multiples of 4, at least 8 (two stride-2 stages "
+               "mirrored by two x2 transposed convolutions; the reflection pad at a quarter of the resolution needs two pixels)", c->H, c->W);
+    SG_REQUIRE(c->ngf > 0 && c->ngf % 16 == 0 && c->ngf <= 1024, "srcgan_resnetgen: ngf = %d must be a multiple of 16, at most 1024", c->ngf);
+    SG_REQUIRE(c->n_blocks >= 0 && c->n_blocks <= 4096, "srcgan_resnetgen: n_blocks = %d must be in 0..4096", c->n_blocks);
+    SG_REQUIRE(c->padding == 0 || c->padding == 1, "srcgan_resnetgen: padding must be 0 ('reflect') or 1 ('zero')");
+    const int F = c->ngf, bp = c->padding == 1 ? 1 : 0;
+    RdBuilder nb(P, c->B);
+    nb.inorm = 1;
+    nb.input(c->in_ch, c->H, c->W);
+    int t = nb.reflect(0, 3);
+    t = nb.conv(t, F, 7, 1, 0, true, false);
+    t = nb.gn(t, -1, 1);
+    for (int i = 0; i < 2; ++i) {
+        t = nb.conv(t, (2 << i) * F, 3, 2, 1, true, false);
+        t = nb.gn(t, -1, 1);
+    }
+    for (int k = 0; k < c->n_blocks; ++k) {         // ResnetBlock (:200-254)
+        const int x = t;
+        t = bp ? x : nb.reflect(x, 1);
+        t = nb.conv(t, 4 * F, 3, 1, bp, true, false);
+        t = nb.gn(t, -1, 1);
+        if (!bp) t = nb.reflect(t, 1);
+        t = nb.conv(t, 4 * F, 3, 1, bp, true, false);
+        t = nb.gn(t, x, 0);
+    }
+    for (int i = 0; i < 2; ++i) {
+        t = nb.deconv3(t, (2 >> i) * F, false);
+        t = nb.gn(t, -1, 1);
+    }
+    t = nb.reflect(t, 3);
+    t = nb.conv(t, c->out_ch, 7, 1, 0, true, false);
+    nb.tanh(t);
+    nb.finish();
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -729,7 +792,7 @@ static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, co
             break;
         case RD_DECONV3: deconv3_pack(packs, params[o.w], wp, o.wf, ti.C, to.C); break;
         case RD_FOLD_TAIL: fold = &o; break;        // composed from two sources, behind the batched launch
-        case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU:
+        case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU: case RD_REFLECT: case RD_TANH:
             break;                      // no packed weights
         }
     }
@@ -788,7 +851,8 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
         case RD_DECONV3: {
             // output pixel (2i + a, 2j + b) = the 1, 2, 2 or 4 taps of parity (a, b) over x[i..i+1][j..j+1]: all four in one launch
             Conv cv(dt, 3, 3, 2);
-            cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0], params[o.bias]).out(out, ti.H, ti.W, to.C).pad(1, 1).scatter(2, 0, 0, to.H, to.W).lrelu();
+            cv.in(xin, B, ti.H, ti.W, ti.C).w(wp + o.wf[0], params[o.bias]).out(out, ti.H, ti.W, to.C).pad(1, 1).scatter(2, 0, 0, to.H, to.W);
+            if (o.relu) cv.lrelu();
             cv.d.slope = 0.f; cv.d.npar = 4; cv.d.wpar_stride = (long)(o.wf[1] - o.wf[0]);
             SG_TRY(cv.run(st));
             break;
@@ -814,6 +878,12 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
                                         (char*)out.p + (size_t)o.ocoff * P.esz, to.cs, B, to.H, to.W, o.oC, o.scale, o.shift, ti.H, ti.W, dt, st));
             break;
         }
+        case RD_REFLECT:        // all cs channels: an image record's zero channels stay zero
+            SG_TRY(srcgan_reflect_pad_nhwc(xin.p, ti.cs, out.p, to.cs, B, ti.H, ti.W, ti.cs, o.pad, dt, st));
+            break;
+        case RD_TANH:
+            SG_TRY(srcgan_tanh_forward(xin.p, ti.cs, out.p, to.cs, (long)B * ti.H * ti.W, ti.cs, dt, st));
+            break;
         }
     }
     return 0;
@@ -908,6 +978,7 @@ RD_INFER_PLAN(ddbpn_infer_plan, srcgan_ddbpn_cfg, ddbpn_plan, "srcgan_ddbpn")
 RD_INFER_PLAN(rdn_infer_plan, srcgan_rdn_cfg, rdn_plan, "srcgan_rdn")
 RD_INFER_PLAN(mdsr_infer_plan, srcgan_mdsr_cfg, mdsr_plan, "srcgan_mdsr")
 RD_INFER_PLAN(vdsr_infer_plan, srcgan_vdsr_cfg, vdsr_plan, "srcgan_vdsr")
+RD_INFER_PLAN(resnetgen_infer_plan, srcgan_resnetgen_cfg, resnetgen_plan, "srcgan_resnetgen")
 #undef RD_INFER_PLAN
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -935,6 +1006,10 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
     char* w8 = (char*)ws; char* s8 = (char*)scratch; char* wp = w8 + P.wpk;
     float* slab = (float*)(s8 + P.slab); float* gnscr = (float*)(s8 + P.gnscr); float* colscr = (float*)(s8 + P.colscr);
     auto G = [&](int idx) { return idx >= 0 ? grads[idx] : nullptr; };
+    // tensors whose gradient nobody wants: the network input when dx_nchw is null, and its reflection-padded copy
+    std::vector<char> nograd(P.T.size(), 0);
+    nograd[0] = !dx_nchw;
+    for (const RdOp& o : P.ops) if (o.type == RD_REFLECT && nograd[o.in]) nograd[o.out] = 1;
     {   // dgrad weight packs
         PackList packs(dt, wp);
         for (const RdOp& o : P.ops) {
@@ -943,7 +1018,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             if (o.share) continue;
             switch (o.type) {
             case RD_CONV:
-                if (o.in == 0 && !dx_nchw) break;       // the network input's gradient is not wanted
+                if (nograd[o.in]) break;                // the network input's gradient is not wanted
                 if (o.proj_form) packs.add((const float*)(wp + o.wst), wp + o.wd[0], cin, cout, o.k, o.k, lay_dgrad_s1(cin, o.k, o.k));     // staged by the forward
                 else if (o.s == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, o.k, o.k, rd_lay_dgrad(o, cin));
                 else if (o.k == 1) packs.add(params[o.w], wp + o.wd[0], cin, cout, 1, 1, 1, (long)cin, 0, 0, 0);
@@ -957,7 +1032,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                 break;
             case RD_FOLD_TAIL:
                 SG_FAIL("%s backward: internal error (a folded tail in a training plan)", tag);
-            case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU:
+            case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU: case RD_REFLECT: case RD_TANH:
                 break;              // no packed weights
             }
         }
@@ -985,10 +1060,11 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             if (to.act) SG_TRY(srcgan_mask_inplace(s8 + P.g[o.out], w8 + to.off, 0.f, (long)B * to.H * to.W * to.cs, dt, st));
             written[o.out] = 1;
         }
+        if (nograd[o.out]) continue;
         SG_REQUIRE(written[o.out], "%s backward: internal error (gradient of tensor %d missing)", tag, o.out);
         const int cin = rd_cin(o, ti), cout = rd_cout(o, to);
         TRef xin = sl(rd_t(w8, ti), o.icoff), dy = sl(gt(o.out), o.ocoff);
-        const bool need_dx = o.in != 0 || dx_nchw;
+        const bool need_dx = !nograd[o.in];
         TRef dx = need_dx ? sl(gt(o.in), o.icoff) : TNULL;
         bool acc = need_dx && written[o.in];
         // a module applied twice (SRDenseNet's shared up- / down-sampler): the later use's parameter gradients add to the earlier one's
@@ -1130,6 +1206,18 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             SG_TRY(srcgan_pixel_shuffle_nhwc(dy.p, to.cs, dx.p, ti.cs, B, ti.H, ti.W, to.C, o.k, 1, dt, st));
             written[o.in] = 1;
             break;
+        case RD_REFLECT:        // a block's input feeds the pad and the block's closing residual: the second contribution adds
+            SG_REQUIRE(!ti.act, "%s backward: internal error (reflection pad of a tensor with a fused activation)", tag);
+            if (need_dx) {
+                SG_TRY(srcgan_reflect_pad_bwd_nhwc(dy.p, to.cs, dx.p, ti.cs, B, ti.H, ti.W, ti.cs, o.pad, acc, dt, st));
+                written[o.in] = 1;
+            }
+            break;
+        case RD_TANH:
+            SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (tanh input has two consumers or a fused activation)", tag);
+            SG_TRY(srcgan_tanh_backward(dy.p, to.cs, w8 + to.off, to.cs, dx.p, ti.cs, (long)B * ti.H * ti.W, ti.cs, 0, dt, st));
+            written[o.in] = 1;
+            break;
         case RD_FOLD_TAIL:
             SG_FAIL("%s backward: internal error (a folded tail in a training plan)", tag);
         }
@@ -1185,6 +1273,7 @@ RD_FAMILY(ddbpn, srcgan_ddbpn_cfg, ddbpn_plan, ddbpn_infer_plan, "ddbpn")
 RD_FAMILY(rdn, srcgan_rdn_cfg, rdn_plan, rdn_infer_plan, "rdn")
 RD_FAMILY(mdsr, srcgan_mdsr_cfg, mdsr_plan, mdsr_infer_plan, mdsr_tag(c->scale_idx))
 RD_FAMILY(vdsr, srcgan_vdsr_cfg, vdsr_plan, vdsr_infer_plan, "vdsr")
+RD_FAMILY(resnetgen, srcgan_resnetgen_cfg, resnetgen_plan, resnetgen_infer_plan, "resnetgen")
 
 // ResDeconv: the inference entry points take fold_tail, and the folded plan's job table has a tag of its own
 RD_TRAIN_ENTRIES(resdeconv, srcgan_resdeconv_cfg, rd_plan, "resdeconv")

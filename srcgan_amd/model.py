@@ -24,8 +24,8 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
-           "get_deconv_params"]
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "ResnetGenerator", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+           "get_deconv_params", "Identity", "get_norm_layer", "init_weights", "init_net", "define_G"]
 
 
 def get_deconv_params(upscale_factor):
@@ -1211,6 +1211,168 @@ class VDSR(_NativeRepr, nn.Module):
 
     def forward(self, x):
         return _oplist_forward(x, _VDSR, (self.n_resblocks, self.n_feats, N.dtype_id(self.compute_dtype)), list(self.parameters()))
+
+
+# ------------------------------------------------------------------------------------------------ ResnetGenerator, define_G
+class Identity(nn.Module):
+    """The module ``get_norm_layer('none')`` puts where a normalisation layer would be: it returns its input."""
+
+    def forward(self, x):
+        return x
+
+
+# norm_type -> the factory ``norm_layer(channels)`` of basicModel.get_norm_layer: BatchNorm2d with affine parameters and running
+# statistics, InstanceNorm2d with neither, or no normalisation at all
+_NORM_FACTORIES = {
+    'batch': functools.partial(nn.BatchNorm2d, affine=True, track_running_stats=True),
+    'instance': functools.partial(nn.InstanceNorm2d, affine=False, track_running_stats=False),
+    'none': lambda channels: Identity(),
+}
+# init_type -> what it does to a weight tensor (init_gain is unused by 'kaiming', as in the reference)
+_WEIGHT_INITS = {
+    'normal': lambda w, gain: nn.init.normal_(w, 0.0, gain),
+    'xavier': lambda w, gain: nn.init.xavier_normal_(w, gain=gain),
+    'kaiming': lambda w, gain: nn.init.kaiming_normal_(w, a=0, mode='fan_in'),
+    'orthogonal': lambda w, gain: nn.init.orthogonal_(w, gain=gain),
+}
+_RESNET_BLOCKS = {'resnet_9blocks': 9, 'resnet_6blocks': 6}
+
+
+def get_norm_layer(norm_type='instance'):
+    """Same name, signature and results as the reference's ``basicModel.get_norm_layer``: 'batch' | 'instance' | 'none' -> a factory
+    called with the channel count (the first two are ``functools.partial`` objects of the torch classes)."""
+    if norm_type not in _NORM_FACTORIES:
+        raise NotImplementedError(f'normalization layer [{norm_type}] is not found')
+    return _NORM_FACTORIES[norm_type]
+
+
+def _init_kind(m):
+    """What init_weights does to a module, by the reference's rule on the class NAME: 'weights' for anything that owns a ``weight``
+    and is called *Conv* or *Linear* (Conv2d, ConvTranspose2d, ...), 'batchnorm' for *BatchNorm2d*, None otherwise."""
+    name = type(m).__name__
+    if hasattr(m, 'weight') and ('Conv' in name or 'Linear' in name):
+        return 'weights'
+    return 'batchnorm' if 'BatchNorm2d' in name else None
+
+
+def init_weights(net, init_type='normal', init_gain=0.02):
+    """Same name, signature and results as the reference's ``basicModel.init_weights``: every convolution / linear weight is drawn by
+    ``init_type`` ('normal': N(0, init_gain) | 'xavier' | 'kaiming' | 'orthogonal') and its bias zeroed; BatchNorm2d weights are drawn from
+    N(1, init_gain), their biases zeroed.  The modules are visited in ``net.modules()`` order; the ones that draw are leaves, and the
+    leaves come in the order ``net.apply`` visits them, so the same seed gives the reference's weights (the fixtures' sketches hold it)."""
+    print(f'initialize network with {init_type}')
+    for m in net.modules():
+        kind = _init_kind(m)
+        if kind == 'weights':
+            if init_type not in _WEIGHT_INITS:
+                raise NotImplementedError(f'initialization method [{init_type}] is not implemented')
+            _WEIGHT_INITS[init_type](m.weight.data, init_gain)
+            if getattr(m, 'bias', None) is not None:
+                m.bias.data.zero_()
+        elif kind == 'batchnorm':
+            nn.init.normal_(m.weight.data, 1.0, init_gain)
+            m.bias.data.zero_()
+
+
+def init_net(net, init_type='normal', init_gain=0.02):
+    """``init_weights`` on ``net``, which is returned (the reference's ``basicModel.init_net``)."""
+    init_weights(net, init_type, init_gain)
+    return net
+
+
+def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal', init_gain=0.02):
+    """Same name and signature as the reference's ``basicModel.define_G``: ``netG`` 'resnet_9blocks' / 'resnet_6blocks' build the native
+    ResnetGenerator with 9 / 6 blocks (which accepts ``norm='instance'`` alone) and initialise it with ``init_net``; 'unet_128' /
+    'unet_256' are not native."""
+    if netG in ('unet_128', 'unet_256'):
+        raise NotImplementedError("UnetGenerator is not native")
+    if netG not in _RESNET_BLOCKS:
+        raise NotImplementedError(f'Generator model name [{netG}] is not recognized')
+    net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=get_norm_layer(norm), use_dropout=use_dropout, n_blocks=_RESNET_BLOCKS[netG])
+    return init_net(net, init_type, init_gain)
+
+
+class _ResnetBlock(_HolderOnly):
+    """Parameter holder of basicModel.py:200-254 ResnetBlock with InstanceNorm2d and biases: conv_block = [pad, conv, norm, ReLU, pad, conv,
+    norm] ('reflect') or [conv, norm, ReLU, conv, norm] ('zero')."""
+
+    def __init__(self, dim, padding_type):
+        super().__init__()
+        blk = []
+        for half in range(2):
+            if padding_type == 'reflect':
+                blk += [nn.ReflectionPad2d(1)]
+            blk += [nn.Conv2d(dim, dim, kernel_size=3, padding=0 if padding_type == 'reflect' else 1, bias=True), nn.InstanceNorm2d(dim)]
+            if half == 0:
+                blk += [nn.ReLU(True)]
+        self.conv_block = nn.Sequential(*blk)
+
+
+def _resnetgen_cfg(x, items):
+    in_ch, out_ch, ngf, n_blocks, padding, dtype = items
+    _check_input(x, "ResnetGenerator", in_ch, f"expected [B,{in_ch},H,W]")
+    B, _, H, W = x.shape
+    return N.ResnetGenCfg(in_ch, out_ch, B, H, W, dtype, ngf, n_blocks, padding), (B, out_ch, H, W)
+
+
+_RESNETGEN = _OpList("ResnetGenerator", "srcgan_resnetgen", _resnetgen_cfg)
+
+
+class ResnetGenerator(_NativeRepr, nn.Module):
+    """ResNet translator of CycleGAN / pix2pix, drop-in for reference ``model.basicModel.ResnetGenerator`` (src/model/basicModel.py:141-197), the
+    network ``multi-task.py`` builds with ``define_G(1, 3, ngf, 'resnet_9blocks', 'instance', ...)``: ReflectionPad2d(3), 7x7, IN, ReLU; two
+    3x3 stride-2 convolutions, each IN + ReLU; ``n_blocks`` ResnetBlocks [pad 1, 3x3, IN, ReLU, pad 1, 3x3, IN, + x]; two
+    ConvTranspose2d(k3, s2, p1, output_padding 1), each IN + ReLU; ReflectionPad2d(3), 7x7, Tanh.  ``forward(x[B,input_nc,H,W]) ->
+    [B,output_nc,H,W]``, H and W multiples of 4, at least 8; ``ngf`` a multiple of 16; 1..8 channels in and out.
+
+    Native: ``norm_layer`` = ``nn.InstanceNorm2d`` or the ``functools.partial`` of ``get_norm_layer('instance')`` (affine=False,
+    track_running_stats=False), ``padding_type`` 'reflect' or 'zero', no dropout.  BatchNorm -- the class default, as in the reference --
+    the identity norm, 'replicate' and dropout raise NotImplementedError.  ``state_dict`` has the reference's keys (``model.1.weight`` ...;
+    36 tensors for 6 blocks): ``model`` is an nn.Sequential with the parameter-free layers in their places, created in the reference's
+    order, so the same seed gives the same weights."""
+
+    def __init__(self, input_nc, output_nc, ngf=64, norm_layer=nn.BatchNorm2d, use_dropout=False, n_blocks=6, padding_type='reflect', dtype=None):
+        assert n_blocks >= 0
+        super().__init__()
+        nkw = {}
+        if isinstance(norm_layer, functools.partial):
+            nkw, norm_layer = dict(norm_layer.keywords), norm_layer.func
+        if norm_layer is nn.BatchNorm2d:
+            raise NotImplementedError("native ResnetGenerator: norm_layer = nn.BatchNorm2d (the class default; define_G's norm='batch') is not "
+                                      "implemented -- the op-list executor has no BatchNorm; use nn.InstanceNorm2d (norm='instance')")
+        if norm_layer is not nn.InstanceNorm2d:
+            raise NotImplementedError("native ResnetGenerator: the identity norm (get_norm_layer('none')) and other norm_layer factories are not "
+                                      "implemented; use nn.InstanceNorm2d (norm='instance')")
+        if nkw.get("affine", False) or nkw.get("track_running_stats", False):
+            raise NotImplementedError("native ResnetGenerator: InstanceNorm2d with affine=True or track_running_stats=True is not implemented "
+                                      "(get_norm_layer('instance') builds it without either)")
+        if use_dropout:
+            raise NotImplementedError("native ResnetGenerator: use_dropout=True is not implemented")
+        if padding_type == 'replicate':
+            raise NotImplementedError("native ResnetGenerator: padding_type 'replicate' is not implemented (use 'reflect' or 'zero')")
+        if padding_type not in ('reflect', 'zero'):
+            raise NotImplementedError('padding [%s] is not implemented' % padding_type)
+        input_nc, output_nc, ngf, n_blocks = int(input_nc), int(output_nc), int(ngf), int(n_blocks)
+        self.compute_dtype = N.dtype_name(dtype)
+        self._cfg = (input_nc, output_nc, ngf, n_blocks, 0 if padding_type == 'reflect' else 1)
+        # the native planner owns the rules (ngf % 16, 1..8 channels): ask it first
+        probe = N.ResnetGenCfg(input_nc, output_nc, 1, 8, 8, N.dtype_id(self.compute_dtype), ngf, n_blocks, self._cfg[4])
+        if N.lib().srcgan_resnetgen_num_params(C.byref(probe)) < 0:
+            raise ValueError("ResnetGenerator: " + (N.lib().srcgan_last_error() or b"").decode())
+        # the layers in the reference's order (creation order = the order the seeded weights are drawn in; index = state_dict key)
+        act_norm = lambda c: [nn.InstanceNorm2d(c, affine=False, track_running_stats=False), nn.ReLU(True)]
+        widths = [ngf, 2 * ngf, 4 * ngf]
+        model = [nn.ReflectionPad2d(3), nn.Conv2d(input_nc, ngf, 7), *act_norm(ngf)]
+        for cin, cout in zip(widths, widths[1:]):
+            model += [nn.Conv2d(cin, cout, 3, stride=2, padding=1), *act_norm(cout)]
+        model += [_ResnetBlock(widths[-1], padding_type) for _ in range(n_blocks)]
+        for cin, cout in zip(widths[::-1], widths[-2::-1]):
+            model += [nn.ConvTranspose2d(cin, cout, 3, stride=2, padding=1, output_padding=1), *act_norm(cout)]
+        model += [nn.ReflectionPad2d(3), nn.Conv2d(ngf, output_nc, 7), nn.Tanh()]
+        self.model = nn.Sequential(*model)
+
+    def forward(self, input):
+        return _oplist_forward(input, _RESNETGEN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class _NLayerDFn(torch.autograd.Function):
