@@ -995,7 +995,8 @@ int srcgan_scene_score(const void* pred, int pred_kind, const void* truth, int t
 
 /* Fused multi-tensor Adam (torch.optim.Adam.step() of trainCas.py:38-41,143-150 / train.py:191-192,331-340; torch's
  * single-tensor arithmetic, default flags: no weight decay, no amsgrad).  tensors_dev: device array of records
- * {float* p; const float* g; float* m; float* v;} (32 bytes); chunks_dev: device array of nchunks records
+ * {float* p; const float* g; float* m; float* v;} (32 bytes; p, m and v 16-byte aligned, g 4-byte aligned is enough --
+ * srcgan_amd.optim.Adam sends anything else through torch's own step); chunks_dev: device array of nchunks records
  * {int tensor; int off; int n; int pad;} (16 bytes; off a multiple of 4, n <= 4096).  `step` = the 1-based step count of
  * every tensor in the launch. */
 int srcgan_adam_step(const void* tensors_dev, const void* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,

@@ -1344,7 +1344,8 @@ __global__ __launch_bounds__(256) void adam_multi_k(const SgAdamTensor* __restri
         }
     }
 }
-// tensors_dev: ntensors records {p, g, m, v} (device f32 pointers, 16-byte aligned); chunks_dev: nchunks records
+// tensors_dev: ntensors records {p, g, m, v} (device f32 pointers; p, m and v 16-byte aligned, g may be 4-byte aligned: the
+// gradients are views of one flat arena at running offsets, and a 16-byte global load needs only dword alignment); chunks_dev: nchunks records
 // {tensor index, element offset (multiple of 4), count <= 4096, 0}.  The chunk table depends only on the shapes; the tensor
 // table is refreshed by the caller (srcgan_amd/optim.py) whenever a pointer (typically a fresh .grad) changes.
 extern "C" int srcgan_adam_step(const void* tensors_dev, const void* chunks_dev, int nchunks, double lr, double beta1, double beta2, double eps,

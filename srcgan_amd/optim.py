@@ -4,7 +4,8 @@
 (``step`` as a CPU scalar tensor, ``exp_avg``, ``exp_avg_sq`` per parameter), so checkpoints written by either load in
 the other.  Only ``step()`` differs: one native launch per parameter group (``srcgan_adam_step``) instead of torch's
 foreach kernel sequence -- 697 tensors for the 23-block generator.  Option combinations the kernel does not implement
-(weight decay, amsgrad, maximize, capturable, differentiable, non-f32 or CPU parameters) fall back to torch's own step.
+(weight decay, amsgrad, maximize, capturable, differentiable, non-f32 or CPU parameters, a parameter or state tensor that is
+not 16-byte aligned) fall back to torch's own step.
 ``fuse(optimizer)`` converts an existing ``torch.optim.Adam`` instance in place (what the reference harness constructs).
 """
 import os
@@ -39,6 +40,7 @@ class Adam(torch.optim.Adam):
                 loss = closure()
         lib = N.lib()
         cache = self.__dict__.setdefault("_srcgan_tables", {})
+        work = []
         for gi, group in enumerate(self.param_groups):
             ps: List[torch.Tensor] = [p for p in group["params"] if p.grad is not None]
             if not ps:
@@ -49,13 +51,21 @@ class Adam(torch.optim.Adam):
                     st["step"] = torch.tensor(0.0, dtype=torch.float32)
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            ptrs = np.array([(p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr())
+                             for p in ps], dtype=np.uint64)
+            work.append((gi, group, ps, ptrs))
+        # the kernel moves p, exp_avg and exp_avg_sq with 16-byte accesses (a gradient may sit at any 4-byte address: the arena's
+        # views do); a parameter or state tensor that is a view at an odd offset sends the whole step through torch, before
+        # anything is changed
+        if any((ptrs[:, [0, 2, 3]] & np.uint64(15)).any() for _, _, _, ptrs in work):
+            super().step()
+            return loss
+        for gi, group, ps, ptrs in work:
             step_ts = [self.state[p]["step"] for p in ps]
             torch._foreach_add_(step_ts, 1)
             steps = {int(step_ts[0]), int(step_ts[-1])} if len(ps) < 64 else {int(t) for t in (step_ts[0], step_ts[len(ps) // 2], step_ts[-1])}
             if len(steps) != 1:             # parameters that joined the group at different times
                 raise RuntimeError("srcgan_amd.optim.Adam: parameters of one group have different step counts; use torch.optim.Adam")
-            ptrs = np.array([(p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr())
-                             for p in ps], dtype=np.uint64)
             shapes = tuple(p.numel() for p in ps)
             ent = cache.get(gi)
             if ent is None or ent["shapes"] != shapes:
