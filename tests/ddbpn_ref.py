@@ -20,6 +20,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import net_ref
+from net_ref import sketch          # noqa: F401  (the fixture test and tests/test_ddbpn_host.py take it from here)
+
 PROJ = {2: (6, 2, 2), 4: (8, 4, 2), 8: (12, 8, 2)}
 N0, NR, DEPTH = 128, 32, 6
 FROZEN = ("sub_mean.weight", "sub_mean.bias", "add_mean.weight", "add_mean.bias")
@@ -30,17 +33,6 @@ PR_CHUNK = 2048         # grid positions per partial-sum block of the PReLU back
 # (measured on the CPU: da 1.55 -> 6.2 -> 7, db 0.92 -> 3.7 -> 4; the terms' own float32 roundings are part of the figure;
 # tests/test_back_proj_teeth.py re-measures it).
 K_RECORDED = {"da": 7.0, "db": 4.0}
-
-
-def sketch(t):
-    """The fixtures' 64-bucket count sketch of a flattened tensor, in float64 (tests/golden/make_golden_srdense.py)."""
-    v = np.asarray(t, dtype=np.float64).reshape(-1)
-    i = np.arange(v.size, dtype=np.uint64)
-    h = (i * np.uint64(2654435761) + np.uint64(40503)) & np.uint64(0xFFFFFFFF)
-    sign = 1.0 - 2.0 * ((h >> np.uint64(15)) & np.uint64(1)).astype(np.float64)
-    out = np.zeros(64, dtype=np.float64)
-    np.add.at(out, (i % np.uint64(64)).astype(np.int64), sign * v)
-    return out
 
 
 def set_slopes(model, seed):
@@ -56,12 +48,6 @@ def set_slopes(model, seed):
                 mod.weight.copy_(torch.from_numpy(v).to(mod.weight.dtype))
                 k += 1
     return k
-
-
-def _q(t, store):
-    if store is None:
-        return t
-    return t + (t.to(store).to(t.dtype) - t).detach()
 
 
 # ------------------------------------------------------------------------------------------------ the stride-1 route
@@ -216,7 +202,7 @@ def forward(sd, x, scale, store=None, s1=False, mut=None):
     """sd: name -> tensor (the model's state_dict, any float dtype; the computation runs in x's dtype, pass float64)."""
     w = {k: v.to(x.dtype) for k, v in sd.items()}
     k, s, p = PROJ[scale]
-    q = lambda t: _q(t, store)
+    q = lambda t: net_ref.q(t, store)
 
     def act(z, slope, res=None, beta=1.0, bias=None):
         return q(prelu_forward(z, w[slope], res, beta, bias, mut))
@@ -254,12 +240,7 @@ def forward(sd, x, scale, store=None, s1=False, mut=None):
 def run(sd, x, target, scale, store=None, s1=False, mut=None, frozen=FROZEN, loss_scale=1.0):
     """Forward, L1 loss against ``target`` (times ``loss_scale``) and backward in float64 -> (y, loss, dx, {name: gradient}) as float64
     CPU tensors."""
-    sd64 = {k: v.detach().double().cpu().clone().requires_grad_(k not in frozen) for k, v in sd.items()}
-    x64 = x.detach().double().cpu().clone().requires_grad_(True)
-    y = forward(sd64, x64, scale, store, s1, mut)
-    loss = (y - target.detach().double().cpu()).abs().mean() * loss_scale
-    loss.backward()
-    return y.detach(), loss.detach(), x64.grad, {k: v.grad for k, v in sd64.items() if k not in frozen}
+    return net_ref.run_l1(lambda w, v: forward(w, v, scale, store, s1, mut), sd, x, target, frozen=frozen, loss_scale=loss_scale)
 
 
 # ------------------------------------------------------------------------------------------------ the kernels' test cases

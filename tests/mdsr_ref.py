@@ -17,22 +17,12 @@ shifts' outputs, every convolution's output behind its fused ReLU / residual) an
 (forward only: the backward is the exact one of the rounded forward); biases and the shifts' parameters stay as they are.
 
 ``mut`` names one deliberate mistake (tests/test_mdsr_teeth.py): MUTATIONS."""
-import numpy as np
-import torch
 import torch.nn.functional as F
 
+import net_ref
+from net_ref import pixel_shuffle, rel_l2, sketch, worst          # noqa: F401  (the tests take them from here)
+
 MUTATIONS = ("wrong_branch", "skip_from_head", "k3_crop", "no_relu", "vdsr_skip_after_add_mean", "inactive_grad")
-
-
-def sketch(t):
-    """The fixtures' 64-bucket count sketch of a flattened tensor, in float64 (tests/golden/make_golden_srdense.py)."""
-    v = np.asarray(t, dtype=np.float64).reshape(-1)
-    i = np.arange(v.size, dtype=np.uint64)
-    h = (i * np.uint64(2654435761) + np.uint64(40503)) & np.uint64(0xFFFFFFFF)
-    sign = 1.0 - 2.0 * ((h >> np.uint64(15)) & np.uint64(1)).astype(np.float64)
-    out = np.zeros(64, dtype=np.float64)
-    np.add.at(out, (i % np.uint64(64)).astype(np.int64), sign * v)
-    return out
 
 
 def up_convs(scale):
@@ -60,26 +50,13 @@ def mdsr_branch(n_resblocks, scales, idx):
     return [n for n in mdsr_names(n_resblocks, scales) if n not in off and not n.startswith(("sub_mean", "add_mean"))]
 
 
-def _q(t, store):
-    if store is None:
-        return t
-    return t + (t.to(store).to(t.dtype) - t).detach()
-
-
-def pixel_shuffle(x, r):
-    """y[c, r h + a, r w + b] = x[c r^2 + a r + b, h, w]"""
-    B, Cr, H, W = x.shape
-    C = Cr // (r * r)
-    return x.reshape(B, C, r, r, H, W).permute(0, 1, 4, 2, 5, 3).reshape(B, C, r * H, r * W)
-
-
 class _Net:
     def __init__(self, sd, x, store, mut):
         self.w = {k: v.to(x.dtype) for k, v in sd.items()}
         self.store, self.mut = store, mut
 
     def q(self, t):
-        return _q(t, self.store)
+        return net_ref.q(t, self.store)
 
     def shift(self, t, name):
         return self.q(F.conv2d(t, self.w[name + ".weight"], self.w[name + ".bias"]))
@@ -131,17 +108,10 @@ def vdsr_forward(sd, x, n_resblocks, store=None, mut=None):
 def run(sd, x, target, forward, store=None, mut=None, loss_scale=1.0):
     """Forward (``forward(sd, x, store, mut)``), L1 loss against ``target`` (times ``loss_scale``) and backward in float64 ->
     (y, loss, dx, {name: gradient}) as float64 CPU tensors.  A parameter that is not on the graph has no entry (the reference leaves
-    its ``.grad`` at None); neither have the frozen shifts."""
-    frozen = lambda k: k.startswith(("sub_mean", "add_mean"))
-    sd64 = {k: v.detach().double().cpu().clone().requires_grad_(not frozen(k)) for k, v in sd.items()}
-    x64 = x.detach().double().cpu().clone().requires_grad_(True)
-    y = forward(sd64, x64, store, mut)
-    loss = (y - target.detach().double().cpu()).abs().mean() * loss_scale
-    loss.backward()
-    grads = {k: v.grad for k, v in sd64.items() if v.grad is not None}
-    if mut == "inactive_grad":          # a zero gradient where the reference has none (what a zero fill of the whole arena would report)
-        grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in sd64.items() if not frozen(k)}
-    return y.detach(), loss.detach(), x64.grad, grads
+    its ``.grad`` at None); neither have the frozen shifts.  ``mut`` "inactive_grad": a zero gradient where the reference has none (what
+    a zero fill of the whole arena would report)."""
+    return net_ref.run_l1(lambda w, v: forward(w, v, store, mut), sd, x, target, frozen=lambda k: k.startswith(("sub_mean", "add_mean")),
+                          loss_scale=loss_scale, missing="zero" if mut == "inactive_grad" else "absent")
 
 
 def mdsr_run(sd, x, target, n_resblocks, scales, idx, **kw):
@@ -150,11 +120,6 @@ def mdsr_run(sd, x, target, n_resblocks, scales, idx, **kw):
 
 def vdsr_run(sd, x, target, n_resblocks, **kw):
     return run(sd, x, target, lambda s, v, store, mut: vdsr_forward(s, v, n_resblocks, store, mut), **kw)
-
-
-def rel_l2(a, b):
-    a, b = torch.as_tensor(np.asarray(a), dtype=torch.float64), torch.as_tensor(np.asarray(b), dtype=torch.float64)
-    return float((a - b).norm() / b.norm().clamp_min(1e-300))
 
 
 def fixture_grad_names(z):
@@ -166,19 +131,9 @@ def fixture_errors(z, y, loss, dx, grads, suffix="", measure=None):
     """{what: relative error} of a run against a fixture's float32 (suffix "") or float64 ("64") values: y, loss, dx and every parameter
     gradient -- whole where the fixture holds it whole, through sketch and first output-channel slice where it does not.  The set of
     parameters with a gradient must be the fixture's.  measure(a, b): rel_l2, or the project's fp32 gate measure, conftest.rel_err."""
-    m = measure or rel_l2
-    e = {"y": m(y, z["y" + suffix]), "loss": abs(float(loss) - float(z["loss" + suffix])) / abs(float(z["loss" + suffix])), "dx": m(dx, z["dx" + suffix])}
+    e = net_ref.fixture_head(z, y, loss, dx, suffix, measure)
     assert sorted(grads) == sorted(fixture_grad_names(z)), sorted(set(grads) ^ set(fixture_grad_names(z)))
     assert not set(grads) & {str(k) for k in z["nograd"]} and not set(grads) & {str(k) for k in z["frozen"]}
     for k, g in grads.items():
-        g = g.detach().double().cpu()
-        if "grad" + suffix + "/" + k in z:
-            e["grad " + k] = m(g, z["grad" + suffix + "/" + k])
-        else:
-            e["grad " + k] = max(m(sketch(g.numpy()), z["gsketch" + suffix + "/" + k]), m(g[0], z["gslice" + suffix + "/" + k]))
+        e["grad " + k] = net_ref.keyed_grad_error(z, k, g, suffix, measure)
     return e
-
-
-def worst(errors):
-    k = max(errors, key=errors.get)
-    return k, errors[k]

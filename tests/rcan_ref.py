@@ -7,28 +7,11 @@ arXiv:1807.02758): a function of a state_dict, so it runs with any weights, on t
 ``store``: None, or a 16-bit torch dtype -- the storage emulation: the input, every tensor an op of the native executor writes and
 every 3x3 convolution weight is rounded to that type (forward only: the backward is the exact one of the rounded forward); biases,
 the attention MLP and the MeanShift parameters stay as they are, as in the native code."""
-import numpy as np
 import torch
 import torch.nn.functional as F
 
-
-def sketch(t):
-    """The fixtures' 64-bucket count sketch of a flattened tensor, in float64 (tests/golden/make_golden_srdense.py): element i goes to
-    bucket i mod 64 with the sign of a fixed integer hash of i.  Equal tensors have equal sketches, bit for bit; the relative error of two
-    sketches estimates the relative L2 error of the tensors."""
-    v = np.asarray(t, dtype=np.float64).reshape(-1)
-    i = np.arange(v.size, dtype=np.uint64)
-    h = (i * np.uint64(2654435761) + np.uint64(40503)) & np.uint64(0xFFFFFFFF)
-    sign = 1.0 - 2.0 * ((h >> np.uint64(15)) & np.uint64(1)).astype(np.float64)
-    out = np.zeros(64, dtype=np.float64)
-    np.add.at(out, (i % np.uint64(64)).astype(np.int64), sign * v)
-    return out
-
-
-def _q(t, store):
-    if store is None:
-        return t
-    return t + (t.to(store).to(t.dtype) - t).detach()
+import net_ref
+from net_ref import sketch          # noqa: F401  (tests/test_rcan_host.py takes it from here)
 
 
 def channel_attention(t, w1, b1, w2, b2):
@@ -40,7 +23,7 @@ def channel_attention(t, w1, b1, w2, b2):
 def forward(sd, x, n_resgroups, n_resblocks, scale, store=None):
     """sd: name -> tensor (the model's state_dict, any float dtype; the computation runs in x's dtype, pass float64)."""
     w = {k: v.to(x.dtype) for k, v in sd.items()}
-    q = lambda t: _q(t, store)
+    q = lambda t: net_ref.q(t, store)
     conv = lambda t, name: F.conv2d(t, q(w[name + ".weight"]), w[name + ".bias"], padding=1)
     t = q(F.conv2d(q(x), w["sub_mean.weight"], w["sub_mean.bias"]))
     head = t = q(conv(t, "head.0"))
@@ -63,9 +46,4 @@ def forward(sd, x, n_resgroups, n_resblocks, scale, store=None):
 
 def run(sd, x, target, n_resgroups, n_resblocks, scale, store=None, frozen=("sub_mean.weight", "sub_mean.bias", "add_mean.weight", "add_mean.bias")):
     """Forward, L1 loss against ``target`` and backward in float64 -> (y, loss, dx, {name: gradient}) as float64 CPU tensors."""
-    sd64 = {k: v.detach().double().cpu().clone().requires_grad_(k not in frozen) for k, v in sd.items()}
-    x64 = x.detach().double().cpu().clone().requires_grad_(True)
-    y = forward(sd64, x64, n_resgroups, n_resblocks, scale, store)
-    loss = (y - target.detach().double().cpu()).abs().mean()
-    loss.backward()
-    return y.detach(), loss.detach(), x64.grad, {k: v.grad for k, v in sd64.items() if k not in frozen}
+    return net_ref.run_l1(lambda w, v: forward(w, v, n_resgroups, n_resblocks, scale, store), sd, x, target, frozen=frozen)

@@ -18,25 +18,12 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+import net_ref
+from net_ref import BIG, first_slice, rel_l2, sketch, worst          # noqa: F401  (the tests and the fixture generator take them from here)
+
 CONFIGS = {"A": (20, 6, 32), "B": (16, 8, 64)}
 MUTATIONS = ("drop_block", "short_read", "slot_off", "lff_no_residual", "gff_swap", "no_global_residual", "shuffle_order", "skip_stage2")
 TDT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
-
-
-def sketch(t):
-    """The fixtures' 64-bucket count sketch of a flattened tensor, in float64 (tests/golden/make_golden_srdense.py)."""
-    v = np.asarray(t, dtype=np.float64).reshape(-1)
-    i = np.arange(v.size, dtype=np.uint64)
-    h = (i * np.uint64(2654435761) + np.uint64(40503)) & np.uint64(0xFFFFFFFF)
-    sign = 1.0 - 2.0 * ((h >> np.uint64(15)) & np.uint64(1)).astype(np.float64)
-    out = np.zeros(64, dtype=np.float64)
-    np.add.at(out, (i % np.uint64(64)).astype(np.int64), sign * v)
-    return out
-
-
-def first_slice(g):
-    """what a fixture keeps of a gradient of more than 2048 elements beside its sketch: its first 64 elements"""
-    return g.reshape(-1)[:64]
 
 
 def config(cfg):
@@ -79,25 +66,20 @@ def random_state_dict(cfg, scale, G0=64, n_colors=3, seed=0, gain=1.0):
     return {k: sd[k] for k in names(cfg, scale)}
 
 
-def _q(t, store):
-    if store is None:
-        return t
-    return t + (t.to(store).to(t.dtype) - t).detach()
-
-
 def pixel_shuffle(x, r, mut=None):
-    """y[c, r h + a, r w + b] = x[c r^2 + a r + b, h, w]"""
+    """net_ref.pixel_shuffle, or with the sub-pixel index in front of the channel ("shuffle_order")"""
+    if mut != "shuffle_order":
+        return net_ref.pixel_shuffle(x, r)
     B, Cr, H, W = x.shape
     C = Cr // (r * r)
-    v = x.reshape(B, r, r, C, H, W).permute(0, 3, 4, 1, 5, 2) if mut == "shuffle_order" else x.reshape(B, C, r, r, H, W).permute(0, 1, 4, 2, 5, 3)
-    return v.reshape(B, C, r * H, r * W)
+    return x.reshape(B, r, r, C, H, W).permute(0, 3, 4, 1, 5, 2).reshape(B, C, r * H, r * W)
 
 
 def forward(sd, x, cfg, scale, store=None, mut=None, gff_once=False):
     """sd: name -> tensor (the model's state_dict, any float dtype; the computation runs in x's dtype, pass float64)."""
     D, C, G = config(cfg)
     w = {k: v.to(x.dtype) for k, v in sd.items()}
-    q = lambda t: _q(t, store)
+    q = lambda t: net_ref.q(t, store)
     G0 = w["SFENet1.weight"].shape[0]
     conv = lambda t, name, pad: F.conv2d(t, q(w[name + ".weight"]), w[name + ".bias"], padding=pad)
     f1 = q(conv(q(x), "SFENet1", 1))
@@ -143,20 +125,7 @@ def forward(sd, x, cfg, scale, store=None, mut=None, gff_once=False):
 def run(sd, x, target, cfg, scale, store=None, mut=None, loss_scale=1.0, gff_once=False):
     """Forward, L1 loss against ``target`` (times ``loss_scale``) and backward in float64 -> (y, loss, dx, {name: gradient}) as float64
     CPU tensors (a parameter a mutation leaves unused has a zero gradient)."""
-    sd64 = {k: v.detach().double().cpu().clone().requires_grad_(True) for k, v in sd.items()}
-    x64 = x.detach().double().cpu().clone().requires_grad_(True)
-    y = forward(sd64, x64, cfg, scale, store, mut, gff_once)
-    loss = (y - target.detach().double().cpu()).abs().mean() * loss_scale
-    loss.backward()
-    return y.detach(), loss.detach(), x64.grad, {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in sd64.items()}
-
-
-def rel_l2(a, b):
-    a, b = torch.as_tensor(np.asarray(a), dtype=torch.float64), torch.as_tensor(np.asarray(b), dtype=torch.float64)
-    return float((a - b).norm() / b.norm().clamp_min(1e-300))
-
-
-BIG = 2048          # a gradient of more elements is kept as sketch + first slice
+    return net_ref.run_l1(lambda w, v: forward(w, v, cfg, scale, store, mut, gff_once), sd, x, target, loss_scale=loss_scale)
 
 
 def pack_gradients(named, suffix=""):
@@ -177,18 +146,13 @@ def fixture_errors(z, y, loss, dx, grads, suffix="", measure=None):
     """{what: relative error} of a run against a fixture's float32 (suffix "") or float64 ("64") values: y, loss, dx and every parameter
     gradient -- whole where the fixture holds it whole, through sketch and first slice where it does not.  measure(a, b): rel_l2, or the
     project's fp32 gate measure, conftest.rel_err."""
-    rel_l2 = measure or globals()["rel_l2"]
-    e = {"y": rel_l2(y, z["y" + suffix]), "loss": abs(float(loss) - float(z["loss" + suffix])) / abs(float(z["loss" + suffix])), "dx": rel_l2(dx, z["dx" + suffix])}
+    m = measure or rel_l2
+    e = net_ref.fixture_head(z, y, loss, dx, suffix, measure)
     assert sorted(grads) == sorted([str(k) for k in z["small"]] + [str(k) for k in z["big"]])
     so, lo = z["gsmall_off"], z["gslice_off"]
     for i, k in enumerate(map(str, z["small"])):
-        e["grad " + k] = rel_l2(grads[k].detach().double().cpu().reshape(-1), z["gsmall" + suffix][so[i]:so[i + 1]])
+        e["grad " + k] = m(grads[k].detach().double().cpu().reshape(-1), z["gsmall" + suffix][so[i]:so[i + 1]])
     for i, k in enumerate(map(str, z["big"])):
         g = grads[k].detach().double().cpu()
-        e["grad " + k] = max(rel_l2(sketch(g.numpy()), z["gsketch" + suffix][i]), rel_l2(first_slice(g).reshape(-1), z["gslice" + suffix][lo[i]:lo[i + 1]]))
+        e["grad " + k] = max(m(sketch(g.numpy()), z["gsketch" + suffix][i]), m(first_slice(g).reshape(-1), z["gslice" + suffix][lo[i]:lo[i + 1]]))
     return e
-
-
-def worst(errors):
-    k = max(errors, key=errors.get)
-    return k, errors[k]

@@ -21,7 +21,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from mdsr_ref import _q, rel_l2, sketch, worst      # noqa: F401
+import net_ref
+from net_ref import rel_l2, sketch, worst          # noqa: F401  (the tests take them from here)
 
 MUTATIONS = ("dropped_mirror", "symmetric", "replicate", "swapped_axes", "acc_overwrites", "term_twice", "tanh_from_z")
 
@@ -112,7 +113,7 @@ def dead_biases(n_blocks, padding="reflect"):
 def forward(sd, x, n_blocks, padding="reflect", store=None):
     """sd: name -> tensor (any float dtype; the computation runs in x's dtype, pass float64)."""
     w = {k: v.to(x.dtype) for k, v in sd.items()}
-    q = lambda t: _q(t, store)
+    q = lambda t: net_ref.q(t, store)
     mods = conv_modules(n_blocks, padding)
     pad = lambda t, p: F.pad(t, (p, p, p, p), mode="reflect")
     conv = lambda t, m, **kw: q(F.conv2d(t, q(w[m + ".weight"]), w[m + ".bias"], **kw))
@@ -135,12 +136,7 @@ def forward(sd, x, n_blocks, padding="reflect", store=None):
 
 def run(sd, x, target, n_blocks, padding="reflect", store=None, loss_scale=1.0):
     """Forward, L1 loss against ``target`` (times ``loss_scale``) and backward in float64 -> (y, loss, dx, {name: gradient})."""
-    sd64 = {k: v.detach().double().cpu().clone().requires_grad_(True) for k, v in sd.items()}
-    x64 = x.detach().double().cpu().clone().requires_grad_(True)
-    y = forward(sd64, x64, n_blocks, padding, store)
-    loss = (y - target.detach().double().cpu()).abs().mean() * loss_scale
-    loss.backward()
-    return y.detach(), loss.detach(), x64.grad, {k: v.grad for k, v in sd64.items()}
+    return net_ref.run_l1(lambda w, v: forward(w, v, n_blocks, padding, store), sd, x, target, loss_scale=loss_scale, missing="absent")
 
 
 def dead_ratio(grads, name):
@@ -152,16 +148,10 @@ def fixture_errors(z, y, loss, dx, grads, suffix="", measure=None):
     """({what: relative error}, {dead bias: dead_ratio}) of a run against a fixture's float32 (suffix "") or float64 ("64") values: y,
     loss, dx and every LIVE parameter gradient -- whole where the fixture holds it whole, through sketch and first slice where it does
     not.  The dead biases are reported in their absolute measure and compared with nothing."""
-    m = measure or rel_l2
-    e = {"y": m(y, z["y" + suffix]), "loss": abs(float(loss) - float(z["loss" + suffix])) / abs(float(z["loss" + suffix])), "dx": m(dx, z["dx" + suffix])}
+    e = net_ref.fixture_head(z, y, loss, dx, suffix, measure)
     dead = [str(k) for k in z["dead"]]
     assert list(grads) == [str(k) for k in z["names"]]
     for k, g in grads.items():
-        if k in dead:
-            continue
-        g = g.detach().double().cpu()
-        if "grad" + suffix + "/" + k in z:
-            e["grad " + k] = m(g, z["grad" + suffix + "/" + k])
-        else:
-            e["grad " + k] = max(m(sketch(g.numpy()), z["gsketch" + suffix + "/" + k]), m(g[0], z["gslice" + suffix + "/" + k]))
+        if k not in dead:
+            e["grad " + k] = net_ref.keyed_grad_error(z, k, g, suffix, measure)
     return e, {k: dead_ratio(grads, k) for k in dead}

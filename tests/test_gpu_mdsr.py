@@ -8,30 +8,12 @@ import pytest
 import torch
 
 import mdsr_ref
-from conftest import load_golden, rel_err, rel_l2
+from conftest import load_golden, rel_err
+from net_checks import STORE, check_16bit, check_exact_tiles, check_fixture, check_fp32, check_no_grad_bits, check_one_tile_scene, step
 from test_mdsr_ref import MDSR_FIXTURES, native
 
 pytestmark = pytest.mark.gpu
-F32_TOL = 1e-3
-STORE = {"bf16": torch.bfloat16, "fp16": torch.float16}
 SCALES = [2, 3, 4]
-
-
-def step(m, x, t, loss_scale=1.0):
-    """forward, L1 loss (times loss_scale), backward -> (y, loss, dx, {name: grad}) on the CPU; a parameter whose .grad is None has no entry"""
-    for p in m.parameters():
-        p.grad = None
-    x = x.detach().cuda().requires_grad_(True)
-    y = m(x)
-    loss = torch.nn.functional.l1_loss(y, t.cuda()) * loss_scale
-    loss.backward()
-    return y.detach().cpu(), float(loss.detach()), x.grad.cpu(), {k: p.grad.cpu() for k, p in m.named_parameters() if p.grad is not None}
-
-
-def report(who, e):
-    worst = sorted(((v, k) for k, v in e.items() if k.startswith("grad ")), reverse=True)
-    print(f"[mdsr] {who}: y {e['y']:.2e} loss {e['loss']:.2e} dx {e['dx']:.2e} worst grads {[(f'{v:.2e}', k[5:]) for v, k in worst[:3]]}")
-    return worst
 
 
 @pytest.mark.parametrize("tag", MDSR_FIXTURES)
@@ -42,10 +24,7 @@ def test_fp32_against_the_reference_fixture(tag):
     y, loss, dx, g = step(m, torch.from_numpy(z["x"]), torch.from_numpy(z["t"]))
     assert list(g) == mdsr_ref.fixture_grad_names(z)
     assert {k for k, p in m.named_parameters() if p.grad is None} == {str(k) for k in z["nograd"]} | {str(k) for k in z["frozen"]}
-    e = mdsr_ref.fixture_errors(z, y, loss, dx, g, "", measure=rel_err)
-    worst = report(f"{tag} fp32 vs reference", e)
-    assert e["y"] < F32_TOL and e["loss"] < F32_TOL and e["dx"] < F32_TOL
-    assert worst[0][0] < F32_TOL, worst[:3]
+    check_fixture("mdsr", f"{tag} fp32 vs reference", mdsr_ref.fixture_errors(z, y, loss, dx, g, "", measure=rel_err))
 
 
 def _case(idx, shape, dtype, seed, n_resblocks=2, n_feats=64, scales=SCALES):
@@ -59,15 +38,6 @@ def _case(idx, shape, dtype, seed, n_resblocks=2, n_feats=64, scales=SCALES):
     return m.cuda(), x, t
 
 
-def compare64(who, got, ref):
-    (y, loss, dx, g), (yr, lr, dxr, gr) = got, ref
-    errs = sorted(((rel_err(g[k], gr[k]), k) for k in gr), reverse=True)
-    print(f"[mdsr] {who} fp32 vs float64: y {rel_err(y, yr):.2e} loss {abs(loss - float(lr)) / float(lr):.2e} dx {rel_err(dx, dxr):.2e} "
-          f"worst grads {[(f'{e:.2e}', k) for e, k in errs[:3]]}")
-    assert list(g) == list(gr)
-    assert rel_err(y, yr) < F32_TOL and abs(loss - float(lr)) < F32_TOL * float(lr) and rel_err(dx, dxr) < F32_TOL and errs[0][0] < F32_TOL
-
-
 # n_feats = 64: two K chunks per tap in the 16-bit types and four in fp32 on the 64-row tile of the 5x5 kernel; 37 columns and 11 / 19 rows:
 # a 32-pixel tile seam and an 8-row tile seam at LR; odd sizes, a batch the fixtures do not have
 @pytest.mark.parametrize("idx, shape", [(0, (2, 3, 11, 37)), (1, (3, 3, 19, 9)), (2, (2, 3, 11, 37))])
@@ -75,22 +45,7 @@ def test_fp32_against_the_float64_restatement(idx, shape):
     m, x, t = _case(idx, shape, "fp32", 3)
     got = step(m, x, t)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
-    compare64(f"x{SCALES[idx]} {shape}", got, mdsr_ref.mdsr_run(sd, x, t, 2, SCALES, idx))
-
-
-def check16(who, dtype, got, ref, emu):
-    """The yardstick of test_gpu_ddbpn.py and test_gpu_rdn.py: against float64, the native relative L2 error may not exceed 1.5 x the
-    error of the float64 restatement with 16-bit STORAGE (+ 5e-3), on y, dx and the worst parameter gradient."""
-    (y, _, dx, g), (yr, _, dxr, gr), (ye, _, dxe, ge) = got, ref, emu
-    nat = sorted(((rel_l2(g[k], gr[k]), k) for k in gr), reverse=True)
-    emv = sorted(((rel_l2(ge[k], gr[k]), k) for k in gr), reverse=True)
-    print(f"[mdsr] {who} {dtype} native vs float64: y {rel_l2(y, yr):.4f} dx {rel_l2(dx, dxr):.4f} worst grads {nat[:2]}")
-    print(f"[mdsr] {who} {dtype} storage emulation vs float64: y {rel_l2(ye, yr):.4f} dx {rel_l2(dxe, dxr):.4f} worst grads {emv[:2]}")
-    bound = lambda e: 1.5 * e + 5e-3
-    assert list(g) == list(gr) and all(torch.isfinite(v).all() for v in g.values())
-    assert rel_l2(y, yr) < bound(rel_l2(ye, yr))
-    assert rel_l2(dx, dxr) < bound(rel_l2(dxe, dxr))
-    assert nat[0][0] < bound(emv[0][0])
+    check_fp32("mdsr", f"x{SCALES[idx]} {shape}", got, mdsr_ref.mdsr_run(sd, x, t, 2, SCALES, idx), names="list")
 
 
 _REF16 = {}
@@ -99,15 +54,15 @@ _REF16 = {}
 @pytest.mark.parametrize("idx", [0, 1, 2])
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_16_bit_modes_against_the_storage_emulation(dtype, idx):
-    """The loss carries a static scale of 1024, as 16-bit training does: the native backward stores its gradient tensors in the 16-bit
-    type, the emulation rounds the forward only."""
+    """net_checks.bound16, with its static loss scale of 1024"""
     shape, scale_loss = (2, 3, 9, 7), 1024.0
     m, x, t = _case(idx, shape, dtype, 5)
     got = step(m, x, t, scale_loss)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
     if idx not in _REF16:           # the float64 run is the same for both 16-bit types (same seed, same weights)
         _REF16[idx] = mdsr_ref.mdsr_run(sd, x, t, 2, SCALES, idx, loss_scale=scale_loss)
-    check16(f"x{SCALES[idx]}", dtype, got, _REF16[idx], mdsr_ref.mdsr_run(sd, x, t, 2, SCALES, idx, store=STORE[dtype], loss_scale=scale_loss))
+    emu = mdsr_ref.mdsr_run(sd, x, t, 2, SCALES, idx, store=STORE[dtype], loss_scale=scale_loss)
+    check_16bit("mdsr", f"x{SCALES[idx]}", dtype, got, _REF16[idx], emu, names="list")
 
 
 def _branch_off(m, idx):
@@ -145,26 +100,14 @@ def test_set_scale_on_one_instance(dtype):
 @pytest.mark.parametrize("idx, dtype", [(0, "bf16"), (1, "fp32"), (2, "fp16")])
 def test_no_grad_path_has_the_bits_of_the_training_forward(idx, dtype):
     m, x, _ = _case(idx, (2, 3, 7, 6), dtype, 7)
-    x = x.cuda()
-    y = m(x)
-    assert y.grad_fn is not None
-    with torch.no_grad():
-        yi = m(x)
-    assert yi.grad_fn is None and not yi.requires_grad and torch.equal(yi, y.detach())
-    y.sum().backward(retain_graph=True)
-    with pytest.raises(RuntimeError, match="twice"):
-        y.sum().backward()
+    check_no_grad_bits(m, x)
 
 
 def test_upscale_scene_on_one_tile_equals_the_forward():
     from srcgan_amd import infer
     m, _, _ = _case(1, (1, 3, 8, 8), "bf16", 9, n_resblocks=1, n_feats=32)
     scene = torch.rand(1, 3, 32, 32, generator=torch.Generator().manual_seed(10)).cuda()
-    assert len(infer.plan_tiles(32, 32, 32, 8, 1).tiles) == 1
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=3, tile=32, halo=8, blend="feather")
-    assert tuple(got.shape) == (1, 3, 96, 96) and torch.equal(got, whole)
+    check_one_tile_scene(m, scene, 3, (1, 3, 96, 96))
     with pytest.raises(ValueError, match=r"not to 64x64 \(up = 2\)"):          # an ``up`` that disagrees with the active scale
         infer.upscale_scene(m, scene, up=2, tile=32, halo=8, blend="feather")
     got8 = infer.upscale_scene(m, scene, up=3, tile=32, halo=8, blend="feather", ensemble=8)
@@ -173,18 +116,8 @@ def test_upscale_scene_on_one_tile_equals_the_forward():
 
 @pytest.mark.parametrize("idx", [0, 2])
 def test_exact_mode_on_a_2x2_tile_plan_equals_the_whole_image_forward(idx):
-    """``upscale_scene`` with halo = receptive_halo (crop) against the same module's whole-image no_grad forward; gate: the exact-mode
-    tests' fp32 gate, rel_err < 1e-3 (tests/test_gpu_infer_scene.py).  The tiles' convolutions see other tile shapes than the whole
-    image's, so the bits may differ; the value is printed.  n_resblocks = 1 keeps the halo at 14."""
-    from srcgan_amd import infer
+    """n_resblocks = 1 keeps the halo at 14"""
     m, _, _ = _case(idx, (1, 3, 8, 8), "fp32", 13, n_resblocks=1, n_feats=32)
     s = SCALES[idx]
     scene = torch.rand(1, 3, 24, 20, generator=torch.Generator().manual_seed(14)).cuda()
-    halo = infer.receptive_halo(m)
-    assert halo == 14 and len(infer.plan_tiles(24, 20, 12, halo, 1).tiles) == 4
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=s, tile=12)
-    err = rel_err(got, whole)
-    print(f"[mdsr] x{s} exact mode, 2 x 2 tiles, halo {halo}: tiled vs whole-image rel_err {err:.3e}")
-    assert tuple(got.shape) == (1, 3, 24 * s, 20 * s) and err < 1e-3
+    check_exact_tiles("mdsr", m, scene, s, 12, 4, (1, 3, 24 * s, 20 * s), halo=14)

@@ -9,6 +9,7 @@ import torch
 
 import oracle
 from conftest import load_golden, sub, rel_err, rel_l2
+from net_checks import bound16 as bound           # the 16-bit yardstick: the 16-bit-storage oracle's own distance from the f32 oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -167,7 +168,6 @@ def test_rddbnet_nb23_bf16_vs_oracle():
         print(f"nb=23 bf16 vs {name}: y {rel_l2(y, a):.4f} dx {rel_l2(dx, b):.4f} worst grads {errs[:3]} median {errs[len(errs) // 2][0]:.4f}")
     fmt = sorted(((rel_l2(ge[k], gr[k]), k) for k in g), reverse=True)
     print(f"   format alone (bf16-storage oracle vs f32 oracle): y {rel_l2(ye, yr):.4f} dx {rel_l2(dxe, dxr):.4f} worst {fmt[:2]} median {fmt[len(fmt) // 2][0]:.4f}")
-    bound = lambda e: 1.5 * e + 5e-3
     assert rel_l2(y, yr) < bound(rel_l2(ye, yr)) and rel_l2(y, yr) < 6e-2
     assert rel_l2(dx, dxr) < bound(rel_l2(dxe, dxr))
     assert max(rel_l2(g[k], gr[k]) for k in g) < bound(fmt[0][0])
@@ -186,7 +186,6 @@ def test_rddbnet_nb23_fp16_vs_oracle():
     fmt = sorted(((rel_l2(ge[k], gr[k]), k) for k in g), reverse=True)
     print(f"nb=23 fp16 vs f32 oracle: y {rel_l2(y, yr):.5f} dx {rel_l2(dx, dxr):.5f} worst grads {errs[:3]} median {errs[len(errs) // 2][0]:.5f}")
     print(f"   format alone (fp16-storage oracle vs f32 oracle): y {rel_l2(ye, yr):.5f} dx {rel_l2(dxe, dxr):.5f} worst {fmt[:2]} median {fmt[len(fmt) // 2][0]:.5f}")
-    bound = lambda e: 1.5 * e + 5e-3
     assert rel_l2(y, yr) < bound(rel_l2(ye, yr)) and rel_l2(y, yr) < 1e-2
     assert rel_l2(dx, dxr) < bound(rel_l2(dxe, dxr))
     assert errs[0][0] < bound(fmt[0][0])
@@ -288,7 +287,6 @@ def test_nlayerd_instance_norm_full_width_vs_oracle(dt):
                 assert rel_err(p.grad.cpu(), gr[k]) < F32_TOL, k
     else:
         ye, dxe, ge = ref(torch.bfloat16 if dt == "bf16" else torch.float16)
-        bound = lambda e: 1.5 * e + 5e-3
         assert rel_l2(y.cpu(), yr) < bound(rel_l2(ye, yr))
         assert rel_l2(xg.grad.cpu(), dxr) < bound(rel_l2(dxe, dxr))
         for k, p in net.named_parameters():
@@ -347,7 +345,6 @@ def test_nlayerd_full_width_vs_oracle(dt, hw):
         assert worst < F32_TOL * 2, worst
     else:
         ye, dxe, emu_sd = ref(True)
-        bound = lambda e: 1.5 * e + 5e-3           # yardstick: the bf16-storage oracle's own distance from the f32 oracle
         assert rel_l2(y.cpu(), ye) < 5e-3 and rel_l2(y.cpu(), yr) < 1.5e-2
         assert rel_l2(xg.grad.cpu(), dxe) < 3e-2 and rel_l2(xg.grad.cpu(), dxr) < bound(rel_l2(dxe, dxr))
         for k, p in net.named_parameters():
@@ -523,7 +520,6 @@ def test_resdeconv_bf16_vs_oracle():
     (yr, sd), (ye, se) = ref(False), ref(True)
     y = net(x.cuda())
     MSELoss()(y, t.cuda()).backward()
-    bound = lambda e: 1.5 * e + 5e-3
     assert rel_l2(y.cpu(), yr) < 5e-2 and rel_l2(y.cpu(), yr) < bound(rel_l2(ye, yr))
     rows = [(k, rel_l2(p.grad.cpu(), sd[k].grad), rel_l2(se[k].grad, sd[k].grad), rel_l2(p.grad.cpu(), se[k].grad)) for k, p in net.named_parameters()]
     worst = sorted(rows, key=lambda r: -r[1])[:3]

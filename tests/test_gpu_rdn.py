@@ -9,24 +9,12 @@ import torch
 
 import conv_exact as CE
 import rdn_ref
-from conftest import load_golden, rel_err, rel_l2
+from conftest import load_golden, rel_err
+from net_checks import STORE, check_16bit, check_exact_tiles, check_fixture, check_fp32, check_no_grad_bits, check_one_tile_scene, step
 from ws_guard import NAN, Guard, guarded_slabs
 
 pytestmark = pytest.mark.gpu
-F32_TOL = 1e-3
 FIXTURES = ("rdn_a_x2", "rdn_b_x3", "rdn_a_x4_gray")
-STORE = {"bf16": torch.bfloat16, "fp16": torch.float16}
-
-
-def step(m, x, t, loss_scale=1.0):
-    """forward, L1 loss (times loss_scale), backward -> (y, loss, dx, {name: grad}) on the CPU"""
-    for p in m.parameters():
-        p.grad = None
-    x = x.detach().cuda().requires_grad_(True)
-    y = m(x)
-    loss = torch.nn.functional.l1_loss(y, t.cuda()) * loss_scale
-    loss.backward()
-    return y.detach().cpu(), float(loss.detach()), x.grad.cpu(), {k: p.grad.cpu() for k, p in m.named_parameters() if p.grad is not None}
 
 
 @pytest.mark.parametrize("tag", FIXTURES)
@@ -38,11 +26,7 @@ def test_fp32_against_the_reference_fixture(tag):
     assert list(m.state_dict().keys()) == [str(n) for n in z["names"]]
     y, loss, dx, g = step(m, torch.from_numpy(z["x"]), torch.from_numpy(z["t"]))
     assert list(g) == [str(n) for n in z["names"]]
-    e = rdn_ref.fixture_errors(z, y, loss, dx, g, "", measure=rel_err)
-    worst = sorted(((v, k) for k, v in e.items() if k.startswith("grad ")), reverse=True)
-    print(f"[rdn] {tag} fp32 vs reference: y {e['y']:.2e} loss {e['loss']:.2e} dx {e['dx']:.2e} worst grads {[(f'{v:.2e}', k[5:]) for v, k in worst[:3]]}")
-    assert e["y"] < F32_TOL and e["loss"] < F32_TOL and e["dx"] < F32_TOL
-    assert worst[0][0] < F32_TOL, worst[:3]
+    check_fixture("rdn", f"{tag} fp32 vs reference", rdn_ref.fixture_errors(z, y, loss, dx, g, "", measure=rel_err))
 
 
 def _case(config, scale, shape, dtype, seed, G0=64):
@@ -59,14 +43,9 @@ def _case(config, scale, shape, dtype, seed, G0=64):
 @pytest.mark.parametrize("config, scale, shape", [("A", 2, (3, 3, 19, 9)), ("B", 2, (2, 3, 9, 11))])
 def test_fp32_against_the_float64_restatement(config, scale, shape):
     m, x, t = _case(config, scale, shape, "fp32", 3)
-    y, loss, dx, g = step(m, x, t)
+    got = step(m, x, t)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
-    yr, lr, dxr, gr = rdn_ref.run(sd, x, t, config, scale)
-    errs = sorted(((rel_err(g[k], gr[k]), k) for k in gr), reverse=True)
-    print(f"[rdn] '{config}' x{scale} {shape} fp32 vs float64: y {rel_err(y, yr):.2e} loss {abs(loss - float(lr)) / float(lr):.2e} dx {rel_err(dx, dxr):.2e} "
-          f"worst grads {[(f'{e:.2e}', k) for e, k in errs[:3]]}")
-    assert set(g) == set(gr)
-    assert rel_err(y, yr) < F32_TOL and abs(loss - float(lr)) < F32_TOL * float(lr) and rel_err(dx, dxr) < F32_TOL and errs[0][0] < F32_TOL
+    check_fp32("rdn", f"'{config}' x{scale} {shape}", got, rdn_ref.run(sd, x, t, config, scale), names="set")
 
 
 _REF16 = {}
@@ -82,66 +61,31 @@ def _ref16(config, scale, sd, x, t, dtype, loss_scale):
 @pytest.mark.parametrize("config, scale", [("A", 2), ("B", 3)])
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_16_bit_modes_against_the_storage_emulation(dtype, config, scale):
-    """The yardstick of test_gpu_ddbpn.py: against float64, the native relative L2 error may not exceed 1.5 x the error of the float64
-    restatement with 16-bit STORAGE (+ 5e-3), on y, dx and the worst parameter gradient.  The loss carries a static scale of 1024, as
-    16-bit training does: the native backward stores its gradient tensors in the 16-bit type, the emulation rounds the forward only.
-    The emulation rounds GFF.0's running sum after every block, as the native plan does."""
+    """net_checks.bound16, with its static loss scale of 1024.  The emulation rounds GFF.0's running sum after every block, as the
+    native plan does."""
     shape, scale_loss = (2, 3, 8, 6), 1024.0
     m, x, t = _case(config, scale, shape, dtype, 5)
-    y, loss, dx, g = step(m, x, t, scale_loss)
+    got = step(m, x, t, scale_loss)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
-    (yr, _, dxr, gr), (ye, _, dxe, ge) = _ref16(config, scale, sd, x, t, dtype, scale_loss)
-    nat = sorted(((rel_l2(g[k], gr[k]), k) for k in gr), reverse=True)
-    emu = sorted(((rel_l2(ge[k], gr[k]), k) for k in gr), reverse=True)
-    print(f"[rdn] '{config}' x{scale} {dtype} native vs float64: y {rel_l2(y, yr):.4f} dx {rel_l2(dx, dxr):.4f} worst grads {nat[:2]}")
-    print(f"[rdn] '{config}' x{scale} {dtype} storage emulation vs float64: y {rel_l2(ye, yr):.4f} dx {rel_l2(dxe, dxr):.4f} worst grads {emu[:2]}")
-    bound = lambda e: 1.5 * e + 5e-3
-    assert set(g) == set(gr) and all(torch.isfinite(v).all() for v in g.values())
-    assert rel_l2(y, yr) < bound(rel_l2(ye, yr))
-    assert rel_l2(dx, dxr) < bound(rel_l2(dxe, dxr))
-    assert nat[0][0] < bound(emu[0][0])
+    check_16bit("rdn", f"'{config}' x{scale}", dtype, got, *_ref16(config, scale, sd, x, t, dtype, scale_loss), names="set")
 
 
 @pytest.mark.parametrize("config, scale, dtype, colors", [("A", 2, "bf16", 3), ("B", 3, "fp32", 3), ((2, 3, 32), 4, "fp16", 1)])
 def test_no_grad_path_has_the_bits_of_the_training_forward(config, scale, dtype, colors):
-    m, x, t = _case(config, scale, (2, colors, 7, 6), dtype, 7)
-    x = x.cuda()
-    y = m(x)
-    assert y.grad_fn is not None
-    with torch.no_grad():
-        yi = m(x)
-    assert yi.grad_fn is None and not yi.requires_grad and torch.equal(yi, y.detach())
-    y.sum().backward(retain_graph=True)
-    with pytest.raises(RuntimeError, match="twice"):
-        y.sum().backward()
+    m, x, _ = _case(config, scale, (2, colors, 7, 6), dtype, 7)
+    check_no_grad_bits(m, x)
 
 
 def test_upscale_scene_on_one_tile_equals_the_forward():
-    from srcgan_amd import infer
     m, _, _ = _case((2, 3, 32), 2, (1, 3, 8, 8), "bf16", 9)
     scene = torch.rand(1, 3, 32, 32, generator=torch.Generator().manual_seed(10)).cuda()
-    assert len(infer.plan_tiles(32, 32, 32, 8, 1).tiles) == 1
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=2, tile=32, halo=8, blend="feather")
-    assert tuple(got.shape) == (1, 3, 64, 64) and torch.equal(got, whole)
+    check_one_tile_scene(m, scene, 2, (1, 3, 64, 64))
 
 
 def test_exact_mode_on_a_2x2_tile_plan_equals_the_whole_image_forward():
-    """``upscale_scene`` with halo = receptive_halo (crop) against the same module's whole-image no_grad forward; gate: the exact-mode
-    tests' fp32 gate, rel_err < 1e-3 (tests/test_gpu_infer_scene.py).  The tiles' convolutions see other tile shapes than the whole
-    image's, so the bits may differ; the value is printed."""
-    from srcgan_amd import infer
     m, _, _ = _case((2, 3, 32), 3, (1, 3, 8, 8), "fp32", 13, G0=32)
     scene = torch.rand(1, 3, 24, 20, generator=torch.Generator().manual_seed(14)).cuda()
-    halo = infer.receptive_halo(m)
-    assert halo == 11 and len(infer.plan_tiles(24, 20, 12, halo, 1).tiles) == 4
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=3, tile=12)
-    err = rel_err(got, whole)
-    print(f"[rdn] x3 exact mode, 2 x 2 tiles, halo {halo}: tiled vs whole-image rel_err {err:.3e}")
-    assert tuple(got.shape) == (1, 3, 72, 60) and err < 1e-3
+    check_exact_tiles("rdn", m, scene, 3, 12, 4, (1, 3, 72, 60), halo=11)
 
 
 # ------------------------------------------------------------------------------------------------ the weight gradient of a K slice

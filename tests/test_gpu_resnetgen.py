@@ -16,8 +16,8 @@ import torch
 import torch.nn as nn
 
 import resnetgen_ref as R
-from conftest import load_golden, rel_err, rel_l2
-from test_gpu_mdsr import F32_TOL, STORE, step
+from conftest import load_golden, rel_err
+from net_checks import F32_TOL, STORE, bound16, check_16bit, check_fp32, check_no_grad_bits, check_one_tile_scene, step
 from test_resnetgen_ref import FIXTURES, native
 
 pytestmark = pytest.mark.gpu
@@ -57,10 +57,8 @@ def _case(cin, cout, shape, dtype, seed, n_blocks=2, ngf=64, padding="reflect"):
     return m.cuda(), x, t
 
 
-def live_and_dead(g, gr, n_blocks, padding, measure):
-    dead = R.dead_biases(n_blocks, padding)
-    errs = sorted(((measure(g[k], gr[k]), k) for k in gr if k not in dead), reverse=True)
-    return errs, {k: R.dead_ratio(g, k) for k in dead}
+def dead_ratios(g, n_blocks, padding="reflect"):
+    return {k: R.dead_ratio(g, k) for k in R.dead_biases(n_blocks, padding)}
 
 
 # ngf = 64: 256 channels at a quarter of the resolution, several K chunks; (12, 20) -> 3 x 5 there, the smallest pad-1 tensors; 0 blocks:
@@ -69,15 +67,12 @@ def live_and_dead(g, gr, n_blocks, padding, measure):
                                                                  (1, 3, (2, 1, 12, 20), 2, "zero")])
 def test_fp32_against_the_float64_restatement(cin, cout, shape, n_blocks, padding):
     m, x, t = _case(cin, cout, shape, "fp32", 3, n_blocks=n_blocks, padding=padding)
-    y, loss, dx, g = step(m, x, t)
+    got = step(m, x, t)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
     assert list(sd) == R.names(n_blocks, padding)
-    yr, lr, dxr, gr = R.run(sd, x, t, n_blocks, padding)
-    errs, dead = live_and_dead(g, gr, n_blocks, padding, rel_err)
-    print(f"[resnetgen] {shape} b{n_blocks} {padding} fp32 vs float64: y {rel_err(y, yr):.2e} loss {abs(loss - float(lr)) / float(lr):.2e} "
-          f"dx {rel_err(dx, dxr):.2e} worst live grads {[(f'{e:.2e}', k) for e, k in errs[:3]]} worst dead-bias ratio {max(dead.values()):.2e}")
-    assert list(g) == list(gr)
-    assert rel_err(y, yr) < F32_TOL and abs(loss - float(lr)) < F32_TOL * float(lr) and rel_err(dx, dxr) < F32_TOL and errs[0][0] < F32_TOL
+    dead = dead_ratios(got[3], n_blocks, padding)
+    check_fp32("resnetgen", f"{shape} b{n_blocks} {padding}", got, R.run(sd, x, t, n_blocks, padding), names="list", skip=tuple(dead),
+               tail=f" worst dead-bias ratio {max(dead.values()):.2e}")
     assert max(dead.values()) <= 1e-3, dead
 
 
@@ -86,47 +81,30 @@ _REF16 = {}
 
 @pytest.mark.parametrize("dtype", ["bf16", "fp16"])
 def test_16_bit_modes_against_the_storage_emulation(dtype):
-    """The yardstick of test_gpu_mdsr.check16 on the live tensors: against float64, the native relative L2 error may not exceed 1.5 x the
-    error of the float64 restatement with 16-bit STORAGE (+ 5e-3), on y, dx and the worst live gradient; the dead biases in the same
-    form on their absolute measure.  The loss carries a static scale of 1024, as 16-bit training does."""
+    """net_checks.bound16 on the live tensors, with its static loss scale of 1024; the dead biases in the same form on their absolute
+    measure."""
     n_blocks, shape, scale_loss = 2, (2, 1, 12, 20), 1024.0
     m, x, t = _case(1, 3, shape, dtype, 5)
-    y, _, dx, g = step(m, x, t, scale_loss)
+    got = step(m, x, t, scale_loss)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
     if "ref" not in _REF16:          # the float64 run is the same for both 16-bit types (same seed, same weights)
         _REF16["ref"] = R.run(sd, x, t, n_blocks, loss_scale=scale_loss)
-    yr, _, dxr, gr = _REF16["ref"]
-    ye, _, dxe, ge = R.run(sd, x, t, n_blocks, store=STORE[dtype], loss_scale=scale_loss)
-    nat, dnat = live_and_dead(g, gr, n_blocks, "reflect", rel_l2)
-    emv, demu = live_and_dead(ge, gr, n_blocks, "reflect", rel_l2)
-    print(f"[resnetgen] {dtype} native vs float64: y {rel_l2(y, yr):.4f} dx {rel_l2(dx, dxr):.4f} worst live grads {nat[:2]} "
-          f"worst dead-bias ratio {max(dnat.values()):.2e}")
-    print(f"[resnetgen] {dtype} storage emulation vs float64: y {rel_l2(ye, yr):.4f} dx {rel_l2(dxe, dxr):.4f} worst live grads {emv[:2]} "
-          f"worst dead-bias ratio {max(demu.values()):.2e}")
-    bound = lambda e: 1.5 * e + 5e-3
-    assert list(g) == list(gr) and all(torch.isfinite(v).all() for v in g.values())
-    assert rel_l2(y, yr) < bound(rel_l2(ye, yr))
-    assert rel_l2(dx, dxr) < bound(rel_l2(dxe, dxr))
-    assert nat[0][0] < bound(emv[0][0])
+    emu = R.run(sd, x, t, n_blocks, store=STORE[dtype], loss_scale=scale_loss)
+    dnat, demu = dead_ratios(got[3], n_blocks), dead_ratios(emu[3], n_blocks)
+    check_16bit("resnetgen", "", dtype, got, _REF16["ref"], emu, names="list", skip=tuple(dnat),
+                tails=tuple(f" worst dead-bias ratio {max(d.values()):.2e}" for d in (dnat, demu)))
     # The emulation rounds the forward only and leaves 1e-15 here, so this bound is its 5e-3 constant.  Measured on an MI355X: bf16 4.88e-3
     # -- 2 % below the bound -- and fp16 4.65e-4.  The kernels are deterministic, so it holds as long as they sum in the same order; a
     # change of the summation order in the norm or bias-gradient kernels that moves bf16 by 2 % fails here without anything being wrong
     # with the gradient's size class: read a failure just above 5e-3 as that, one far above it as a bias that is no longer dead.
-    assert max(dnat.values()) <= bound(max(demu.values())), (dnat, demu)
+    assert max(dnat.values()) <= bound16(max(demu.values())), (dnat, demu)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 def test_no_grad_path_has_the_bits_of_the_training_forward(dtype):
     m, x, _ = _case(1, 3, (2, 1, 8, 12), dtype, 7, ngf=16)
-    x = x.cuda()
-    y = m(x)
-    assert y.grad_fn is not None and tuple(y.shape) == (2, 3, 8, 12) and float(y.detach().abs().max()) <= 1.0
-    with torch.no_grad():
-        yi = m(x)
-    assert yi.grad_fn is None and not yi.requires_grad and torch.equal(yi, y.detach())
-    y.sum().backward(retain_graph=True)
-    with pytest.raises(RuntimeError, match="twice"):
-        y.sum().backward()
+    y = check_no_grad_bits(m, x)
+    assert tuple(y.shape) == (2, 3, 8, 12) and float(y.detach().abs().max()) <= 1.0
 
 
 def test_the_input_gradient_is_optional_and_changes_nothing():
@@ -143,11 +121,7 @@ def test_upscale_scene_on_one_tile_equals_the_forward():
     from srcgan_amd import infer
     m, _, _ = _case(3, 3, (1, 3, 8, 8), "bf16", 9, ngf=16, n_blocks=1)
     scene = torch.rand(1, 3, 32, 32, generator=torch.Generator().manual_seed(10)).cuda()
-    assert len(infer.plan_tiles(32, 32, 32, 8, 1).tiles) == 1
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=1, tile=32, halo=8, blend="feather")
-    assert tuple(got.shape) == (1, 3, 32, 32) and torch.equal(got, whole)
+    check_one_tile_scene(m, scene, 1, (1, 3, 32, 32))
     with pytest.raises(ValueError, match=r"up = 2"):
         infer.upscale_scene(m, scene, up=2, tile=32, halo=8, blend="feather")
     with pytest.raises(ValueError, match="per-image statistics make tiles inexact"):          # exact mode: halo=None

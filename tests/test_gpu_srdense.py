@@ -9,13 +9,12 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, rel_err, rel_l2
+from net_checks import F32_TOL, bound16 as bound, check_no_grad_bits
 from test_srdense_host import BIG, TAGS, build_from_fixture, check_grads, restate_run, sketch
 
 pytestmark = pytest.mark.gpu
 
-F32_TOL = 1e-3
 TORCH_DT = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
-bound = lambda e: 1.5 * e + 5e-3
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -126,6 +125,7 @@ def test_inference_equals_the_training_forward_bit_for_bit(tag, dtype):
     assert torch.equal(yi, yt)
     print(f"{tag} {dtype}: peak bytes no_grad {mi}, grad mode {mt}")
     assert mi <= mt
+    check_no_grad_bits(net, x)                   # behind the measurement: its backward leaves gradients allocated
 
 
 # ------------------------------------------------------------------------------------------------ 5. defaults (16, 8, 8)

@@ -9,7 +9,7 @@ import torch
 
 import mdsr_ref
 from conftest import load_golden, rel_err
-from test_gpu_mdsr import F32_TOL, STORE, check16, compare64, report, step
+from net_checks import STORE, check_16bit, check_exact_tiles, check_fixture, check_fp32, check_no_grad_bits, check_one_tile_scene, step
 from test_mdsr_ref import native
 
 pytestmark = pytest.mark.gpu
@@ -23,10 +23,7 @@ def test_fp32_against_the_reference_fixture():
     assert tuple(y.shape) == tuple(z["x"].shape)
     assert list(g) == mdsr_ref.fixture_grad_names(z) and len(z["nograd"]) == 0
     assert {k for k, p in m.named_parameters() if p.grad is None} == {str(k) for k in z["frozen"]}
-    e = mdsr_ref.fixture_errors(z, y, loss, dx, g, "", measure=rel_err)
-    worst = report("vdsr fp32 vs reference", e)
-    assert e["y"] < F32_TOL and e["loss"] < F32_TOL and e["dx"] < F32_TOL
-    assert worst[0][0] < F32_TOL, worst[:3]
+    check_fixture("mdsr", "vdsr fp32 vs reference", mdsr_ref.fixture_errors(z, y, loss, dx, g, "", measure=rel_err))
 
 
 def _case(shape, dtype, seed, n_resblocks=4, n_feats=64):
@@ -43,7 +40,7 @@ def test_fp32_against_the_float64_restatement(n, shape):
     m, x, t = _case(shape, "fp32", 3, n_resblocks=n)
     got = step(m, x, t)
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
-    compare64(f"vdsr r{n} {shape}", got, mdsr_ref.vdsr_run(sd, x, t, n))
+    check_fp32("mdsr", f"vdsr r{n} {shape}", got, mdsr_ref.vdsr_run(sd, x, t, n), names="list")
 
 
 _REF16 = {}
@@ -57,46 +54,26 @@ def test_16_bit_modes_against_the_storage_emulation(dtype):
     sd = {k: v.cpu() for k, v in m.state_dict().items()}
     if "ref" not in _REF16:          # the float64 run is the same for both 16-bit types (same seed, same weights)
         _REF16["ref"] = mdsr_ref.vdsr_run(sd, x, t, 4, loss_scale=scale_loss)
-    check16("vdsr", dtype, got, _REF16["ref"], mdsr_ref.vdsr_run(sd, x, t, 4, store=STORE[dtype], loss_scale=scale_loss))
+    check_16bit("mdsr", "vdsr", dtype, got, _REF16["ref"], mdsr_ref.vdsr_run(sd, x, t, 4, store=STORE[dtype], loss_scale=scale_loss), names="list")
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16", "fp16"])
 def test_no_grad_path_has_the_bits_of_the_training_forward(dtype):
     m, x, _ = _case((2, 3, 7, 6), dtype, 7)
-    x = x.cuda()
-    y = m(x)
-    assert y.grad_fn is not None and tuple(y.shape) == (2, 3, 7, 6)
-    with torch.no_grad():
-        yi = m(x)
-    assert yi.grad_fn is None and not yi.requires_grad and torch.equal(yi, y.detach())
-    y.sum().backward(retain_graph=True)
-    with pytest.raises(RuntimeError, match="twice"):
-        y.sum().backward()
+    assert tuple(check_no_grad_bits(m, x).shape) == (2, 3, 7, 6)
 
 
 def test_upscale_scene_on_one_tile_equals_the_forward():
     from srcgan_amd import infer
     m, _, _ = _case((1, 3, 8, 8), "bf16", 9, n_feats=32)
     scene = torch.rand(1, 3, 32, 32, generator=torch.Generator().manual_seed(10)).cuda()
-    assert len(infer.plan_tiles(32, 32, 32, 8, 1).tiles) == 1
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=1, tile=32, halo=8, blend="feather")
-    assert tuple(got.shape) == (1, 3, 32, 32) and torch.equal(got, whole)
+    check_one_tile_scene(m, scene, 1, (1, 3, 32, 32))
     with pytest.raises(ValueError, match=r"up = 2"):
         infer.upscale_scene(m, scene, up=2, tile=32, halo=8, blend="feather")
 
 
 def test_exact_mode_on_a_2x2_tile_plan_equals_the_whole_image_forward():
-    """as tests/test_gpu_mdsr.py's; receptive_halo = n_resblocks = 4"""
-    from srcgan_amd import infer
+    """receptive_halo = n_resblocks = 4"""
     m, _, _ = _case((1, 3, 8, 8), "fp32", 13, n_feats=32)
     scene = torch.rand(1, 3, 24, 20, generator=torch.Generator().manual_seed(14)).cuda()
-    halo = infer.receptive_halo(m)
-    assert halo == 4 and len(infer.plan_tiles(24, 20, 12, halo, 1).tiles) == 4
-    with torch.no_grad():
-        whole = m(scene)
-    got = infer.upscale_scene(m, scene, up=1, tile=12)
-    err = rel_err(got, whole)
-    print(f"[vdsr] exact mode, 2 x 2 tiles, halo {halo}: tiled vs whole-image rel_err {err:.3e}")
-    assert tuple(got.shape) == (1, 3, 24, 20) and err < 1e-3
+    check_exact_tiles("vdsr", m, scene, 1, 12, 4, (1, 3, 24, 20), halo=4)

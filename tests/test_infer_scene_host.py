@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import oracle
+from net_ref import stitch
 from srcgan_amd import infer
 from srcgan_amd import ESPCN, SRCNN, EDSR, RDDBNet, RDDBNetB, ResDeconv, plan_tiles, receptive_halo, upscale_scene
 
@@ -64,20 +65,6 @@ def test_plan_ramps_are_as_wide_as_the_halo_allows():
     assert len(plan_tiles(37, 53, 4, 0).tiles) == 140
 
 
-def _stitch(forward, x, up, tile, halo):
-    """Apply the plan with torch slicing: run ``forward`` on every tile and keep its core."""
-    H, W = x.shape[2:]
-    plan = plan_tiles(H, W, tile, halo)
-    out = None
-    for t in plan.tiles:
-        y = forward(x[:, :, t.y0:t.y0 + t.th, t.x0:t.x0 + t.tw])
-        if out is None:
-            out = torch.full((1, y.shape[1], H * up, W * up), float("nan"), dtype=y.dtype)
-        cy0, cy1, cx0, cx1 = t.core
-        out[:, :, cy0 * up:cy1 * up, cx0 * up:cx1 * up] = y[:, :, (cy0 - t.y0) * up:(cy1 - t.y0) * up, (cx0 - t.x0) * up:(cx1 - t.x0) * up]
-    return out
-
-
 def _sd64(net):
     return {k: v.detach().double() for k, v in net.state_dict().items()}
 
@@ -108,8 +95,8 @@ def test_receptive_halo_is_sufficient_in_float64(case):
     halo = receptive_halo(net)
     with torch.no_grad():
         whole = forward(x)
-        tiled = _stitch(forward, x, up, 16, halo)
-        short = _stitch(forward, x, up, 16, halo - 1)
+        tiled = stitch(forward, x, up, 16, halo)
+        short = stitch(forward, x, up, 16, halo - 1)
     assert tuple(whole.shape[2:]) == (40 * up, 56 * up)
     rel = float((tiled - whole).abs().max() / whole.abs().max())
     rel_short = float((short - whole).abs().max() / whole.abs().max())

@@ -5,7 +5,7 @@ import torch
 
 import mdsr_ref
 from conftest import load_golden
-from srcgan_amd import plan_tiles
+from net_ref import stitch
 
 MDSR_FIXTURES = ("mdsr_s234_idx0", "mdsr_s234_idx1", "mdsr_s234_idx2")
 FIXTURES = MDSR_FIXTURES + ("vdsr",)
@@ -71,24 +71,11 @@ def test_storage_emulation_in_float64_rounds_nothing():
     assert 1e-4 < mdsr_ref.rel_l2(c[0], y) < 5e-2
 
 
-def _stitch(forward, x, up, tile, halo):
-    """Apply the plan with torch slicing: run ``forward`` on every tile and keep its core (the pattern of tests/test_infer_scene_host.py)."""
-    H, W = x.shape[2:]
-    out = None
-    for t in plan_tiles(H, W, tile, halo).tiles:
-        y = forward(x[:, :, t.y0:t.y0 + t.th, t.x0:t.x0 + t.tw])
-        if out is None:
-            out = torch.full((1, y.shape[1], H * up, W * up), float("nan"), dtype=y.dtype)
-        cy0, cy1, cx0, cx1 = t.core
-        out[:, :, cy0 * up:cy1 * up, cx0 * up:cx1 * up] = y[:, :, (cy0 - t.y0) * up:(cy1 - t.y0) * up, (cx0 - t.x0) * up:(cx1 - t.x0) * up]
-    return out
-
-
 def _sufficient_and_tight(forward, x, up, halo, who):
     with torch.no_grad():
         whole = forward(x)
-        tiled = _stitch(forward, x, up, 16, halo)
-        short = _stitch(forward, x, up, 16, halo - 1)
+        tiled = stitch(forward, x, up, 16, halo)
+        short = stitch(forward, x, up, 16, halo - 1)
     assert tuple(whole.shape[2:]) == (x.shape[2] * up, x.shape[3] * up)
     rel = float((tiled - whole).abs().max() / whole.abs().max())
     rel_short = float((short - whole).abs().max() / whole.abs().max())

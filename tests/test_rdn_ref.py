@@ -5,7 +5,7 @@ import torch
 
 import rdn_ref
 from conftest import load_golden
-from srcgan_amd import plan_tiles
+from net_ref import stitch
 
 FIXTURES = ("rdn_a_x2", "rdn_b_x3", "rdn_a_x4_gray")
 _RUNS = {}
@@ -47,19 +47,6 @@ def test_storage_emulation_and_slice_order_are_the_same_function_in_float64():
     assert 1e-4 < rdn_ref.rel_l2(c[0], a[0]) < 5e-2
 
 
-def _stitch(forward, x, up, tile, halo):
-    """Apply the plan with torch slicing: run ``forward`` on every tile and keep its core (the pattern of tests/test_infer_scene_host.py)."""
-    H, W = x.shape[2:]
-    out = None
-    for t in plan_tiles(H, W, tile, halo).tiles:
-        y = forward(x[:, :, t.y0:t.y0 + t.th, t.x0:t.x0 + t.tw])
-        if out is None:
-            out = torch.full((1, y.shape[1], H * up, W * up), float("nan"), dtype=y.dtype)
-        cy0, cy1, cx0, cx1 = t.core
-        out[:, :, cy0 * up:cy1 * up, cx0 * up:cx1 * up] = y[:, :, (cy0 - t.y0) * up:(cy1 - t.y0) * up, (cx0 - t.x0) * up:(cx1 - t.x0) * up]
-    return out
-
-
 @pytest.mark.parametrize("scale", [2, 3, 4])
 def test_receptive_halo_is_sufficient_and_tight_in_float64(scale):
     """Crop-stitched tiles with halo = receptive_halo == the whole-scene forward to 1e-10 in float64; one pixel less is NOT enough."""
@@ -72,8 +59,8 @@ def test_receptive_halo_is_sufficient_and_tight_in_float64(scale):
     x = torch.rand(1, 3, 40, 56, generator=torch.Generator().manual_seed(7), dtype=torch.float64)
     with torch.no_grad():
         whole = forward(x)
-        tiled = _stitch(forward, x, scale, 16, halo)
-        short = _stitch(forward, x, scale, 16, halo - 1)
+        tiled = stitch(forward, x, scale, 16, halo)
+        short = stitch(forward, x, scale, 16, halo - 1)
     assert tuple(whole.shape[2:]) == (40 * scale, 56 * scale)
     rel = float((tiled - whole).abs().max() / whole.abs().max())
     rel_short = float((short - whole).abs().max() / whole.abs().max())

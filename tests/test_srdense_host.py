@@ -15,19 +15,10 @@ import torch
 import torch.nn.functional as F
 
 from conftest import load_golden, rel_err
+from net_ref import run_l1, sketch
 
 TAGS = ["srdense_a_x2", "srdense_a_x4", "srdense_b_x2", "srdense_b_x4"]
 BIG = "deconv.0.weight"
-
-
-def sketch(t):
-    v = np.asarray(torch.as_tensor(t).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
-    i = np.arange(v.size, dtype=np.uint64)
-    h = (i * np.uint64(2654435761) + np.uint64(40503)) & np.uint64(0xFFFFFFFF)
-    sign = 1.0 - 2.0 * ((h >> np.uint64(15)) & np.uint64(1)).astype(np.float64)
-    out = np.zeros(64, dtype=np.float64)
-    np.add.at(out, (i % np.uint64(64)).astype(np.int64), sign * v)
-    return out
 
 
 def expected_keys(num_blocks, num_layers):
@@ -64,12 +55,7 @@ def restate(sd, x, kind, num_blocks, num_layers, up, store=None):
 
 def restate_run(sd, x, t, kind, nb, nl, up, dtype=torch.float64, store=None):
     """-> (y, loss, dx, {name: grad}) of the restatement under the fixtures' L1 loss."""
-    p = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in sd.items()}
-    xx = torch.as_tensor(x).detach().clone().to(dtype).requires_grad_(True)
-    y = restate(p, xx, kind, nb, nl, up, store)
-    loss = F.l1_loss(y, torch.as_tensor(t).to(dtype))
-    loss.backward()
-    return y.detach(), loss.detach(), xx.grad, {k: v.grad for k, v in p.items()}
+    return run_l1(lambda p, xx: restate(p, xx, kind, nb, nl, up, store), sd, x, t, dtype=dtype, missing="absent")
 
 
 def build_from_fixture(g, tag, dtype=None):
