@@ -315,8 +315,28 @@ int srcgan_sum2x2_nhwc(const void* src, int s_cs, void* dst, int d_cs, const voi
  * Loss reductions on flat f32 arrays (replace aten::l1_loss / mse_loss and their
  * backward; losses.py:95-147, train.py:67-128).  out: device f32 scalar.
  *   kind 0: mean |a-b|          kind 1: mean (a-b)^2      kind 2: mean (a-label)^2
- * bwd: da[i] = gscale * d/da of the mean (gscale = upstream grad, device scalar * host scale)
+ *   kind 3: mean of max(a,0) - a label + log1p(exp(-|a|))  (BCE with logits against the scalar label, the stable form)
+ *   kind 4: mean of label * a   (label = -1 / +1: -mean for real, +mean for fake)
+ * Kinds 0 and 1 need b; kinds 2..4 ignore it (it may be NULL).  a and b: contiguous f32 at ANY 4-byte alignment.  Where they share a
+ * 16-byte phase the forward reads a scalar head, 16-byte groups and a scalar tail, where they differ it reads element by element; the
+ * summation order therefore depends on the phases (and on nothing else: two calls give the same bits, and 16-byte aligned operands
+ * sum as n / 4 groups plus the tail in block 0).  No front end copies to re-align.
+ * fwd: out[0] = (sum of the terms, two stages of fixed order, f32) * (float)(1.0 / n).
+ * bwd: da[i] = d term / d a[i] * g,  g = gout[0] * (gscale / (float)n): gout is a DEVICE scalar (the upstream gradient, never read on
+ *      the host), gscale a host factor divided by (float)n on the host; gscale = -1 gives the gradient w.r.t. b of kinds 0 and 1.
+ *      d/da: sign(a-b) with sign(0) = 0 | 2 (a-b) | 2 (a-label) | 1 / (1 + exp(-a)) - label | label.  Every element of da is written once;
+ *      da needs 4-byte alignment only.
+ * Refused (non-zero return, nothing launched): a NULL a / out / scratch / gout / da, n <= 0, a kind outside 0..4, kind 0 or 1 without b.
  * scratch: srcgan_loss_scratch_floats() floats.
+ * Pinned by tests/test_gpu_mean_loss.py:
+ *   - small-integer operands (every partial sum an integer < 2^24): out has the bits of f32(S) * f32(1.0 / n) at n = 1..8, 1023, 1024,
+ *     1027, around the capped grid (1 048 572 .. 1 048 579) and over two grid-stride trips (2 097 157), with a at byte phase 0, 4, 8, 12
+ *     and b at the same and at another phase; da of kinds 0 and 4 has the bits of sign * g / label * g for gout 1, 3, -0.5, gscale +-1.
+ *   - reals: |out - float64| <= (D + 4) 2^-24 mean|term|, D the longest chain of additions of the launch; da of kinds 1 and 2 within
+ *     5 * 2^-24 |float64| per element; kind 3 within 3 * 2^-24 N (value) and 12 * 2^-24 N (gradient), N the sum of the absolute terms,
+ *     with logits of +-100 planted.
+ *   - scratch may hold NaN on entry; nothing is written behind scratch, out or da, and a and b are unchanged.
+ *   - srcgan_psnr_from_mse: within 3 * 2^-24 (|psnr| + 10 / ln 10) of float64; mse = 1 gives exactly 0, mse = 0 gives +inf.
  * ------------------------------------------------------------------------- */
 int srcgan_loss_scratch_floats(void);
 int srcgan_loss_fwd(int kind, const float* a, const float* b, float label, long n, float* out,

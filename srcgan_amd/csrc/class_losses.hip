@@ -40,32 +40,12 @@ __global__ __launch_bounds__(256) void cl_final_k(const float* __restrict__ part
     if (threadIdx.x == 0) *out = ((red[0] + red[1]) + (red[2] + red[3])) * scale;
 }
 
-// [0, head) element by element, then nv groups of four from `head` (16-byte aligned in every pointer), then the rest element by element
-struct ClSpan { long head, nv, n; };
-
-static ClSpan cl_span(long n, const void* p0, const void* p1, const void* p2 = nullptr) {
-    ClSpan s = {0, 0, n};
-    const uintptr_t ph = (uintptr_t)p0 % 16;
-    if (ph % 4 || (uintptr_t)p1 % 16 != ph || (p2 && (uintptr_t)p2 % 16 != ph)) return s;       // phases differ: all scalar
-    s.head = (long)((16 - ph) % 16 / 4);
-    if (s.head > n) s.head = n;
-    s.nv = (n - s.head) / 4;
-    return s;
-}
-
+// the head / 16-byte body / tail split of a flat range: common.h's SgSpan, shared with the mean losses of elementwise.hip
 static int cl_blocks(long items, int cap, int threads) {
     const long b = cdivl(items, threads);
     return (int)(b > cap ? cap : (b < 1 ? 1 : b));
 }
-static int cl_span_blocks(const ClSpan& s, int cap, int threads) { return cl_blocks(s.nv + (s.n - 4 * s.nv), cap, threads); }
-
-template <typename FV, typename FS>
-__device__ __forceinline__ void cl_for_each(const ClSpan& sp, FV fv, FS fs) {
-    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
-    for (long v = t0; v < sp.nv; v += stride) fv(sp.head + v * 4);
-    const long ns = sp.n - sp.nv * 4;
-    for (long i = t0; i < ns; i += stride) fs(i < sp.head ? i : i + sp.nv * 4);
-}
+static int cl_span_blocks(const SgSpan& s, int cap, int threads) { return cl_blocks(s.nv + (s.n - 4 * s.nv), cap, threads); }
 
 // ------------------------------------------------------------------------------------------------ element-wise terms
 // Focal loss on o = clamp(x, lo, hi), lo = (float)1e-6, hi = (float)(1.0 - 1e-6) (torch.clamp's float32 bounds; a NaN stays a NaN):
@@ -135,10 +115,10 @@ struct ClL1 {
 };
 
 template <typename OP>
-__global__ __launch_bounds__(CL_FWD_THREADS) void cl_flat_fwd_k(const float* __restrict__ a, const float* __restrict__ t, ClSpan sp, OP op,
+__global__ __launch_bounds__(CL_FWD_THREADS) void cl_flat_fwd_k(const float* __restrict__ a, const float* __restrict__ t, SgSpan sp, OP op,
                                                      float* __restrict__ partial) {
     float s = 0.f;
-    cl_for_each(sp,
+    sg_span_each(sp,
         [&](long e) {
             const f32x4 av = *(const f32x4*)(a + e), tv = *(const f32x4*)(t + e);
 #pragma unroll
@@ -150,10 +130,10 @@ __global__ __launch_bounds__(CL_FWD_THREADS) void cl_flat_fwd_k(const float* __r
 
 // da[e] = op.bwd * gout[0] * gscale over the span, then zeros over [sp.n, sp.n + nzero)
 template <typename OP>
-__global__ __launch_bounds__(256) void cl_flat_bwd_k(const float* __restrict__ a, const float* __restrict__ t, ClSpan sp, OP op,
+__global__ __launch_bounds__(256) void cl_flat_bwd_k(const float* __restrict__ a, const float* __restrict__ t, SgSpan sp, OP op,
                                                      const float* __restrict__ gout, float gscale, float* __restrict__ da, long nzero) {
     const float g = gout[0] * gscale;
-    cl_for_each(sp,
+    sg_span_each(sp,
         [&](long e) {
             const f32x4 av = *(const f32x4*)(a + e), tv = *(const f32x4*)(t + e);
             f32x4 d;
@@ -169,7 +149,7 @@ template <typename OP>
 static int cl_flat_fwd(const char* what, const float* a, const float* t, long n, OP op, double scale, float* out, float* scratch, void* stream) {
     SG_REQUIRE(a && t && out && scratch && n > 0, "%s: bad arguments", what);
     SG_REQUIRE(srcgan_loss_scratch_floats() >= CL_FWD_BLOCKS, "%s: scratch too small", what);
-    const ClSpan sp = cl_span(n, a, t);
+    const SgSpan sp = sg_span(n, a, t);
     const int nb = cl_span_blocks(sp, CL_FWD_BLOCKS, CL_FWD_THREADS);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(cl_flat_fwd_k<OP>, dim3(nb), dim3(CL_FWD_THREADS), 0, st, a, t, sp, op, scratch);
@@ -183,7 +163,7 @@ template <typename OP>
 static int cl_flat_bwd(const char* what, const float* a, const float* t, long n, OP op, const float* gout, float gscale, float* da,
                        long nzero, void* stream) {
     SG_REQUIRE(a && t && gout && da && n > 0 && nzero >= 0, "%s: bad arguments", what);
-    const ClSpan sp = cl_span(n, a, t, da);
+    const SgSpan sp = sg_span(n, a, t, da);
     hipLaunchKernelGGL(cl_flat_bwd_k<OP>, dim3(cl_span_blocks(sp, CL_BWD_BLOCKS, CL_BWD_THREADS)), dim3(CL_BWD_THREADS), 0, (hipStream_t)stream, a, t, sp, op, gout,
                        gscale, da, nzero);
     SG_LAUNCH_CHECK();

@@ -103,6 +103,29 @@ __host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / 
 __host__ __device__ static inline long cdivl(long a, long b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ---------------------------------------------------------------- flat f32 ranges at any 4-byte alignment (class_losses.hip, elementwise.hip)
+// [0, head) element by element, then nv groups of four from `head` (16-byte aligned in every pointer), then the rest element by element
+struct SgSpan { long head, nv, n; };
+
+static inline SgSpan sg_span(long n, const void* p0, const void* p1 = nullptr, const void* p2 = nullptr) {
+    SgSpan s = {0, 0, n};
+    const uintptr_t ph = (uintptr_t)p0 % 16;
+    if (ph % 4 || (p1 && (uintptr_t)p1 % 16 != ph) || (p2 && (uintptr_t)p2 % 16 != ph)) return s;       // phases differ: all scalar
+    s.head = (long)((16 - ph) % 16 / 4);
+    if (s.head > n) s.head = n;
+    s.nv = (n - s.head) / 4;
+    return s;
+}
+
+// every thread of the grid: its groups of four (fv(first element)) grid-stride, then its single elements (fs(element)) grid-stride
+template <typename FV, typename FS>
+__device__ __forceinline__ void sg_span_each(const SgSpan& sp, FV fv, FS fs) {
+    const long t0 = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+    for (long v = t0; v < sp.nv; v += stride) fv(sp.head + v * 4);
+    const long ns = sp.n - sp.nv * 4;
+    for (long i = t0; i < ns; i += stride) fs(i < sp.head ? i : i + sp.nv * 4);
+}
+
 // ---------------------------------------------------------------- diagnostics
 // The production library carries NO run-time experiment switches: SG_DBG(p, bit) is the constant 0 and sg_env() returns
 // nullptr unless the file is compiled with -DSG_DIAG (scripts/build_variant.sh builds such variants side by side and

@@ -933,23 +933,23 @@ __device__ __forceinline__ float loss_grad(float x, float t) {       // d elem /
     if (KIND == 4) return t;
     return 2.f * (x - t);
 }
+// Operands at any 4-byte alignment (common.h, SgSpan): a thread adds its groups of four, then its single elements -- the head before the
+// first 16-byte boundary and the tail, or every element when a and b differ in phase.  With both operands 16-byte aligned that is
+// n / 4 groups and the n % 4 tail elements in the first threads of block 0.
 template <int KIND>
 __global__ __launch_bounds__(256) void loss_fwd_k(const float* __restrict__ a, const float* __restrict__ b, float label,
-                                                  long n, float* __restrict__ partial) {
+                                                  SgSpan sp, float* __restrict__ partial) {
     __shared__ float red[4];
     float s = 0.f;
-    const long n4 = n / 4;
-    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n4; e += (long)gridDim.x * 256) {
-        const f32x4 av = *(const f32x4*)(a + e * 4);
-        f32x4 bv = {label, label, label, label};
-        if (KIND < 2) bv = *(const f32x4*)(b + e * 4);
+    sg_span_each(sp,
+        [&](long e) {
+            const f32x4 av = *(const f32x4*)(a + e);
+            f32x4 bv = {label, label, label, label};
+            if (KIND < 2) bv = *(const f32x4*)(b + e);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) s += loss_elem<KIND>(av[i], bv[i]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {       // tail
-        const long e = n4 * 4 + threadIdx.x;
-        s += loss_elem<KIND>(a[e], KIND >= 2 ? label : b[e]);
-    }
+            for (int i = 0; i < 4; ++i) s += loss_elem<KIND>(av[i], bv[i]);
+        },
+        [&](long e) { s += loss_elem<KIND>(a[e], KIND >= 2 ? label : b[e]); });
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -969,14 +969,16 @@ __global__ __launch_bounds__(256) void loss_final_k(const float* __restrict__ pa
 extern "C" int srcgan_loss_fwd(int kind, const float* a, const float* b, float label, long n, float* out, float* scratch, void* stream) {
     SG_REQUIRE(a && out && scratch && n > 0 && kind >= 0 && kind <= 4, "srcgan_loss_fwd: bad arguments");
     SG_REQUIRE(kind >= 2 || b, "srcgan_loss_fwd: kind %d needs b", kind);
-    SG_REQUIRE(((uintptr_t)a % 16) == 0 && (kind >= 2 || ((uintptr_t)b % 16) == 0), "srcgan_loss_fwd: inputs must be 16-byte aligned");
-    long nb = cdivl(n / 4 + 1, 256); if (nb > LOSS_BLOCKS) nb = LOSS_BLOCKS;
+    SG_REQUIRE(((uintptr_t)a % 4) == 0 && (kind >= 2 || ((uintptr_t)b % 4) == 0), "srcgan_loss_fwd: inputs must be 4-byte aligned");
+    const SgSpan sp = sg_span(n, a, kind < 2 ? b : nullptr);
+    const long ns = n - 4 * sp.nv;                         // single elements: head + tail (<= 6), or all of them when the phases differ
+    long nb = cdivl(sp.nv + 1 > ns ? sp.nv + 1 : ns, 256); if (nb > LOSS_BLOCKS) nb = LOSS_BLOCKS;
     hipStream_t st = (hipStream_t)stream;
-    if (kind == 0) hipLaunchKernelGGL(loss_fwd_k<0>, dim3((int)nb), dim3(256), 0, st, a, b, label, n, scratch);
-    else if (kind == 1) hipLaunchKernelGGL(loss_fwd_k<1>, dim3((int)nb), dim3(256), 0, st, a, b, label, n, scratch);
-    else if (kind == 2) hipLaunchKernelGGL(loss_fwd_k<2>, dim3((int)nb), dim3(256), 0, st, a, b, label, n, scratch);
-    else if (kind == 3) hipLaunchKernelGGL(loss_fwd_k<3>, dim3((int)nb), dim3(256), 0, st, a, b, label, n, scratch);
-    else hipLaunchKernelGGL(loss_fwd_k<4>, dim3((int)nb), dim3(256), 0, st, a, b, label, n, scratch);
+    if (kind == 0) hipLaunchKernelGGL(loss_fwd_k<0>, dim3((int)nb), dim3(256), 0, st, a, b, label, sp, scratch);
+    else if (kind == 1) hipLaunchKernelGGL(loss_fwd_k<1>, dim3((int)nb), dim3(256), 0, st, a, b, label, sp, scratch);
+    else if (kind == 2) hipLaunchKernelGGL(loss_fwd_k<2>, dim3((int)nb), dim3(256), 0, st, a, b, label, sp, scratch);
+    else if (kind == 3) hipLaunchKernelGGL(loss_fwd_k<3>, dim3((int)nb), dim3(256), 0, st, a, b, label, sp, scratch);
+    else hipLaunchKernelGGL(loss_fwd_k<4>, dim3((int)nb), dim3(256), 0, st, a, b, label, sp, scratch);
     SG_LAUNCH_CHECK();
     hipLaunchKernelGGL(loss_final_k, dim3(1), dim3(256), 0, st, scratch, (int)nb, (float)(1.0 / (double)n), out);
     SG_LAUNCH_CHECK();

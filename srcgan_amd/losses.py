@@ -733,7 +733,7 @@ class _VggFramesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, output, loss, grad):
-        ctx.grad = grad
+        ctx.grad, ctx.in_dtype = grad, output.dtype
         return loss.clone()
 
     @staticmethod
@@ -741,7 +741,7 @@ class _VggFramesFn(torch.autograd.Function):
         if ctx.grad is None:
             raise RuntimeError("perceptual loss: backward called a second time (the stored gradient is released by the first)")
         grad, ctx.grad = ctx.grad, None
-        return (grad.float() * gout.float()).to(grad.dtype), None, None
+        return (grad * gout.float()).to(ctx.in_dtype), None, None      # the f32 gradient, scaled, cast once to a 16-bit input's dtype
 
 
 class VGG16Loss3D(VGG16Loss):
@@ -801,7 +801,7 @@ class VGG16Loss3D(VGG16Loss):
             total = total + part * share      # stream-ordered: `part` is rewritten by the next chunk only after this read
         if not need_grad:
             return total
-        return _VggFramesFn.apply(output, total, grad.to(output.dtype))
+        return _VggFramesFn.apply(output, total, grad)
 
 
 class PerceptionLoss(_VggLossBase):

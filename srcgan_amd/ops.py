@@ -29,6 +29,7 @@ def to_nchw(x: torch.Tensor, Cc: Optional[int] = None, coff: int = 0) -> torch.T
     """NHWC (compute dtype) -> NCHW f32, channels [coff, coff+C)."""
     N.require_cuda(x, "to_nchw")
     dt = N.dtype_id(x.dtype)
+    x = x.contiguous()                  # the kernel addresses [B,H,W,cs] densely: a strided view is copied, never read as if dense
     B, H, W, cs = x.shape
     Cc = Cc or cs - coff
     out = torch.empty(B, Cc, H, W, dtype=torch.float32, device=x.device)
