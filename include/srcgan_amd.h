@@ -786,6 +786,44 @@ size_t srcgan_resnetgen_infer_act_bytes(const srcgan_resnetgen_cfg* c);
 int srcgan_resnetgen_infer_plan(const srcgan_resnetgen_cfg* c, size_t* ranges, int cap);
 int srcgan_resnetgen_infer(const srcgan_resnetgen_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
 
+/* The U-Net's skip connection without a concatenation (csrc/unet_skip.hip), NHWC, channel strides *_cs elements, all three dtypes, 64-bit
+ * addresses, no atomics, every output element written exactly once.
+ *   srcgan_in_skip_forward: InstanceNorm2d without an affine part, two activated outputs from one read of the normalised value z:
+ *                           a = LeakyReLU(z, slope), dense; r = ReLU(z) into channels [r_coff, r_coff + C) of a buffer of r_cs channels.
+ *                           The statistics are srcgan_gn_forward's with G == C (the same kernels): a and r have the bits of that entry with
+ *                           (relu = 1, slope) and (relu = 1, 0), stats [B][C]{mean, rstd} is its saved layout (srcgan_gn_backward serves),
+ *                           scratch is srcgan_gn_scratch_floats(B, C).  16-byte accesses: C, strides and r_coff multiples of 4 (f32) / 8.
+ *   srcgan_relu_nhwc:       y[.., y_coff : y_coff + C] = max(x, 0) on npix records; 16-byte accesses where C, strides and bases allow them,
+ *                           element by element otherwise. */
+int srcgan_in_skip_forward(const void* x, int x_cs, void* a, int a_cs, void* r, int r_cs, int r_coff, float* stats, int B, long hw, int C,
+                           float eps, float slope, int dtype, float* scratch, void* stream);
+int srcgan_relu_nhwc(const void* x, int x_cs, void* y, int y_cs, int y_coff, long npix, int C, int dtype, void* stream);
+
+/* UnetGenerator (reference src/model/basicModel.py:257-354) with InstanceNorm2d (no parameters) and use_bias = True.  Levels l = 1 (outermost)
+ * .. n = num_downs, widths C_l = ngf min(2^(l-1), 8).  Down: d_1 = conv4x4 s2 p1 (in -> C_1), d_l = IN(conv4x4 s2 p1(LeakyReLU(d_{l-1}, 0.2))),
+ * the innermost d_n without the IN.  Up: u_{n-1} = IN(deconv(ReLU(d_n))), u_{l-1} = IN(deconv([ReLU(d_l) | ReLU(u_l)])), deconv =
+ * ConvTranspose2d(k4, s2, p1); y = tanh(deconv([ReLU(d_1) | ReLU(u_1)]) (2 C_1 -> out)).  [B,in_ch,H,W] f32 NCHW -> [B,out_ch,H,W].
+ * The skip [ReLU(d_l) | ReLU(u_l)] is one 2 C_l-channel buffer written in place by its two producers; nothing is concatenated.
+ * params / grads in parameters() order: the down convolutions' {weight, bias} outermost first, then the transposed convolutions'
+ * innermost first: 4 num_downs tensors.  Refused: num_downs < 5, H or W no positive multiple of 2^num_downs, ngf not 16, 32, 64 or 128
+ * (a multiple of 16 whose widths InstanceNorm's kernels take), in_ch or out_ch outside 1..8.  Entry points as srcgan_resnetgen_*. */
+typedef struct srcgan_unet_cfg {
+    int in_ch, out_ch;
+    int B, H, W;
+    int dtype;
+    int ngf, num_downs;
+} srcgan_unet_cfg;
+int srcgan_unet_num_params(const srcgan_unet_cfg* c);
+size_t srcgan_unet_ws_bytes(const srcgan_unet_cfg* c);
+size_t srcgan_unet_bwd_scratch_bytes(const srcgan_unet_cfg* c);
+int srcgan_unet_forward(const srcgan_unet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+int srcgan_unet_backward(const srcgan_unet_cfg* c, const float* dy_nchw, const float* const* params, void* ws, void* scratch,
+                         float* const* grads, float* dx_nchw, void* stream);
+size_t srcgan_unet_infer_ws_bytes(const srcgan_unet_cfg* c);
+size_t srcgan_unet_infer_act_bytes(const srcgan_unet_cfg* c);
+int srcgan_unet_infer_plan(const srcgan_unet_cfg* c, size_t* ranges, int cap);
+int srcgan_unet_infer(const srcgan_unet_cfg* c, const float* x_nchw, const float* const* params, void* ws, float* y_nchw, void* stream);
+
 /* Kernels of the frozen VGG feature path, NHWC, channel stride *_cs elements, all three dtypes (16-byte accesses along the channels
  * when strides and bases allow them, element by element otherwise).
  *   srcgan_maxpool2_nhwc:     nn.MaxPool2d(2, 2), ceil_mode = False: [B,H,W,C] -> [B,H/2,W/2,C]; an odd last row / column is dropped.

@@ -6,12 +6,12 @@ Everything computes in libsrcgan_amd.so (hand-written HIP for gfx950); there is 
 """
 from ._native import set_default_dtype, LIB_PATH
 from .model import RDDBNet, RDDBNetA, RDDBNetB, LegacyRDDBNet, ResDeconv, ESPCN, SRCNN, EDSR, SRDN, SRDenseNetA, SRDenseNetB, RCAN, DDBPN, RDN, MDSR, VDSR, NLayerDiscriminator, ResidualDenseBlock_5, RRDB
-from .model import ResnetGenerator, define_G, get_norm_layer, init_weights, init_net
+from .model import ResnetGenerator, UnetGenerator, define_G, get_norm_layer, init_weights, init_net
 from .losses import (L1Loss, MSELoss, PSNRLoss, GANLoss, DSSIMLoss, VGG16Loss, PerceptionLoss, NearestSelector, NearestL1Loss,
                      L1Loss3D, DSSIMLoss3D, VGG16Loss3D, FLoss, CELoss, ConLoss, CrossLoss)
 from .infer import plan_tiles, receptive_halo, upscale_scene, cascade_scene
 from .metrics import score_scene
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "ResnetGenerator", "define_G", "get_norm_layer", "init_weights", "init_net", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "ResnetGenerator", "UnetGenerator", "define_G", "get_norm_layer", "init_weights", "init_net", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB",
            "L1Loss", "MSELoss", "PSNRLoss", "GANLoss", "DSSIMLoss", "VGG16Loss", "PerceptionLoss", "NearestSelector", "NearestL1Loss", "L1Loss3D", "DSSIMLoss3D", "VGG16Loss3D", "FLoss", "CELoss", "ConLoss", "CrossLoss", "plan_tiles", "receptive_halo", "upscale_scene", "cascade_scene", "score_scene", "set_default_dtype", "LIB_PATH"]
 __version__ = "0.1.0"

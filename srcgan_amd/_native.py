@@ -128,6 +128,10 @@ class ResnetGenCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("in_ch", "out_ch", "B", "H", "W", "dtype", "ngf", "n_blocks", "padding")]
 
 
+class UnetCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("in_ch", "out_ch", "B", "H", "W", "dtype", "ngf", "num_downs")]
+
+
 class VggLossCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("kind", "B", "H", "W", "dtype")]
 
@@ -178,6 +182,8 @@ SIGNATURES = {
     "srcgan_reflect_pad_bwd_nhwc": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_tanh_forward": (_I, [_P, _I, _P, _I, _L, _I, _I, _P]),
     "srcgan_tanh_backward": (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _I, _I, _P]),
+    "srcgan_in_skip_forward": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _I, _L, _I, _F, _F, _I, _P, _P]),
+    "srcgan_relu_nhwc": (_I, [_P, _I, _P, _I, _I, _L, _I, _I, _P]),
     "srcgan_upsample2_nhwc": (_I, [_P, _I, _I, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
     "srcgan_sum2x2_nhwc": (_I, [_P, _I, _P, _I, _P, _I, _F, _I, _I, _I, _I, _I, _P]),
     "srcgan_loss_scratch_floats": (_I, []),
@@ -284,10 +290,10 @@ def _infer_rows(stem, cfg):
 
 
 for _stem, _cfg in (("resdeconv", ResDeconvCfg), ("srnet", SrNetCfg), ("srdense", SrDenseCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg), ("rdn", RdnCfg),
-                    ("mdsr", MdsrCfg), ("vdsr", VdsrCfg), ("resnetgen", ResnetGenCfg)):
+                    ("mdsr", MdsrCfg), ("vdsr", VdsrCfg), ("resnetgen", ResnetGenCfg), ("unet", UnetCfg)):
     SIGNATURES.update(_train_rows(_stem, _cfg))
 for _stem, _cfg in (("srnet", SrNetCfg), ("rcan", RcanCfg), ("ddbpn", DdbpnCfg), ("rdn", RdnCfg),
-                    ("mdsr", MdsrCfg), ("vdsr", VdsrCfg), ("resnetgen", ResnetGenCfg)):
+                    ("mdsr", MdsrCfg), ("vdsr", VdsrCfg), ("resnetgen", ResnetGenCfg), ("unet", UnetCfg)):
     SIGNATURES.update(_infer_rows(_stem, _cfg))
 SIGNATURES.update({
     "srcgan_resdeconv_infer_ws_bytes": (_S, [C.POINTER(ResDeconvCfg), _I]),       # ResDeconv: fold_tail

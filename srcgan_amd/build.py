@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libsrcgan_amd.so")
-SOURCES = ["conv_entry.hip", "conv_igemm.hip", "conv_par4.hip", "deconv_k3s2.hip", "conv3x3_dma.hip", "conv_wgrad.hip", "wgrad_dense.hip", "elementwise.hip", "class_losses.hip", "groupnorm.hip", "chan_attn.hip", "back_proj.hip", "reflect_pad.hip", "metrics.hip", "shift_select.hip", "scene_score.hip", "colour.hip", "tiles.hip", "vgg_loss.hip", "nets.hip", "oplist.hip"]
+SOURCES = ["conv_entry.hip", "conv_igemm.hip", "conv_par4.hip", "deconv_k3s2.hip", "conv3x3_dma.hip", "conv_wgrad.hip", "wgrad_dense.hip", "elementwise.hip", "class_losses.hip", "groupnorm.hip", "chan_attn.hip", "back_proj.hip", "reflect_pad.hip", "unet_skip.hip", "metrics.hip", "shift_select.hip", "scene_score.hip", "colour.hip", "tiles.hip", "vgg_loss.hip", "nets.hip", "oplist.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -179,4 +179,7 @@ int sg_meanshift(const void* x, void* y, const float* w, const float* bias, int 
 // w [kdim][rows][k][k]) weight <-> its stride-1 form over the space-to-depth view, a Conv2d weight with T = ceil(k / s) taps per axis:
 // form 0 [rows][s*s*kdim][T][T], form 1 [s*s*rows][kdim][T][T] (taps flipped).  back != 0: the stride-1 form's gradient -> the stored layout
 int sg_proj_repack(const float* src, float* dst, int form, int rows, int kdim, int k, int s, int back, hipStream_t st);
+// InstanceNorm / GroupNorm statistics alone (unet_skip.hip -> groupnorm.hip): the partial and fold launches of srcgan_gn_forward with its
+// arguments, its scratch and its stats layout [B][G]{mean, rstd} -- the same kernels, so the same bits
+int sg_gn_stats(const void* x, int x_cs, float* stats, int B, long hw, int C, int G, float eps, int dtype, float* scratch, hipStream_t st);
 int sg_fill_zero_guarded(void* p, size_t bytes, const unsigned long long* guard, hipStream_t st);     // guard == nullptr: plain hipMemsetAsync

@@ -236,6 +236,21 @@ extern "C" int srcgan_gn_forward(const void* x, int x_cs, const void* res, int r
     return 0;
 }
 
+// the statistics pass of srcgan_gn_forward on its own (common.h): a kernel that applies them in its own way launches behind it
+int sg_gn_stats(const void* x, int x_cs, float* stats, int B, long hw, int C, int G, float eps, int dtype, float* scratch, hipStream_t st) {
+    SG_REQUIRE(x && stats && scratch, "sg_gn_stats: null pointer");
+    SG_TRY(gn_check("sg_gn_stats", B, hw, C, G, dtype));
+    const int epp = dtype == SRCGAN_F32 ? 4 : 8;
+    SG_REQUIRE(x_cs % epp == 0, "sg_gn_stats: the channel stride must be a multiple of %d", epp);
+    const int nblk = gn_nblk(hw, C, epp);
+    DISPATCH_DTYPE(dtype, {
+        hipLaunchKernelGGL((gn_partial_k<T, 0>), dim3(nblk, B), dim3(256), 0, st, (const T*)x, x_cs, (const T*)nullptr, 0, (const T*)nullptr, 0, (const float*)nullptr, hw, C, G, 0.f, scratch);
+        hipLaunchKernelGGL(gn_fold_k<0>, dim3(B), dim3(256), 0, st, (const float*)scratch, nblk, C, G, hw, eps, (const float*)nullptr, stats, (float*)nullptr);
+    });
+    SG_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int srcgan_gn_backward(const void* dy, int dy_cs, const void* yact, int ya_cs, const void* x, int x_cs, const float* gamma, const float* stats,
                                   void* dx, int dx_cs, void* dres, int dres_cs, int dres_accumulate, float* dgamma, float* dbeta, int accumulate,
                                   float slope, int B, long hw, int C, int G, int dtype, float* scratch, void* stream) {

@@ -134,8 +134,10 @@ struct S2Dgrad {
     // dy [B, OH, OW, cout] -> dx [B, H, W, cin].  acc: dx already holds a contribution, add to it; mz: multiply by LeakyReLU' of
     // this tensor (either may be TNULL).  fuse: all four parities from one staged dy tile in ONE launch (conv_par4.hip: 4x4 p1,
     // equally spaced packs, 16-byte accessible operands) where that applies; SRCGAN_NO_PAR4 (diagnostic builds) keeps the four.
+    // bias: per dx channel, added in either form -- the same four sub-convolutions ARE ConvTranspose2d(k4, s2, p1) of dy with the
+    // stored weight [in][out][4][4] read as w [cout][cin][4][4] (the op-list executor's RD_DECONV4).
     int run(int dt, TRef dy, int B, int OH, int OW, TRef dx, int H, int W, const char* wp, const size_t wd[4], TRef acc, TRef mz,
-            bool fuse, void* st, float mslope = 0.2f) const {
+            bool fuse, void* st, float mslope = 0.2f, const float* bias = nullptr) const {
         static const bool no_par4 = sg_env("SRCGAN_NO_PAR4") != nullptr;
         auto launch = [&](Conv& cv) {
             if (acc.p) cv.res1(acc, cin, 1.f);
@@ -145,9 +147,9 @@ struct S2Dgrad {
         const int vec = 16 / (dt == SRCGAN_F32 ? 4 : 2);
         const size_t wstep = wd[1] - wd[0];
         const bool even = wd[2] - wd[1] == wstep && wd[3] - wd[2] == wstep;
-        if (fuse && !no_par4 && k == 4 && pad == 1 && even && H >= 2 && W >= 2 && cin % vec == 0 && dx.cs % vec == 0) {
+        if (fuse && !no_par4 && k == 4 && pad == 1 && even && H >= 2 && W >= 2 && cin % vec == 0 && dx.cs % vec == 0 && (uintptr_t)bias % 16 == 0) {
             Conv cv(dt, 2, 2, 1);
-            cv.in(dy, B, OH, OW, cout).w(wp + wd[0]).out(dx, (H + 1) / 2, (W + 1) / 2, cin).scatter(2, 0, 0, H, W);
+            cv.in(dy, B, OH, OW, cout).w(wp + wd[0], bias).out(dx, (H + 1) / 2, (W + 1) / 2, cin).scatter(2, 0, 0, H, W);
             cv.d.npar = 4; cv.d.wpar_stride = (long)wstep;
             return launch(cv);
         }
@@ -157,7 +159,7 @@ struct S2Dgrad {
             if (mh <= 0 || mw <= 0) continue;
             const Par2 py = par2(k, pad, a), px = par2(k, pad, b);
             Conv cv(dt, py.n, px.n, 1);
-            cv.in(dy, B, OH, OW, cout).w(wp + wd[q]).out(dx, mh, mw, cin).pad(py.lead, px.lead).scatter(2, a, b, H, W);
+            cv.in(dy, B, OH, OW, cout).w(wp + wd[q], bias).out(dx, mh, mw, cin).pad(py.lead, px.lead).scatter(2, a, b, H, W);
             SG_TRY(launch(cv));
         }
         return 0;

@@ -5,7 +5,7 @@
 //   ResDeconv, ESPCN, SRCNN, EDSR     reference src/model/{resdeconv,espcn,srcnn,edsr}.py
 //   SRDenseNetA / SRDenseNetB         reference src/model/model.py:643-786
 //   RCAN, DDBPN, RDN, MDSR, VDSR      reference src/model/{rcan,ddbpn,rdn,mdsr,vdsr}.py
-//   ResnetGenerator                   reference src/model/basicModel.py:141-254
+//   ResnetGenerator, UnetGenerator    reference src/model/basicModel.py:141-354
 //   frozen VGG16 / VGG19 features     reference src/losses.py:344-393, 455-470 (VGG16Loss, PerceptionLoss)
 #include "net_common.h"
 #include <map>
@@ -22,8 +22,11 @@
 // convolution with a fused ReLU is the gradient w.r.t. its pre-activation: whoever writes it applies the mask (the consumer's
 // dgrad epilogue, or srcgan_mask_inplace for the gradient arriving from the loss).
 namespace {
-struct RdT { int C, cs, H, W, act; size_t off; int act0; };      // act: produced by a convolution with a fused ReLU -- its channels from act0 on
-                                                                  // (RDN's dense buffers: the prefix [0, G0) is a block's input, a plain sum)
+struct RdT { int C, cs, H, W, act; size_t off; int act0; float aslope; int skip; };
+// act: produced with a fused activation, so its stored gradient is the one w.r.t. the pre-activation -- its channels from act0 on (RDN's
+// dense buffers: the prefix [0, G0) is a block's input, a plain sum); aslope: that activation's negative slope (0 = ReLU), which the
+// backward masks take.  skip != 0 (the U-Net): the tensor is LeakyReLU(z), and ReLU(z) of the same z sits in channels [0, C) of the skip
+// buffer `skip`, whose gradient slice the tensor's one consumer folds into its input gradient (tensor 0 is the network input: never a skip)
 // What an op does.  Every place that branches on the kind is a switch over this enum WITHOUT a default, so -Wswitch names the switch a
 // new kind is missing from: a kind a walker has nothing to do for gets an explicit empty case, one it must never meet an "internal error".
 enum RdKind {
@@ -43,6 +46,11 @@ enum RdKind {
                       // w = the slope's parameter, bias = the transposed projection's bias or -1, res at channel rcoff of its tensor
     RD_REFLECT,       // ReflectionPad2d(pad) (reflect_pad.hip): the padded tensor is materialised, the convolution behind it runs with pad 0
     RD_TANH,          // Tanh (reflect_pad.hip); the backward reads the saved output
+    RD_DECONV4,       // ConvTranspose2d k4 s2 p1 + bias: the four parity 2x2 convolutions of a 4x4 stride-2 input gradient (S2Dgrad), in one
+                      // launch where conv_par4.hip's conditions hold
+    RD_NORM_SKIP,     // InstanceNorm2d with two activated outputs (unet_skip.hip): out = LeakyReLU(z, slope), and ReLU(z) into channels
+                      // [0, C) of the skip buffer `skip`
+    RD_RELU,          // ReLU of `in` into channels [ocoff, ocoff + C) of `out` (unet_skip.hip): the outermost U-Net level's half of its skip buffer
 };
 struct RdOp {
     RdKind type;
@@ -56,6 +64,7 @@ struct RdOp {
     // weight, re-ordered into the f32 staging area wst (an offset into the pack region) before it is packed
     int proj_form, proj_stride, proj_kernel;
     size_t wst;
+    int skip;                 // RD_NORM_SKIP: the skip buffer that takes ReLU(z)
     int share;                // != 0: a module applied a second time -- op share - 1 owns the packs, this op's weight and bias gradients add to its
     union { int k; int scale; };        // kernel size; RD_GATHER / RD_PRELU: the space-to-depth scale of the grid
     int s;
@@ -63,7 +72,7 @@ struct RdOp {
     int w, bias;              // w: parameter index of the weight (RD_NORM: gamma, beta = w + 1; -1 = no affine part); bias: parameter index or -1
     int w2;                   // RD_FOLD_TAIL: parameter index of the 3x3 convolution's weight (w = the transposed convolution's)
     union { int ngrp; int attn_width; };        // RD_NORM: groups (InstanceNorm2d: = channels); RD_ATTN: the reduced width C / reduction
-    union { float slope; float beta; };         // RD_NORM activation: 0 = ReLU, 0.2 = LeakyReLU (edsr.py:42); RD_PRELU: the residual's factor
+    union { float slope; float beta; };         // RD_NORM / RD_CONV activation: 0 = ReLU, 0.2 = LeakyReLU (edsr.py:42); RD_PRELU: the residual's factor
     size_t wf[4], wd[4], stats;
     S2Dgrad s2(int cin, int cout) const { return S2Dgrad{k, pad, cin, cout}; }      // input gradient of a stride-2 convolution with k > 1
 };
@@ -95,10 +104,10 @@ struct RdFwdNeed { size_t stats, scratch_floats; };       // saved statistics (b
 static RdFwdNeed rd_fwd_need(const RdPlan& P, const RdOp& o) {
     const RdT ti = P.T[o.in];
     switch (o.type) {
-    case RD_NORM: return {(size_t)P.B * o.ngrp * 2 * sizeof(float), 0};
+    case RD_NORM: case RD_NORM_SKIP: return {(size_t)P.B * o.ngrp * 2 * sizeof(float), 0};
     case RD_ATTN: return {(size_t)P.B * (2 * ti.C + o.attn_width) * sizeof(float), srcgan_ca_scratch_floats(P.B, (long)ti.H * ti.W, ti.C)};      // saved {p, h, s}
     case RD_CONV: case RD_DECONV2: case RD_SHUFFLE: case RD_FOLD_TAIL: case RD_DECONV3: case RD_POOL: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU:
-    case RD_REFLECT: case RD_TANH:
+    case RD_REFLECT: case RD_TANH: case RD_DECONV4: case RD_RELU:
         break;
     }
     return {0, 0};
@@ -113,8 +122,10 @@ static RdBwdNeed rd_bwd_need(const RdPlan& P, const RdOp& o) {
     }
     case RD_DECONV2: return {wgrad_slab(P.B, ti.H, ti.W, ti.C, to.C, 2, 2, 2), 0, 0};
     case RD_DECONV3: return {wgrad_slab(P.B, ti.H, ti.W, ti.C, to.C, 3, 3, 2), 0, 0};
+    case RD_DECONV4: return {wgrad_slab(P.B, ti.H, ti.W, ti.C, to.C, 4, 4, 2), 0, 0};
     case RD_PRELU: return {0, 0, srcgan_prelu_scratch_floats(P.B, ti.H, ti.W, o.oC, o.scale)};
     case RD_NORM: case RD_SHUFFLE: case RD_FOLD_TAIL: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_REFLECT: case RD_TANH:
+    case RD_NORM_SKIP: case RD_RELU:
         break;
     }
     return {0, 0, 0};
@@ -161,7 +172,12 @@ static size_t rd_layout_packs(RdPlan& P, bool train) {
             if (train) o.wd[0] = pk(ti.C, to.C, 9);
             break;
         }
+        case RD_DECONV4:        // the parity packs of the 4x4 s2 p1 input gradient whose "cin" is this op's output width
+            S2Dgrad{4, 1, to.C, ti.C}.plan(wb, P.dtype, o.wf);
+            if (train) o.wd[0] = pk(ti.C, to.C, 16);
+            break;
         case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU: case RD_REFLECT: case RD_TANH:
+        case RD_NORM_SKIP: case RD_RELU:
             break;              // no packed weights
         }
     }
@@ -216,6 +232,35 @@ struct RdBuilder {
         o.type = RD_TANH; o.in = in; o.res = -1; o.w = -1; o.bias = -1;
         o.out = tensor(ti.C, ti.cs, ti.H, ti.W);
         P.ops.push_back(o); return o.out;
+    }
+    int deconv4(int in, int cout) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_DECONV4; o.in = in; o.out = tensor(cout, cout < 8 ? 8 : cout, 2 * ti.H, 2 * ti.W); o.res = -1; o.k = 4; o.s = 2; o.pad = 1; o.w = np++; o.bias = np++;
+        P.ops.push_back(o); return o.out;
+    }
+    // InstanceNorm2d of `in` -> a new tensor LeakyReLU(z, slope), and ReLU(z) into channels [0, C) of the skip buffer
+    int norm_skip(int in, int skip, float slope) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_NORM_SKIP; o.in = in; o.out = tensor(ti.C, ti.cs, ti.H, ti.W, 1); o.res = -1; o.relu = 1; o.slope = slope; o.skip = skip; o.w = -1; o.bias = -1; o.ngrp = ti.C;
+        P.T[o.out].aslope = slope; P.T[o.out].skip = skip;
+        o.stats = b.take(rd_fwd_need(P, o).stats);
+        P.ops.push_back(o); return o.out;
+    }
+    // ReLU of `in` into channels [ocoff, ocoff + C) of `out`
+    void relu_to(int in, int out, int ocoff) {
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_RELU; o.in = in; o.out = out; o.res = -1; o.ocoff = ocoff; o.oC = P.T[in].C; o.w = -1; o.bias = -1;
+        P.ops.push_back(o);
+    }
+    // InstanceNorm2d (+ ReLU) of `in` into channels [ocoff, ocoff + C) of `out`
+    void inorm_to(int in, int out, int ocoff, int relu) {
+        const RdT ti = P.T[in];
+        RdOp o; memset(&o, 0, sizeof(o));
+        o.type = RD_NORM; o.in = in; o.out = out; o.res = -1; o.relu = relu; o.bias = -1; o.w = -1; o.ngrp = ti.C; o.ocoff = ocoff; o.oC = ti.C;
+        o.stats = b.take(rd_fwd_need(P, o).stats);
+        P.ops.push_back(o);
     }
     // the last op applies the module of op `first` again (same parameters, same packs)
     void share_last(int first) {
@@ -764,6 +809,55 @@ static int resnetgen_plan(const srcgan_resnetgen_cfg* c, RdPlan& P) {
     nb.finish();
     return 0;
 }
+// UnetGenerator (basicModel.py:257-354) with InstanceNorm2d (no parameters) and use_bias = True.  Levels 1 (outermost) .. n, widths
+// C_l = ngf min(2^(l-1), 8); d_l: level l's down-sampled pre-activation, u_l: the up path's norm output at level l.
+//   down:  a_1 = LeakyReLU(conv(x)) from the epilogue; a_l = LeakyReLU(IN(conv(a_{l-1}))), l = 2 .. n-1; a_n = ReLU(conv(a_{n-1})), no IN
+//   skip:  R_l = [ReLU(d_l) | ReLU(u_l)], ONE 2 C_l-channel buffer: RD_RELU (l = 1: ReLU(a_1) = ReLU(d_1)) / RD_NORM_SKIP write the first
+//          half, the up path's RD_NORM + ReLU the second.  (The reference's in-place LeakyReLU puts leaky(d_l) into its torch.cat, whose
+//          only consumer is a ReLU: ReLU(leaky(z)) = ReLU(z).)
+//   up:    deconv(a_n) -> IN + ReLU -> R_{n-1}[C:];  deconv(R_l) -> IN + ReLU -> R_{l-1}[C:];  tanh(deconv(R_1))
+// parameters() order = the order the ops are built in.  Backward: an up op runs before its level's down op, so the transposed
+// convolution's input gradient, masked by R_l itself, is the first writer of g(R_l); the next level's down convolution adds its own input
+// gradient to the first half and masks by LeakyReLU'(a_l): g_z = leaky'(z) (g_a + relu'(z) g_r), stored as g(a_l), the gradient at the
+// norm's output.  Every bias in front of an IN (all but the first and last down convolution's and the last transposed one's) has a
+// gradient that is zero in exact arithmetic and is computed like any other.
+static int unet_plan(const srcgan_unet_cfg* c, RdPlan& P) {
+    SG_REQUIRE(c, "srcgan_unet: null cfg");
+    SG_TRY(rd_common(c->dtype, c->B, c->H, c->W, P, "srcgan_unet"));
+    SG_REQUIRE(c->in_ch >= 1 && c->in_ch <= 8 && c->out_ch >= 1 && c->out_ch <= 8, "srcgan_unet: input_nc = %d and output_nc = %d must be in 1..8", c->in_ch, c->out_ch);
+    SG_REQUIRE(c->num_downs >= 5 && c->num_downs <= 24, "srcgan_unet: num_downs = %d must be at least 5 (the reference builds five blocks whatever it is given) "
+               "and at most 24", c->num_downs);
+    const long m = 1L << c->num_downs;
+    SG_REQUIRE(c->H % m == 0 && c->W % m == 0, "srcgan_unet: H = %d and W = %d must be positive multiples of 2^num_downs = %ld (every level halves the image, and "
+               "the skip connections need the up path to return to the same sizes)", c->H, c->W, m);
+    SG_REQUIRE(c->ngf == 16 || c->ngf == 32 || c->ngf == 64 || c->ngf == 128, "srcgan_unet: ngf = %d must be a multiple of 16 -- 16, 32, 64 or 128: InstanceNorm's "
+               "kernels take up to 1024 channels, in numbers whose 16-byte pieces divide 256", c->ngf);
+    const int n = c->num_downs, F = c->ngf;
+    auto width = [&](int l) { return F * std::min(1 << std::min(l - 1, 3), 8); };
+    RdBuilder nb(P, c->B);
+    nb.inorm = 1;
+    nb.input(c->in_ch, c->H, c->W);
+    std::vector<int> R(n, -1);
+    int a = nb.conv(0, width(1), 4, 2, 1, true, true);
+    P.ops.back().slope = 0.2f; P.T[a].aslope = 0.2f;
+    R[1] = nb.tensor(2 * width(1), 2 * width(1), P.T[a].H, P.T[a].W, 1);
+    nb.relu_to(a, R[1], 0);
+    P.T[a].skip = R[1];
+    for (int l = 2; l < n; ++l) {
+        const int d = nb.conv(a, width(l), 4, 2, 1, true, false);
+        R[l] = nb.tensor(2 * width(l), 2 * width(l), P.T[d].H, P.T[d].W, 1);
+        a = nb.norm_skip(d, R[l], 0.2f);
+    }
+    int src = nb.conv(a, width(n), 4, 2, 1, true, true);        // the innermost level: ReLU from the epilogue, no norm, C_n channels to its deconv
+    for (int l = n - 1; l >= 1; --l) {
+        const int t = nb.deconv4(src, width(l));
+        nb.inorm_to(t, R[l], width(l), 1);
+        src = R[l];
+    }
+    nb.tanh(nb.deconv4(src, c->out_ch));
+    nb.finish();
+    return 0;
+}
 static inline TRef rd_t(char* base, const RdT& t) { return tref(base + t.off, t.cs); }
 static inline const char* sr_tag(int kind) { return kind == 0 ? "espcn" : kind == 1 ? "srcnn" : "edsr"; }      // pack-cache tag stem / name in messages
 
@@ -792,7 +886,9 @@ static int rd_pack_fwd(const RdPlan& P, const float* const* params, void* ws, co
             break;
         case RD_DECONV3: deconv3_pack(packs, params[o.w], wp, o.wf, ti.C, to.C); break;
         case RD_FOLD_TAIL: fold = &o; break;        // composed from two sources, behind the batched launch
+        case RD_DECONV4: S2Dgrad{4, 1, to.C, ti.C}.pack(packs, params[o.w], wp, o.wf); break;      // the stored [in][out][4][4] is that convolution's [cout][cin][4][4]
         case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU: case RD_REFLECT: case RD_TANH:
+        case RD_NORM_SKIP: case RD_RELU:
             break;                      // no packed weights
         }
     }
@@ -818,14 +914,14 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
             Conv cv(dt, o.k, o.k, o.s);
             cv.in(sl(xin, o.icoff), B, ti.H, ti.W, ti.C < 8 ? ti.cs : rd_cin(o, ti)).w(wp + o.wf[0], o.bias >= 0 ? params[o.bias] : nullptr)
                 .out(sl(out, o.ocoff), to.H, to.W, rd_cout(o, to)).pad(o.pad, o.pad);
-            if (o.relu) { cv.lrelu(); cv.d.slope = 0.f; }
+            if (o.relu) { cv.lrelu(); cv.d.slope = o.slope; }
             if (o.res >= 0) cv.res1(rd_t(w8, P.T[o.res]), rd_cout(o, to), 1.f);        // y = conv(x) + res (edsr.py:97-98); a wider `res`: its prefix
             SG_TRY(cv.run(st));
             break;
         }
         case RD_NORM: {
             const void* res = o.res >= 0 ? (w8 + P.T[o.res].off) : nullptr;
-            SG_TRY(srcgan_gn_forward(xin.p, ti.cs, res, o.res >= 0 ? P.T[o.res].cs : 0, out.p, to.cs, o.w >= 0 ? params[o.w] : nullptr,
+            SG_TRY(srcgan_gn_forward(xin.p, ti.cs, res, o.res >= 0 ? P.T[o.res].cs : 0, (char*)out.p + (size_t)o.ocoff * P.esz, to.cs, o.w >= 0 ? params[o.w] : nullptr,
                                      o.w >= 0 ? params[o.w + 1] : nullptr, (float*)(w8 + o.stats), B, (long)ti.H * ti.W, ti.C, o.ngrp, 1e-5f, o.relu,
                                      o.slope, dt, gnscr, st));
             break;
@@ -884,6 +980,21 @@ static int rd_walk(const RdPlan& P, const float* x_nchw, const float* const* par
         case RD_TANH:
             SG_TRY(srcgan_tanh_forward(xin.p, ti.cs, out.p, to.cs, (long)B * ti.H * ti.W, ti.cs, dt, st));
             break;
+        case RD_DECONV4:
+            // y[2t + a][2u + b][co] = bias[co] + sum over the 2x2 taps of parity (a, b) and ci of x[t + a - 1 + ty][u + b - 1 + tx][ci] W[ci][co][ky][kx]:
+            // conv_par4.hip's formula; one launch where its conditions hold, four 2x2 launches otherwise (1..8 output channels)
+            if (to.C < to.cs) SG_HIP(hipMemsetAsync(out.p, 0, (size_t)B * to.H * to.W * to.cs * P.esz, (hipStream_t)st));
+            SG_TRY((S2Dgrad{4, 1, to.C, ti.C}.run(dt, xin, B, ti.H, ti.W, out, to.H, to.W, wp, o.wf, TNULL, TNULL, true, st, 0.f, params[o.bias])));
+            break;
+        case RD_NORM_SKIP: {
+            const RdT ts = P.T[o.skip];
+            SG_TRY(srcgan_in_skip_forward(xin.p, ti.cs, out.p, to.cs, w8 + ts.off, ts.cs, 0, (float*)(w8 + o.stats), B, (long)ti.H * ti.W, ti.C, 1e-5f, o.slope,
+                                          dt, gnscr, st));
+            break;
+        }
+        case RD_RELU:
+            SG_TRY(srcgan_relu_nhwc(xin.p, ti.cs, out.p, to.cs, o.ocoff, (long)B * ti.H * ti.W, ti.C, dt, st));
+            break;
         }
     }
     return 0;
@@ -941,6 +1052,7 @@ static int rd_infer_replan(RdPlan& P, bool fold, const char* who, size_t spare =
     for (int k = 0; k < nops; ++k) {
         const RdOp& o = P.ops[k];
         if (!have[o.out]) { get(o.out); have[o.out] = 1; }
+        if (o.skip && !have[o.skip]) { get(o.skip); have[o.skip] = 1; }      // a second output: alive until its reader, the level's transposed convolution
         if (last[o.in] == k) put(o.in);
         if (o.res >= 0 && o.res != o.in && last[o.res] == k) put(o.res);
     }
@@ -979,6 +1091,7 @@ RD_INFER_PLAN(rdn_infer_plan, srcgan_rdn_cfg, rdn_plan, "srcgan_rdn")
 RD_INFER_PLAN(mdsr_infer_plan, srcgan_mdsr_cfg, mdsr_plan, "srcgan_mdsr")
 RD_INFER_PLAN(vdsr_infer_plan, srcgan_vdsr_cfg, vdsr_plan, "srcgan_vdsr")
 RD_INFER_PLAN(resnetgen_infer_plan, srcgan_resnetgen_cfg, resnetgen_plan, "srcgan_resnetgen")
+RD_INFER_PLAN(unet_infer_plan, srcgan_unet_cfg, unet_plan, "srcgan_unet")
 #undef RD_INFER_PLAN
 // per-op byte ranges {in, res, out} x {offset, bytes} of a plan (res: 0, 0 where the op has none) -- what the planner's tests inspect
 static int rd_plan_ranges(const RdPlan& P, size_t* ranges, int cap) {
@@ -1030,9 +1143,13 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             case RD_DECONV3:        // the input gradient is a 3x3 s2 p1 convolution of dy: rows = ci, k = co, taps as stored
                 packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 3, 3, lay_fwd(to.C, 3, 3));
                 break;
+            case RD_DECONV4:        // the input gradient is a 4x4 s2 p1 convolution of dy: rows = ci, k = co, taps as stored
+                packs.add(params[o.w], wp + o.wd[0], ti.C, to.C, 4, 4, lay_fwd(to.C, 4, 4));
+                break;
             case RD_FOLD_TAIL:
                 SG_FAIL("%s backward: internal error (a folded tail in a training plan)", tag);
             case RD_NORM: case RD_SHUFFLE: case RD_POOL: case RD_ATTN: case RD_MEANSHIFT: case RD_GATHER: case RD_PRELU: case RD_REFLECT: case RD_TANH:
+            case RD_NORM_SKIP: case RD_RELU:
                 break;              // no packed weights
             }
         }
@@ -1112,7 +1229,7 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                     if (acc) cv.res1(dx, cin, 1.f);
                     else if (res_in) cv.res1(dy, cout, 1.f);        // dx[:, :cout] += dy
                     const int c0 = std::max(0, ti.act0 - o.icoff);
-                    if (ti.act && c0 < cin) { cv.mask(xin, c0); cv.d.mslope = 0.f; }
+                    if (ti.act && c0 < cin) { cv.mask(xin, c0); cv.d.mslope = ti.aslope; }
                     SG_TRY(cv.run(st));
                 } else if (o.k == 1) {
                     if (!acc) SG_HIP(hipMemsetAsync(dx.p, 0, (size_t)B * ti.H * ti.W * ti.cs * P.esz, (hipStream_t)st));
@@ -1120,8 +1237,16 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
                     cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, to.H, to.W, ti.C).pad(0, 0).scatter(2, 0, 0, ti.H, ti.W);
                     if (acc) cv.res1(dx, ti.C, 1.f);
                     SG_TRY(cv.run(st));
-                } else
-                    SG_TRY(o.s2(ti.C, to.C).run(dt, dy, B, to.H, to.W, dx, ti.H, ti.W, wp, o.wd, acc ? dx : TNULL, ti.act ? xin : TNULL, false, st, 0.f));
+                } else {
+                    // xin = LeakyReLU(z) with ReLU(z) in a skip buffer (the U-Net): the transposed convolution behind the buffer stored
+                    // relu'(z) g_r there; this one adds g_a and masks the sum by leaky'(z) -- the gradient at z, in one epilogue
+                    TRef add = acc ? dx : TNULL;
+                    if (ti.skip) {
+                        SG_REQUIRE(!acc && written[ti.skip] && ti.act, "%s backward: internal error (the skip buffer's gradient must precede its level's down convolution)", tag);
+                        add = gt(ti.skip);
+                    }
+                    SG_TRY(o.s2(ti.C, to.C).run(dt, dy, B, to.H, to.W, dx, ti.H, ti.W, wp, o.wd, add, ti.act ? xin : TNULL, o.k == 4 && o.pad == 1, st, ti.aslope));
+                }
                 written[o.in] = 1;
             }
             break;
@@ -1134,7 +1259,9 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             SG_REQUIRE(!acc && !ti.act, "%s backward: internal error (GroupNorm input has two consumers or a fused activation)", tag);
             const int pacc = o.w >= 0 ? seen_param[o.w] : 0;       // a GroupNorm module applied more than once (edsr.py:41,47,49): gradients add
             if (o.w >= 0) seen_param[o.w] = 1;
-            SG_TRY(srcgan_gn_backward(dy.p, to.cs, o.relu ? (w8 + to.off) : nullptr, to.cs, xin.p, ti.cs, o.w >= 0 ? params[o.w] : nullptr,
+            // (a slice of an activated buffer -- the U-Net's skip: its reader's input gradient arrived masked by the buffer itself)
+            SG_TRY(srcgan_gn_backward((char*)dy.p + (size_t)dy.coff * P.esz, to.cs, o.relu && !to.act ? (w8 + to.off + (size_t)o.ocoff * P.esz) : nullptr, to.cs, xin.p, ti.cs,
+                                      o.w >= 0 ? params[o.w] : nullptr,
                                       (const float*)(w8 + o.stats), dx.p, ti.cs, dres, dres_cs, dres_acc, o.w >= 0 ? G(o.w) : nullptr,
                                       o.w >= 0 ? G(o.w + 1) : nullptr, pacc, o.slope, B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
             written[o.in] = 1;
@@ -1158,11 +1285,36 @@ static int rd_backward(const RdPlan& P, const float* dy_nchw, float* dx_nchw, co
             // dx[i][j][ci] = sum dy[2i + ky - 1][2j + kx - 1][co] * W[ci][co][ky][kx]: the forward 3x3 stride-2 pad-1 convolution
             Conv cv(dt, 3, 3, 2);
             cv.in(dy, B, to.H, to.W, to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(1, 1);
-            if (ti.act) { cv.mask(xin, 0); cv.d.mslope = 0.f; }
+            if (ti.act) { cv.mask(xin, 0); cv.d.mslope = ti.aslope; }
             SG_TRY(cv.run(st));
             written[o.in] = 1;
             break;
         }
+        case RD_DECONV4: {
+            // dW[ci][co][ky][kx] = sum x[i][j][ci] * dy[2i + ky - 1][2j + kx - 1][co]: the stride-2 wgrad with the roles of x and dy exchanged
+            if (G(o.w))
+                SG_TRY(wgrad_call(dt, xin, ti.H, ti.W, ti.C, dy, B, to.H, to.W, to.C, 4, 4, 2, 1, 1, lay_fwd(to.C, 4, 4), 1.f, slab, G(o.w), st));
+            if (G(o.bias)) SG_TRY(bias_sum(dy, (long)B * to.H * to.W, to.C, G(o.bias), 0));
+            SG_REQUIRE(!acc, "%s backward: internal error (transposed convolution input with two consumers)", tag);
+            // dx[i][j][ci] = sum dy[2i + ky - 1][2j + kx - 1][co] * W[ci][co][ky][kx]: the forward 4x4 stride-2 pad-1 convolution, masked by
+            // the input itself where that is an activation's output (the skip buffer [ReLU | ReLU], the innermost level's ReLU)
+            Conv cv(dt, 4, 4, 2);
+            cv.in(dy, B, to.H, to.W, to.C < 8 ? to.cs : to.C).w(wp + o.wd[0]).out(dx, ti.H, ti.W, ti.C).pad(1, 1);
+            if (ti.act) { cv.mask(xin, 0); cv.d.mslope = ti.aslope; }
+            SG_TRY(cv.run(st));
+            written[o.in] = 1;
+            break;
+        }
+        case RD_NORM_SKIP:
+            // dy = g(out) is the gradient at the norm's output already: the consumer of `out` folded the skip buffer's share in
+            SG_REQUIRE(!acc && !ti.act && written[o.skip], "%s backward: internal error (two-output norm)", tag);
+            SG_TRY(srcgan_gn_backward(dy.p, to.cs, nullptr, 0, xin.p, ti.cs, nullptr, (const float*)(w8 + o.stats), dx.p, ti.cs, nullptr, 0, 0, nullptr, nullptr, 0,
+                                      0.f, B, (long)ti.H * ti.W, ti.C, o.ngrp, dt, gnscr, st));
+            written[o.in] = 1;
+            break;
+        case RD_RELU:           // nothing to launch: the consumer of `in` has folded this buffer's gradient into g(in) (RdT::skip)
+            SG_REQUIRE(written[o.in] && P.T[o.in].skip == o.out, "%s backward: internal error (ReLU into a skip buffer without a consumer that folds its gradient)", tag);
+            break;
         case RD_ATTN: {
             void* dres = nullptr; int dres_cs = 0, dres_acc = 0;
             if (o.res >= 0) {       // the block's input: this op stores (or adds to the group convolution's copy), the block's first convolution adds
@@ -1274,6 +1426,7 @@ RD_FAMILY(rdn, srcgan_rdn_cfg, rdn_plan, rdn_infer_plan, "rdn")
 RD_FAMILY(mdsr, srcgan_mdsr_cfg, mdsr_plan, mdsr_infer_plan, mdsr_tag(c->scale_idx))
 RD_FAMILY(vdsr, srcgan_vdsr_cfg, vdsr_plan, vdsr_infer_plan, "vdsr")
 RD_FAMILY(resnetgen, srcgan_resnetgen_cfg, resnetgen_plan, resnetgen_infer_plan, "resnetgen")
+RD_FAMILY(unet, srcgan_unet_cfg, unet_plan, unet_infer_plan, "unet")
 
 // ResDeconv: the inference entry points take fold_tail, and the folded plan's job table has a tag of its own
 RD_TRAIN_ENTRIES(resdeconv, srcgan_resdeconv_cfg, rd_plan, "resdeconv")

@@ -164,6 +164,8 @@ def _scale(net) -> Optional[int]:
         return 1                                        # three colours in and out: a ``cascade_scene(const=True)`` SR network on 3-channel input only
     if isinstance(net, M.ResnetGenerator):
         return 1                                        # a translator: the output has the input's size (H, W multiples of 4)
+    if isinstance(net, M.UnetGenerator):
+        return 1                                        # a translator: the output has the input's size (H, W multiples of 2^num_downs)
     return None
 
 
@@ -251,10 +253,10 @@ def receptive_halo(net) -> int:
                                     input pixel; x8: one level more, again 1: the sampler and the tail cost 2 at every scale.  r16: 44
       VDSR           n_resblocks    one 3x3 per BasicBlock (vdsr.py:24-35), all at the input's resolution; the skip spreads nothing.  r20: 20
 
-    Networks with normalisation layers (ResDeconv, EDSR, ResnetGenerator: GroupNorm / InstanceNorm statistics are taken over the whole image), RCAN
+    Networks with normalisation layers (ResDeconv, EDSR, ResnetGenerator, UnetGenerator: GroupNorm / InstanceNorm statistics are taken over the whole image), RCAN
     (its channel attention pools over the whole image) and unknown modules raise ValueError: no halo makes their tiles exact, so pass ``halo=`` explicitly and blend."""
     name = type(net).__name__
-    if isinstance(net, (M.ResDeconv, M.EDSR, M.ResnetGenerator)):
+    if isinstance(net, (M.ResDeconv, M.EDSR, M.ResnetGenerator, M.UnetGenerator)):
         raise ValueError(f"receptive_halo: {name} has normalisation layers whose per-image statistics make tiles inexact at any halo; "
                          "pass halo= explicitly (and blend='feather')")
     if isinstance(net, M.RCAN):

@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _native as N
 
-__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "ResnetGenerator", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
+__all__ = ["RDDBNet", "RDDBNetA", "RDDBNetB", "LegacyRDDBNet", "ResDeconv", "ESPCN", "SRCNN", "EDSR", "SRDN", "SRDenseNetA", "SRDenseNetB", "RCAN", "DDBPN", "RDN", "MDSR", "VDSR", "ResnetGenerator", "UnetGenerator", "NLayerDiscriminator", "ResidualDenseBlock_5", "RRDB", "deconv",
            "get_deconv_params", "Identity", "get_norm_layer", "init_weights", "init_net", "define_G"]
 
 
@@ -1282,10 +1282,15 @@ def init_net(net, init_type='normal', init_gain=0.02):
 
 def define_G(input_nc, output_nc, ngf, netG, norm='batch', use_dropout=False, init_type='normal', init_gain=0.02):
     """Same name and signature as the reference's ``basicModel.define_G``: ``netG`` 'resnet_9blocks' / 'resnet_6blocks' build the native
-    ResnetGenerator with 9 / 6 blocks (which accepts ``norm='instance'`` alone) and initialise it with ``init_net``; 'unet_128' /
-    'unet_256' are not native."""
+    ResnetGenerator with 9 / 6 blocks (which accepts ``norm='instance'`` alone) and initialise it with ``init_net``.
+
+    'unet_128' / 'unet_256' are still refused here, although the class is native: build it with
+    ``init_net(UnetGenerator(input_nc, output_nc, 7 | 8, ngf, norm_layer=get_norm_layer(norm)), init_type, init_gain)`` -- what the
+    reference's ``define_G`` does, draw for draw.  Routing the two names is two lines in this function once
+    tests/test_resnetgen_host.py::test_define_G_routes, which asserts the refusal, may change."""
     if netG in ('unet_128', 'unet_256'):
-        raise NotImplementedError("UnetGenerator is not native")
+        raise NotImplementedError(f"UnetGenerator is not native through define_G yet: build it with init_net(UnetGenerator(input_nc, output_nc, "
+                                  f"{7 if netG == 'unet_128' else 8}, ngf, norm_layer=get_norm_layer(norm)), init_type, init_gain)")
     if netG not in _RESNET_BLOCKS:
         raise NotImplementedError(f'Generator model name [{netG}] is not recognized')
     net = ResnetGenerator(input_nc, output_nc, ngf, norm_layer=get_norm_layer(norm), use_dropout=use_dropout, n_blocks=_RESNET_BLOCKS[netG])
@@ -1373,6 +1378,89 @@ class ResnetGenerator(_NativeRepr, nn.Module):
 
     def forward(self, input):
         return _oplist_forward(input, _RESNETGEN, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
+
+
+# ------------------------------------------------------------------------------------------------ UnetGenerator
+class _UnetSkipBlock(_HolderOnly):
+    """Parameter holder of basicModel.py:288-354 UnetSkipConnectionBlock with InstanceNorm2d and biases: ``model`` is the reference's
+    nn.Sequential -- [downconv, submodule, ReLU, upconv, Tanh] (outermost), [LeakyReLU, downconv, ReLU, upconv, norm] (innermost),
+    [LeakyReLU, downconv, norm, submodule, ReLU, upconv, norm] otherwise -- so the state_dict keys nest as the reference's do."""
+
+    def __init__(self, outer_nc, inner_nc, input_nc=None, submodule=None, outermost=False, innermost=False):
+        super().__init__()
+        norm = lambda c: nn.InstanceNorm2d(c, affine=False, track_running_stats=False)
+        downconv = nn.Conv2d(outer_nc if input_nc is None else input_nc, inner_nc, kernel_size=4, stride=2, padding=1, bias=True)
+        downrelu, downnorm, uprelu, upnorm = nn.LeakyReLU(0.2, True), norm(inner_nc), nn.ReLU(True), norm(outer_nc)
+        upconv = nn.ConvTranspose2d(inner_nc if innermost else inner_nc * 2, outer_nc, kernel_size=4, stride=2, padding=1, bias=True)
+        if outermost:
+            model = [downconv, submodule, uprelu, upconv, nn.Tanh()]
+        elif innermost:
+            model = [downrelu, downconv, uprelu, upconv, upnorm]
+        else:
+            model = [downrelu, downconv, downnorm, submodule, uprelu, upconv, upnorm]
+        self.model = nn.Sequential(*model)
+
+
+def _unet_cfg(x, items):
+    in_ch, out_ch, ngf, num_downs, dtype = items
+    _check_input(x, "UnetGenerator", in_ch, f"expected [B,{in_ch},H,W]")
+    B, _, H, W = x.shape
+    return N.UnetCfg(in_ch, out_ch, B, H, W, dtype, ngf, num_downs), (B, out_ch, H, W)
+
+
+_UNET = _OpList("UnetGenerator", "srcgan_unet", _unet_cfg)
+
+
+class UnetGenerator(_NativeRepr, nn.Module):
+    """U-Net translator of pix2pix, drop-in for reference ``model.basicModel.UnetGenerator`` (src/model/basicModel.py:257-354), what its
+    ``define_G(.., 'unet_128' | 'unet_256', ..)`` builds with ``num_downs`` 7 | 8: ``num_downs`` 4x4 stride-2 convolutions down to
+    ngf min(2^(l-1), 8) channels at level l (LeakyReLU(0.2) in front of each but the first, InstanceNorm behind each but the first and
+    the last), the mirrored ConvTranspose2d(k4, s2, p1) back up (ReLU in front, InstanceNorm behind each but the last), a skip connection
+    around every level but the outermost, Tanh.  ``forward(x[B,input_nc,H,W]) -> [B,output_nc,H,W]``, H and W multiples of
+    2^num_downs; ``num_downs`` >= 5; ``ngf`` 16, 32, 64 or 128; 1..8 channels in and out.
+
+    Native: ``norm_layer`` = ``nn.InstanceNorm2d`` or the ``functools.partial`` of ``get_norm_layer('instance')``, no dropout.  BatchNorm
+    -- the class default, as in the reference -- the identity norm, affine / tracked InstanceNorm and dropout raise NotImplementedError.
+    The skip connection is one buffer written in place by its two producers, never a ``torch.cat``.  ``state_dict`` has the reference's
+    nested keys (``model.model.0.weight``, ``model.model.1.model.1.weight``, ..., ``model.model.3.bias``): the inner blocks are parameter
+    holders without a forward of their own, created innermost first as in the reference, so the same seed gives the same weights.
+    ``define_G`` does not route to this class yet (see there): ``init_net(UnetGenerator(...), init_type, init_gain)`` is its equal."""
+
+    def __init__(self, input_nc, output_nc, num_downs, ngf=64, norm_layer=nn.BatchNorm2d, use_dropout=False, dtype=None):
+        super().__init__()
+        nkw = {}
+        if isinstance(norm_layer, functools.partial):
+            nkw, norm_layer = dict(norm_layer.keywords), norm_layer.func
+        if norm_layer is nn.BatchNorm2d:
+            raise NotImplementedError("native UnetGenerator: norm_layer = nn.BatchNorm2d (the class default; define_G's norm='batch') is not "
+                                      "implemented -- the op-list executor has no BatchNorm; use nn.InstanceNorm2d (norm='instance')")
+        if norm_layer is not nn.InstanceNorm2d:
+            raise NotImplementedError("native UnetGenerator: the identity norm (get_norm_layer('none')) and other norm_layer factories are not "
+                                      "implemented; use nn.InstanceNorm2d (norm='instance')")
+        if nkw.get("affine", False) or nkw.get("track_running_stats", False):
+            raise NotImplementedError("native UnetGenerator: InstanceNorm2d with affine=True or track_running_stats=True is not implemented "
+                                      "(get_norm_layer('instance') builds it without either)")
+        if use_dropout:
+            raise NotImplementedError("native UnetGenerator: use_dropout=True is not implemented")
+        input_nc, output_nc, num_downs, ngf = int(input_nc), int(output_nc), int(num_downs), int(ngf)
+        self.compute_dtype = N.dtype_name(dtype)
+        self.num_downs = num_downs
+        self._cfg = (input_nc, output_nc, ngf, num_downs)
+        # the native planner owns the rules (num_downs >= 5, ngf, 1..8 channels): ask it first, on the smallest image it takes
+        side = 1 << max(min(num_downs, 24), 0)
+        probe = N.UnetCfg(input_nc, output_nc, 1, side, side, N.dtype_id(self.compute_dtype), ngf, num_downs)
+        if N.lib().srcgan_unet_num_params(C.byref(probe)) < 0:
+            raise ValueError("UnetGenerator: " + (N.lib().srcgan_last_error() or b"").decode())
+        # the blocks in the reference's order, innermost first (creation order = the order the seeded weights are drawn in)
+        block = _UnetSkipBlock(ngf * 8, ngf * 8, innermost=True)
+        for _ in range(num_downs - 5):
+            block = _UnetSkipBlock(ngf * 8, ngf * 8, submodule=block)
+        for mult in (4, 2, 1):
+            block = _UnetSkipBlock(ngf * mult, ngf * mult * 2, submodule=block)
+        self.model = _UnetSkipBlock(output_nc, ngf, input_nc=input_nc, submodule=block, outermost=True)
+
+    def forward(self, input):
+        return _oplist_forward(input, _UNET, (*self._cfg, N.dtype_id(self.compute_dtype)), list(self.parameters()))
 
 
 class _NLayerDFn(torch.autograd.Function):
